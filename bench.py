@@ -2,7 +2,7 @@
 """
 bench.py -- from_differential solves/sec on the 1M-vertex plane (BASELINE.json metric, configs[3] / cfg4).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -237,6 +237,23 @@ def describe(workload, cfg, V, nnz):
     return f"{workload}: {mesh}, V={V}, nnz(M)={nnz}, {mat}, u=M v, k=3"
 
 
+DUMP_LIMIT_BYTES = 64 * 1024 * 1024
+
+
+def dump_output(out_dir, name, t):
+    """What the timed path returned in its last step, as out_dir/<name>.npy (float32 / float64), for comparing two builds output for
+    output. Above DUMP_LIMIT_BYTES only a fixed, seeded sample of the rows is written (sorted), so that two runs with the same
+    arguments still dump the same elements."""
+    a = t.detach().cpu().numpy()
+    if a.dtype not in (np.float32, np.float64):
+        raise TypeError(f"--dump-outputs: {name} is {a.dtype}, not float32 / float64")
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        keep = a.shape[0] * DUMP_LIMIT_BYTES // a.nbytes
+        a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def run_single(args):
     from largesteps.geometry import compute_matrix
     from largesteps.parameterize import to_differential, from_differential
@@ -284,6 +301,8 @@ def run_single(args):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     gc.enable()
+    if args.dump_outputs:                                 # x of the last timed step: what from_differential's caller receives
+        dump_output(args.dump_outputs, "x", x)
     info = dict(solver.last_info)
     ms = elapsed / args.steps * 1e3
     method = info["method"]
@@ -706,7 +725,14 @@ def main():
     ap.add_argument("--shard", default="auto", choices=["auto", "vertex", "columns", "halo", "replicas"],
                     help="N > 1: vertex blocks = subtrees of the direct solver's elimination tree (default), right-hand-side columns across "
                          "ranks, vertex blocks of the iteration with halo exchange, or independent replicas (weak scaling)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the solution x of the last one as DIR/x.npy (float32; a fixed, seeded sample of its rows "
+                         "above 64 MB), e.g. DIR=bench_outputs. --gpus 1 only")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--dump-outputs is implemented for one process on one GPU only")
     if args.iterative:
         os.environ["LARGESTEPS_NO_DIRECT"] = "1"
     if not torch.cuda.is_available():

@@ -139,3 +139,31 @@ def test_shard_model_is_the_committed_table():
     assert bench.shard_model("cfg2_bunny70k", 2) is None and bench.shard_model("cfg4_plane1m", 3) is None
     one = bench.shard_model("cfg4_plane1m", 1)
     assert one["collective_us_assumed"] == [0.0, 0.0]
+
+
+def test_dump_output_writes_what_the_caller_receives(tmp_path, monkeypatch):
+    """--dump-outputs: the array as float32 .npy; above the size limit a fixed, seeded, sorted sample of its rows that two runs share;
+    and the argument checks that run before any device is touched."""
+    import sys
+    import numpy as np
+    import pytest
+    import torch
+    bench = load_bench()
+    x = torch.arange(3000, dtype=torch.float32).reshape(1000, 3)
+    bench.dump_output(str(tmp_path / "full"), "x", x)
+    got = np.load(tmp_path / "full" / "x.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1200)
+    for d in ("a", "b"):
+        bench.dump_output(str(tmp_path / d), "x", x)
+    a, b = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "b" / "x.npy")
+    assert a.nbytes <= 1200 and a.shape == (100, 3) and np.array_equal(a, b)
+    rows = a[:, 0].astype(np.int64) // 3
+    assert (np.diff(rows) > 0).all() and np.array_equal(a, x.numpy()[rows])
+    with pytest.raises(TypeError):
+        bench.dump_output(str(tmp_path / "c"), "x", x.to(torch.int32))
+    for argv in (["--steps", "0"], ["--warmup", "-1"], ["--gpus", "2", "--dump-outputs", str(tmp_path)]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        with pytest.raises(SystemExit) as e:
+            bench.main()
+        assert e.value.code == 2

@@ -221,15 +221,19 @@ def test_rccl_process_group_initialises():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("world,launch,workload", [(2, "torchrun", "cfg2_bunny70k"), (8, "torchrun", "cfg2_bunny70k"),
-                                                   (2, "plain", "cfg2_bunny70k"), (8, "plain", "cfg4_plane1m")])
+@pytest.mark.parametrize("world,launch,workload", [(2, "torchrun", "cfg2_bunny70k"), (4, "torchrun", "cfg2_bunny70k"),
+                                                   (2, "plain", "cfg2_bunny70k"), (2, "plain", "cfg4_plane1m")])
 def test_bench_line_of_a_multi_process_run(world, launch, workload):
     """`bench.py --gpus N` in both forms it may be started in -- as the driver launches N > 1 (torch.distributed.run, one process per rank,
     127.0.0.1) and PLAINLY (`python bench.py --gpus N`, the shape of the driver's N = 1 command: bench.py starts the ranks itself) -- in
     loopback on the one GPU (every rank on cuda:0, gloo transport): rank 0 must print ONE JSON line with the keys the driver parses, for
     the subtree-sharded direct solver, with the sharded answer correct, the ranks that took part, every rank's kernel / collective times
     and, for the headline workload, the model's prediction for that N. (The first SCALE record can only be taken on an 8-GPU node; this
-    keeps the command from failing there for a reason a 1-GPU box could have shown.)"""
+    keeps the command from failing there for a reason a 1-GPU box could have shown.)
+    At most six processes may hold the one device at a time: this test process, torch.distributed.run (it initialises HIP), bench.py's
+    own process when started plainly, and the ranks -- so N is at most 4 with torchrun and 2 plainly (3 has no model row). The eight-rank
+    split itself is checked in one process by test_sharded_direct_solver_at_world_eight_in_one_process, the N = 8 model row on the CPU
+    by tests/test_bench_model.py."""
     import json
     import socket
     import subprocess
@@ -276,7 +280,7 @@ def test_bench_line_of_a_multi_process_run(world, launch, workload):
     assert chk["max_abs_diff_vs_unsharded"] <= chk["tolerance_rel"] * chk["max_abs_x"]
     if workload == "cfg4_plane1m":
         m = c["model"]
-        assert m["kernel_us_per_rank"] == 121.6 and m["predicted_ms_per_step"][0] < m["predicted_ms_per_step"][1]
+        assert m["kernel_us_per_rank"] == 147.4 and m["predicted_ms_per_step"][0] < m["predicted_ms_per_step"][1]
     else:
         assert c["model"] is None
     rf = d["roofline"]
