@@ -29,6 +29,10 @@
  *   ls_face_normals* / ls_vertex_normals*   scripts/geometry.py:91-110 (compute_face_normals), :115-147
  *                        (compute_vertex_normals) and the autograd graph torch records through them -- the consumer
  *                        right after from_differential in every optimisation step (scripts/main.py:178-179)
+ *   ls_average_edge_length*   scripts/geometry.py:13-33 (average_edge_length: the remesher's target edge length,
+ *                        scripts/main.py:146) and its autograd gradient
+ *   ls_massmatrix_voronoi*    scripts/geometry.py:35-89 (massmatrix_voronoi: Voronoi area per vertex, obtuse-triangle rule)
+ *                        and its autograd gradient
  */
 #ifndef LARGESTEPS_HIP_H
 #define LARGESTEPS_HIP_H
@@ -543,6 +547,31 @@ int ls_normals_pair_backward_faces(const float* verts, const void* faces, int id
 int ls_normals_pair_backward_verts(const float* verts, const void* faces, int idx_bytes, int64_t F, int64_t V, const int32_t* vptr,
                                    const int32_t* cpos, const float* norms, const float* g_raw, const float* gN, const float* g_fn,
                                    float* grad_verts, void* workspace, size_t ws_bytes, int device, void* stream);
+
+/* ---- meshgeom: average_edge_length and massmatrix_voronoi ------------------------------------------------------
+ * faces (F, 3) int32 / int64 (idx_bytes 4 / 8), verts (V, 3) fp32, vptr / cpos / order the corner ranking of ls_corner_ranks
+ * (order[3 F] = its inverse permutation, rank -> corner id 3 f + i), as for the normals above. Same PRECONDITION as
+ * ls_vertex_normals_gathered: the ranking was built FOR THESE faces (ls_corner_ranks has range-checked them and returns
+ * LS_E_INDEX otherwise); the kernels index verts through faces / order without a range check. No entry point allocates or
+ * synchronises; no atomics -- every result is bitwise reproducible for a given ranking. ASYNC.
+ *   ls_massmatrix_voronoi      mass (V) fp32: the reference's per-face cells in its fp32 operation order, summed per vertex as its
+ *                              scatter_add_ + sum(dim=1) does (per corner slot j in ascending face id, then (s0 + s1) + s2);
+ *                              vertex-major, one launch, no workspace. Unreferenced vertex: 0; a face with a zero-length edge: NaN.
+ *   ls_massmatrix_voronoi_backward   grad_verts (V, 3) = d sum(g_mass * mass) / d verts (torch's backward rules), overwritten.
+ *   ls_average_edge_length     out[0] = (sum over faces of l0 + l1 + l2) / F / 3 (fp64 partial sums in a fixed order, the two
+ *                              divisions in fp32 as the reference writes them); F == 0: NaN. Needs no ranking.
+ *   ls_average_edge_length_backward  grad_verts (V, 3) = g_out[0] * d out / d verts; g_out is read on the device, overwritten. */
+int ls_meshgeom_workspace_bytes(int64_t F, int64_t V, size_t* h_bytes);
+int ls_massmatrix_voronoi(const float* verts, const void* faces, int idx_bytes, int64_t F, int64_t V, const int32_t* vptr,
+                          const int32_t* order, float* mass, int device, void* stream);
+int ls_massmatrix_voronoi_backward(const float* verts, const void* faces, int idx_bytes, int64_t F, int64_t V, const int32_t* vptr,
+                                   const int32_t* cpos, const float* g_mass, float* grad_verts, void* workspace, size_t ws_bytes,
+                                   int device, void* stream);
+int ls_average_edge_length(const float* verts, const void* faces, int idx_bytes, int64_t F, int64_t V, float* out, void* workspace,
+                           size_t ws_bytes, int device, void* stream);
+int ls_average_edge_length_backward(const float* verts, const void* faces, int idx_bytes, int64_t F, int64_t V, const int32_t* vptr,
+                                    const int32_t* cpos, const float* g_out, float* grad_verts, void* workspace, size_t ws_bytes,
+                                    int device, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * AdamUniform step (optimize.py:18-41) on n contiguous fp32 elements, two kernels, no host sync:

@@ -89,6 +89,13 @@ _SIGNATURES = {
     "ls_normals_pair_backward_verts": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "ls_vertex_normals_gathered": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "ls_meshgeom_workspace_bytes": (c_int, [c_i64, c_i64, ctypes.POINTER(c_size_t)]),
+    "ls_massmatrix_voronoi": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "ls_massmatrix_voronoi_backward": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_size_t, c_int, c_void_p]),
+    "ls_average_edge_length": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_i64, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "ls_average_edge_length_backward": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_size_t, c_int, c_void_p]),
     "ls_shard_plan_create": (c_int, [c_i64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
     "ls_shard_plan_destroy": (c_int, [c_void_p]),
     "ls_shard_plan_info": (c_int, [c_void_p] + [ctypes.POINTER(c_i64)] * 5 + [ctypes.POINTER(c_int)] * 2 + [ctypes.POINTER(c_i64)]),

@@ -3,13 +3,30 @@ Mesh bookkeeping the optimisation loop needs around a remesh, on the MI355X (SUR
 
 `remove_duplicates` is the reference's scripts/geometry.py:3-11 with the same name, argument order and return values
 (unique vertices in the order torch.unique(dim=0) gives them, re-indexed faces, inverse map) -- one native call
-(`ls_remove_duplicates`: hand-written radix sort + compaction) instead of torch.unique's library sort. There is no CPU path.
+(`ls_remove_duplicates`: hand-written radix sort + compaction) instead of torch.unique's library sort.
+
+`average_edge_length` (scripts/geometry.py:13-33; scripts/main.py:146 takes the remesher's target edge length from it) and
+`massmatrix_voronoi` (:35-89, the Voronoi area of every vertex) keep the reference's names, argument order and shapes (a 0-dim
+tensor, a (V,) tensor) and are differentiable with respect to the vertices (autograd Functions over csrc/meshgeom.hip: a
+hand-written forward and backward each, no atomics, bitwise reproducible, no host synchronisation once the face tensor's corner
+ranking is cached -- so they can sit in a captured graph). The results are float32, as the reference's are for fp32 vertices.
+Faces may be int32 or int64 (the reference needs int64 for scatter_add_). The reference's quirks are kept:
+  * a face with a zero-length edge has NaN cells (0 / 0 in its cosines), so its vertices' mass is NaN;
+  * an unreferenced vertex has mass 0;
+  * the obtuse-triangle rule tests `cos < 0` on the fp32 cosine: a right angle whose cosine rounds to a slightly negative value
+    takes the obtuse branch (same cells at exactly 90 degrees, a different gradient) -- the branch follows the reference's fp32
+    arithmetic, which the kernel reproduces operation for operation;
+  * average_edge_length counts an interior edge twice and a boundary edge once (it averages over the 3 F face edges); F == 0
+    gives NaN, and massmatrix_voronoi then returns zeros.
+There is no CPU path.
 """
 import ctypes
 
 import torch
+from torch.autograd import Function
 
 from . import _native
+from .normals import _on, _prep
 
 
 def remove_duplicates(v, f):
@@ -47,3 +64,106 @@ def remove_duplicates(v, f):
                                                _native.stream_of(dev)))
     return unique[: nu.value], new_faces, inverse
 
+
+
+_ws_bytes = {}
+
+
+def _workspace(F, V, dev):
+    n = _ws_bytes.get((F, V))
+    if n is None:
+        c = ctypes.c_size_t(0)
+        _native.check(_native.lib().ls_meshgeom_workspace_bytes(F, V, ctypes.byref(c)))
+        if len(_ws_bytes) > 64:
+            _ws_bytes.clear()
+        n = _ws_bytes[(F, V)] = c.value
+    return torch.empty(n, dtype=torch.uint8, device=dev)
+
+
+# Both Functions validate the faces through the corner ranking of normals._prep (built once per face tensor: the range check
+# raises IndexError and is the only host synchronisation); the kernels trust that plan.
+class _AverageEdgeLength(Function):
+    @staticmethod
+    def forward(ctx, verts, faces):
+        v, f, vptr, vcorner, _ = _prep(verts, faces)
+        F, V, dev = f.shape[0], v.shape[0], v.device
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        ws = _workspace(F, V, dev)
+        with _on(dev):
+            _native.check(_native.lib().ls_average_edge_length(_native.ptr(v), _native.ptr(f), f.element_size(), F, V, _native.ptr(out),
+                                                               _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
+        ctx.save_for_backward(v, f, vptr, vcorner)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        v, f, vptr, vcorner = ctx.saved_tensors
+        F, V, dev = f.shape[0], v.shape[0], v.device
+        g = g.to(torch.float32).contiguous()
+        gv = torch.empty_like(v)
+        ws = _workspace(F, V, dev)
+        with _on(dev):
+            _native.check(_native.lib().ls_average_edge_length_backward(_native.ptr(v), _native.ptr(f), f.element_size(), F, V, _native.ptr(vptr),
+                                                                        _native.ptr(vcorner), _native.ptr(g), _native.ptr(gv), _native.ptr(ws),
+                                                                        ws.numel(), dev.index, _native.stream_of(dev)))
+        return gv, None
+
+
+class _MassmatrixVoronoi(Function):
+    @staticmethod
+    def forward(ctx, verts, faces):
+        v, f, vptr, vcorner, order = _prep(verts, faces)
+        F, V, dev = f.shape[0], v.shape[0], v.device
+        mass = torch.empty(V, dtype=torch.float32, device=dev)
+        with _on(dev):
+            _native.check(_native.lib().ls_massmatrix_voronoi(_native.ptr(v), _native.ptr(f), f.element_size(), F, V, _native.ptr(vptr),
+                                                              _native.ptr(order), _native.ptr(mass), dev.index, _native.stream_of(dev)))
+        ctx.save_for_backward(v, f, vptr, vcorner)
+        return mass
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        v, f, vptr, vcorner = ctx.saved_tensors
+        F, V, dev = f.shape[0], v.shape[0], v.device
+        g = g.to(torch.float32).contiguous()
+        gv = torch.empty_like(v)
+        ws = _workspace(F, V, dev)
+        with _on(dev):
+            _native.check(_native.lib().ls_massmatrix_voronoi_backward(_native.ptr(v), _native.ptr(f), f.element_size(), F, V, _native.ptr(vptr),
+                                                                       _native.ptr(vcorner), _native.ptr(g), _native.ptr(gv), _native.ptr(ws),
+                                                                       ws.numel(), dev.index, _native.stream_of(dev)))
+        return gv, None
+
+
+@_native.retry_on_oom
+def average_edge_length(verts, faces):
+    """
+    Compute the average length of all edges in a given mesh (scripts/geometry.py:13-33). Returns a 0-dim float32 tensor.
+
+    Parameters
+    ----------
+    verts : torch.Tensor
+        Vertex positions (V, 3), on a HIP device.
+    faces : torch.Tensor
+        array of triangle faces (F, 3), int32 or int64.
+    """
+    return _AverageEdgeLength.apply(verts, faces)
+
+
+@_native.retry_on_oom
+def massmatrix_voronoi(verts, faces):
+    """
+    Compute the area of the Voronoi cell around each vertex in the mesh (scripts/geometry.py:35-89). Returns a (V,) float32
+    tensor.
+
+    params
+    ------
+
+    verts: vertex positions (V, 3), on a HIP device
+    faces: triangle indices (F, 3), int32 or int64
+    """
+    return _MassmatrixVoronoi.apply(verts, faces)

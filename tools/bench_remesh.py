@@ -2,6 +2,7 @@
 mesh changes, and everything that hangs off the connectivity is rebuilt --
     remove_duplicates -> compute_matrix -> to_differential -> CholeskySolver (symbolic analysis + numeric factorisation)
     -> AdamUniform re-initialised
+(preceded, as in main.py:146, by average_edge_length of the current mesh: the target edge length h the remesher is handed)
 then `period` optimisation steps (from_differential -> normals -> loss -> backward incl. the adjoint solve -> AdamUniform).
 No remesher is available in this environment (SURVEY: remesh_botsch is out of scope): a remesh event is emulated by handing
 the loop the same surface as a triangle SOUP with the vertex storage reshuffled -- what a remesher returns -- so that all
@@ -12,7 +13,7 @@ sys.path[:0] = [_R, os.path.join(_R, "large-steps-pytorch_amd")]
 import numpy as np, torch
 from largesteps import synthetic
 from largesteps.geometry import compute_matrix
-from largesteps.meshops import remove_duplicates
+from largesteps.meshops import average_edge_length, remove_duplicates
 from largesteps.parameterize import to_differential, from_differential
 from largesteps.normals import compute_face_normals, compute_vertex_normals
 from largesteps.optimize import AdamUniform
@@ -39,9 +40,12 @@ def sync():
 
 
 rebuild, steps_ms = [], []
+x_cur, f_cur = torch.from_numpy(v).to(dev), torch.from_numpy(f).to(dev)     # the mesh the first remesh starts from
 for c in range(cycles):
     v_src, f_src = soup()
     t0 = sync()
+    with torch.no_grad():
+        h = average_edge_length(x_cur, f_cur) * 0.5     # main.py:146: the target edge length of the remesher (none here)
     vu, fu, dup = remove_duplicates(v_src, f_src)
     t1 = sync()
     M = compute_matrix(vu, fu, lam, alpha=cfg["alpha"], cotan=cfg["cotan"])
@@ -61,6 +65,7 @@ for c in range(cycles):
         loss.backward()
         opt.step()
     t5 = sync()
+    x_cur, f_cur = x.detach(), fu
     rebuild.append((t1 - t0, t2 - t1, t3 - t2, t4 - t3))
     steps_ms.append((t5 - t4) / period * 1e3)
     del M
@@ -71,7 +76,7 @@ r = np.array(rebuild[skip:]).mean(0) * 1e3
 s = float(np.mean(steps_ms[skip:]))
 tot = float(r.sum())
 print(f"{workload}: V={vu.shape[0]} (soup of {v_src.shape[0]} rows), remesh every {period} steps")
-print(f"  rebuild per remesh: remove_duplicates {r[0]:.2f} ms | compute_matrix + to_differential {r[1]:.2f} ms | solver constructor "
+print(f"  rebuild per remesh: average_edge_length + remove_duplicates {r[0]:.2f} ms | compute_matrix + to_differential {r[1]:.2f} ms | solver constructor "
       f"(analysis + factorisation, first solve) {r[2]:.2f} ms | optimizer + targets {r[3]:.2f} ms | total {tot:.1f} ms")
 ctor = np.array(rebuild)[:, 2] * 1e3
 steady = ctor[skip:]
