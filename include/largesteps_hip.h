@@ -390,6 +390,27 @@ typedef struct ls_direct_options {
 int ls_direct_options_default(ls_direct_options* opt);
 int ls_direct_factor_ex(const int32_t* d_rowptr, const int32_t* d_col, const float* d_val, int64_t V, int64_t nnz,
                         const float* d_positions, const ls_direct_options* opt, int device, void* stream, ls_direct** out);
+/* Same-pattern refactorisation: new values, same sparsity pattern, no new symbolic analysis.
+ * ls_direct_factor_refactorable: exactly ls_direct_factor_ex (same plan, same layouts, bit-identical solves), but the handle also keeps
+ *   what a numeric refactorisation needs -- a device copy of the analysed pattern (rowptr, col), the tree's index lists and node table,
+ *   the recorded chain of numeric launches (its descriptors as offsets into the scratch, not pointers) and, with sparse leaves, where
+ *   every stored entry's value lives in their lists (8 bytes per entry). ~120 MB at 1M vertices (profiles/refactor_bench.json); the fp64 scratch (3-4 GB) is NOT kept.
+ *   A sharded handle (shard_count > 1) keeps nothing. SYNC.
+ * ls_direct_refactor: SYNC. The caller's pattern is compared with the kept one on the device (one flag read back): V, nnz, rowptr or col
+ *   different -> LS_E_INVALID, the factor untouched. Otherwise scratch comes from the buffer pool, the KEPT pattern plus the caller's values
+ *   are assembled (no caller array steers a write), the constructor's numeric chain runs into the handle's own factor arrays in place,
+ *   and the scratch goes back to the pool. The result is bitwise what ls_direct_factor_ex(new values) with the same positions and
+ *   options would give. No buffer a solve reads or writes moves: a graph captured around solves of this handle replays with the new
+ *   factor. A front that is not positive definite -> LS_E_INVALID and the handle is UNFACTORED (ls_direct_solve / _solve_part return
+ *   LS_E_STATE) until a later ls_direct_refactor succeeds. LS_E_STATE: the handle was not made by ls_direct_factor_refactorable (or is
+ *   sharded), or `stream` is being captured (the call synchronises).
+ * ls_direct_refactorable: host only; *h_yes = 1 if ls_direct_refactor can run on the handle, *h_retained_device_bytes = what it keeps
+ *   for that (either pointer may be NULL). */
+int ls_direct_factor_refactorable(const int32_t* d_rowptr, const int32_t* d_col, const float* d_val, int64_t V, int64_t nnz,
+                                  const float* d_positions, const ls_direct_options* opt, int device, void* stream, ls_direct** out);
+int ls_direct_refactor(ls_direct* d, const int32_t* d_rowptr, const int32_t* d_col, const float* d_val, int64_t V, int64_t nnz,
+                       void* stream);
+int ls_direct_refactorable(const ls_direct* d, int* h_yes, size_t* h_retained_device_bytes);
 /* The direct solver keeps its device buffers (>= 256 KB: the constructor's fp64 fronts and work arrays -- 3-4 GB at 1M vertices, 14 GB
  * at 4M --, the analysis' scratch, a destroyed handle's factor arrays, index tables and vectors) in a per-process pool instead of freeing them: a remesh loop
  * (scripts/main.py:137-169) destroys a solver and constructs one of nearly the same size again and again, and the runtime gives freed

@@ -846,6 +846,14 @@ struct LevelPlan { int up_first = 0, up_tiles = 0, up_nw = 1, down_first = 0, do
 
 using namespace ls;
 
+namespace ls {          // nd_factor.hip: what a refactorable handle keeps (ls_direct_factor_refactorable) and the refactorisation itself
+struct RefactorState;
+void refactor_state_free(RefactorState* R);
+size_t refactor_state_bytes(const RefactorState* R);
+int refactor_run(RefactorState* R, const int32_t* d_rowptr, const int32_t* d_col, const float* d_val, int64_t V, int64_t nnz, hipStream_t st,
+                 bool* touched);
+}
+
 struct ls_direct {
     int device = 0, levels = 0, arity = 2, n_nodes = 0, kmax = 4;
     int64_t V = 0, n_bnd = 0, n_front = 0;
@@ -874,6 +882,8 @@ struct ls_direct {
     std::vector<std::pair<void*, size_t>> tables;      // index tables and vectors of the handle (pool_take / pool_alloc in ls_direct_create; back to the pool with the handle)
     std::vector<void*> owned;           // device arrays adopted from ls_direct_factor (handed to the buffer pool / freed with the handle)
     std::vector<size_t> owned_bytes;
+    ls::RefactorState* refac = nullptr; // ls_direct_factor_refactorable: what ls_direct_refactor needs (nullptr: the handle cannot refactor)
+    bool factored = true;               // false after a refactorisation that failed once it had started writing the factor: solves refuse
     // subtree sharding (one process per GPU): this handle runs the subtrees [sub_lo, sub_hi) of level `cut` and, replicated on
     // every rank, the levels above; the ranks meet once per solve in a sum over the slots of level cut - 1 (exch_f0 .. exch_f1)
     int shard_rank = 0, shard_count = 1, cut = 0;
@@ -1680,6 +1690,7 @@ extern "C" int ls_direct_destroy(ls_direct* d) {
         if (!ls::pool_give(d->device, t.first, t.second)) (void)hipFree(t.first);
     for (size_t i = 0; i < d->owned.size(); ++i)
         if (!ls::pool_give(d->device, d->owned[i], i < d->owned_bytes.size() ? d->owned_bytes[i] : 0)) (void)hipFree(d->owned[i]);
+    ls::refactor_state_free(d->refac);
     for (hipEvent_t e : d->ev) (void)hipEventDestroy(e);
 #ifdef LS_TIER_STAMPS
     if (d->stamps) (void)hipFree(d->stamps);
@@ -1822,6 +1833,7 @@ static int direct_solve_k(ls_direct* d, const float* b, float* x, hipStream_t st
 extern "C" int ls_direct_solve(ls_direct* d, const float* b, float* x, int k, void* stream) {
     LS_REQUIRE(d && b && x && k >= 1 && k <= d->kmax, LS_E_INVALID, "ls_direct_solve: bad argument (1 <= k <= %d)", d ? d->kmax : 4);
     LS_REQUIRE(b != x, LS_E_INVALID, "ls_direct_solve: b and x must not alias");
+    LS_REQUIRE(d->factored, LS_E_STATE, "ls_direct_solve: the handle is unfactored (its last ls_direct_refactor failed)");
     DeviceGuard g(d->device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
@@ -1848,6 +1860,7 @@ extern "C" int ls_direct_solve(ls_direct* d, const float* b, float* x, int k, vo
 extern "C" int ls_direct_solve_part(ls_direct* d, const float* b, float* x, int k, int part, float* exchange, void* stream) {
     LS_REQUIRE(d && b && x && k >= 1 && k <= d->kmax && (part == 0 || part == 1), LS_E_INVALID, "ls_direct_solve_part: bad argument");
     LS_REQUIRE(b != x, LS_E_INVALID, "ls_direct_solve_part: b and x must not alias");
+    LS_REQUIRE(d->factored, LS_E_STATE, "ls_direct_solve_part: the handle is unfactored (its last ls_direct_refactor failed)");
     LS_REQUIRE(exchange || d->exch_f1 == d->exch_f0, LS_E_INVALID, "ls_direct_solve_part: the exchange buffer is missing");
     DeviceGuard g(d->device);
     LS_HIP(g.err);
@@ -1914,6 +1927,40 @@ int ls_direct_adopt(ls_direct* d, void* const* owned, const size_t* owned_bytes,
     d->owned_bytes.assign(owned_bytes, owned_bytes + n_owned);
     for (int i = 0; i < 3; ++i) d->factor_s[i] = seconds3[i];
     for (int i = 0; i < 4; ++i) d->plan_q[i] = quality4[i];
+    return LS_OK;
+}
+
+int ls_direct_adopt_refactor(ls_direct* d, ls::RefactorState* state) {
+    ls::refactor_state_free(d->refac);
+    d->refac = state;
+    return LS_OK;
+}
+
+// New values, same pattern: the numeric factorisation again, into the handle's own factor arrays (nd_factor.hip, refactor_run). No buffer a
+// solve reads or writes moves, so a graph captured around solves of this handle replays with the new factor.
+extern "C" int ls_direct_refactor(ls_direct* d, const int32_t* d_rowptr, const int32_t* d_col, const float* d_val, int64_t V, int64_t nnz,
+                                  void* stream) {
+    LS_REQUIRE(d && d_rowptr && d_col && d_val && V > 0 && nnz > 0, LS_E_INVALID, "ls_direct_refactor: bad argument");
+    LS_REQUIRE(d->refac, LS_E_STATE, "ls_direct_refactor: %s", d->shard_count > 1 ? "a sharded handle cannot refactor"
+                                                                                  : "the handle was not made by ls_direct_factor_refactorable");
+    DeviceGuard g(d->device);
+    LS_HIP(g.err);
+    hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (st) (void)hipStreamIsCapturing(st, &cap);
+    LS_REQUIRE(cap == hipStreamCaptureStatusNone, LS_E_STATE, "ls_direct_refactor: not capturable (it synchronises the stream)");
+    if (d->used && st != d->last_stream) LS_HIP(hipStreamWaitEvent(st, d->busy, 0));      // solves in flight on another stream read the factor
+    bool touched = false;
+    const int rc = ls::refactor_run(d->refac, d_rowptr, d_col, d_val, V, nnz, st, &touched);
+    if (rc == LS_OK) d->factored = true;
+    else if (touched) d->factored = false;
+    return rc;
+}
+
+extern "C" int ls_direct_refactorable(const ls_direct* d, int* h_yes, size_t* h_retained_device_bytes) {
+    LS_REQUIRE(d, LS_E_INVALID, "ls_direct_refactorable: bad argument");
+    if (h_yes) *h_yes = d->refac ? 1 : 0;
+    if (h_retained_device_bytes) *h_retained_device_bytes = ls::refactor_state_bytes(d->refac);
     return LS_OK;
 }
 

@@ -394,11 +394,93 @@ __global__ void k_convert(const int* __restrict__ ids, const FactorNode* __restr
     }
 }
 
+// ---- same-pattern refactorisation (ls_direct_refactor) -----------------------------------------------------------------------------
+// Does the caller's pattern differ from the analysed one? Every writer of the flag writes the same 1 (no read-modify-write).
+__global__ void k_pattern_differs(int64_t V, int64_t nnz, const int* __restrict__ rowptr_a, const int* __restrict__ col_a,
+                                  const int* __restrict__ rowptr_b, const int* __restrict__ col_b, int* __restrict__ flag) {
+    const int64_t n = std::max(V + 1, nnz);
+    bool diff = false;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        if (i <= V && rowptr_a[i] != rowptr_b[i]) diff = true;
+        if (i < nnz && col_a[i] != col_b[i]) diff = true;
+    }
+    if (diff) *flag = 1;
+}
+
+// where a sparse leaf's off-diagonal entry ended up in the two lists AFTER k_leaf_sort: the boundary-row slot and the own-row slot of
+// every stored entry e (-1: not an entry of a sparse leaf's A_bs). The index field is unique within a row, so a binary search finds it.
+struct LeafSlot { int b, s; };
+__global__ void k_leaf_slots(int64_t nnz, const int* __restrict__ rowidx, const int* __restrict__ col, const int* __restrict__ inv,
+                             const int* __restrict__ node_of_new, const FactorNode* __restrict__ nodes, const int* __restrict__ bnd, long long bnd0,
+                             const int* __restrict__ ptr_s, const int* __restrict__ ptr_b, const SpEnt* __restrict__ ent, int n_ent,
+                             LeafSlot* __restrict__ slots) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= nnz) return;
+    LeafSlot out{-1, -1};
+    const int r = inv[rowidx[e]];
+    const FactorNode nd = nodes[node_of_new[r]];
+    const int c = inv[col[e]];
+    if (nd.layout == 2 && c >= nd.own_start + nd.s) {
+        const int* B = bnd + nd.bnd_off;
+        int lo = 0, hi = nd.b;
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (B[mid] < c) lo = mid + 1; else hi = mid; }
+        if (lo < nd.b && B[lo] == c) {
+            auto find = [&](int first, int last, int key) {
+                while (first < last) { const int mid = (first + last) >> 1; if (ent[mid].idx < key) first = mid + 1; else last = mid; }
+                return first;
+            };
+            const long long rb = nd.bnd_off - bnd0 + lo;
+            const int pb = find(ptr_b[rb], ptr_b[rb + 1], r - nd.own_start), ps = find(n_ent + ptr_s[r], n_ent + ptr_s[r + 1], lo);
+            if (pb < ptr_b[rb + 1] && ent[pb].idx == r - nd.own_start && ps < n_ent + ptr_s[r + 1] && ent[ps].idx == lo) out = LeafSlot{pb, ps};
+        }
+    }
+    slots[e] = out;
+}
+
+// the new values of the sparse leaves' off-diagonal blocks, written into both lists (one writer per slot: the pattern has no duplicates)
+__global__ void k_leaf_values(int64_t nnz, const LeafSlot* __restrict__ slots, const float* __restrict__ val, SpEnt* __restrict__ ent) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= nnz) return;
+    const LeafSlot sl = slots[e];
+    if (sl.b < 0) return;
+    const float v = val[e];
+    ent[sl.b].val = v;
+    ent[sl.s].val = v;
+}
+
+// The recorded descriptors of a refactorable handle hold OFFSETS (in doubles) into the concatenation [fronts | xs | ws | work] of the
+// scratch, not pointers; this turns them into pointers into the scratch a refactorisation took from the pool.
+struct Arena { double* base[4]; long long end[4]; };              // end[k]: where region k ends in the concatenation
+__device__ inline double* arena_ptr(const Arena& a, const void* off) {
+    const long long o = (long long)(uintptr_t)off;
+    long long start = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (o < a.end[k]) return a.base[k] + (o - start);
+        start = a.end[k];
+    }
+    return a.base[0];                                             // (not reached: the host maps every operand into the concatenation)
+}
+__global__ void k_rebase(int n_gemm, const GemmDesc* __restrict__ gsrc, GemmDesc* __restrict__ gdst, int n_inv, const InvDesc* __restrict__ isrc,
+                         InvDesc* __restrict__ idst, Arena a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_gemm) {
+        GemmDesc d = gsrc[i];
+        d.A = arena_ptr(a, d.A); d.B = arena_ptr(a, d.B); d.C = arena_ptr(a, d.C);
+        gdst[i] = d;
+    } else if (i < n_gemm + n_inv) {
+        InvDesc d = isrc[i - n_gemm];
+        d.M = arena_ptr(a, d.M); d.X = arena_ptr(a, d.X);
+        idst[i - n_gemm] = d;
+    }
+}
+
 }  // namespace ls
 
 using namespace ls;
 
 // ---- host driver -------------------------------------------------------------------------------------------------------------------
+namespace ls { hipStream_t side_stream(int device, int which); }
 namespace {
 
 struct Blk { double* M; double* X; double* ws; int n, ldm, ldx; };
@@ -486,12 +568,191 @@ void inverse_rec(FactorCtx& c, const std::vector<Blk>& v, int depth) {
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
+// The numeric factorisation from the values -- ONE path for ls_direct_factor and ls_direct_refactor: the fronts zeroed and assembled,
+// the recorded chain (descriptors already on the device as pointers into this scratch), the fp32 conversion of every finished level on
+// the side stream. Everything is only enqueued; `flag` tells afterwards whether a front was not positive definite (1) or the pattern
+// not symmetric (2). `evs` are the events of the side stream's ordering: the caller destroys them once the stream is synchronised.
+struct NumericRun {
+    int64_t nnz;
+    const int *rowidx, *col;
+    const float* val;
+    const int *inv, *non, *bnd, *ppos, *ids;
+    const FactorNode* nodes;
+    const GemmDesc* gemm;
+    const InvDesc* invd;
+    const std::vector<Cmd>* cmds;
+    double *fronts, *xs, *ws;
+    int64_t f_tot;
+    float *finv, *wf, *wb, *u4, *d4, *tri;
+    int* flag;
+};
+
+hipError_t numeric_run(const NumericRun& a, int device, hipStream_t st, std::vector<hipEvent_t>& evs, int* launches) {
+    hipError_t e = hipMemsetAsync(a.fronts, 0, sizeof(double) * (size_t)std::max<int64_t>(a.f_tot, 1), st);
+    if (e == hipSuccess) e = hipMemsetAsync(a.flag, 0, sizeof(int), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_assemble, dim3((unsigned)div_up(a.nnz, 256)), dim3(256), 0, st, a.nnz, a.rowidx, a.col, a.val, a.inv, a.non, a.nodes, a.bnd,
+                       a.fronts, a.flag);
+    // The fp32 conversion of a finished level runs on the side stream, beside the next level's chain of small launches (the upper levels
+    // are inverses of one workgroup and products of a few tiles: the chip is nearly empty there, and the conversions were 1.0 of the
+    // 10.6 ms of kernels of a 1M-vertex factorisation). Events order it: after its level's products, before the stream's end.
+    hipStream_t sc = side_stream(device, 1);
+#ifdef LS_ND_EXPERIMENTS
+    exp_round_configure();
+#endif
+    const size_t ev0 = evs.size();
+    for (const Cmd& c : *a.cmds) {
+        if (e != hipSuccess) break;
+        hipStream_t sk = st;
+        if (c.kind == 3 && sc) {
+            hipEvent_t ev = nullptr;
+            if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess) {
+                evs.push_back(ev);
+                if (hipEventRecord(ev, st) == hipSuccess && hipStreamWaitEvent(sc, ev, 0) == hipSuccess) sk = sc;
+            }
+        }
+        for (int b0 = 0; b0 < c.n; b0 += 65535) {
+            const int nb = std::min(65535, c.n - b0);
+            switch (c.kind) {
+            case 0:
+                if (c.nmax == 32) hipLaunchKernelGGL(k_gemm_batched<32>, dim3(c.gx, nb), dim3(256), 0, st, (const GemmDesc*)(a.gemm + c.off + b0));
+                else hipLaunchKernelGGL(k_gemm_batched<64>, dim3(c.gx, nb), dim3(256), 0, st, (const GemmDesc*)(a.gemm + c.off + b0));
+                break;
+            case 1:
+                if (c.nmax <= 64) hipLaunchKernelGGL((k_spd_inverse_reg<64, 16>), dim3(nb), dim3(256), 0, st, (const InvDesc*)(a.invd + c.off + b0), a.flag);
+                else if (nb <= 64) hipLaunchKernelGGL((k_spd_inverse_reg<128, 32>), dim3(nb), dim3(1024), 0, st, (const InvDesc*)(a.invd + c.off + b0), a.flag);
+                else hipLaunchKernelGGL((k_spd_inverse_reg<128, 16>), dim3(nb), dim3(256), 0, st, (const InvDesc*)(a.invd + c.off + b0), a.flag);   // a block per CU and more: 256 blocks 132 us, with 1024 threads 197
+                break;
+            case 2: hipLaunchKernelGGL(k_extend_add, dim3(c.gx, nb), dim3(256), 0, st, (const int*)(a.ids + c.off + b0), nb, a.nodes, a.ppos, a.fronts); break;
+            default:
+                hipLaunchKernelGGL(k_convert, dim3(c.gx, nb), dim3(256), 0, sk, (const int*)(a.ids + c.off + b0), a.nodes, a.xs, a.ws, a.finv, a.wf, a.wb,
+                                   a.u4, a.d4, a.tri);
+            }
+        }
+        if (launches) ++*launches;
+    }
+    if (sc && evs.size() > ev0) {                              // join: the caller's stream continues after the last conversion
+        hipEvent_t ev = nullptr;
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        if (ev) evs.push_back(ev);
+        if (e == hipSuccess) e = hipEventRecord(ev, sc);
+        if (e == hipSuccess) e = hipStreamWaitEvent(st, ev, 0);
+    }
+    return e == hipSuccess ? hipGetLastError() : e;
+}
+
 }  // namespace
+
+namespace ls {
+// What a refactorable handle keeps beyond the solve's tables (ls_direct_factor_refactorable): device copies of the analysed pattern and of
+// the numeric chain's inputs, the chain's descriptors as OFFSETS into the scratch, and where the sparse leaves' values live. The fp64
+// scratch (fronts, xs, ws, work) is not kept: ls_direct_refactor takes it from the pool again.
+struct RefactorState {
+    int device = 0;
+    int64_t V = 0, nnz = 0, f_tot = 0, x_tot = 0, w_tot = 0, work_tot = 0;
+    int32_t *rowptr = nullptr, *col = nullptr;
+    int *inv = nullptr, *non = nullptr, *bnd = nullptr, *ppos = nullptr, *ids = nullptr;
+    FactorNode* nodes = nullptr;
+    GemmDesc* gemm = nullptr;                    // A / B / C: offsets in doubles into [fronts | xs | ws | work]
+    InvDesc* invd = nullptr;                     // M / X: the same
+    LeafSlot* slots = nullptr;                   // nnz entries, nullptr without sparse leaves
+    std::vector<Cmd> cmds;
+    size_t n_gemm = 0, n_inv = 0;
+    float *finv = nullptr, *wf = nullptr, *wb = nullptr, *u4 = nullptr, *d4 = nullptr, *tri = nullptr;   // the handle's factor arrays
+    SpEnt* sp_ent = nullptr;
+    std::vector<std::pair<void*, size_t>> bufs;  // the device buffers above (back to the pool with the handle)
+};
+
+void refactor_state_free(RefactorState* R) {
+    if (!R) return;
+    for (const auto& b : R->bufs) if (!pool_give(R->device, b.first, b.second)) (void)hipFree(b.first);
+    delete R;
+}
+
+size_t refactor_state_bytes(const RefactorState* R) {
+    size_t n = 0;
+    if (R) for (const auto& b : R->bufs) n += b.second;
+    return n;
+}
+
+// ls_direct_refactor's work (the caller, direct.hip, has checked the handle and ordered `st` after its solves). *touched: the factor
+// arrays may have been written (a failure after that leaves the handle unfactored).
+int refactor_run(RefactorState* R, const int32_t* d_rowptr, const int32_t* d_col, const float* d_val, int64_t V, int64_t nnz, hipStream_t st,
+                 bool* touched) {
+    *touched = false;
+    LS_REQUIRE(V == R->V && nnz == R->nnz, LS_E_INVALID, "ls_direct_refactor: the pattern differs from the analysed one (V = %lld, nnz = %lld; the handle's: %lld, %lld; the factor is unchanged)",
+               (long long)V, (long long)nnz, (long long)R->V, (long long)R->nnz);
+    const int device = R->device;
+    std::vector<std::pair<void*, size_t>> scratch;
+    hipError_t e = hipSuccess;
+    auto take = [&](void** p, size_t bytes) -> bool {
+        const size_t want = std::max<size_t>(bytes, 16) + 16;
+        size_t cap = want;
+        *p = pool_take(device, want, &cap);
+        if (!*p && (e = pool_alloc(device, p, want)) != hipSuccess) { *p = nullptr; return false; }
+        scratch.emplace_back(*p, cap);
+        return true;
+    };
+    auto give_back = [&] {
+        (void)hipStreamSynchronize(st);
+        for (const auto& s : scratch) if (!pool_give(device, s.first, s.second)) (void)hipFree(s.first);
+        scratch.clear();
+    };
+    int *flag = nullptr, *rowidx = nullptr;
+    if (!take((void**)&flag, sizeof(int)) || !take((void**)&rowidx, sizeof(int) * (size_t)nnz)) { give_back(); return hip_fail(e, "ls_direct_refactor allocation", __FILE__, __LINE__); }
+    // 1. the caller's pattern against the analysed one, on the device; one flag comes back
+    int h_flag = 0;
+    e = hipMemsetAsync(flag, 0, sizeof(int), st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_pattern_differs, dim3((unsigned)std::min(div_up(std::max(V + 1, nnz), 256), 2048)), dim3(256), 0, st, V, nnz,
+                           (const int*)R->rowptr, (const int*)R->col, (const int*)d_rowptr, (const int*)d_col, flag);
+        e = hipMemcpyAsync(&h_flag, flag, sizeof(int), hipMemcpyDeviceToHost, st);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) { give_back(); return hip_fail(e, "ls_direct_refactor pattern check", __FILE__, __LINE__); }
+    if (h_flag) { give_back(); set_error("ls_direct_refactor: the pattern differs from the analysed one (the factor is unchanged)"); return LS_E_INVALID; }
+    // 2. scratch from the pool, the chain's descriptors pointed into it
+    double *fronts = nullptr, *xs = nullptr, *ws = nullptr, *work = nullptr;
+    GemmDesc* gemm = nullptr;
+    InvDesc* invd = nullptr;
+    if (!take((void**)&fronts, sizeof(double) * R->f_tot) || !take((void**)&xs, sizeof(double) * R->x_tot) || !take((void**)&ws, sizeof(double) * R->w_tot) ||
+        !take((void**)&work, sizeof(double) * R->work_tot) || !take((void**)&gemm, sizeof(GemmDesc) * R->n_gemm) || !take((void**)&invd, sizeof(InvDesc) * R->n_inv)) {
+        give_back();
+        return hip_fail(e, "ls_direct_refactor allocation", __FILE__, __LINE__);
+    }
+    Arena arena{{fronts, xs, ws, work}, {R->f_tot, R->f_tot + R->x_tot, R->f_tot + R->x_tot + R->w_tot, R->f_tot + R->x_tot + R->w_tot + R->work_tot}};
+    *touched = true;
+    // 3. the values: the RETAINED pattern steers every write, the caller's arrays only supply values
+    hipLaunchKernelGGL(k_expand_rows, dim3((unsigned)div_up(V, 256)), dim3(256), 0, st, V, (const int*)R->rowptr, rowidx);
+    if (R->slots) hipLaunchKernelGGL(k_leaf_values, dim3((unsigned)div_up(nnz, 256)), dim3(256), 0, st, nnz, (const LeafSlot*)R->slots, d_val, R->sp_ent);
+    if (R->n_gemm + R->n_inv)
+        hipLaunchKernelGGL(k_rebase, dim3((unsigned)div_up((int64_t)(R->n_gemm + R->n_inv), 256)), dim3(256), 0, st, (int)R->n_gemm, (const GemmDesc*)R->gemm, gemm,
+                           (int)R->n_inv, (const InvDesc*)R->invd, invd, arena);
+    // 4. the same numeric chain as the constructor's, into the handle's factor arrays in place
+    std::vector<hipEvent_t> evs;
+    const NumericRun run{nnz, rowidx, R->col, d_val, R->inv, R->non, R->bnd, R->ppos, R->ids, R->nodes, gemm, invd, &R->cmds,
+                         fronts, xs, ws, R->f_tot, R->finv, R->wf, R->wb, R->u4, R->d4, R->tri, flag};
+    e = hipGetLastError();
+    if (e == hipSuccess) e = numeric_run(run, device, st, evs, nullptr);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h_flag, flag, sizeof(int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    give_back();
+    for (hipEvent_t ev : evs) (void)hipEventDestroy(ev);
+    if (e != hipSuccess) return hip_fail(e, "ls_direct_refactor kernels", __FILE__, __LINE__);
+    if (h_flag) {
+        set_error("ls_direct_refactor: a front is not positive definite (the handle is unfactored until a refactorisation succeeds)");
+        return LS_E_INVALID;
+    }
+    return LS_OK;
+}
+}  // namespace ls
 
 // defined in direct.hip: builds the handle from plan + factor arrays and takes ownership of the device arrays
 extern "C" int ls_direct_create(const ls_direct_arrays* A, int device, void* stream, ls_direct** out);
 int ls_direct_adopt(ls_direct* d, void* const* owned, const size_t* owned_bytes, int n_owned, const double* seconds3, const double* quality4);
-namespace ls { hipStream_t side_stream(int device, int which); extern std::atomic<long long> g_malloc_calls, g_malloc_us, g_malloc_bytes; }
+int ls_direct_adopt_refactor(ls_direct* d, ls::RefactorState* state);
+namespace ls { extern std::atomic<long long> g_malloc_calls, g_malloc_us, g_malloc_bytes; }
 bool direct_tier_fits(int levels, int arity, const int* s, const int* b, const int* own_start, int tier_levels, bool sparse_leaves, int waves);
 bool direct_tier_full16(int64_t V, int arity, int levels, int tier_levels, int shard_count, int tier_waves);
 
@@ -534,7 +795,8 @@ extern "C" int ls_direct_pick_tree(int64_t V, int* leaf_size_io, int* arity_io) 
 
 static int direct_factor_impl(const int32_t* d_rowptr, const int32_t* d_col, const float* d_val, int64_t V, int64_t nnz,
                               const float* d_positions, int leaf_size, int arity, int tier_levels, int sparse_leaves, int shard_rank,
-                              int shard_count, int ordering_arg, int tier_waves, int device, void* stream, ls_direct** out);
+                              int shard_count, int ordering_arg, int tier_waves, int device, void* stream, ls_direct** out,
+                              bool refactorable = false);
 
 extern "C" int ls_direct_factor(const int32_t* d_rowptr, const int32_t* d_col, const float* d_val, int64_t V, int64_t nnz,
                                 const float* d_positions, int leaf_size, int arity, int tier_levels, int sparse_leaves, int shard_rank,
@@ -544,8 +806,8 @@ extern "C" int ls_direct_factor(const int32_t* d_rowptr, const int32_t* d_col, c
 }
 
 // the same constructor with every choice as an ARGUMENT (round 6: `ordering` used to travel through the process environment)
-extern "C" int ls_direct_factor_ex(const int32_t* d_rowptr, const int32_t* d_col, const float* d_val, int64_t V, int64_t nnz,
-                                   const float* d_positions, const ls_direct_options* opt, int device, void* stream, ls_direct** out) {
+static int direct_factor_opt(const int32_t* d_rowptr, const int32_t* d_col, const float* d_val, int64_t V, int64_t nnz, const float* d_positions,
+                             const ls_direct_options* opt, int device, void* stream, ls_direct** out, bool refactorable) {
     ls_direct_options o;
     ls_direct_options_default(&o);
     if (opt) {
@@ -556,7 +818,18 @@ extern "C" int ls_direct_factor_ex(const int32_t* d_rowptr, const int32_t* d_col
     LS_REQUIRE(o.ordering >= LS_ND_ORDER_AUTO && o.ordering <= LS_ND_ORDER_MINSEP, LS_E_INVALID, "ls_direct_factor_ex: ordering must be LS_ND_ORDER_AUTO / _LONGEST / _MINSEP");
     LS_REQUIRE(o.tier_waves == 0 || o.tier_waves == 4 || o.tier_waves == 8 || o.tier_waves == 16, LS_E_INVALID, "ls_direct_factor_ex: tier_waves must be 0 (library's rule), 4, 8 or 16");
     return direct_factor_impl(d_rowptr, d_col, d_val, V, nnz, d_positions, o.leaf_size, o.arity, o.tier_levels, o.sparse_leaves, o.shard_rank,
-                              o.shard_count, o.ordering, o.tier_waves, device, stream, out);
+                              o.shard_count, o.ordering, o.tier_waves, device, stream, out, refactorable);
+}
+
+extern "C" int ls_direct_factor_ex(const int32_t* d_rowptr, const int32_t* d_col, const float* d_val, int64_t V, int64_t nnz,
+                                   const float* d_positions, const ls_direct_options* opt, int device, void* stream, ls_direct** out) {
+    return direct_factor_opt(d_rowptr, d_col, d_val, V, nnz, d_positions, opt, device, stream, out, false);
+}
+
+// ls_direct_factor_ex whose handle also keeps what ls_direct_refactor needs (same plan, same factor, bit-identical solves)
+extern "C" int ls_direct_factor_refactorable(const int32_t* d_rowptr, const int32_t* d_col, const float* d_val, int64_t V, int64_t nnz,
+                                             const float* d_positions, const ls_direct_options* opt, int device, void* stream, ls_direct** out) {
+    return direct_factor_opt(d_rowptr, d_col, d_val, V, nnz, d_positions, opt, device, stream, out, true);
 }
 
 extern "C" int ls_direct_options_default(ls_direct_options* o) {
@@ -570,7 +843,8 @@ extern "C" int ls_direct_options_default(ls_direct_options* o) {
 
 static int direct_factor_impl(const int32_t* d_rowptr, const int32_t* d_col, const float* d_val, int64_t V, int64_t nnz,
                               const float* d_positions, int leaf_size, int arity, int tier_levels, int sparse_leaves, int shard_rank,
-                              int shard_count, int ordering_arg, int tier_waves, int device, void* stream, ls_direct** out) {
+                              int shard_count, int ordering_arg, int tier_waves, int device, void* stream, ls_direct** out,
+                              bool refactorable) {
     LS_REQUIRE(out && d_rowptr && d_col && d_val && V > 0 && nnz > 0 && nnz < INT32_MAX, LS_E_INVALID, "ls_direct_factor: bad argument");
     *out = nullptr;
     { const int rc_pick = ls_direct_pick_tree(V, &leaf_size, &arity); if (rc_pick) return rc_pick; }      // leaf_size / arity <= 0: picked from V
@@ -688,10 +962,13 @@ static int direct_factor_impl(const int32_t* d_rowptr, const int32_t* d_col, con
     }
     const double t2 = now_s();
     // ---- device storage ---------------------------------------------------------------------------------------------------------------
-    std::vector<void*> owned, scratch;
-    std::vector<size_t> owned_bytes, scratch_bytes;
+    // keep: 0 scratch (back to the pool at the end), 1 the handle's (factor arrays), 2 the refactor state's when the handle is refactorable
+    // (sharded handles are not: ls_direct_refactor reports LS_E_STATE for them), scratch otherwise
+    const bool retain = refactorable && shard_count <= 1;
+    std::vector<void*> owned, scratch, kept;
+    std::vector<size_t> owned_bytes, scratch_bytes, kept_bytes;
     int rc = LS_OK;
-    auto dalloc = [&](void** p, size_t bytes, bool keep, bool zero) -> bool {
+    auto dalloc = [&](void** p, size_t bytes, int keep, bool zero) -> bool {
         const double ta = timing ? now_s() : 0.0;
         const size_t want = std::max<size_t>(bytes, 16) + 16;
         hipError_t e = hipSuccess;
@@ -707,8 +984,8 @@ static int direct_factor_impl(const int32_t* d_rowptr, const int32_t* d_col, con
                     (now_s() - tb) * 1e3);
         }
         if (e != hipSuccess) { rc = hip_fail(e, "ls_direct_factor allocation", __FILE__, __LINE__); *p = nullptr; return false; }
-        (keep ? owned : scratch).push_back(*p);
-        (keep ? owned_bytes : scratch_bytes).push_back(cap);
+        (keep == 1 ? owned : keep == 2 && retain ? kept : scratch).push_back(*p);
+        (keep == 1 ? owned_bytes : keep == 2 && retain ? kept_bytes : scratch_bytes).push_back(cap);
         return true;
     };
     float *finv = nullptr, *wf = nullptr, *wb = nullptr, *u4 = nullptr, *d4 = nullptr, *tri = nullptr;
@@ -718,19 +995,22 @@ static int direct_factor_impl(const int32_t* d_rowptr, const int32_t* d_col, con
     FactorNode* d_nodes = nullptr;
     FactorCtx ctx;
     int* d_flag = nullptr;
-    GemmDesc* d_gemm = nullptr; InvDesc* d_invd = nullptr;
+    GemmDesc *d_gemm = nullptr, *d_gemm_off = nullptr; InvDesc *d_invd = nullptr, *d_invd_off = nullptr;
+    int32_t *d_rowptr_kept = nullptr, *d_col_kept = nullptr;
+    LeafSlot* d_slots = nullptr;
     int64_t work_tot = 0;
     for (int i = 1; i <= n_nodes; ++i) work_tot += ((int64_t)P.s[i] * P.s[i] + 1) / 2 + 64;
     bool ok = dalloc((void**)&finv, sizeof(float) * o_finv, true, false) && dalloc((void**)&wf, sizeof(float) * o_w, true, false) &&
               dalloc((void**)&wb, sizeof(float) * o_w, true, false) && dalloc((void**)&u4, sizeof(float) * o_u4, true, true) &&
               dalloc((void**)&d4, sizeof(float) * o_d4, true, true) && dalloc((void**)&tri, sizeof(float) * o_tri, true, true) &&
               dalloc((void**)&d_sp_ptr, sizeof(int32_t) * n_sp_ptr, true, false) &&
-              dalloc((void**)&fronts, sizeof(double) * f_tot, false, true) && dalloc((void**)&xs, sizeof(double) * x_tot, false, false) &&
+              dalloc((void**)&fronts, sizeof(double) * f_tot, false, false) && dalloc((void**)&xs, sizeof(double) * x_tot, false, false) &&
               dalloc((void**)&ws, sizeof(double) * w_tot, false, false) && dalloc((void**)&work, sizeof(double) * work_tot, false, false) &&
-              dalloc((void**)&d_inv, sizeof(int) * V, false, false) && dalloc((void**)&d_non, sizeof(int) * V, false, false) &&
-              dalloc((void**)&d_bnd, sizeof(int) * P.n_bnd, false, false) && dalloc((void**)&d_ppos, sizeof(int) * P.n_bnd, false, false) &&
+              dalloc((void**)&d_inv, sizeof(int) * V, 2, false) && dalloc((void**)&d_non, sizeof(int) * V, 2, false) &&
+              dalloc((void**)&d_bnd, sizeof(int) * P.n_bnd, 2, false) && dalloc((void**)&d_ppos, sizeof(int) * P.n_bnd, 2, false) &&
               dalloc((void**)&d_rowidx, sizeof(int) * nnz, false, false) &&
-              dalloc((void**)&d_nodes, sizeof(FactorNode) * (n_nodes + 1), false, false) && dalloc((void**)&d_flag, sizeof(int), false, true);
+              dalloc((void**)&d_nodes, sizeof(FactorNode) * (n_nodes + 1), 2, false) && dalloc((void**)&d_flag, sizeof(int), false, true) &&
+              (!retain || (dalloc((void**)&d_rowptr_kept, sizeof(int32_t) * (V + 1), 2, false) && dalloc((void**)&d_col_kept, sizeof(int32_t) * nnz, 2, false)));
     auto cleanup = [&](bool all) {
         (void)hipStreamSynchronize(st);
         for (size_t i = 0; i < scratch.size(); ++i) if (!pool_give(device, scratch[i], scratch_bytes[i])) (void)hipFree(scratch[i]);
@@ -738,6 +1018,8 @@ static int direct_factor_impl(const int32_t* d_rowptr, const int32_t* d_col, con
         if (all) {
             for (size_t i = 0; i < owned.size(); ++i) if (!pool_give(device, owned[i], owned_bytes[i])) (void)hipFree(owned[i]);
             owned.clear(); owned_bytes.clear();
+            for (size_t i = 0; i < kept.size(); ++i) if (!pool_give(device, kept[i], kept_bytes[i])) (void)hipFree(kept[i]);
+            kept.clear(); kept_bytes.clear();
         }
     };
     if (!ok) { cleanup(true); return rc; }
@@ -747,6 +1029,8 @@ static int direct_factor_impl(const int32_t* d_rowptr, const int32_t* d_col, con
     h2d(d_inv, P.inv.data(), sizeof(int) * V); h2d(d_non, P.node_of_new.data(), sizeof(int) * V);
     h2d(d_bnd, P.bnd.data(), sizeof(int) * P.n_bnd); h2d(d_ppos, P.ppos.data(), sizeof(int) * P.n_bnd);
     h2d(d_nodes, fn.data(), sizeof(FactorNode) * (n_nodes + 1));
+    if (retain && e == hipSuccess) e = hipMemcpyAsync(d_rowptr_kept, d_rowptr, sizeof(int32_t) * (V + 1), hipMemcpyDeviceToDevice, st);
+    if (retain && e == hipSuccess) e = hipMemcpyAsync(d_col_kept, d_col, sizeof(int32_t) * nnz, hipMemcpyDeviceToDevice, st);
     if (e != hipSuccess) { cleanup(true); return hip_fail(e, "ls_direct_factor uploads", __FILE__, __LINE__); }
     hipLaunchKernelGGL(k_expand_rows, dim3((unsigned)div_up(V, 256)), dim3(256), 0, st, V, d_rowptr, d_rowidx);
     int64_t n_ent = 0;
@@ -780,6 +1064,11 @@ static int direct_factor_impl(const int32_t* d_rowptr, const int32_t* d_col, con
         if (rows_s) hipLaunchKernelGGL(k_leaf_sort, dim3((unsigned)div_up(rows_s, 256)), dim3(256), 0, st, rows_s, (const int*)ptr_s, (int)n_ent, d_sp_ent);
         hipLaunchKernelGGL(k_leaf_ptrs, dim3((unsigned)(leaf1 - leaf0)), dim3(64), 0, st, (int)leaf0, d_nodes, (long long)bnd0, (const int*)d_off_b,
                            (const int*)d_off_s, (const int*)ptr_b, (const int*)ptr_s, (int)n_ent, d_sp_ptr);
+        if (retain) {                                           // where every value went, taken after the sort (ls_direct_refactor rewrites them there)
+            if (!dalloc((void**)&d_slots, sizeof(LeafSlot) * nnz, 2, false)) { cleanup(true); return rc; }
+            hipLaunchKernelGGL(k_leaf_slots, dim3(eg), dim3(256), 0, st, nnz, d_rowidx, d_col, d_inv, d_non, d_nodes, d_bnd, (long long)bnd0,
+                               (const int*)ptr_s, (const int*)ptr_b, (const SpEnt*)d_sp_ent, (int)n_ent, d_slots);
+        }
     } else if (!dalloc((void**)&d_sp_ent, 16, true, true)) { cleanup(true); return rc; }
     if (e != hipSuccess) { cleanup(true); return hip_fail(e, "ls_direct_factor uploads", __FILE__, __LINE__); }
     lap("uploads");
@@ -828,57 +1117,40 @@ static int direct_factor_impl(const int32_t* d_rowptr, const int32_t* d_col, con
         id_launch(ctx, 3, ids, std::min(256, div_up(emax, 256)));
     }
     ok = dalloc((void**)&d_gemm, sizeof(GemmDesc) * ctx.gemm.size(), false, false) && dalloc((void**)&d_invd, sizeof(InvDesc) * ctx.inv.size(), false, false) &&
-         dalloc((void**)&d_ids, sizeof(int) * ctx.ids.size(), false, false);
+         dalloc((void**)&d_ids, sizeof(int) * ctx.ids.size(), 2, false) &&
+         (!retain || (dalloc((void**)&d_gemm_off, sizeof(GemmDesc) * ctx.gemm.size(), 2, false) && dalloc((void**)&d_invd_off, sizeof(InvDesc) * ctx.inv.size(), 2, false)));
     if (!ok) { cleanup(true); return rc; }
     h2d(d_gemm, ctx.gemm.data(), sizeof(GemmDesc) * ctx.gemm.size());
     h2d(d_invd, ctx.inv.data(), sizeof(InvDesc) * ctx.inv.size());
     h2d(d_ids, ctx.ids.data(), sizeof(int) * ctx.ids.size());
-    if (e == hipSuccess)
-        hipLaunchKernelGGL(k_assemble, dim3((unsigned)div_up(nnz, 256)), dim3(256), 0, st, nnz, d_rowidx, d_col, d_val, d_inv, d_non, d_nodes, d_bnd,
-                           fronts, d_flag);
-    // The fp32 conversion of a finished level runs on the side stream, beside the next level's chain of small launches (the upper levels
-    // are inverses of one workgroup and products of a few tiles: the chip is nearly empty there, and the conversions were 1.0 of the
-    // 10.6 ms of kernels of a 1M-vertex factorisation). Events order it: after its level's products, before the stream's end.
-    hipStream_t sc = side_stream(device, 1);
-    std::vector<hipEvent_t> evs;
-#ifdef LS_ND_EXPERIMENTS
-    exp_round_configure();
-#endif
-    for (const Cmd& c : ctx.cmds) {
-        if (e != hipSuccess) break;
-        hipStream_t sk = st;
-        if (c.kind == 3 && sc) {
-            hipEvent_t ev = nullptr;
-            if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess) {
-                evs.push_back(ev);
-                if (hipEventRecord(ev, st) == hipSuccess && hipStreamWaitEvent(sc, ev, 0) == hipSuccess) sk = sc;
+    std::vector<GemmDesc> gemm_off;
+    std::vector<InvDesc> inv_off;
+    if (retain) {
+        // the descriptors as offsets (in doubles) into [fronts | xs | ws | work]: k_rebase points them into a refactorisation's scratch.
+        // An operand no region holds belongs to an empty product (K = 0, never read): offset 0.
+        const uintptr_t base[4] = {(uintptr_t)fronts, (uintptr_t)xs, (uintptr_t)ws, (uintptr_t)work};
+        const int64_t len[4] = {f_tot, x_tot, w_tot, work_tot};
+        auto off = [&](const double* p) -> double* {
+            const uintptr_t q = (uintptr_t)p;
+            int64_t start = 0;
+            for (int k = 0; k < 4; ++k) {
+                if (q >= base[k] && q < base[k] + sizeof(double) * (size_t)len[k]) return (double*)(uintptr_t)(start + (int64_t)((q - base[k]) / sizeof(double)));
+                start += len[k];
             }
-        }
-        for (int b0 = 0; b0 < c.n; b0 += 65535) {
-            const int nb = std::min(65535, c.n - b0);
-            switch (c.kind) {
-            case 0:
-                if (c.nmax == 32) hipLaunchKernelGGL(k_gemm_batched<32>, dim3(c.gx, nb), dim3(256), 0, st, (const GemmDesc*)(d_gemm + c.off + b0));
-                else hipLaunchKernelGGL(k_gemm_batched<64>, dim3(c.gx, nb), dim3(256), 0, st, (const GemmDesc*)(d_gemm + c.off + b0));
-                break;
-            case 1:
-                if (c.nmax <= 64) hipLaunchKernelGGL((k_spd_inverse_reg<64, 16>), dim3(nb), dim3(256), 0, st, (const InvDesc*)(d_invd + c.off + b0), d_flag);
-                else if (nb <= 64) hipLaunchKernelGGL((k_spd_inverse_reg<128, 32>), dim3(nb), dim3(1024), 0, st, (const InvDesc*)(d_invd + c.off + b0), d_flag);
-                else hipLaunchKernelGGL((k_spd_inverse_reg<128, 16>), dim3(nb), dim3(256), 0, st, (const InvDesc*)(d_invd + c.off + b0), d_flag);   // a block per CU and more: 256 blocks 132 us, with 1024 threads 197
-                break;
-            case 2: hipLaunchKernelGGL(k_extend_add, dim3(c.gx, nb), dim3(256), 0, st, (const int*)(d_ids + c.off + b0), nb, d_nodes, d_ppos, fronts); break;
-            default:
-                hipLaunchKernelGGL(k_convert, dim3(c.gx, nb), dim3(256), 0, sk, (const int*)(d_ids + c.off + b0), d_nodes, xs, ws, finv, wf, wb, u4, d4, tri);
-            }
-        }
-        ++ctx.launches;
+            return nullptr;
+        };
+        gemm_off = ctx.gemm;
+        for (GemmDesc& g : gemm_off) { g.A = off(g.A); g.B = off(g.B); g.C = off(g.C); }
+        inv_off = ctx.inv;
+        for (InvDesc& v : inv_off) { v.M = off(v.M); v.X = off(v.X); }
+        h2d(d_gemm_off, gemm_off.data(), sizeof(GemmDesc) * gemm_off.size());
+        h2d(d_invd_off, inv_off.data(), sizeof(InvDesc) * inv_off.size());
     }
-    if (sc && !evs.empty()) {                                  // join: the caller's stream continues after the last conversion
-        hipEvent_t ev = nullptr;
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-        if (ev) evs.push_back(ev);
-        if (e == hipSuccess) e = hipEventRecord(ev, sc);
-        if (e == hipSuccess) e = hipStreamWaitEvent(st, ev, 0);
+    std::vector<hipEvent_t> evs;
+    if (e == hipSuccess) {
+        const NumericRun run{nnz, d_rowidx, d_col, d_val, d_inv, d_non, d_bnd, d_ppos, d_ids, d_nodes, d_gemm, d_invd, &ctx.cmds,
+                             fronts, xs, ws, f_tot, finv, wf, wb, u4, d4, tri, d_flag};
+        e = numeric_run(run, device, st, evs, &ctx.launches);
     }
     struct EventGuard { std::vector<hipEvent_t>& v; ~EventGuard() { for (hipEvent_t x : v) (void)hipEventDestroy(x); } } ev_guard{evs};
     if (e == hipSuccess) e = hipGetLastError();
@@ -908,6 +1180,17 @@ static int direct_factor_impl(const int32_t* d_rowptr, const int32_t* d_col, con
         return LS_E_INVALID;
     }
     cleanup(false);
+    if (retain) {
+        RefactorState* R = new RefactorState;
+        R->device = device; R->V = V; R->nnz = nnz; R->f_tot = f_tot; R->x_tot = x_tot; R->w_tot = w_tot; R->work_tot = work_tot;
+        R->rowptr = d_rowptr_kept; R->col = d_col_kept; R->inv = d_inv; R->non = d_non; R->bnd = d_bnd; R->ppos = d_ppos; R->ids = d_ids;
+        R->nodes = d_nodes; R->gemm = d_gemm_off; R->invd = d_invd_off; R->slots = d_slots;
+        R->cmds = ctx.cmds; R->n_gemm = ctx.gemm.size(); R->n_inv = ctx.inv.size();
+        R->finv = finv; R->wf = wf; R->wb = wb; R->u4 = u4; R->d4 = d4; R->tri = tri; R->sp_ent = d_sp_ent;
+        for (size_t i = 0; i < kept.size(); ++i) R->bufs.emplace_back(kept[i], kept_bytes[i]);
+        kept.clear(); kept_bytes.clear();
+        ls_direct_adopt_refactor(*out, R);
+    }
     const double t3 = now_s();
     lap("numeric factorisation + solve tables (overlapped)");
     if (timing) {

@@ -122,6 +122,10 @@ _SIGNATURES = {
                                  c_void_p, ctypes.POINTER(c_void_p)]),
     "ls_direct_factor_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_int, c_void_p, ctypes.POINTER(c_void_p)]),
     "ls_direct_options_default": (c_int, [c_void_p]),
+    "ls_direct_factor_refactorable": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_int, c_void_p,
+                                              ctypes.POINTER(c_void_p)]),
+    "ls_direct_refactor": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_void_p]),
+    "ls_direct_refactorable": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_size_t)]),
     "ls_direct_solve_part": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "ls_direct_shard_info": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_i64),
                                      c_void_p]),

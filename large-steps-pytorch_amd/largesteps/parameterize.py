@@ -101,3 +101,44 @@ def from_differential(L, u, method='Cholesky'):
     else:
         solver = hit[0]
     return solve(solver, u)
+
+
+def update_matrix(L_old, L_new, method='Cholesky'):
+    """
+    Hand the cached solver of L_old over to L_new, a matrix with the same sparsity pattern and new values (a cotangent Laplacian
+    re-linearised on the current vertices, a new lambda / alpha on the same mesh). Returns L_new.
+
+    'Cholesky': a refactorable solver cached for L_old is refactorised in place (no new symbolic analysis, the same solver object,
+    every device address kept: a graph captured around from_differential(L_old, ...) replays with L_new) and filed under L_new;
+    the L_old entry goes away. Otherwise a refactorable solver is constructed for L_new and cached, so that the next update is fast.
+    'CG': the L_old entry is dropped (the iteration reads the matrix at every call; from_differential(L_new, ...) builds its own).
+
+    Raises ValueError when L_new's pattern differs from the analysed one (the L_old entry is kept, unchanged) or L_new is not
+    positive definite (the solver is unfactored: the L_old entry is dropped). A backward pass through a forward made before the
+    update raises RuntimeError.
+    """
+    if method not in ('Cholesky', 'CG'):
+        raise ValueError(f"Unknown solver type '{method}'.")
+    if not isinstance(L_new, torch.Tensor) or L_new.layout != torch.sparse_coo:
+        raise TypeError("update_matrix: L_new must be a torch sparse COO matrix (as returned by compute_matrix)")
+    _native.require_device(L_new, "L_new")
+    key_old = (id(L_old), method)
+    hit = _cache.get(key_old)
+    solver = hit[0] if hit is not None and hit[1]() is L_old else None
+    if method == 'CG':
+        if hit is not None:
+            _cache.pop(key_old, None)
+        return L_new
+    if solver is not None and getattr(solver, "refactorable", False):
+        try:
+            solver.refactor(L_new)
+        except ValueError:
+            if not getattr(solver, "factored", True):
+                _cache.pop(key_old, None)          # not positive definite: that solver holds no factor any more
+            raise
+    else:
+        solver = CholeskySolver(L_new, refactorable=True)
+    if L_new is not L_old:
+        _cache.pop(key_old, None)
+    cache_put((id(L_new), method), solver, L_new)
+    return L_new

@@ -27,6 +27,8 @@ class Solver:
     What `solve()` below expects of a solver object (reference: solvers.py:6-24): a constructor that takes the matrix and a
     `solve(b, backward)` method. Subclass it to plug in any other linear solver.
     """
+    generation = 0      # bumped by every successful `refactor` (DifferentiableSolve checks it between forward and backward)
+
     def __init__(self, M):
         pass
 
@@ -252,7 +254,7 @@ class _NativeDirect:
 
     _ORDERINGS = {None: -1, "auto": -1, "longest-axis": 0, "trial-cuts": 1}      # LS_ND_ORDER_AUTO / _LONGEST / _MINSEP
 
-    def __init__(self, csr, leaf_size, arity, tier_levels, sparse_leaves, shard=(0, 1), ordering=None, tier_waves=0):
+    def __init__(self, csr, leaf_size, arity, tier_levels, sparse_leaves, shard=(0, 1), ordering=None, tier_waves=0, refactorable=False):
         self.device = csr.device
         self._h = ctypes.c_void_p(None)
         pos = csr.positions
@@ -270,9 +272,15 @@ class _NativeDirect:
         opt.leaf_size, opt.arity, opt.tier_levels, opt.sparse_leaves = int(leaf_size or 0), int(arity or 0), int(tier_levels), int(bool(sparse_leaves))
         opt.shard_rank, opt.shard_count = int(shard[0]), int(shard[1])
         opt.ordering, opt.tier_waves = self._ORDERINGS[ordering], int(tier_waves)
+        # refactorable: the same factorisation, and the handle keeps what ls_direct_refactor needs (include/largesteps_hip.h)
+        factor = lib.ls_direct_factor_refactorable if refactorable else lib.ls_direct_factor_ex
         with torch.cuda.device(dev):
-            _native.check(lib.ls_direct_factor_ex(_native.ptr(csr.rowptr), _native.ptr(csr.col), _native.ptr(csr.val), csr.V, csr.nnz,
-                                                  _native.ptr(pos), ctypes.byref(opt), dev.index, _native.stream_of(dev), ctypes.byref(self._h)))
+            _native.check(factor(_native.ptr(csr.rowptr), _native.ptr(csr.col), _native.ptr(csr.val), csr.V, csr.nnz,
+                                 _native.ptr(pos), ctypes.byref(opt), dev.index, _native.stream_of(dev), ctypes.byref(self._h)))
+        self.factored = True
+        yes, kept = ctypes.c_int(0), ctypes.c_size_t(0)
+        _native.check(lib.ls_direct_refactorable(self._h, ctypes.byref(yes), ctypes.byref(kept)))
+        self.refactorable, self.retained_bytes = bool(yes.value), int(kept.value)
         s3 = (ctypes.c_double * 3)()
         _native.check(_native.lib().ls_direct_factor_seconds(self._h, ctypes.byref(s3)))
         self.timings = dict(plan_seconds=s3[0], table_seconds=s3[1], factor_seconds=s3[2])
@@ -306,6 +314,18 @@ class _NativeDirect:
         rc = self._solve(self._h, b.data_ptr(), x.data_ptr(), b.shape[1], _native.raw_stream(self.device))
         if rc:
             _native.check(rc)
+
+    def refactor(self, csr):
+        """New values of the analysed pattern into this handle's factor, in place (ls_direct_refactor: SYNC). ValueError: the pattern
+        differs (the factor is unchanged) or a front is not positive definite (the handle then refuses to solve until a refactor succeeds)."""
+        if not self._h.value:
+            raise RuntimeError("this solver was closed")
+        with torch.cuda.device(self.device):
+            rc = _native.lib().ls_direct_refactor(self._h, _native.ptr(csr.rowptr), _native.ptr(csr.col), _native.ptr(csr.val), csr.V, csr.nnz,
+                                                  _native.stream_of(self.device))
+        # a failure before the factor was touched (a pattern mismatch, a handle that cannot refactor) keeps the old factor
+        self.factored = rc == 0 or (self.factored and (rc == _native.LS_E_STATE or "the factor is unchanged" in _native.last_error()))
+        _native.check(rc)
 
     def set_option(self, name, value):
         _native.check(_native.lib().ls_direct_set(self._h, name.encode(), int(value)))
@@ -376,6 +396,20 @@ def release_scratch(device=None):
 _DIRECT_INFO = types.MappingProxyType(dict(iterations=0, converged=True, method="nested-dissection"))
 
 
+def _refactor_operand(M_new, V, nnz, device, who):
+    """The checks of a refactor's new matrix that need no device (type, size, number of entries, device), then its CSR side car."""
+    if not isinstance(M_new, torch.Tensor) or M_new.layout != torch.sparse_coo:
+        raise TypeError(f"{who}: expected a torch sparse COO matrix (as returned by largesteps.geometry.compute_matrix)")
+    if M_new.dim() != 2 or tuple(M_new.shape) != (V, V):
+        raise ValueError(f"{who}: the new matrix has shape {tuple(M_new.shape)}, the solver's is ({V}, {V}) -- a new pattern needs a new solver")
+    _native.require_device(M_new, "the new matrix")
+    if M_new.device != device:
+        raise RuntimeError(f"{who}: the solver lives on {device}, the new matrix on {M_new.device}")
+    if nnz is not None and M_new.is_coalesced() and M_new._nnz() != nnz:
+        raise ValueError(f"{who}: the new matrix has {M_new._nnz()} entries, the solver's pattern {nnz} -- a new pattern needs a new solver")
+    return _native.csr_of(M_new)
+
+
 class NestedDissectionSolver(Solver):
     """
     Factor-once / re-solve direct solver (what the reference's default method does through cholespy / CHOLMOD,
@@ -400,6 +434,8 @@ class NestedDissectionSolver(Solver):
     vertices constructs in 78 ms instead of 150), and a size class whose previous solver served >= AUTO_TRIAL_CUTS_AFTER solves gets them too.
     tier_waves=4 / 8 / 16 picks the tier kernel's workgroup shape (0: the library's rule; A/B runs and tests). Raises ValueError when the matrix is not symmetric or not
     positive definite, RuntimeError when the mesh does not dissect into fronts that fit the kernels.
+    refactorable=True keeps what `refactor` needs (the same factor and solves; ~120 MB more device memory at 1M vertices,
+    `retained_bytes`): new values of the same pattern are then factorised again without a new analysis, in place.
     """
 
     # A remesh loop tells the library its own period: when the previous solver of the same size class (same device, vertex count
@@ -430,9 +466,10 @@ class NestedDissectionSolver(Solver):
             key = self._surface_key_cached = self._class_key + box
         return key
 
-    def __init__(self, M, leaf_size=None, arity=None, shard=(0, 1), ordering=None, tier_waves=0):
+    def __init__(self, M, leaf_size=None, arity=None, shard=(0, 1), ordering=None, tier_waves=0, refactorable=False):
         import time
         csr = _native.csr_of(M)
+        self.generation = 0
         self._csr = csr
         self.last_info = None
         self.solves_served = 0
@@ -452,7 +489,10 @@ class NestedDissectionSolver(Solver):
         t0 = time.perf_counter()
         tier = max(-1, min(6, int(os.environ.get("LS_ND_TIER_H", "-1"))))      # -1: the library picks (and never picks one that does not fit)
         sparse = not os.environ.get("LS_ND_DENSE_LEAVES")
-        self._direct = _NativeDirect(csr, leaf_size, arity, tier, sparse, shard=shard, ordering=ordering, tier_waves=tier_waves)
+        self._direct = _NativeDirect(csr, leaf_size, arity, tier, sparse, shard=shard, ordering=ordering, tier_waves=tier_waves,
+                                     refactorable=refactorable)
+        self.refactorable = self._direct.refactorable
+        self.retained_bytes = self._direct.retained_bytes
         torch.cuda.synchronize(csr.device)
         self.build_seconds = time.perf_counter() - t0
         self.timings = self._direct.timings
@@ -489,6 +529,30 @@ class NestedDissectionSolver(Solver):
                 x[:, c0:c1] = xb
         self.last_info = _DIRECT_INFO
         return x.squeeze(1) if squeeze else x
+
+    def refactor(self, M_new):
+        """
+        Factorise new values of the SAME pattern into this solver, in place: no new symbolic analysis, and every device address stays
+        (a graph captured around this solver's solves replays with the new matrix). The plan -- and so the result, bit for bit -- is
+        what a new solver with the same positions would build for M_new. Needs refactorable=True at construction.
+
+        Raises ValueError when M_new's pattern differs from the analysed one (the factor is unchanged) or M_new is not symmetric or
+        not positive definite (the solver then refuses to solve until a later refactor succeeds); TypeError / RuntimeError for a
+        matrix of the wrong kind or device. A backward pass through a solve made before a successful refactor raises RuntimeError.
+        """
+        csr = _refactor_operand(M_new, self._csr.V, self._csr.nnz, self._csr.device, "NestedDissectionSolver.refactor")
+        if not self.refactorable:
+            raise RuntimeError("NestedDissectionSolver.refactor: this solver was constructed with refactorable=False")
+        if not _native.is_symmetric(csr):
+            raise ValueError("NestedDissectionSolver.refactor: the matrix is not symmetric")
+        self._direct.refactor(csr)
+        self._csr = csr
+        self.generation += 1
+
+    @property
+    def factored(self):
+        """False after a refactor that failed on a matrix that is not positive definite: solves raise until a refactor succeeds."""
+        return self._direct.factored
 
     def set_option(self, name, value):
         self._direct.set_option(name, value)
@@ -545,9 +609,15 @@ class CholeskySolver(Solver):
       Jacobi-PCG run to a residual reduction `rtol`).
     `direct=False` (or LARGESTEPS_NO_DIRECT=1) forces the iterative path; `method` says which one is in use and every
     other attribute is the chosen solver's.
+    `refactorable=True`: `refactor(M_new)` takes new values of the same pattern (see NestedDissectionSolver.refactor).
     """
 
-    def __init__(self, M, rtol=1e-6, max_iter=10000, chebyshev=True, patch_columns=3, direct=None, leaf_size=None, arity=None):
+    def __init__(self, M, rtol=1e-6, max_iter=10000, chebyshev=True, patch_columns=3, direct=None, leaf_size=None, arity=None,
+                 refactorable=False):
+        self.refactorable = bool(refactorable)
+        self.generation = 0
+        self._iter_args = dict(rtol=rtol, max_iter=max_iter, chebyshev=chebyshev, patch_columns=patch_columns)
+        self._devices = None
         if direct is None:
             direct = not os.environ.get("LARGESTEPS_NO_DIRECT")
         self._impl = None
@@ -558,13 +628,14 @@ class CholeskySolver(Solver):
             try:
                 from .distributed import MultiDeviceDirect
                 self._impl = MultiDeviceDirect(M, devices, leaf_size=leaf_size, arity=arity)      # None: the tree ls_direct_pick_tree picks, as on one device
+                self._devices = (devices, leaf_size, arity)
             except (ValueError, RuntimeError) as e:
                 self.direct_error = str(e)
                 warnings.warn(f"CholeskySolver: LARGESTEPS_DEVICES={','.join(devices)} could not be used ({e}); one device instead",
                               RuntimeWarning, stacklevel=2)
         if direct and self._impl is None:
             try:
-                self._impl = NestedDissectionSolver(M, leaf_size=leaf_size, arity=arity)
+                self._impl = NestedDissectionSolver(M, leaf_size=leaf_size, arity=arity, refactorable=refactorable)
             except (ValueError, RuntimeError) as e:      # no positions / fronts too large / numerically not SPD
                 self.direct_error = str(e)
                 if _native.csr_of(M).positions is not None:      # unexpected for a compute_matrix matrix: say so
@@ -579,6 +650,29 @@ class CholeskySolver(Solver):
 
     def solve(self, b, backward=False):                  # (documentation and the class-level contract; instances call _impl.solve directly)
         return self._impl.solve(b, backward=backward)
+
+    def refactor(self, M_new):
+        """
+        New values of the same pattern (needs refactorable=True). The nested-dissection implementation factorises them in place
+        (NestedDissectionSolver.refactor: no new analysis). Any other implementation -- the Chebyshev / PCG fallback, the multi-device
+        solver -- is REBUILT for M_new: correct, but no faster than a new CholeskySolver. Errors as NestedDissectionSolver.refactor.
+        """
+        if not self.refactorable:
+            raise RuntimeError("CholeskySolver.refactor: this solver was constructed with refactorable=False")
+        impl = self._impl
+        if isinstance(impl, NestedDissectionSolver):
+            impl.refactor(M_new)
+        else:
+            V, device = (impl._csr.V, impl._csr.device) if isinstance(impl, PCGSolver) else (impl.V, impl.home)
+            _refactor_operand(M_new, V, None, device, "CholeskySolver.refactor")
+            if isinstance(impl, IterativeCholeskySolver):
+                self._impl = IterativeCholeskySolver(M_new, **self._iter_args)
+            else:
+                from .distributed import MultiDeviceDirect
+                devices, leaf_size, arity = self._devices
+                self._impl = MultiDeviceDirect(M_new, devices, leaf_size=leaf_size, arity=arity)
+            self.solve = self._impl.solve
+        self.generation += 1
 
     @property
     def last_info(self):
@@ -619,10 +713,15 @@ class DifferentiableSolve(Function):
     @staticmethod
     def forward(ctx, solver, b):
         ctx.solver = solver
+        ctx.generation = getattr(solver, "generation", 0)
         return solver.solve(b, backward=False)
 
     @staticmethod
     def backward(ctx, grad_output):
+        if getattr(ctx.solver, "generation", 0) != ctx.generation:
+            # the solver now holds another matrix: its solve is not the adjoint of this forward pass any more
+            raise RuntimeError("DifferentiableSolve: the solver was refactored (given a new matrix) after this forward pass; "
+                               "backward would differentiate through the new matrix")
         grad_b = ctx.solver.solve(grad_output.contiguous(), backward=True) if ctx.needs_input_grad[1] else None
         return None, grad_b
 
