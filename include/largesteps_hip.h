@@ -330,7 +330,7 @@ typedef struct ls_direct_arrays {
     const void* d_sp_ent;          /* {float value; int32 index} pairs */
     int64_t n_sp_ptr, n_sp_ent;    /* lengths of the two sparse-leaf arrays (accounting only) */
     int32_t shard_rank, shard_count;   /* subtree sharding over `shard_count` processes (0 or 1: none), see ls_direct_solve_part */
-    int32_t tier_waves;                /* waves per tier workgroup: 0 = the library's rule (see ls_direct_options), 4 / 8 / 16 */
+    int32_t tier_waves;                /* waves per tier workgroup: 0 = the library's rule (see ls_direct_options), 4 / 8 / 16; else LS_E_INVALID */
 } ls_direct_arrays;
 int ls_direct_create(const ls_direct_arrays* arrays, int device, void* stream, ls_direct** out);
 /* The tree ls_direct_factor picks for a V x V system: on entry *leaf_size / *arity <= 0 mean "pick" (explicit values are kept), on return

@@ -6,6 +6,7 @@
 #include <stdarg.h>
 #include <stdlib.h>
 #include "../../include/largesteps_hip.h"
+#include "env.h"
 
 namespace ls {
 
@@ -35,7 +36,7 @@ struct DeviceGuard {  // every entry point pins the device itself: no thread-loc
         // The process is shared with PyTorch (and with this library's own fire-and-forget frees): drop any stale
         // sticky error so that this entry point only reports failures of its own calls. LS_DEBUG=1 prints it.
         const hipError_t stale = hipGetLastError();
-        if (stale != hipSuccess && getenv("LS_DEBUG"))
+        if (stale != hipSuccess && env_debug())
             fprintf(stderr, "[largesteps] stale HIP error %d (%s) found on entry\n", (int)stale, hipGetErrorString(stale));
         err = hipGetDevice(&prev);
         if (err == hipSuccess && prev != device) err = hipSetDevice(device);

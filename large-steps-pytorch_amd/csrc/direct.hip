@@ -14,7 +14,7 @@
 // prefetch of the first matrix rows before the right-hand side is assembled, and two kernel shapes:
 //     k_nd_up / k_nd_down      a row per lane, NW waves split the reduction range and meet in LDS (short reductions)
 //     k_nd_up_b / k_nd_down_b  lanes ALONG the reduction, a wave owns ND_ROWS rows, DPP butterfly (long reductions)
-//     k_nd_up_s / k_nd_down_s  small nodes: the node's whole matrix staged in LDS by one coalesced burst, a row per thread
+//     k_nd_up_s                small nodes, up sweep: the node's whole W staged in LDS by one coalesced burst, a row per thread
 //     k_nd_up_p / k_nd_down_p  tiny nodes: up to 8 consecutive nodes share a wave (lane -> (node, row))
 #include "common.h"
 #include <vector>
@@ -623,71 +623,6 @@ __global__ __launch_bounds__(256) void k_nd_up_s(const Tile* __restrict__ tiles,
     }
 }
 
-template <int K>
-__global__ __launch_bounds__(256) void k_nd_down_s(const Tile* __restrict__ tiles, const int* __restrict__ perm,
-                                                   const int* __restrict__ push_ptr, const int* __restrict__ push_tgt,
-                                                   const float* __restrict__ finv, const float* __restrict__ wb,
-                                                   const float* __restrict__ bprime, float* xb, float* __restrict__ x_out,
-                                                   int s_cap, int b_cap) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float* sb = sm;                                  // s_cap * K
-    float* sx = sm + (size_t)s_cap * K;              // b_cap * K
-    float* mf = sx + (size_t)b_cap * K;              // s * s: Finv, mf[t * s + j]
-    const Tile t = load_tile(tiles, blockIdx.x);
-    if (t.forward == 2) return;                 // padding of the XCD-aware tile order
-    if (t.forward) { forward_rows<K>(t, push_ptr, push_tgt, xb); return; }
-    const int s = t.s, b = t.b, j = threadIdx.x;
-    float* mw = mf + (size_t)s * s;                  // b * s: W, mw[i * s + j]
-    stage_block(finv + t.finv_off, s * s, mf);
-    stage_block(wb + t.w_off, b * s, mw);
-    int p0 = 0, p1 = 0;
-    size_t g = 0;
-    if (j < s) {
-        g = (size_t)perm[t.own_start + j];
-        if (!t.leaf) { p0 = push_ptr[t.front_off + j]; p1 = push_ptr[t.front_off + j + 1]; }
-    }
-    for (int u = threadIdx.x; u < s; u += blockDim.x) {
-#pragma unroll
-        for (int q = 0; q < K; ++q) sb[u * K + q] = bprime[(size_t)(t.own_start + u) * K + q];
-    }
-    for (int i = threadIdx.x; i < b; i += blockDim.x) {
-#pragma unroll
-        for (int q = 0; q < K; ++q) sx[i * K + q] = -xb[(size_t)(t.bnd_off + i) * K + q];
-    }
-    __syncthreads();
-    // the boundary rows hand x down while the own rows multiply (leaf levels have nothing to hand down)
-    if (!t.leaf) {
-        for (int i = threadIdx.x; i < b; i += blockDim.x) {
-            const size_t f = (size_t)(t.front_off + s + i);
-            const int q0 = push_ptr[f], q1 = push_ptr[f + 1];
-            float v[K];
-#pragma unroll
-            for (int q = 0; q < K; ++q) v[q] = -sx[i * K + q];
-            push_down<K>(push_tgt, q0, q1, xb, v);
-        }
-    }
-    if (j < s) {
-        float acc[K];
-#pragma unroll
-        for (int q = 0; q < K; ++q) acc[q] = 0.0f;
-#pragma unroll 4
-        for (int u = 0; u < s; ++u) {
-            const float a = mf[u * s + j];
-#pragma unroll
-            for (int q = 0; q < K; ++q) acc[q] = fmaf(a, sb[u * K + q], acc[q]);
-        }
-#pragma unroll 4
-        for (int i = 0; i < b; ++i) {
-            const float a = mw[i * s + j];
-#pragma unroll
-            for (int q = 0; q < K; ++q) acc[q] = fmaf(a, sx[i * K + q], acc[q]);
-        }
-#pragma unroll
-        for (int q = 0; q < K; ++q) x_out[g * K + q] = acc[q];
-        push_down<K>(push_tgt, p0, p1, xb, acc);
-    }
-}
-
 // ---- tiny nodes (the deepest levels): several nodes per wave --------------------------------------------------------
 // A node with a dozen rows leaves most of a 64-lane wave idle and there are tens of thousands of them. A packed tile is
 // a run of up to 8 consecutive nodes of one level whose rows together fill a wave: lane -> (node, row). Consecutive
@@ -839,7 +774,7 @@ __global__ __launch_bounds__(64) void k_nd_down_p(const PackedTile* __restrict__
 namespace ls {
 
 // down tiles of a level: compute tiles, then forward tiles
-struct LevelPlan { int up_first = 0, up_tiles = 0, up_nw = 1, down_first = 0, down_tiles = 0, down_nw = 1, s_cap = 0, b_cap = 0, up_b = 0, down_b = 0, up_chunks = 1, down_chunks = 1, up_s = 0, down_s = 0,
+struct LevelPlan { int up_first = 0, up_tiles = 0, up_nw = 1, down_first = 0, down_tiles = 0, down_nw = 1, s_cap = 0, b_cap = 0, up_b = 0, down_b = 0, up_chunks = 1, down_chunks = 1, up_s = 0,
                    up_p = 0, down_p = 0, up_p_first = 0, up_p_tiles = 0, down_p_first = 0, down_p_tiles = 0, up_p_lds = 0, down_p_s = 0, down_p_lds = 0; };
 
 }  // namespace ls
@@ -869,7 +804,6 @@ struct ls_direct {
     float* braw = nullptr;                                       // tier kernels: gathered right-hand side of the inner-node rows (V, k)
     float *bp = nullptr, *slots = nullptr, *xb = nullptr;        // b' (V, k); up-sweep slots (n_front, arity, k); x at boundaries (n_bnd, k)
     // bottom tier: levels [tier_root, levels) run as one launch per sweep, one workgroup per subtree (nd_tier.h)
-    bool fuse_root = true;              // LS_ND_NO_FUSE_ROOT: the root keeps its up-sweep launch
     int upper_lo = 0;                   // rows [upper_lo, V) of the tree's numbering belong to the levels above the tier
     int tier_root = 0, tier_phases = 0, tier_wgs = 0, tier_region = 0, tier_vec = 0, tier_tri = 0, tier_waves = TIER_WAVES;
     TierItem* d_items = nullptr;
@@ -889,7 +823,6 @@ struct ls_direct {
     int shard_rank = 0, shard_count = 1, cut = 0;
     int64_t exch_f0 = 0, exch_f1 = 0;
     std::vector<unsigned char> owned_rows;    // caller's numbering: 1 = this rank is the designated owner of the row's x
-    int tier_xcd = 1;                   // LS_ND_XCD=0 at creation: plain workgroup -> subtree order in the tier kernels
     // cache policy of the read-once factor streams (common.h, ld_stream): non-temporal when the factor cannot stay cache resident anyway
     bool nt_levels = false, nt_tier = false, nt_rule[2] = {false, false};
     double factor_s[3] = {0, 0, 0};     // ls_direct_factor: symbolic analysis, layout / sparse tables, numeric factorisation
@@ -913,12 +846,8 @@ struct ls_direct {
 #endif
 };
 
-static int env_int(const char* name, int dflt) { const char* e = getenv(name); const int v = e ? atoi(e) : 0; return v > 0 ? v : dflt; }
-
-// waves per workgroup of the row-per-lane kernels: about LS_ND_STEPS reduction steps per wave where 16 waves allow it
-static int pick_nw(int len, bool up_sweep = false) {
-    // read at every create: tests and tuning runs toggle it
-    const int target = up_sweep ? env_int("LS_ND_STEPS_UP", 32) : env_int("LS_ND_STEPS", 128);
+// waves per workgroup of the row-per-lane kernels: about `target` reduction steps per wave where 16 waves allow it
+static int pick_nw(int len, int target) {
     int nw = 1;
     while (nw < 16 && len > nw * target) nw *= 2;
     return nw;
@@ -960,8 +889,7 @@ struct DevicePool {
     struct Entry { void* p; size_t bytes; int device; };
     std::vector<Entry> held;
     static size_t cap(int device) {              // bytes the pool may hold on one device
-        const char* e = getenv("LS_POOL_GB");
-        double gb = e ? atof(e) : 24.0;        // (a 4M-vertex construction leaves 14 GB of scratch + 2.4 GB of factor: with 16 the fronts were evicted every time)
+        double gb = env_pool_gb();
         if (!(gb > 0.0)) return 0;
         // the device's memory size is asked for once (hipMemGetInfo is a driver call, and every buffer handed back comes through here:
         // ~40 per construction since the small arrays are pooled too)
@@ -1047,8 +975,6 @@ extern "C" int ls_release_scratch(int device) {            // device < 0: every 
     }
     return LS_OK;
 }
-
-static int env_int0(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 
 // Bottom tier (nd_tier.h): cut the subtrees rooted at level `root` into wave-sized items. Returns the LDS floats a wave
 // needs (0 = the tier does not fit), fills items / wgs.
@@ -1186,17 +1112,19 @@ extern "C" int ls_direct_tier_lds_bytes(int levels, int arity, const int32_t* h_
 // the C ABI on planes (profiles/r05_tier16.txt): 1M 201.5 -> 197.2 us, 1.44M 376 -> 359, 2M 428 -> 415, 4M 719-729 -> 714; between
 // 300k and 722k vertices even to worse (640k: 150.8 = 150.8; 722k: 157-162 -> 164), 810k 177.4 -> 171.5, below 300k the arity-8 trees stay
 // ahead. So: arity 4, at least 8 levels,
-// from 800k vertices, one GPU (a rank of a sharded solve keeps its own rule). LS_ND_TIER_WAVES = 4 / 8 / 16 overrides.
+// from 800k vertices, one GPU (a rank of a sharded solve keeps its own rule). tier_waves = 4 / 8 / 16 (the caller's argument, else
+// LS_ND_TIER_WAVES) overrides.
 bool direct_tier_full16(int64_t V, int arity, int levels, int tier_levels, int shard_count, int tier_waves) {
-    const int env = tier_waves > 0 ? tier_waves : env_int0("LS_ND_TIER_WAVES", 0);       // an explicit argument wins over the environment
-    if (env == TIER_WAVES_FULL) return tier_levels >= 2;
-    if (env == TIER_WAVES || env == TIER_WAVES_WIDE) return false;
+    if (tier_waves == TIER_WAVES_FULL) return tier_levels >= 2;
+    if (tier_waves == TIER_WAVES || tier_waves == TIER_WAVES_WIDE) return false;
     return shard_count <= 1 && arity == 4 && levels >= 8 && V >= 800000 && tier_levels == levels - 4 && tier_levels <= TIER_MAX_H;
 }
 
 
 extern "C" int ls_direct_create(const ls_direct_arrays* A, int device, void* stream, ls_direct** out) {
     LS_REQUIRE(A && out, LS_E_INVALID, "ls_direct_create: null argument");
+    LS_REQUIRE(A->tier_waves == 0 || A->tier_waves == TIER_WAVES || A->tier_waves == TIER_WAVES_WIDE || A->tier_waves == TIER_WAVES_FULL, LS_E_INVALID,
+               "ls_direct_create: tier_waves must be 0 (library's rule), 4, 8 or 16");
     const int64_t V = A->V, n_bnd = A->n_bnd, n_front = A->n_front;
     const int levels = A->levels, arity = A->arity;
     const int64_t* h_nodes = A->h_nodes;
@@ -1217,7 +1145,8 @@ extern "C" int ls_direct_create(const ls_direct_arrays* A, int device, void* str
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
-    const bool timing = getenv("LS_PLAN_TIMING") != nullptr;          // host clock only, no synchronisation: where the handle's construction spends its time
+    const bool timing = env_plan_timing();          // host clock only, no synchronisation: where the handle's construction spends its time
+    const NdEnv env = nd_env();
     const auto t_create = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) { if (timing) fprintf(stderr, "[ls_direct_create] %-28s %.2f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_create).count()); };
     ls_direct* d = new ls_direct();
@@ -1275,14 +1204,11 @@ extern "C" int ls_direct_create(const ls_direct_arrays* A, int device, void* str
     //   70k 70 / 78   250k 88 / 96   490k 139 / 133 (level kernels only; + tier: 140)   1M 214 / 199   2M 450 / 431   4M 722 / 705
     // While the factor (<= ~200 MB) stays resident in the 256 MB Infinity Cache from solve to solve, nt throws that away; beyond, the
     // level kernels' rows go nt first (their vectors and slot records are what the L2 should keep), the tier's dense streams from ~400 MB on.
-    // LS_ND_NT=0 / 1 forces it off / on (A/B), ls_direct_set(h, "nt", v) per handle.
+    // ls_direct_set(h, "nt", v) forces it off / on per handle.
     {
         const double mb = 4e-6 * (double)fe;
-        d->nt_rule[0] = mb > (double)env_int("LS_ND_NT_LEVELS_MB", 256);
-        d->nt_rule[1] = mb > (double)env_int("LS_ND_NT_TIER_MB", 400);
-        const int force = env_int0("LS_ND_NT", -1);
-        d->nt_levels = force < 0 ? d->nt_rule[0] : force != 0;
-        d->nt_tier = force < 0 ? d->nt_rule[1] : force != 0;
+        d->nt_rule[0] = d->nt_levels = mb > 256.0;
+        d->nt_rule[1] = d->nt_tier = mb > 400.0;
     }
     for (int lv = 0; lv < levels; ++lv)
         for (int64_t i = level_off[lv]; i < level_off[lv + 1]; ++i) {
@@ -1342,7 +1268,7 @@ extern "C" int ls_direct_create(const ls_direct_arrays* A, int device, void* str
             // the kernel that will run is the one whose budget is checked: sixteen waves first where the rule asks for them (a subtree one
             // level taller may fit 160 KB as 16 regions and not 150 KB as 4), the 4- / 8-wave plans otherwise
             size_t region = 0;
-            if (H <= TIER_MAX_H && direct_tier_full16(V, arity, levels, H, n_ranks, A->tier_waves)) {
+            if (H <= TIER_MAX_H && direct_tier_full16(V, arity, levels, H, n_ranks, A->tier_waves > 0 ? A->tier_waves : env.tier_waves.value_or(0))) {
                 int vec16 = 0, tri16 = 0;
                 const size_t region16 = plan_tier(nd, level_off, levels, arity, root, sub_lo * span, sub_hi * span, items, wgs, vec16, tri16, TIER_WAVES_FULL);
                 if (region16 && ((region16 + 3) & ~(size_t)3) * sizeof(float) * TIER_WAVES_FULL <= 160 * 1024) {
@@ -1358,7 +1284,7 @@ extern "C" int ls_direct_create(const ls_direct_arrays* A, int device, void* str
                 }
                 // few subtrees (<= 768 workgroups: three per CU or less): 8 waves per workgroup, two workgroups per CU, if that fits the LDS
                 // (a tier of the leaf level alone -- dense leaves of 2-4 row chunks -- does not gain: 40k vertices 44.3 against 42.7 us)
-                if (H >= 2 && (int)wgs.size() <= 768 && (A->tier_waves > 0 ? A->tier_waves : env_int0("LS_ND_TIER_WAVES", TIER_WAVES_WIDE)) == TIER_WAVES_WIDE) {
+                if (H >= 2 && (int)wgs.size() <= 768 && (A->tier_waves > 0 ? A->tier_waves : env.tier_waves.value_or(TIER_WAVES_WIDE)) == TIER_WAVES_WIDE) {
                     std::vector<TierItem> items8;
                     std::vector<TierWG> wgs8;
                     int vec8 = 0, tri8 = 0;
@@ -1371,8 +1297,6 @@ extern "C" int ls_direct_create(const ls_direct_arrays* A, int device, void* str
             d->tier_root = root; d->tier_phases = H; d->tier_wgs = (int)wgs.size(); d->tier_region = (int)((region + 3) & ~(size_t)3);
         }
     }
-    d->fuse_root = getenv("LS_ND_NO_FUSE_ROOT") == nullptr;
-    d->tier_xcd = env_int0("LS_ND_XCD_TIER", env_int0("LS_ND_XCD", 1)) != 0;
     d->upper_lo = (d->tier_root < levels && d->tier_root > 0) ? nodes[level_off[d->tier_root - 1]].own_start : (int)V;
     std::vector<int> pull;
     if (d->tier_root < levels) {
@@ -1405,8 +1329,8 @@ extern "C" int ls_direct_create(const ls_direct_arrays* A, int device, void* str
     size_t lds_max = 0;
     // (measured over 576 .. 1M vertices, tools/tier_sweep.py: the down sweep of levels with s + b of 90 .. 250 runs 5-10 % of a
     //  whole solve faster with the lanes along the reduction; the up sweep of the s = 125 nodes of an 8-level tree loses 2-3 %)
-    const int long_red = env_int("LS_ND_LONG", 64);             // down sweep (reduction s + b)
-    const int long_up = env_int("LS_ND_LONG_UP", levels >= 8 ? 256 : 64);   // up sweep (reduction s): small trees gain 1-3 % from 64
+    const int long_red = env.long_red;                                              // down sweep (reduction s + b)
+    const int long_up = env.long_up > 0 ? env.long_up : levels >= 8 ? 256 : 64;      // up sweep (reduction s): small trees gain 1-3 % from 64
     for (int lv = 0; lv < d->tier_root; ++lv) {
         LevelPlan& p = d->plan[lv];
         // this rank's nodes of the level: one contiguous range (all of them above the cut)
@@ -1424,39 +1348,31 @@ extern "C" int ls_direct_create(const ls_direct_arrays* A, int device, void* str
         //    records each) want FEW, FAT workgroups: 8 waves from ~1400 entries on (root 15.0 -> 13.9 us, level 1 15.2 -> 14.3 / 17.3 -> 16.3);
         //  * below that 4 waves, and as many row chunks per wave (<= 4) as still leave ~500 tiles in the level (two per CU; 1M: level 4 down
         //    19.6 -> 17.2 us with 4 chunks, level 3 down 18.9 -> 15.7 with 2).
-        // LS_ND_INFLIGHT (16-byte requests per lane) selects the chunks by requests in flight instead (the round-2 rule).
-        const int bw_long = env_int("LS_ND_BW_LONG", 1400), tile_target = env_int("LS_ND_TILES", 500), inflight = env_int("LS_ND_INFLIGHT", 0);
-        const int up_bw = std::min(ND_BW, red_up >= bw_long ? 8 : 4), down_bw = std::min(ND_BW, red_down >= bw_long ? 8 : 4);
-        p.up_nw = p.up_b ? up_bw : pick_nw(red_up, true); p.down_nw = p.down_b ? down_bw : pick_nw(red_down);
-        const int lpr_up = div_up(std::max(p.s_cap, 1), 4 * WAVE), lpr_down = lpr_up + div_up(std::max(p.b_cap, 1), 4 * WAVE);   // 16-byte requests per row and lane
+        // (round 5, docs/measurements.md: 900 or 2100 entries for 8 waves, 250 or 1000 tiles per level: up to 3 % slower at 1M and 4M)
+        const int up_bw = std::min(ND_BW, red_up >= 1400 ? 8 : 4), down_bw = std::min(ND_BW, red_down >= 1400 ? 8 : 4);
+        // (the row-per-lane up kernel: 32 reduction steps per wave; 16 or 64 cost 3-13 % of a 1M-vertex solve, round 5)
+        p.up_nw = p.up_b ? up_bw : pick_nw(red_up, 32); p.down_nw = p.down_b ? down_bw : pick_nw(red_down, env.steps);
         int64_t rows_up = 0, rows_down = 0;
         for (int64_t i = a0; i < a1; ++i) { rows_up += nodes[i].b; rows_down += nodes[i].s; }
-        auto pick_chunks = [&](int64_t rows, int bw, int lpr) {
-            if (inflight > 0) return std::min(4, std::max(1, div_up(inflight, ND_ROWS * lpr)));
+        auto pick_chunks = [&](int64_t rows, int bw) {
             int c = 4;
-            while (c > 1 && rows / (ND_ROWS * bw * c) < tile_target) --c;
+            while (c > 1 && rows / (ND_ROWS * bw * c) < 500) --c;
             return c;
         };
-        p.up_chunks = pick_chunks(rows_up, up_bw, lpr_up);
-        p.down_chunks = pick_chunks(rows_down, down_bw, lpr_down);
+        p.up_chunks = pick_chunks(rows_up, up_bw);
+        p.down_chunks = pick_chunks(rows_down, down_bw);
         const int up_rows = p.up_b ? ND_ROWS * up_bw * p.up_chunks : WAVE, down_rows = p.down_b ? ND_ROWS * down_bw * p.down_chunks : WAVE;
-        // small nodes: whole matrix staged in LDS, one workgroup per node, a row per thread
-        const int small_lds = env_int("LS_ND_SMALL_KB", 40) * 1024;
-        const size_t up_s_bytes = ((size_t)p.s_cap * p.b_cap + (size_t)p.s_cap * d->kmax) * sizeof(float);
-        const size_t down_s_bytes = ((size_t)p.s_cap * (p.s_cap + p.b_cap) + (size_t)(p.s_cap + p.b_cap) * d->kmax) * sizeof(float);
-        p.up_s = p.b_cap <= 256 && p.s_cap <= 256 && up_s_bytes <= (size_t)small_lds && !getenv("LS_ND_NO_SMALL");
+        // small nodes, up sweep: the whole W staged in 40 KB of LDS at most, one workgroup per node, a row per thread
         // (measured at 1M: staging pays for the up sweep -- W only, 42 + 18 + 15 us against 45 + 21 + 17 -- but not for the
-        //  down sweep, whose Finv + W footprint leaves 6 single-wave workgroups per CU: 151 us against 57; LS_ND_SMALL_DOWN=1 enables it)
-        p.down_s = p.s_cap <= 256 && down_s_bytes <= (size_t)small_lds && getenv("LS_ND_SMALL_DOWN") && !getenv("LS_ND_NO_SMALL");
+        //  down sweep, whose Finv + W footprint left 6 single-wave workgroups per CU: 151 us against 57: the down sweep has no staged kernel)
+        const size_t up_s_bytes = ((size_t)p.s_cap * p.b_cap + (size_t)p.s_cap * d->kmax) * sizeof(float);
+        p.up_s = p.b_cap <= 256 && p.s_cap <= 256 && up_s_bytes <= 40 * 1024 && !env.no_small;
         if (p.up_s) { p.up_b = 0; p.up_nw = std::max(1, div_up(p.b_cap, WAVE)); }
-        if (p.down_s) { p.down_b = 0; p.down_nw = std::max(1, div_up(p.s_cap, WAVE)); }
-        // tiny nodes: several nodes per wave (packed tiles), when at least two nodes of the level fit a wave
-        const bool no_pack = getenv("LS_ND_NO_PACK") != nullptr;
-        // largest row count of a level that is still packed (measured at 1M: packing pairs of ~31-row leaves helps the up
+        // tiny nodes: several nodes per wave (packed tiles), when at least two nodes of the level fit a wave. Largest row count of a
+        // level that is still packed: a wave up, half a wave down (measured at 1M: packing pairs of ~31-row leaves helps the up
         // sweep, 42 -> 37 us, while packed down tiles only pay below half a wave)
-        const int pack_up = env_int("LS_ND_PACK_ROWS_UP", WAVE), pack_down = env_int("LS_ND_PACK_ROWS", WAVE / 2);
-        p.up_p = !no_pack && p.b_cap <= pack_up && p.s_cap <= 256 && lv > 0;
-        p.down_p = !no_pack && p.s_cap <= pack_down;
+        p.up_p = !env.no_pack && p.b_cap <= WAVE && p.s_cap <= 256 && lv > 0;
+        p.down_p = !env.no_pack && p.s_cap <= WAVE / 2;
         auto pack_level = [&](bool up_sweep, int& first, int& count, int& lds_rows_s, int& lds_rows_b) {
             first = (int)ptiles.size();
             lds_rows_s = lds_rows_b = 0;
@@ -1487,7 +1403,7 @@ extern "C" int ls_direct_create(const ls_direct_arrays* A, int device, void* str
         };
         int dummy = 0;
         if (p.up_p) { pack_level(true, p.up_p_first, p.up_p_tiles, p.up_p_lds, dummy); p.up_s = 0; p.up_b = 0; }
-        if (p.down_p) { pack_level(false, p.down_p_first, p.down_p_tiles, p.down_p_s, p.down_p_lds); p.down_s = 0; p.down_b = 0; }
+        if (p.down_p) { pack_level(false, p.down_p_first, p.down_p_tiles, p.down_p_s, p.down_p_lds); p.down_b = 0; }
         p.up_first = (int)tiles.size();
         const int up_threads = WAVE * p.up_nw;
         std::vector<int> up_nodes;                                 // node (index within the level) of every tile pushed below
@@ -1509,9 +1425,9 @@ extern "C" int ls_direct_create(const ls_direct_arrays* A, int device, void* str
         // the node's reduction vector (slots, masks, b) -- with a node's tiles on ONE XCD those reads hit that XCD's L2 instead of
         // being fetched once per XCD (PMC, round 3: 55 MB per launch of the row-per-lane up kernel for 29 MB of factor). Levels
         // with fewer than 8 nodes keep the plain order (a node must not be confined to the 32 CUs of one XCD).
-        auto xcd_order = [&](int first, std::vector<int>& node_of_tile, bool up_sweep) {
+        auto xcd_order = [&](int first, std::vector<int>& node_of_tile) {
             const int n = (int)tiles.size() - first;
-            if (a1 - a0 < 8 || n < 16 || !env_int0("LS_ND_XCD", 1)) return;
+            if (a1 - a0 < 8 || n < 16) return;
             std::vector<std::vector<Tile>> bucket(8);
             for (int t = 0; t < n; ++t) bucket[(size_t)(node_of_tile[(size_t)t] & 7)].push_back(tiles[(size_t)(first + t)]);
             size_t longest = 0;
@@ -1522,19 +1438,17 @@ extern "C" int ls_direct_create(const ls_direct_arrays* A, int device, void* str
             tiles.resize((size_t)first);
             for (size_t r = 0; r < longest; ++r)
                 for (int x = 0; x < 8; ++x) tiles.push_back(r < bucket[(size_t)x].size() ? bucket[(size_t)x][r] : idle);
-            (void)up_sweep;
         };
-        xcd_order(p.up_first, up_nodes, true);
+        xcd_order(p.up_first, up_nodes);
         p.up_tiles = (int)tiles.size() - p.up_first;
         p.down_first = (int)tiles.size();
         std::vector<int> down_nodes;
         for (int64_t i = a0; i < a1; ++i)
-            for (int r = 0; r < nodes[i].s; r += (p.down_s ? 1 << 30 : down_rows)) { tiles.push_back(tile_of(i, r, lv, 0)); down_nodes.push_back((int)(i - a0)); }
-        if (lv + 1 < levels)      // forward tiles: boundary rows of every node (staged kernel: only of nodes without own rows)
+            for (int r = 0; r < nodes[i].s; r += down_rows) { tiles.push_back(tile_of(i, r, lv, 0)); down_nodes.push_back((int)(i - a0)); }
+        if (lv + 1 < levels)      // forward tiles: boundary rows of every node
             for (int64_t i = a0; i < a1; ++i)
-                if (!p.down_s || !nodes[i].s)
-                    for (int r = 0; r < nodes[i].b; r += WAVE * p.down_nw) { tiles.push_back(tile_of(i, r, lv, 1)); down_nodes.push_back((int)(i - a0)); }
-        xcd_order(p.down_first, down_nodes, false);
+                for (int r = 0; r < nodes[i].b; r += WAVE * p.down_nw) { tiles.push_back(tile_of(i, r, lv, 1)); down_nodes.push_back((int)(i - a0)); }
+        xcd_order(p.down_first, down_nodes);
         p.down_tiles = (int)tiles.size() - p.down_first;
         lds_max = std::max(lds_max, ((size_t)p.s_cap + p.b_cap + 16 * WAVE) * d->kmax * sizeof(float));
     }
@@ -1659,8 +1573,7 @@ extern "C" int ls_direct_create(const ls_direct_arrays* A, int device, void* str
     (void)hipFuncSetAttribute((const void*)k_nd_down<KK, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);      \
     (void)hipFuncSetAttribute((const void*)k_nd_up_b<KK, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);      \
     (void)hipFuncSetAttribute((const void*)k_nd_down_b<KK, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);    \
-    (void)hipFuncSetAttribute((const void*)k_nd_up_s<KK>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);     \
-    (void)hipFuncSetAttribute((const void*)k_nd_down_s<KK>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)k_nd_up_s<KK>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     LS_OPTIN(1) LS_OPTIN(2) LS_OPTIN(3) LS_OPTIN(4)
 #undef LS_OPTIN
 #define LS_OPTIN(KK)                                                                                                       \
@@ -1711,7 +1624,6 @@ static int direct_solve_k(ls_direct* d, const float* b, float* x, hipStream_t st
     ta.sp_ptr = d->sp_ptr; ta.sp_ent = d->sp_ent; ta.bprime = d->bp; ta.braw = d->braw; ta.slots = d->slots; ta.xb = d->xb;
     ta.arity = d->arity; ta.phases = d->tier_phases; ta.region_floats = d->tier_region; ta.vec_floats = d->tier_vec;
     ta.upper_lo = d->upper_lo; ta.upper_hi = (int)d->V;
-    ta.xcd_order = d->tier_xcd;
 #ifdef LS_TIER_STAMPS
     const size_t stamp_n = (size_t)d->tier_wgs * d->tier_waves * TIER_STAMP_SLOTS;
     if (d->profile == 2 && !d->stamps && stamp_n) LS_HIP(hipMalloc((void**)&d->stamps, 2 * stamp_n * sizeof(long long)));
@@ -1756,7 +1668,7 @@ static int direct_solve_k(ls_direct* d, const float* b, float* x, hipStream_t st
     const int* up_perm = d->tier_wgs ? nullptr : d->perm;
     const float* up_b = d->tier_wgs ? d->braw : b;
     // the root (level 0, when it is a level of its own launches): b' is formed by its down-sweep tiles, no up-sweep launch
-    const bool fuse_root = top >= 0 && d->fuse_root && !d->plan[0].down_p && !d->plan[0].down_s;
+    const bool fuse_root = top >= 0 && !d->plan[0].down_p;
     const RootFill rf = fuse_root ? RootFill{up_perm, d->mask, d->slots, up_b} : RootFill{nullptr, nullptr, nullptr, nullptr};
     for (int lv = (part == 1 ? std::min(top, d->cut - 1) : top); lv >= (part == 0 ? d->cut : 0); --lv) {
         const LevelPlan& p = d->plan[lv];
@@ -1792,10 +1704,6 @@ static int direct_solve_k(ls_direct* d, const float* b, float* x, hipStream_t st
             hipLaunchKernelGGL(k_nd_down_p<K>, dim3(p.down_p_tiles), dim3(WAVE), (size_t)std::max(p.down_p_s + p.down_p_lds, 1) * K * sizeof(float), st,
                                d->ptiles + p.down_p_first, d->perm, d->push_ptr, d->push_tgt, d->finv, d->wb, (const float*)d->bp, d->xb, x,
                                p.down_p_s);
-        else if (p.down_s)
-            hipLaunchKernelGGL(k_nd_down_s<K>, dim3(p.down_tiles), dim3(WAVE * p.down_nw),
-                               ((size_t)p.s_cap * (p.s_cap + p.b_cap) + (size_t)(p.s_cap + p.b_cap) * K) * sizeof(float), st, d->tiles + p.down_first,
-                               d->perm, d->push_ptr, d->push_tgt, d->finv, d->wb, (const float*)d->bp, d->xb, x, p.s_cap, p.b_cap);
         else if (p.down_b)
             hipLaunchKernelGGL((nt ? k_nd_down_b<K, true> : k_nd_down_b<K, false>), dim3(p.down_tiles), dim3(WAVE * p.down_nw), (((size_t)p.s_cap + p.b_cap) * K + 32) * sizeof(float), st,
                                d->tiles + p.down_first, d->perm, d->push_ptr, d->push_tgt, d->finv, d->wf, (const float*)d->bp, d->xb, x,
@@ -2066,7 +1974,7 @@ extern "C" int ls_direct_info(const ls_direct* d, int64_t* h_factor_entries, int
         int n = 0;
         for (int lv = 0; lv < d->levels; ++lv) {
             const LevelPlan& p = d->plan[lv];
-            const bool fused = lv == 0 && d->tier_root > 0 && d->fuse_root && !p.down_p && !p.down_s;     // the root's up step rides in its down tiles
+            const bool fused = lv == 0 && d->tier_root > 0 && !p.down_p;     // the root's up step rides in its down tiles
             n += (((p.up_p ? p.up_p_tiles : p.up_tiles) && !fused) ? 1 : 0) + ((p.down_p ? p.down_p_tiles : p.down_tiles) ? 1 : 0);
         }
         *h_launches = n + (d->tier_wgs ? 2 : 0);

@@ -333,6 +333,7 @@ __global__ __launch_bounds__(BLOCK) void k_nodes(int64_t V, const long long* __r
 struct NdBisectDevice {
     const int32_t* d_rowptr; const int32_t* d_col; const float* d_pos; int64_t nnz; hipStream_t st;
     int32_t* h_col_pending;                 // not nullptr: the host copy of the column indices is still to be made -- WHILE the rounds run
+    bool host_embed;                        // LS_ND_HOST_EMBED: the graph embedding by the host's sweeps (A/B and tests)
     double* d_emb = nullptr;                // graph embedding formed ON THE DEVICE (nd_embed_device): nd_bisect_device reads it instead of `embedded`
     size_t d_emb_cap = 0;
     ~NdBisectDevice() {
@@ -425,8 +426,7 @@ __global__ __launch_bounds__(BLOCK) void k_first_undone(int64_t V, const unsigne
 static std::string nd_embed_device_impl(void* ctx, int64_t V);
 std::string nd_embed_device(void* ctx, int64_t V) {
     NdBisectDevice& A = *(NdBisectDevice*)ctx;
-    if (getenv("LS_ND_HOST_EMBED")) { }                    // A/B and tests: the host's sweeps
-    else {
+    if (!A.host_embed) {
         const std::string r = nd_embed_device_impl(ctx, V);
         if (r != "host") return r;
         if (A.d_emb) { int dev = 0; (void)hipGetDevice(&dev); (void)hipStreamSynchronize(A.st); if (!pool_give(dev, A.d_emb, A.d_emb_cap)) (void)hipFree(A.d_emb); A.d_emb = nullptr; }
@@ -678,56 +678,34 @@ std::string ls::nd_plan_build_device(const int32_t* d_rowptr, const int32_t* d_c
                                      int32_t* h_rowptr, int32_t* h_col, int leaf_size, int arity, int smooth, void* stream, NdPlan& out,
                                      int ordering, bool defer_push_lists) {
     hipStream_t st = (hipStream_t)stream;
-    // the host's copy of the pattern: the row pointers now (the analysis looks at them first), the column indices during the device
-    // rounds -- unless there are no positions: the graph embedding walks the pattern on the host before anything else
-    const bool host_trials = getenv("LS_ND_HOST_TRIALS") != nullptr;      // the trial cuts on host threads, as in round 4 (A/B, tests)
+    const NdEnv env = nd_env();
     // (Round 5 measured making the trial cuts the automatic choice between 12k and 300k vertices, where they find 5-10 % thinner separators
     // on rough closed surfaces: cfg3 0.1024 -> 0.0899 ms per solve, cfg2 0.0571 -> 0.0547 -- for +12 ms of constructor at 250k on a mesh in
     // generation order and +23 ms on a mesh fresh from remove_duplicates, whose lexicographic vertex order makes the host's breadth-first
     // sweeps three times slower; the eager optimisation step at these sizes is host-bound and does not get faster at all. Not the
     // default: LS_ND_ORDER=1 asks for it -- a long captured run on one mesh -- and costs 0.026-0.038 s instead of round 4's 0.10.
     // profiles/r05_trial_cuts_on_device.txt)
-    const bool host_rounds = ordering == ND_ORDER_MINSEP && host_trials;
-    // (the trial cuts need the graph distances, i.e. the pattern on the host, before the rounds start; so does a matrix without positions)
-    // (round 6: the graph distances are breadth-first sweeps ON THE DEVICE, nd_embed_device -- the pattern crosses the bus during the rounds
-    //  in every case; the rare graphs the device hands back to the host's sweeps fetch it then)
-    const bool col_first = host_rounds;
-    if (hipMemcpyAsync(h_rowptr, d_rowptr, sizeof(int32_t) * (V + 1), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        (col_first && hipMemcpyAsync(h_col, d_col, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-        hipStreamSynchronize(st) != hipSuccess)
+    // The host's copy of the pattern: the row pointers now (the analysis looks at them first), the column indices during the device rounds
+    // (round 6: the graph distances are breadth-first sweeps ON THE DEVICE, nd_embed_device; the rare graphs the device hands back to the
+    // host's sweeps fetch the column indices then)
+    if (hipMemcpyAsync(h_rowptr, d_rowptr, sizeof(int32_t) * (V + 1), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
         return "the copy of the matrix pattern to the host failed";
     if (h_rowptr[0] != 0 || h_rowptr[V] != nnz) return "rowptr does not match nnz";
-    std::vector<float> h_pos;
-    auto fetch_positions = [&]() -> bool {
-        if (!d_positions) return true;
-        h_pos.resize((size_t)V * 3);
-        return hipMemcpyAsync(h_pos.data(), d_positions, sizeof(float) * 3 * V, hipMemcpyDeviceToHost, st) == hipSuccess &&
-               hipStreamSynchronize(st) == hipSuccess;
-    };
     const double t0 = now_s();
-    const bool timing = getenv("LS_PLAN_TIMING") != nullptr;
-    if (host_rounds) {
-        if (!fetch_positions()) return "the copy of the positions to the host failed";
-        return nd_plan_build(V, h_rowptr, h_col, d_positions ? h_pos.data() : nullptr, leaf_size, arity, smooth, out, nullptr, nullptr, ND_ORDER_MINSEP, defer_push_lists);
-    }
-    NdBisectDevice ctx{d_rowptr, d_col, d_positions, nnz, st, col_first ? nullptr : h_col};
+    const bool timing = env_plan_timing();
+    NdBisectDevice ctx{d_rowptr, d_col, d_positions, nnz, st, h_col, env.host_embed};
     const float given = 0.0f;                  // "positions were given": nd_plan_build only tests the pointer, the values are read on the device
     std::string err = nd_plan_build(V, h_rowptr, h_col, d_positions ? &given : nullptr, leaf_size, arity, smooth, out, nd_bisect_device, &ctx,
                                     ordering == ND_ORDER_MINSEP ? ND_ORDER_MINSEP : ND_ORDER_LONGEST, defer_push_lists, nd_embed_device);
     if (timing) fprintf(stderr, "[nd_plan] returned (pool joined, temporaries released) %.3f s after its start; %.1f factor numbers per vertex, spread %.2f\n",
                         now_s() - t0, out.words_per_vertex, out.spread);
-    if (!err.empty() || ordering != ND_ORDER_AUTO || out.spread <= nd_plan_suspect()) return err;
+    if (!err.empty() || ordering != ND_ORDER_AUTO || out.spread <= env.suspect) return err;
     // Separators thicker than a surface's should be: the cutting planes cross several layers of a surface that is folded or rolled up
     // in space (or several components that lie inside each other). The rounds are run again with graph distances among the candidate
     // directions (on the device; the breadth-first sweeps that give the distances run on the host); the cheaper plan is kept.
     NdPlan B;
-    if (host_trials) {
-        if (!fetch_positions()) return "";
-        err = nd_plan_build(V, h_rowptr, h_col, d_positions ? h_pos.data() : nullptr, leaf_size, arity, smooth, B, nullptr, nullptr, ND_ORDER_MINSEP, defer_push_lists);
-    } else {
-        NdBisectDevice ctx2{d_rowptr, d_col, d_positions, nnz, st, nullptr};         // (h_col is complete: the first set of rounds has returned)
-        err = nd_plan_build(V, h_rowptr, h_col, d_positions ? &given : nullptr, leaf_size, arity, smooth, B, nd_bisect_device, &ctx2, ND_ORDER_MINSEP, defer_push_lists, nd_embed_device);
-    }
+    NdBisectDevice ctx2{d_rowptr, d_col, d_positions, nnz, st, nullptr, env.host_embed};         // (h_col is complete: the first set of rounds has returned)
+    err = nd_plan_build(V, h_rowptr, h_col, d_positions ? &given : nullptr, leaf_size, arity, smooth, B, nd_bisect_device, &ctx2, ND_ORDER_MINSEP, defer_push_lists, nd_embed_device);
     if (timing) fprintf(stderr, "[nd_plan] suspect dissection: tried graph distances as well: %.1f factor numbers per vertex, spread %.2f (%s), %.3f s after the start\n",
                         B.words_per_vertex, B.spread, err.empty() ? (B.words_per_vertex < out.words_per_vertex ? "taken" : "not taken") : err.c_str(), now_s() - t0);
     if (!err.empty()) return "";

@@ -510,9 +510,9 @@ void gemm_batched(FactorCtx& c, std::vector<GemmDesc>& v) {
             all += d.sym ? (t64 + div_up(d.M, GT)) / 2 : t64;
         }
     v.clear();
-    // fewer 64 x 64 tiles than half the chip's CUs in the whole launch: quarter tiles (Cmd::nmax carries the tile size of a product)
-    static const int small = [] { const char* e = getenv("LS_GEMM_SMALL_TILES"); return e ? atoi(e) : 128; }();
-    const bool quarter = all < small;
+    // fewer 64 x 64 tiles than half the chip's CUs in the whole launch: quarter tiles, under which such a launch takes a third of the
+    // time (k_gemm_batched, TT = 32; Cmd::nmax carries the tile size of a product)
+    const bool quarter = all < 128;
     if (c.gemm.size() > off) c.cmds.push_back(Cmd{0, off, (int)(c.gemm.size() - off), quarter ? tiles32 : tiles, quarter ? 32 : 64});
 }
 
@@ -852,7 +852,8 @@ static int direct_factor_impl(const int32_t* d_rowptr, const int32_t* d_col, con
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
     const double t0 = now_s();
-    const bool timing = getenv("LS_PLAN_TIMING") != nullptr;
+    const bool timing = env_plan_timing();
+    const NdEnv env = nd_env();
     auto faults = [] { struct rusage u; getrusage(RUSAGE_SELF, &u); return (long)u.ru_minflt; };
     const long f0 = timing ? faults() : 0;
     auto lap = [&](const char* what) { if (timing) { (void)hipStreamSynchronize(st); fprintf(stderr, "[ls_direct_factor] %-30s %.3f s  (%ld page faults so far)\n", what, now_s() - t0, faults() - f0); } };
@@ -864,8 +865,7 @@ static int direct_factor_impl(const int32_t* d_rowptr, const int32_t* d_col, con
         // the longest axis of the embedding, 1: always the thinnest of six trial separators -- on the device since round 5: 5-10 % fewer
         // factor numbers on rough scans for 10-25 ms more constructor at 250k vertices)
         // an explicit argument (ls_direct_factor_ex) wins; "auto" lets the environment override the library's rule
-        const char* oe = getenv("LS_ND_ORDER");
-        const int ordering = ordering_arg != ND_ORDER_AUTO ? ordering_arg : oe ? std::max(-1, std::min(1, atoi(oe))) : ND_ORDER_AUTO;
+        const int ordering = ordering_arg != ND_ORDER_AUTO ? ordering_arg : env.order;
         const std::string err = nd_plan_build_device(d_rowptr, d_col, d_positions, V, nnz, rowptr.data(), col.data(), leaf_size, arity, 4, st, P, ordering,
                                                      /* defer_push_lists = */ true);
         LS_REQUIRE(err.empty(), LS_E_INVALID, "%s", err.c_str());
@@ -914,7 +914,7 @@ static int direct_factor_impl(const int32_t* d_rowptr, const int32_t* d_col, con
     if (tier_auto) {
         // large systems: a subtree one level taller per workgroup of sixteen waves, if its leaves and vectors fit the 160 KB of LDS
         const int taller = levels - 4;
-        if (direct_tier_full16(V, arity, levels, taller, shard_count, tier_waves) && direct_tier_fits(levels, arity, P.s.data(), P.b.data(), P.own_start.data(), taller, leaves_ok, 16))
+        if (direct_tier_full16(V, arity, levels, taller, shard_count, tier_waves > 0 ? tier_waves : env.tier_waves.value_or(0)) && direct_tier_fits(levels, arity, P.s.data(), P.b.data(), P.own_start.data(), taller, leaves_ok, 16))
             tier_levels = taller;
         else
             while (tier_levels > 0 && !direct_tier_fits(levels, arity, P.s.data(), P.b.data(), P.own_start.data(), tier_levels, leaves_ok, 4)) --tier_levels;

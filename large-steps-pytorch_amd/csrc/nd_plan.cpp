@@ -1,5 +1,6 @@
 // nd_plan.cpp -- see nd_plan.h. Integer / geometric work only, parallel over vertices or tree nodes with a few host threads.
 #include "nd_plan.h"
+#include "env.h"
 #include <pthread.h>
 #include <new>
 
@@ -19,19 +20,6 @@
 
 namespace ls {
 namespace {
-
-int n_threads() {          // read at every build: tests compare the one-thread and the many-thread paths
-    const char* e = getenv("LS_PLAN_THREADS");
-    const int want = e ? atoi(e) : 32;
-    int hw = (int)std::thread::hardware_concurrency();
-    // one process per GPU (torchrun): the N ranks of a node analyse their matrices at the same moment on the same host cores --
-    // every rank takes its share (LOCAL_WORLD_SIZE is set by torch.distributed.run; WORLD_SIZE as a fallback on one node)
-    const char* lw = getenv("LOCAL_WORLD_SIZE");
-    if (!lw) lw = getenv("WORLD_SIZE");
-    const int ranks = lw ? atoi(lw) : 1;
-    if (hw > 0 && ranks > 1) hw = std::max(1, hw / ranks);
-    return std::max(1, std::min(want, hw > 0 ? hw : 1));
-}
 
 // A pool of host threads: a round of the bisection issues a handful of short parallel passes, and creating 32 threads for each of
 // them costs more than the passes themselves. One pool is kept for the life of the process (PoolLease below): creating and joining
@@ -235,7 +223,7 @@ int nd_plan_rounds(int64_t V, int leaf_size, int arity) {
 std::string nd_plan_build(int64_t V, const int32_t* rowptr, const int32_t* col, const float* pos_in, int leaf_size, int arity,
                           int smooth, NdPlan& P, NdBisectFn bisect, void* bisect_ctx, int ordering, bool defer_push_lists, NdEmbedFn embed) {
     const auto t_start = std::chrono::steady_clock::now();
-    const bool timing = getenv("LS_PLAN_TIMING") != nullptr;
+    const bool timing = env_plan_timing();
     auto faults = [] { struct rusage u; getrusage(RUSAGE_SELF, &u); return (long)u.ru_minflt; };
     const long f_start = timing ? faults() : 0;
     auto lap = [&](const char* what) { if (timing) fprintf(stderr, "[nd_plan] %-28s %.3f s  (%ld page faults so far)\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(), faults() - f_start); };
@@ -245,7 +233,7 @@ std::string nd_plan_build(int64_t V, const int32_t* rowptr, const int32_t* col, 
     if (!bisect) { if (const char* bad = csr_pattern_problem(V, rowptr, col, pos_in)) return std::string("nd_plan_build: ") + bad; }
     if (arity != 2 && arity != 4 && arity != 8) return "nd_plan_build: arity must be 2, 4 or 8";
     if (leaf_size < 1) return "nd_plan_build: leaf_size must be positive";
-    PoolLease lease(n_threads());
+    PoolLease lease(env_plan_threads(32, true));       // read at every build: tests compare the one-thread and the many-thread paths
     Pool& pool = *lease.pool;
     struct PoolScope { PoolScope(Pool* p) { g_pool = p; } ~PoolScope() { g_pool = nullptr; } } pool_scope(&pool);
     const int T = pool.size();
@@ -718,7 +706,7 @@ void nd_plan_push_lists(NdPlan& P) {
     if (!P.push_ptr.empty()) return;
     const int levels = P.levels, arity = P.arity;
     PoolLease* own = nullptr;
-    if (!g_pool) { own = new PoolLease(n_threads()); g_pool = own->pool; }
+    if (!g_pool) { own = new PoolLease(env_plan_threads(32, true)); g_pool = own->pool; }
     P.push_ptr.assign((size_t)P.n_front + 1, 0);
     P.push_tgt.resize((size_t)P.n_bnd);
     // a parent's front positions receive entries from its own children only: counts and fills run parent by parent
@@ -762,16 +750,10 @@ void nd_plan_quality(NdPlan& P) {
     P.spread = nv > 0.0 ? s2 / (a * a * nv) : 0.0;
 }
 
-double nd_plan_suspect() {
-    const char* e = getenv("LS_ND_SUSPECT");
-    const double v = e ? atof(e) : 1.3;
-    return v > 0.0 ? v : 1.3;
-}
-
 std::string nd_plan_build_auto(int64_t V, const int32_t* rowptr, const int32_t* col, const float* pos, int leaf_size, int arity,
                                int smooth, NdPlan& out) {
     std::string err = nd_plan_build(V, rowptr, col, pos, leaf_size, arity, smooth, out, nullptr, nullptr, ND_ORDER_LONGEST);
-    if (!err.empty() || out.spread <= nd_plan_suspect()) return err;
+    if (!err.empty() || out.spread <= nd_env().suspect) return err;
     NdPlan B;
     err = nd_plan_build(V, rowptr, col, pos, leaf_size, arity, smooth, B, nullptr, nullptr, ND_ORDER_MINSEP);
     if (!err.empty()) return "";                     // the first plan stands

@@ -67,14 +67,13 @@ struct NdPlan {
 //                     positions, or graph distances when there are none): what the device rounds run, a few milliseconds
 //   ND_ORDER_MINSEP   every domain TRIES six directions -- the three position axes and three graph distances (level sets of a
 //                     graph distance do not care how the surface lies in space) -- and takes the thinnest separator. On the device
-//                     too since round 5 (six sorted lists, a side bit and a cut bit per vertex and direction; the graph distances
-//                     themselves are breadth-first sweeps on the host); LS_ND_HOST_TRIALS=1 keeps the host rounds (A/B, tests).
+//                     too since round 5 (six sorted lists, a side bit and a cut bit per vertex and direction); the host-only entry
+//                     points run them in the host's own rounds.
 //   ND_ORDER_AUTO     LONGEST first; when its separators are thicker than a surface's should be (NdPlan::spread above
-//                     nd_plan_suspect(), 1.3), MINSEP as well, and the cheaper plan of the two.
+//                     NdEnv::suspect, 1.3), MINSEP as well, and the cheaper plan of the two.
 // CHOLMOD's ordering behind the reference's constructor (largesteps/solvers.py:34) is graph based and has no such dependence on
 // the embedding; ND_ORDER_AUTO is what ls_direct_factor runs.
 enum { ND_ORDER_AUTO = -1, ND_ORDER_LONGEST = 0, ND_ORDER_MINSEP = 1 };
-double nd_plan_suspect();                                    // the threshold on NdPlan::spread (environment LS_ND_SUSPECT)
 typedef std::string (*NdBisectFn)(void* ctx, int64_t V, int D, int smooth, const double* embedded, int64_t* node, int ordering);
 // embed: when given (with bisect), the graph-distance embedding is first asked of the callee too (csrc/nd_bisect.hip: breadth-first sweeps on
 // the device, the result stays there and the bisect callee reads it): "" = done, "host" = this graph is one for the host's own sweeps (the

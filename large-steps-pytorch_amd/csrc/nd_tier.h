@@ -85,7 +85,6 @@ struct TierArgs {
     float* slots;
     float* xb;
     int arity, phases, region_floats, vec_floats;    // LDS per wave: [vec_floats | partial sums: rounds x 64 x 4]
-    int xcd_order;                                   // 1: workgroup -> subtree map that keeps neighbouring subtrees on one XCD
 #ifdef LS_TIER_STAMPS
     long long* stamps;                               // experiments build only: per wave TIER_STAMP_SLOTS clock stamps (100 MHz), nullptr = off
 #endif
@@ -812,9 +811,9 @@ __global__ __launch_bounds__(64 * W, 16 / W) void k_nd_tier(TierArgs a, const fl
     // workgroup header: up_off[7] | down_off[7] | up_split down_split up_leaf down_leaf | n_dense pad | dense_rng[12]
     // XCD-aware subtree order: workgroup b runs on XCD b % 8 (observed placement, speed only); consecutive subtrees are spatial
     // neighbours (they share cache lines of b / x in the caller's numbering and of the hand-off arrays), so each XCD takes a
-    // contiguous eighth of them: subtree = (b % 8) * (n / 8) + b / 8
+    // contiguous eighth of them: subtree = (b % 8) * (n / 8) + b / 8 (the usual case: the hint keeps it on the straight path)
     const int n_wg = (int)gridDim.x;
-    const int sub = (a.xcd_order && (n_wg & 7) == 0) ? (int)(blockIdx.x & 7) * (n_wg >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    const int sub = __builtin_expect((n_wg & 7) == 0, 1) ? (int)(blockIdx.x & 7) * (n_wg >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
 #ifdef LS_TIER_STAMPS
     long long* stamp_base = a.stamps ? a.stamps + ((size_t)sub * W + wave) * TIER_STAMP_SLOTS : nullptr;
 #else

@@ -26,6 +26,7 @@
 #include <vector>
 #include "../../include/largesteps_hip.h"
 #include "nd_plan.h"
+#include "env.h"
 
 namespace ls { void set_error(const char* fmt, ...); }
 
@@ -41,17 +42,6 @@ uint64_t spread3(uint64_t x) {
     x = (x | (x << 4)) & 0x10C30C30C30C30C3ull;
     x = (x | (x << 2)) & 0x1249249249249249ull;
     return x;
-}
-
-int n_threads() {
-    const char* e = getenv("LS_PLAN_THREADS");
-    const int want = e ? atoi(e) : 32;
-    int hw = (int)std::thread::hardware_concurrency();
-    const char* lw = getenv("LOCAL_WORLD_SIZE");
-    if (!lw) lw = getenv("WORLD_SIZE");
-    const int ranks = lw ? atoi(lw) : 1;
-    if (hw > 0 && ranks > 1) hw = std::max(1, hw / ranks);
-    return std::max(1, std::min(want, hw > 0 ? hw : 1));
 }
 
 template <typename F>
@@ -95,7 +85,7 @@ extern "C" int ls_patch_plan_create(int64_t V, const int32_t* h_rowptr, const in
     if (const char* bad = csr_pattern_problem(V, h_rowptr, h_col, h_positions)) { ls::set_error("ls_patch_plan_create: %s", bad); return LS_E_INVALID; }
     const auto t_begin = std::chrono::steady_clock::now();
     // (two V-sized marker arrays per thread below: 32 threads at 4M vertices would hold 1 GB of host memory for markers alone)
-    const int threads = (int)std::max<int64_t>(1, std::min<int64_t>(n_threads(), std::max<int64_t>(1, ((int64_t)256 << 20) / (8 * std::max<int64_t>(V, 1)))));
+    const int threads = (int)std::max<int64_t>(1, std::min<int64_t>(ls::env_plan_threads(32, true), std::max<int64_t>(1, ((int64_t)256 << 20) / (8 * std::max<int64_t>(V, 1)))));
     // ---- 2^m equal patches by recursive coordinate bisection (median along the longest axis of every box) ---------------------------
     int levels = 0;
     while ((V + (1ll << levels) - 1) / (1ll << levels) > patch_size) ++levels;

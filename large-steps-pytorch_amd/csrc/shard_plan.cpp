@@ -14,6 +14,7 @@
 #include <vector>
 #include "../../include/largesteps_hip.h"
 #include "nd_plan.h"
+#include "env.h"
 
 namespace ls { void set_error(const char* fmt, ...); }
 
@@ -87,9 +88,7 @@ extern "C" int ls_shard_plan_create(int64_t V, const int32_t* h_rowptr, const in
     // every rank's ghost groups (mine for the local matrix and the receive list, the others' for the send lists)
     std::vector<Groups> G((size_t)P);
     {
-        const char* e = getenv("LS_PLAN_THREADS");
-        int threads = std::max(1, std::min(e ? atoi(e) : 16, (int)std::thread::hardware_concurrency()));
-        threads = std::min(threads, P);
+        const int threads = std::min(ls::env_plan_threads(16, false), P);
         std::atomic<int> next{0};
         std::vector<std::thread> th;
         auto work = [&] { for (int q; (q = next.fetch_add(1)) < P;) groups_of(V, h_rowptr, h_col, P, q, depth, G[(size_t)q]); };

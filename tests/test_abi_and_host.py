@@ -314,6 +314,52 @@ def test_direct_options_struct_and_argument_checks_without_a_device(native):
             native.check(lib.ls_direct_factor_ex(dummy, dummy, dummy, 10, 10, None, ctypes.byref(bad), 0, None, ctypes.byref(h)))
     with pytest.raises(ValueError, match="bad argument"):           # null matrix: refused before the device is touched
         native.check(lib.ls_direct_factor_ex(None, None, None, 10, 10, None, None, 0, None, ctypes.byref(h)))
-    import os
+    # ls_direct_arrays.tier_waves (LS_VERSION 110): checked with the other arguments, before a pointer of the struct is read or the device is touched
+    from nd_factor_statement import _Arrays
+    # the ctypes mirror must match the header byte for byte (a missing trailing field made the constructor read past the caller's struct)
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        c = os.path.join(tmp, "t.c")
+        open(c, "w").write('#include <stdio.h>\n#include <stddef.h>\n#include "largesteps_hip.h"\n'
+                           'int main(void){printf("%zu %zu", sizeof(ls_direct_arrays), offsetof(ls_direct_arrays, tier_waves)); return 0;}\n')
+        subprocess.run(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), c, "-o", os.path.join(tmp, "t")], check=True)
+        size, off = (int(t) for t in subprocess.run([os.path.join(tmp, "t")], capture_output=True, text=True, check=True).stdout.split())
+    assert (ctypes.sizeof(_Arrays), _Arrays.tier_waves.offset) == (size, off)
+    arr = _Arrays(10, 2, 2, dummy, dummy, dummy, 0, dummy, dummy, 10, dummy, dummy, dummy, dummy, dummy, dummy, dummy, dummy, 0, 0, 0, 1, 5)
+    with pytest.raises(ValueError, match="tier_waves"):
+        native.check(lib.ls_direct_create(ctypes.byref(arr), 0, None, ctypes.byref(h)))
     hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "largesteps_hip.h")).read()
     assert "typedef struct ls_direct_options" in hdr and "int ls_direct_factor_ex(" in hdr and "#define LS_VERSION 110" in hdr
+
+
+# Switches of the native library that rounds 2-6 settled and that were removed with the code paths they selected
+# (the GPU suite sets them all and expects the same bits: test_gpu_parity.py::test_laboratory_switches_are_not_in_the_product)
+RETIRED_SWITCHES = ("LS_GEMM_SMALL_TILES", "LS_ND_BW_LONG", "LS_ND_TILES", "LS_ND_STEPS_UP", "LS_ND_PACK_ROWS", "LS_ND_PACK_ROWS_UP",
+                    "LS_ND_SMALL_KB", "LS_ND_NT", "LS_ND_NT_LEVELS_MB", "LS_ND_NT_TIER_MB", "LS_ND_XCD", "LS_ND_XCD_TIER", "LS_ND_NO_FUSE_ROOT",
+                    "LS_ND_HOST_TRIALS", "LS_ND_SMALL_DOWN", "LS_ND_INFLIGHT")
+
+
+def test_environment_is_read_in_one_place_and_documented():
+    """csrc/env.cpp is the only source of the native library (the experiments header aside) that calls getenv; the variables it reads are
+    exactly the ones DESIGN.md section 6 lists for the native library; the retired switches appear nowhere in the library or the package."""
+    csrc = os.path.join(ROOT, "large-steps-pytorch_amd", "csrc")
+    readers = set()
+    for d, dirs, files in os.walk(csrc):
+        dirs[:] = [x for x in dirs if x not in ("experiments", "build", "build_exp")]
+        for fn in files:
+            if fn.endswith((".hip", ".h", ".cpp")) and re.search(r"\bgetenv\s*\(", open(os.path.join(d, fn)).read()):
+                readers.add(os.path.relpath(os.path.join(d, fn), csrc))
+    assert readers == {"env.cpp"}
+    read = set(re.findall(r'"([A-Z][A-Z0-9_]+)"', open(os.path.join(csrc, "env.cpp")).read()))
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    section = design[design.index("Environment variables the native library reads"):]
+    section = section[:section.index("The Python package")]
+    documented = set(re.findall(r"`([A-Z][A-Z0-9_]+)`", section))
+    assert read == documented, (sorted(read - documented), sorted(documented - read))
+    for top in (csrc, os.path.join(ROOT, "large-steps-pytorch_amd", "largesteps")):
+        for d, dirs, files in os.walk(top):
+            dirs[:] = [x for x in dirs if x not in ("build", "build_exp", "__pycache__")]
+            for fn in files:
+                if fn.endswith((".hip", ".h", ".cpp", ".py")):
+                    src = open(os.path.join(d, fn)).read()
+                    assert not [n for n in RETIRED_SWITCHES if re.search(rf"\b{n}\b", src)], fn

@@ -506,15 +506,17 @@ def test_direct_solver_widths_and_trees(dev, k, leaf, arity):
     assert inf["factor_entries"] > 0 and inf["launches"] >= 1
 
 
-@pytest.mark.parametrize("env", [{"LS_ND_NO_SMALL": "1"}, {"LS_ND_NO_PACK": "1"}, {"LS_ND_NO_PACK": "1", "LS_ND_NO_SMALL": "1"}, {"LS_ND_SMALL_DOWN": "1", "LS_ND_SMALL_KB": "150"}, {"LS_ND_LONG": "16"},
-                                 {"LS_ND_LONG": "100000", "LS_ND_STEPS": "8"}, {"LS_ND_INFLIGHT": "200", "LS_ND_LONG": "16"},
+# (ids env3 and env6 -- the staged down-sweep kernel and the round-2 chunk rule -- went with their code paths; the other cases keep theirs)
+@pytest.mark.parametrize("env", [{"LS_ND_NO_SMALL": "1"}, {"LS_ND_NO_PACK": "1"}, {"LS_ND_NO_PACK": "1", "LS_ND_NO_SMALL": "1"}, {"LS_ND_LONG": "16"},
+                                 {"LS_ND_LONG": "100000", "LS_ND_STEPS": "8"},
                                  {"LS_ND_TIER_H": "1"}, {"LS_ND_TIER_H": "2"}, {"LS_ND_TIER_H": "3"}, {"LS_ND_TIER_H": "4"}, {"LS_ND_TIER_H": "6"},
                                  {"LS_ND_LONG": "256", "LS_ND_LONG_UP": "64"}, {"LS_ND_TIER_H": "3", "LS_ND_LONG": "256"},
                                  {"LS_ND_DENSE_LEAVES": "1"}, {"LS_ND_DENSE_LEAVES": "1", "LS_ND_TIER_H": "0"},
-                                 {"LS_ND_DENSE_LEAVES": "1", "LS_ND_TIER_H": "5"}])
+                                 {"LS_ND_DENSE_LEAVES": "1", "LS_ND_TIER_H": "5"}],
+                         ids=[f"env{i}" for i in (0, 1, 2, 4, 5, *range(7, 17))])
 def test_direct_solver_kernel_shapes(dev, monkeypatch, env):
     """Every kernel shape of the re-solve (row per lane with 1..16 waves, lanes along the reduction with 1..4 row chunks,
-    LDS-staged small nodes in either sweep; bottom tier of 0..6 levels per workgroup, sparse or dense leaves) forced onto
+    LDS-staged small nodes in the up sweep; bottom tier of 0..6 levels per workgroup, sparse or dense leaves) forced onto
     the same tree: same answer."""
     from largesteps.geometry import compute_matrix
     from largesteps.solvers import NestedDissectionSolver
@@ -537,14 +539,21 @@ def test_laboratory_switches_are_not_in_the_product(dev, monkeypatch):
     """The timing experiments of rounds 2-4 (ablation bits, staggered workgroups, the persistent upper-level launch) are archived source
     (tools/archive/lab/), not code paths of the library: their environment variables change nothing and their options are unknown
     (judge's findings, rounds 2 and 4). The per-wave clock stamps of the tier kernels exist as a BUILD VARIANT only (-DLS_TIER_STAMPS,
-    tools/build_variant.sh): the product library refuses the option."""
+    tools/build_variant.sh): the product library refuses the option. The switches of rounds 2-6 that went with the code paths they selected
+    (test_abi_and_host.RETIRED_SWITCHES) change nothing either: not a bit, not a launch."""
+    from test_abi_and_host import RETIRED_SWITCHES
     from largesteps.geometry import compute_matrix
     from largesteps.solvers import NestedDissectionSolver
     from largesteps import synthetic
     v, f = synthetic.plane(150)
     M = compute_matrix(_t(v, dev), _t(f, dev), 25.0)
     b = _t(np.random.default_rng(3).standard_normal((v.shape[0], 3)).astype(np.float32), dev)
-    x_ref = NestedDissectionSolver(M).solve(b)
+    s0 = NestedDissectionSolver(M)
+    x_ref, n_ref = s0.solve(b), s0.info()["launches"]
+    for name in RETIRED_SWITCHES:           # each set to a value that selected another path while the switch existed
+        monkeypatch.setenv(name, "0" if name in ("LS_ND_XCD", "LS_ND_XCD_TIER", "LS_GEMM_SMALL_TILES") else "1")
+    s = NestedDissectionSolver(M)
+    assert torch.equal(x_ref, s.solve(b)) and s.info()["launches"] == n_ref
     monkeypatch.setenv("LS_ND_ABLATE", "31")
     monkeypatch.setenv("LS_ND_STAGGER", "5")
     monkeypatch.setenv("LS_ND_PERSIST", "1")
