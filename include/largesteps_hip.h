@@ -595,6 +595,37 @@ int ls_average_edge_length_backward(const float* verts, const void* faces, int i
                                     int device, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Botsch-Kobbelt isotropic remeshing (scripts/main.py:149 calls remesh_botsch(v, f, 5, h, True) of an external CPU build):
+ * one iteration = split -> collapse -> flip -> relax -> project, fp32, every phase in rounds of conflict-free operations
+ * ("Isotropic remeshing"; tests/remesh_statement.py states every rule). The output is bitwise reproducible: no float
+ * atomics, ties broken by (value, edge id), new ids from exclusive scans. The output size is not known in advance, hence a handle:
+ *   ls_remesh_create    copies verts (V, 3) fp32 and faces (F, 3) int32 / int64 (idx_bytes 4 / 8) of the device, checks that the
+ *                       mesh is an edge-manifold, consistently oriented triangle mesh whose vertices' faces form one fan each
+ *                       (LS_E_INVALID otherwise, LS_E_INDEX for an index outside [0, V)), drops unreferenced vertices and keeps
+ *                       the result as the projection target. h > 0 is the target edge length (split above 4/3 h, collapse
+ *                       below 4/5 h); project != 0: every iteration ends with the projection. Synchronises the stream.
+ *   ls_remesh_run       `iterations` full iterations. Reads sizes on the host every round: not capturable. SYNC.
+ *   ls_remesh_phase     ONE phase on the current mesh (LS_REMESH_SPLIT / COLLAPSE / FLIP: up to max_rounds rounds, fewer when a
+ *                       round finds nothing to do; RELAX / PROJECT: one pass). For tests of each phase on its own. SYNC.
+ *   ls_remesh_info      V, F of the current mesh; counters[6] = rounds of split, collapse, flip, then splits, collapses, flips
+ *                       done (over all calls); seconds[5] = host wall time per phase (split, collapse, flip, relax, project).
+ *   ls_remesh_copy_out  verts (V, 3) fp32 and faces (F, 3) int32 / int64, device buffers of the caller. ASYNC.
+ *   ls_remesh_destroy   gives the handle's buffers back to the scratch pool (ls_release_scratch empties it).
+ * --------------------------------------------------------------------------------------------- */
+#define LS_REMESH_SPLIT 0
+#define LS_REMESH_COLLAPSE 1
+#define LS_REMESH_FLIP 2
+#define LS_REMESH_RELAX 3
+#define LS_REMESH_PROJECT 4
+int ls_remesh_create(const float* verts, int64_t V, const void* faces, int idx_bytes, int64_t F, float h, int project, int device,
+                     void* stream, void** handle);
+int ls_remesh_run(void* handle, int iterations);
+int ls_remesh_phase(void* handle, int phase, int max_rounds);
+int ls_remesh_info(void* handle, int64_t* V, int64_t* F, int64_t* counters, double* seconds);
+int ls_remesh_copy_out(void* handle, float* verts, void* faces, int idx_bytes);
+int ls_remesh_destroy(void* handle);
+
+/* ------------------------------------------------------------------------------------------------
  * AdamUniform step (optimize.py:18-41) on n contiguous fp32 elements, two kernels, no host sync:
  *   g1 = b1 g1 + (1-b1) g ; g2 = b2 g2 + (1-b2) g^2 ; p -= lr * (g1/(1-b1^t)) / (1e-8 + max sqrt(g2/(1-b2^t)))
  * scratch: at least 4096 bytes of device memory owned by the caller. ASYNC.

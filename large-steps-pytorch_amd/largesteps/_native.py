@@ -96,6 +96,12 @@ _SIGNATURES = {
     "ls_average_edge_length": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_i64, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "ls_average_edge_length_backward": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                 c_size_t, c_int, c_void_p]),
+    "ls_remesh_create": (c_int, [c_void_p, c_i64, c_void_p, c_int, c_i64, c_float, c_int, c_int, c_void_p, ctypes.POINTER(c_void_p)]),
+    "ls_remesh_run": (c_int, [c_void_p, c_int]),
+    "ls_remesh_phase": (c_int, [c_void_p, c_int, c_int]),
+    "ls_remesh_info": (c_int, [c_void_p, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64 * 6), ctypes.POINTER(c_double * 5)]),
+    "ls_remesh_copy_out": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
+    "ls_remesh_destroy": (c_int, [c_void_p]),
     "ls_shard_plan_create": (c_int, [c_i64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
     "ls_shard_plan_destroy": (c_int, [c_void_p]),
     "ls_shard_plan_info": (c_int, [c_void_p] + [ctypes.POINTER(c_i64)] * 5 + [ctypes.POINTER(c_int)] * 2 + [ctypes.POINTER(c_i64)]),
