@@ -22,11 +22,10 @@
 #include <algorithm>
 #include <atomic>
 #include <string.h>
+#include <memory>
 #include <mutex>
 
 namespace ls {
-
-struct NodeDesc { int s, b, own_start, bnd_off, front_off, parent; long long finv_off, w_off; };
 
 // one workgroup's job: a range of rows (from row0) of one node; everything the kernels need in one 64-byte record
 struct alignas(64) Tile {
@@ -813,9 +812,9 @@ struct ls_direct {
     hipEvent_t busy = nullptr;          // recorded after every solve: a solve on another stream waits for it (one workspace)
     hipStream_t last_stream = nullptr;
     bool used = false;
-    std::vector<std::pair<void*, size_t>> tables;      // index tables and vectors of the handle (pool_take / pool_alloc in ls_direct_create; back to the pool with the handle)
-    std::vector<void*> owned;           // device arrays adopted from ls_direct_factor (handed to the buffer pool / freed with the handle)
-    std::vector<size_t> owned_bytes;
+    // index tables and vectors of the handle (pool_take / pool_alloc in ls_direct_create), then the factor arrays adopted from
+    // ls_direct_factor: back to the pool (or freed) with the handle
+    std::vector<std::pair<void*, size_t>> tables;
     ls::RefactorState* refac = nullptr; // ls_direct_factor_refactorable: what ls_direct_refactor needs (nullptr: the handle cannot refactor)
     bool factored = true;               // false after a refactorisation that failed once it had started writing the factor: solves refuse
     // subtree sharding (one process per GPU): this handle runs the subtrees [sub_lo, sub_hi) of level `cut` and, replicated on
@@ -852,8 +851,6 @@ static int pick_nw(int len, int target) {
     while (nw < 16 && len > nw * target) nw *= 2;
     return nw;
 }
-
-int ls_direct_adopt(ls_direct* d, void* const* owned, const size_t* owned_bytes, int n_owned, const double* seconds3, const double* quality4);
 
 // ---- pool of large device buffers --------------------------------------------------------------------------------------------------
 // A remesh loop (scripts/main.py:137-169) destroys a solver and constructs one of nearly the same size again and again. The runtime gives
@@ -1063,16 +1060,6 @@ static size_t plan_tier(const std::vector<NodeD>& nd, const std::vector<int64_t>
 }
 
 
-// Host only, called by ls_direct_factor BEFORE it lays the factor out: would a tier of `tier_levels` levels (sparse or dense leaves)
-// fit the tier kernels' LDS budget on this tree? (s, b, own_start: per node id, 1-based, level-major.)
-static size_t direct_tier_lds(int levels, int arity, const int* s, const int* b, const int* own_start, int tier_levels, bool sparse_leaves, int waves);
-bool direct_tier_fits(int levels, int arity, const int* s, const int* b, const int* own_start, int tier_levels, bool sparse_leaves, int waves) {
-    if (tier_levels <= 0) return true;
-    if (tier_levels > levels || tier_levels > TIER_MAX_H) return false;
-    const size_t bytes = direct_tier_lds(levels, arity, s, b, own_start, tier_levels, sparse_leaves, waves);
-    return bytes && bytes <= (size_t)(waves == TIER_WAVES_FULL ? 160 : 150) * 1024;
-}
-
 // Host only: the dynamic LDS in bytes a tier workgroup of `waves` waves needs for this tree (0 = the tier cannot be planned). Exported as
 // ls_direct_tier_lds_bytes: the CPU tests hold the 1M-vertex closed scan against the 160 KB of a CU with it (round 6: its leaves' 83 boundary
 // rows once made the 16-wave plan 2668 floats per wave -- 4 % over -- and the solve fell back, silently, to 11 launches).
@@ -1098,6 +1085,15 @@ static size_t direct_tier_lds(int levels, int arity, const int* s, const int* b,
     return region ? ((region + 3) & ~(size_t)3) * sizeof(float) * waves : 0;
 }
 
+// Host only, called by ls_direct_factor BEFORE it lays the factor out: would a tier of `tier_levels` levels (sparse or dense leaves)
+// fit the tier kernels' LDS budget on this tree? (s, b, own_start: per node id, 1-based, level-major.)
+bool direct_tier_fits(int levels, int arity, const int* s, const int* b, const int* own_start, int tier_levels, bool sparse_leaves, int waves) {
+    if (tier_levels <= 0) return true;
+    if (tier_levels > levels || tier_levels > TIER_MAX_H) return false;
+    const size_t bytes = direct_tier_lds(levels, arity, s, b, own_start, tier_levels, sparse_leaves, waves);
+    return bytes && bytes <= (size_t)(waves == TIER_WAVES_FULL ? TIER_LDS_FULL : TIER_LDS);
+}
+
 extern "C" int ls_direct_tier_lds_bytes(int levels, int arity, const int32_t* h_s, const int32_t* h_b, const int32_t* h_own_start, int tier_levels,
                                         int sparse_leaves, int waves, size_t* h_bytes) {
     LS_REQUIRE(h_s && h_b && h_own_start && h_bytes && levels >= 1 && levels <= 30 && (arity == 2 || arity == 4 || arity == 8) &&
@@ -1121,68 +1117,48 @@ bool direct_tier_full16(int64_t V, int arity, int levels, int tier_levels, int s
 }
 
 
-extern "C" int ls_direct_create(const ls_direct_arrays* A, int device, void* stream, ls_direct** out) {
-    LS_REQUIRE(A && out, LS_E_INVALID, "ls_direct_create: null argument");
-    LS_REQUIRE(A->tier_waves == 0 || A->tier_waves == TIER_WAVES || A->tier_waves == TIER_WAVES_WIDE || A->tier_waves == TIER_WAVES_FULL, LS_E_INVALID,
-               "ls_direct_create: tier_waves must be 0 (library's rule), 4, 8 or 16");
-    const int64_t V = A->V, n_bnd = A->n_bnd, n_front = A->n_front;
-    const int levels = A->levels, arity = A->arity;
-    const int64_t* h_nodes = A->h_nodes;
-    const int32_t *h_perm = A->h_perm, *h_ppos = A->h_ppos, *h_push_ptr = A->h_push_ptr, *h_push_tgt = A->h_push_tgt;
-    LS_REQUIRE(h_nodes && h_perm && h_push_ptr && V > 0 && levels >= 1 && levels <= 30 && n_bnd >= 0 && n_front >= V &&
-               (arity == 2 || arity == 4 || arity == 8), LS_E_INVALID, "ls_direct_create: bad argument");
-    LS_REQUIRE(V < INT32_MAX && n_bnd < INT32_MAX && n_front * arity < INT32_MAX, LS_E_OVERFLOW, "ls_direct_create: plan exceeds int32 offsets");
-    *out = nullptr;
-    std::vector<int64_t> level_off((size_t)levels + 1);
-    {
-        int64_t cnt = 1, off = 1;
-        for (int lv = 0; lv <= levels; ++lv) {
-            level_off[lv] = off; off += cnt; cnt *= arity;
-            LS_REQUIRE(off < ((int64_t)1 << 30), LS_E_OVERFLOW, "ls_direct_create: tree too large");
-        }
-    }
-    const int n_nodes = (int)(level_off[levels] - 1);
-    DeviceGuard g(device);
-    LS_HIP(g.err);
-    hipStream_t st = (hipStream_t)stream;
-    const bool timing = env_plan_timing();          // host clock only, no synchronisation: where the handle's construction spends its time
-    const NdEnv env = nd_env();
-    const auto t_create = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) { if (timing) fprintf(stderr, "[ls_direct_create] %-28s %.2f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_create).count()); };
-    ls_direct* d = new ls_direct();
-    d->device = device; d->levels = levels; d->arity = arity; d->n_nodes = n_nodes; d->V = V; d->n_bnd = n_bnd; d->n_front = n_front;
-    d->finv = A->d_finv; d->wf = A->d_wf; d->wb = A->d_wb;
-    d->u4 = A->d_u4; d->d4 = A->d_d4;
-    d->tri = A->d_tri; d->sp_ptr = A->d_sp_ptr; d->sp_ent = (const SpEnt*)A->d_sp_ent;
-    // subtree sharding: the cut level is the first one with at least `count` subtrees; rank r takes a contiguous share of them
-    const int n_ranks = std::max(1, (int)A->shard_count), rank = std::min(std::max(0, (int)A->shard_rank), n_ranks - 1);
-    int cut = 0;
-    while (cut + 1 < levels && level_off[cut + 1] - level_off[cut] < n_ranks) ++cut;
-    if (n_ranks == 1) cut = 0;
-    const int64_t n_sub = level_off[cut + 1] - level_off[cut];
-    const int64_t sub_lo = n_sub * rank / n_ranks, sub_hi = n_sub * (rank + 1) / n_ranks;
-    auto active = [&](int64_t i, int lv) -> bool {
+// ---- ls_direct_create's host stages (no device call): the caller's tree (nodes by id, 1-based, level-major), this rank's share of
+// the subtrees of level `cut`, and the tables they build for the upload
+namespace {
+struct CreatePlan {
+    int levels = 0, arity = 0, cut = 0;
+    int64_t sub_lo = 0, sub_hi = 1;
+    std::vector<int64_t> level_off;
+    std::vector<NodeD> nd;
+    std::vector<int> parent;
+    std::vector<unsigned char> mask;
+    std::vector<TierItem> items;
+    std::vector<TierWG> wgs;
+    std::vector<int> pull;
+    std::vector<Tile> tiles;
+    std::vector<PackedTile> ptiles;
+    int64_t span(int from, int to) const { int64_t s = 1; for (int t = from; t < to; ++t) s *= arity; return s; }
+    bool active(int64_t i, int lv) const {
         if (lv < cut) return true;
         int64_t q = i - level_off[lv];
         for (int t = cut; t < lv; ++t) q /= arity;
         return q >= sub_lo && q < sub_hi;
-    };
-    d->shard_rank = rank; d->shard_count = n_ranks; d->cut = cut;
-    std::vector<NodeDesc> nodes((size_t)n_nodes + 1);
-    std::vector<NodeD> nd((size_t)n_nodes + 1);
-    memset(nd.data(), 0, nd.size() * sizeof(NodeD));
+    }
+};
+
+// the node rows, checked: the planner's records, per-level factor words and rows, the nt rule, the children mask
+int read_nodes(const ls_direct_arrays* A, CreatePlan& T, ls_direct* d) {
+    const int levels = T.levels, n_nodes = d->n_nodes;
+    T.nd.assign((size_t)n_nodes + 1, NodeD());
+    T.parent.assign((size_t)n_nodes + 1, 0);
+    d->lvl_up.assign((size_t)levels, 0); d->lvl_down.assign((size_t)levels, 0); d->lvl_rows.assign((size_t)levels, 0); d->lvl_bnd.assign((size_t)levels, 0);
     int64_t fe = 0, fe_up = 0, fe_down = 0;
     for (int i = 1; i <= n_nodes; ++i) {
-        const int64_t* r = h_nodes + (size_t)i * LS_DIRECT_NODE_COLS;
-        NodeDesc& n = nodes[i];
+        const int64_t* r = A->h_nodes + (size_t)i * LS_DIRECT_NODE_COLS;
+        NodeD& n = T.nd[i];
         n.s = (int)r[0]; n.b = (int)r[1]; n.own_start = (int)r[2]; n.bnd_off = (int)r[3]; n.front_off = (int)r[4];
-        n.finv_off = r[5]; n.w_off = r[6]; n.parent = (int)r[7];
+        n.finv_off = r[5]; n.w_off = r[6];
+        const int parent = T.parent[i] = (int)r[7];
         const bool sparse = r[8] >= 0, quad = r[11] != 0;
-        if (n.s < 0 || n.b < 0 || n.own_start < 0 || (int64_t)n.own_start + n.s > V || (int64_t)n.bnd_off + n.b > n_bnd ||
-            (int64_t)n.front_off + n.s + n.b > n_front || (i == 1 ? n.b != 0 : (n.parent < 1 || n.parent >= i)) ||
-            (sparse && (i < level_off[levels - 1] || n.s > 64 || n.s < 1 || !A->d_tri || !A->d_sp_ptr || !A->d_sp_ent || (r[8] & 3))) ||
+        if (n.s < 0 || n.b < 0 || n.own_start < 0 || (int64_t)n.own_start + n.s > d->V || (int64_t)n.bnd_off + n.b > d->n_bnd ||
+            (int64_t)n.front_off + n.s + n.b > d->n_front || (i == 1 ? n.b != 0 : (parent < 1 || parent >= i)) ||
+            (sparse && (i < T.level_off[levels - 1] || n.s > 64 || n.s < 1 || !A->d_tri || !A->d_sp_ptr || !A->d_sp_ent || (r[8] & 3))) ||
             (quad && (sparse || !A->d_u4 || !A->d_d4 || (n.finv_off & 3) || (n.w_off & 3)))) {
-            delete d;
             set_error("ls_direct_create: node %d of the plan is inconsistent", i);
             return LS_E_INVALID;
         }
@@ -1191,14 +1167,18 @@ extern "C" int ls_direct_create(const ls_direct_arrays* A, int device, void* str
         const int64_t down_w = sparse ? tri_w : quad ? (s4 + b4) * n.s : (int64_t)n.s * n.s + (int64_t)n.s * n.b;
         fe += up_w + down_w; fe_up += up_w; fe_down += down_w;
         int lv = 0;
-        while (lv + 1 < levels && i >= level_off[lv + 1]) ++lv;
-        if (d->lvl_up.empty()) { d->lvl_up.assign((size_t)levels, 0); d->lvl_down.assign((size_t)levels, 0); d->lvl_rows.assign((size_t)levels, 0); d->lvl_bnd.assign((size_t)levels, 0); }
+        while (lv + 1 < levels && i >= T.level_off[lv + 1]) ++lv;
         d->lvl_up[(size_t)lv] += up_w; d->lvl_down[(size_t)lv] += down_w;
         d->lvl_rows[(size_t)lv] += n.s; d->lvl_bnd[(size_t)lv] += n.b;
+        n.pfront_off = i > 1 ? T.nd[parent].front_off : -1;
+        n.cix = lv ? (int)((i - T.level_off[lv]) % T.arity) : 0;
+        n.flags = (lv + 1 >= levels ? NODE_LEAF : 0) | (sparse ? NODE_SPARSE : 0) | (quad ? NODE_QUAD : 0);
+        if (sparse) n.finv_off = r[8];
+        n.spb_off = (int)r[9]; n.sps_off = (int)r[10];
     }
     fe += 2 * A->n_sp_ent + A->n_sp_ptr;        // each CSR list is read by one sweep (8-byte entries, 4-byte pointers)
     fe_up += A->n_sp_ent + A->n_sp_ptr / 2; fe_down += A->n_sp_ent + A->n_sp_ptr - A->n_sp_ptr / 2;
-    if (!d->lvl_up.empty()) { d->lvl_up[(size_t)levels - 1] += A->n_sp_ent + A->n_sp_ptr / 2; d->lvl_down[(size_t)levels - 1] += A->n_sp_ent + A->n_sp_ptr - A->n_sp_ptr / 2; }
+    d->lvl_up[(size_t)levels - 1] += A->n_sp_ent + A->n_sp_ptr / 2; d->lvl_down[(size_t)levels - 1] += A->n_sp_ent + A->n_sp_ptr - A->n_sp_ptr / 2;
     d->factor_entries = fe; d->words_up = fe_up; d->words_down = fe_down;
     // Cache policy of the read-once factor streams (common.h, ld_stream; profiles/r05_nt_policy.txt: us per solve, default / nt):
     //   70k 70 / 78   250k 88 / 96   490k 139 / 133 (level kernels only; + tier: 140)   1M 214 / 199   2M 450 / 431   4M 722 / 705
@@ -1210,322 +1190,337 @@ extern "C" int ls_direct_create(const ls_direct_arrays* A, int device, void* str
         d->nt_rule[0] = d->nt_levels = mb > 256.0;
         d->nt_rule[1] = d->nt_tier = mb > 400.0;
     }
-    for (int lv = 0; lv < levels; ++lv)
-        for (int64_t i = level_off[lv]; i < level_off[lv + 1]; ++i) {
-            const NodeDesc& n = nodes[i];
-            const int64_t* r = h_nodes + (size_t)i * LS_DIRECT_NODE_COLS;
-            NodeD& q = nd[i];
-            q.s = n.s; q.b = n.b; q.own_start = n.own_start; q.bnd_off = n.bnd_off; q.front_off = n.front_off;
-            q.pfront_off = i > 1 ? nodes[n.parent].front_off : -1;
-            q.cix = lv ? (int)((i - level_off[lv]) % arity) : 0;
-            q.flags = (lv + 1 >= levels ? NODE_LEAF : 0) | (r[8] >= 0 ? NODE_SPARSE : 0) | (r[11] != 0 ? NODE_QUAD : 0);
-            q.finv_off = r[8] >= 0 ? r[8] : n.finv_off; q.w_off = n.w_off;
-            q.spb_off = (int)r[9]; q.sps_off = (int)r[10];
-        }
-    // which children contribute to a front position: bit c of mask[f]
-    std::vector<unsigned char> mask((size_t)n_front, 0);
-    for (int lv = 1; lv < levels; ++lv)
-        for (int64_t i = level_off[lv]; i < level_off[lv + 1]; ++i) {
-            const NodeDesc& n = nodes[i];
-            const int cix = (int)((i - level_off[lv]) % arity);
-            const NodeDesc& p = nodes[n.parent];
+    for (int lv = 1; lv < levels; ++lv)             // which children contribute to a front position: bit c of mask[f]
+        for (int64_t i = T.level_off[lv]; i < T.level_off[lv + 1]; ++i) {
+            const NodeD &n = T.nd[i], &p = T.nd[T.parent[i]];
             for (int k = 0; k < n.b; ++k) {
-                const int pp = h_ppos[n.bnd_off + k];
+                const int pp = A->h_ppos[n.bnd_off + k];
                 if (pp < 0 || pp >= p.s + p.b) {
-                    delete d;
                     set_error("ls_direct_create: ppos out of range at node %lld", (long long)i);
                     return LS_E_INVALID;
                 }
-                mask[(size_t)p.front_off + pp] |= (unsigned char)(1u << cix);
+                T.mask[(size_t)p.front_off + pp] |= (unsigned char)(1u << n.cix);
             }
         }
-    // bottom tier: the levels whose nodes the caller stored in the tier kernels' layouts (quad-interleaved / sparse leaves)
-    // run as one launch per sweep; every level above is one launch per sweep (unpadded finv / wf / wb)
-    std::vector<TierItem> items;
-    std::vector<TierWG> wgs;
-    {
-        int root = levels;
-        for (int lv = levels - 1; lv >= 0; --lv) {
-            bool tiered = false, plain = false;
-            for (int64_t i = level_off[lv]; i < level_off[lv + 1]; ++i) {
-                if (nd[i].s == 0 && nd[i].b == 0) continue;
-                if (nd[i].flags & (NODE_SPARSE | NODE_QUAD)) tiered = true; else plain = true;
-            }
-            if (tiered && plain) { delete d; set_error("ls_direct_create: level %d mixes tier-layout and plain nodes", lv); return LS_E_INVALID; }
-            if (plain) break;
-            if (tiered && root != lv + 1) { delete d; set_error("ls_direct_create: tier-layout levels must be the deepest ones"); return LS_E_INVALID; }
-            if (tiered) root = lv;
+    return LS_OK;
+}
+
+// Bottom tier: the levels whose nodes the caller stored in the tier kernels' layouts (quad-interleaved / sparse leaves) run as one
+// launch per sweep; every level above is one launch per sweep (unpadded finv / wf / wb). The kernel that will run is the one whose
+// budget is checked: sixteen waves first where the rule asks for them (a subtree one level taller may fit 160 KB as 16 regions and not
+// 150 KB as 4), else four, else eight for few subtrees. Sets the handle's tier_* fields (tier_root = levels: no tier) and the pull table.
+int choose_tier(CreatePlan& T, const int32_t* h_ppos, int tier_waves, const NdEnv& env, ls_direct* d) {
+    const int levels = T.levels;
+    int root = levels;
+    for (int lv = levels - 1; lv >= 0; --lv) {
+        bool tiered = false, plain = false;
+        for (int64_t i = T.level_off[lv]; i < T.level_off[lv + 1]; ++i) {
+            if (T.nd[i].s == 0 && T.nd[i].b == 0) continue;
+            if (T.nd[i].flags & (NODE_SPARSE | NODE_QUAD)) tiered = true; else plain = true;
         }
-        for (int lv = 0; lv < root; ++lv)
-            for (int64_t i = level_off[lv]; i < level_off[lv + 1]; ++i)
-                if (nd[i].flags & (NODE_SPARSE | NODE_QUAD)) { delete d; set_error("ls_direct_create: tier-layout node above the tier"); return LS_E_INVALID; }
-        d->tier_root = levels;
-        if (root < levels) {
-            const int H = levels - root;
-            if (cut > root) { delete d; set_error("ls_direct_create: %d ranks need a cut below the tier's root level (tree too small)", n_ranks); return LS_E_INVALID; }
-            int64_t span = 1;
-            for (int t = cut; t < root; ++t) span *= arity;
-            // the kernel that will run is the one whose budget is checked: sixteen waves first where the rule asks for them (a subtree one
-            // level taller may fit 160 KB as 16 regions and not 150 KB as 4), the 4- / 8-wave plans otherwise
-            size_t region = 0;
-            if (H <= TIER_MAX_H && direct_tier_full16(V, arity, levels, H, n_ranks, A->tier_waves > 0 ? A->tier_waves : env.tier_waves.value_or(0))) {
-                int vec16 = 0, tri16 = 0;
-                const size_t region16 = plan_tier(nd, level_off, levels, arity, root, sub_lo * span, sub_hi * span, items, wgs, vec16, tri16, TIER_WAVES_FULL);
-                if (region16 && ((region16 + 3) & ~(size_t)3) * sizeof(float) * TIER_WAVES_FULL <= 160 * 1024) {
-                    d->tier_vec = vec16; d->tier_tri = tri16; region = region16; d->tier_waves = TIER_WAVES_FULL;
-                }
-            }
-            if (!region) {
-                region = H <= TIER_MAX_H ? plan_tier(nd, level_off, levels, arity, root, sub_lo * span, sub_hi * span, items, wgs, d->tier_vec, d->tier_tri) : 0;
-                if (!region || region * sizeof(float) * TIER_WAVES > 150 * 1024) {
-                    delete d;
-                    set_error("ls_direct_create: a tier of %d levels does not fit the kernel (LDS per wave: %zu floats)", H, region);
-                    return LS_E_WORKSPACE;
-                }
-                // few subtrees (<= 768 workgroups: three per CU or less): 8 waves per workgroup, two workgroups per CU, if that fits the LDS
-                // (a tier of the leaf level alone -- dense leaves of 2-4 row chunks -- does not gain: 40k vertices 44.3 against 42.7 us)
-                if (H >= 2 && (int)wgs.size() <= 768 && (A->tier_waves > 0 ? A->tier_waves : env.tier_waves.value_or(TIER_WAVES_WIDE)) == TIER_WAVES_WIDE) {
-                    std::vector<TierItem> items8;
-                    std::vector<TierWG> wgs8;
-                    int vec8 = 0, tri8 = 0;
-                    const size_t region8 = plan_tier(nd, level_off, levels, arity, root, sub_lo * span, sub_hi * span, items8, wgs8, vec8, tri8, TIER_WAVES_WIDE);
-                    if (region8 && ((region8 + 3) & ~(size_t)3) * sizeof(float) * TIER_WAVES_WIDE <= 80 * 1024) {
-                        items.swap(items8); wgs.swap(wgs8); d->tier_vec = vec8; d->tier_tri = tri8; region = region8; d->tier_waves = TIER_WAVES_WIDE;
-                    }
-                }
-            }
-            d->tier_root = root; d->tier_phases = H; d->tier_wgs = (int)wgs.size(); d->tier_region = (int)((region + 3) & ~(size_t)3);
-        }
+        if (tiered && plain) { set_error("ls_direct_create: level %d mixes tier-layout and plain nodes", lv); return LS_E_INVALID; }
+        if (plain) break;
+        if (tiered && root != lv + 1) { set_error("ls_direct_create: tier-layout levels must be the deepest ones"); return LS_E_INVALID; }
+        if (tiered) root = lv;
     }
-    d->upper_lo = (d->tier_root < levels && d->tier_root > 0) ? nodes[level_off[d->tier_root - 1]].own_start : (int)V;
-    std::vector<int> pull;
-    if (d->tier_root < levels) {
-        // only the tier's inner nodes are parents inside the tier: their front positions are one range (fronts are numbered level by level)
-        d->pull_base = nodes[level_off[d->tier_root]].front_off;
-        const int64_t pull_end = nodes[level_off[levels - 1]].front_off;
-        pull.assign((size_t)std::max<int64_t>(0, pull_end - d->pull_base) * arity, -1);
-        for (int lv = d->tier_root + 1; lv < levels; ++lv)
-            for (int64_t i = level_off[lv]; i < level_off[lv + 1]; ++i) {
-                const NodeDesc& n = nodes[i];
-                const int cix = (int)((i - level_off[lv]) % arity);
-                const int64_t pf = nodes[n.parent].front_off;
-                for (int k = 0; k < n.b; ++k) pull[(size_t)(pf - d->pull_base + h_ppos[n.bnd_off + k]) * arity + cix] = n.bnd_off + k;
-            }
+    for (int lv = 0; lv < root; ++lv)
+        for (int64_t i = T.level_off[lv]; i < T.level_off[lv + 1]; ++i)
+            if (T.nd[i].flags & (NODE_SPARSE | NODE_QUAD)) { set_error("ls_direct_create: tier-layout node above the tier"); return LS_E_INVALID; }
+    d->tier_root = levels;
+    if (root == levels) return LS_OK;
+    const int H = levels - root;
+    if (T.cut > root) { set_error("ls_direct_create: %d ranks need a cut below the tier's root level (tree too small)", d->shard_count); return LS_E_INVALID; }
+    const int64_t span = T.span(T.cut, root), q_lo = T.sub_lo * span, q_hi = T.sub_hi * span;
+    size_t region = 0;
+    // a plan for `waves` waves per workgroup, taken when its region (rounded to 4 floats) fits `budget` bytes
+    auto take_if_fits = [&](int waves, int budget) {
+        std::vector<TierItem> items;
+        std::vector<TierWG> wgs;
+        int vec = 0, tri = 0;
+        const size_t r = plan_tier(T.nd, T.level_off, levels, T.arity, root, q_lo, q_hi, items, wgs, vec, tri, waves);
+        if (!r || ((r + 3) & ~(size_t)3) * sizeof(float) * waves > (size_t)budget) return;
+        T.items.swap(items); T.wgs.swap(wgs); d->tier_vec = vec; d->tier_tri = tri; region = r; d->tier_waves = waves;
+    };
+    if (H <= TIER_MAX_H && direct_tier_full16(d->V, T.arity, levels, H, d->shard_count, tier_waves > 0 ? tier_waves : env.tier_waves.value_or(0)))
+        take_if_fits(TIER_WAVES_FULL, TIER_LDS_FULL);
+    if (!region) {
+        region = H <= TIER_MAX_H ? plan_tier(T.nd, T.level_off, levels, T.arity, root, q_lo, q_hi, T.items, T.wgs, d->tier_vec, d->tier_tri) : 0;
+        // (the region unrounded here, rounded to 4 floats in direct_tier_fits and the 8- and 16-wave checks)
+        if (!region || region * sizeof(float) * TIER_WAVES > TIER_LDS) {
+            set_error("ls_direct_create: a tier of %d levels does not fit the kernel (LDS per wave: %zu floats)", H, region);
+            return LS_E_WORKSPACE;
+        }
+        // few subtrees (<= 768 workgroups: three per CU or less): 8 waves per workgroup, two workgroups per CU, if that fits the LDS
+        // (a tier of the leaf level alone -- dense leaves of 2-4 row chunks -- does not gain: 40k vertices 44.3 against 42.7 us)
+        if (H >= 2 && (int)T.wgs.size() <= 768 && (tier_waves > 0 ? tier_waves : env.tier_waves.value_or(TIER_WAVES_WIDE)) == TIER_WAVES_WIDE)
+            take_if_fits(TIER_WAVES_WIDE, TIER_LDS_WIDE);
     }
-    // tiles of the upper levels: a range of rows of one node each
-    std::vector<Tile> tiles;
-    std::vector<PackedTile> ptiles;
-    auto tile_of = [&](int64_t i, int r, int lv, int forward) {
-        const NodeDesc& n = nodes[i];
+    d->tier_root = root; d->tier_phases = H; d->tier_wgs = (int)T.wgs.size(); d->tier_region = (int)((region + 3) & ~(size_t)3);
+    // tier up sweep: (front position - pull_base, child) -> child boundary entry. Only the tier's inner nodes are parents inside the tier:
+    // their front positions are one range (fronts are numbered level by level)
+    d->pull_base = T.nd[T.level_off[root]].front_off;
+    T.pull.assign((size_t)std::max<int64_t>(0, T.nd[T.level_off[levels - 1]].front_off - d->pull_base) * T.arity, -1);
+    for (int lv = root + 1; lv < levels; ++lv)
+        for (int64_t i = T.level_off[lv]; i < T.level_off[lv + 1]; ++i) {
+            const NodeD& n = T.nd[i];
+            for (int k = 0; k < n.b; ++k) T.pull[(size_t)(n.pfront_off - d->pull_base + h_ppos[n.bnd_off + k]) * T.arity + n.cix] = n.bnd_off + k;
+        }
+    return LS_OK;
+}
+
+// One level above the tier: kernel shapes, tiles and packed tiles of this rank's nodes. Returns the LDS bytes its front needs.
+size_t plan_level(CreatePlan& T, int lv, int long_up, const NdEnv& env, int kmax, LevelPlan& p) {
+    std::vector<Tile>& tiles = T.tiles;
+    // this rank's nodes of the level: one contiguous range (all of them above the cut)
+    int64_t a0 = T.level_off[lv], a1 = T.level_off[lv + 1];
+    if (lv >= T.cut) { const int64_t span = T.span(T.cut, lv); a0 = T.level_off[lv] + T.sub_lo * span; a1 = T.level_off[lv] + T.sub_hi * span; }
+    auto tile_of = [&](int64_t i, int r, int forward) {          // a range of rows of one node
+        const NodeD& n = T.nd[i];
         Tile t;
         t.store = 0; t.row0 = r; t.s = n.s; t.b = n.b; t.own_start = n.own_start; t.bnd_off = n.bnd_off; t.front_off = n.front_off;
-        t.leaf = lv + 1 >= levels;
-        t.pfront_off = i > 1 ? nodes[n.parent].front_off : -1;
-        t.cix = lv ? (int)((i - level_off[lv]) % arity) : 0;
-        t.forward = forward; t.arity = arity; t.finv_off = n.finv_off; t.w_off = n.w_off;
+        t.leaf = lv + 1 >= T.levels; t.pfront_off = n.pfront_off; t.cix = n.cix;
+        t.forward = forward; t.arity = T.arity; t.finv_off = n.finv_off; t.w_off = n.w_off;
         return t;
     };
+    int red_up = 0, red_down = 0;
+    for (int64_t i = a0; i < a1; ++i) {
+        p.s_cap = std::max(p.s_cap, T.nd[i].s); p.b_cap = std::max(p.b_cap, T.nd[i].b);
+        red_up = std::max(red_up, T.nd[i].s); red_down = std::max(red_down, T.nd[i].s + T.nd[i].b);
+    }
+    // long reductions: lanes along the reduction (k_nd_*_b), ND_ROWS * ND_BW rows per tile; short: a row per lane
+    p.up_b = red_up >= long_up; p.down_b = red_down >= env.long_red;
+    // *_b kernels, shape per level (measured at 1M vertices, profiles/r03_level_kernel_variants.txt):
+    //  * every tile assembles its node's whole reduction vector -- long vectors (the top levels: 2000 entries, four 16-byte slot
+    //    records each) want FEW, FAT workgroups: 8 waves from ~1400 entries on (root 15.0 -> 13.9 us, level 1 15.2 -> 14.3 / 17.3 -> 16.3);
+    //  * below that 4 waves, and as many row chunks per wave (<= 4) as still leave ~500 tiles in the level (two per CU; 1M: level 4 down
+    //    19.6 -> 17.2 us with 4 chunks, level 3 down 18.9 -> 15.7 with 2).
+    // (round 5, docs/measurements.md: 900 or 2100 entries for 8 waves, 250 or 1000 tiles per level: up to 3 % slower at 1M and 4M)
+    const int up_bw = std::min(ND_BW, red_up >= 1400 ? 8 : 4), down_bw = std::min(ND_BW, red_down >= 1400 ? 8 : 4);
+    // (the row-per-lane up kernel: 32 reduction steps per wave; 16 or 64 cost 3-13 % of a 1M-vertex solve, round 5)
+    p.up_nw = p.up_b ? up_bw : pick_nw(red_up, 32); p.down_nw = p.down_b ? down_bw : pick_nw(red_down, env.steps);
+    int64_t rows_up = 0, rows_down = 0;
+    for (int64_t i = a0; i < a1; ++i) { rows_up += T.nd[i].b; rows_down += T.nd[i].s; }
+    auto pick_chunks = [&](int64_t rows, int bw) {
+        int c = 4;
+        while (c > 1 && rows / (ND_ROWS * bw * c) < 500) --c;
+        return c;
+    };
+    p.up_chunks = pick_chunks(rows_up, up_bw);
+    p.down_chunks = pick_chunks(rows_down, down_bw);
+    const int up_rows = p.up_b ? ND_ROWS * up_bw * p.up_chunks : WAVE, down_rows = p.down_b ? ND_ROWS * down_bw * p.down_chunks : WAVE;
+    // small nodes, up sweep: the whole W staged in 40 KB of LDS at most, one workgroup per node, a row per thread
+    // (measured at 1M: staging pays for the up sweep -- W only, 42 + 18 + 15 us against 45 + 21 + 17 -- but not for the
+    //  down sweep, whose Finv + W footprint left 6 single-wave workgroups per CU: 151 us against 57: the down sweep has no staged kernel)
+    const size_t up_s_bytes = ((size_t)p.s_cap * p.b_cap + (size_t)p.s_cap * kmax) * sizeof(float);
+    p.up_s = p.b_cap <= 256 && p.s_cap <= 256 && up_s_bytes <= 40 * 1024 && !env.no_small;
+    if (p.up_s) { p.up_b = 0; p.up_nw = std::max(1, div_up(p.b_cap, WAVE)); }
+    // tiny nodes: several nodes per wave (packed tiles), when at least two nodes of the level fit a wave. Largest row count of a
+    // level that is still packed: a wave up, half a wave down (measured at 1M: packing pairs of ~31-row leaves helps the up
+    // sweep, 42 -> 37 us, while packed down tiles only pay below half a wave)
+    p.up_p = !env.no_pack && p.b_cap <= WAVE && p.s_cap <= 256 && lv > 0;
+    p.down_p = !env.no_pack && p.s_cap <= WAVE / 2;
+    auto pack_level = [&](bool up_sweep, int& first, int& count, int& lds_rows_s, int& lds_rows_b) {
+        first = (int)T.ptiles.size();
+        lds_rows_s = lds_rows_b = 0;
+        int64_t i = a0;
+        while (i < a1) {
+            PackedTile t;
+            memset(&t, 0, sizeof(t));
+            t.leaf = lv + 1 >= T.levels; t.arity = T.arity;
+            int rows = 0;
+            while (i < a1 && t.n < ND_PACK) {
+                const NodeD& nd = T.nd[i];
+                const int r = up_sweep ? nd.b : nd.s;
+                if (t.n && rows + r > WAVE) break;
+                NodeP& q = t.d[t.n];
+                q.s = nd.s; q.b = nd.b; q.own_start = nd.own_start; q.bnd_off = nd.bnd_off; q.front_off = nd.front_off;
+                q.pfront_off = nd.pfront_off; q.cix = nd.cix; q.pad = 0; q.finv_off = nd.finv_off; q.w_off = nd.w_off;
+                t.row0[t.n + 1] = t.row0[t.n] + r;
+                t.sb0[t.n + 1] = t.sb0[t.n] + nd.s;
+                t.sx0[t.n + 1] = t.sx0[t.n] + nd.b;
+                rows += r; ++t.n; ++i;
+            }
+            for (int c = t.n + 1; c <= ND_PACK; ++c) { t.row0[c] = t.row0[t.n]; t.sb0[c] = t.sb0[t.n]; t.sx0[c] = t.sx0[t.n]; }
+            lds_rows_s = std::max(lds_rows_s, t.sb0[t.n]); lds_rows_b = std::max(lds_rows_b, t.sx0[t.n]);
+            T.ptiles.push_back(t);
+        }
+        count = (int)T.ptiles.size() - first;
+    };
+    int dummy = 0;
+    if (p.up_p) { pack_level(true, p.up_p_first, p.up_p_tiles, p.up_p_lds, dummy); p.up_s = 0; p.up_b = 0; }
+    if (p.down_p) { pack_level(false, p.down_p_first, p.down_p_tiles, p.down_p_s, p.down_p_lds); p.down_b = 0; }
+    p.up_first = (int)tiles.size();
+    const int up_threads = WAVE * p.up_nw;
+    std::vector<int> up_nodes;                                 // node (index within the level) of every tile pushed below
+    for (int64_t i = a0; i < a1; ++i) {
+        // b' of the own rows is kept for the down sweep: by the first compute tile (small nodes, or nodes whose only
+        // tile exists for that purpose), or by store-only tiles of blockDim rows each (large nodes: the one tile
+        // would walk s / blockDim dependent load chains)
+        const bool store_tiles = !p.up_s && T.nd[i].s > 2 * up_threads;
+        const int rows = std::max(T.nd[i].b, (T.nd[i].s && !store_tiles) ? 1 : 0);
+        for (int r = 0; r < rows; r += (p.up_s ? 1 << 30 : up_rows)) {
+            tiles.push_back(tile_of(i, r, 0));
+            tiles.back().store = (r == 0 && !store_tiles) ? 1 : 0;
+            up_nodes.push_back((int)(i - a0));
+        }
+        if (store_tiles)
+            for (int r = 0; r < T.nd[i].s; r += up_threads) { tiles.push_back(tile_of(i, r, 0)); tiles.back().store = 2; up_nodes.push_back((int)(i - a0)); }
+    }
+    // XCD-aware order: workgroup b runs on XCD b % 8 (observed placement, speed only) and every tile of a node re-assembles the node's
+    // reduction vector (slots, masks, b) -- with a node's tiles on ONE XCD those reads hit that XCD's L2 instead of being fetched once per
+    // XCD (PMC, round 3: 55 MB per launch of the row-per-lane up kernel for 29 MB of factor). Levels with fewer than 8 nodes keep the
+    // plain order (a node must not be confined to the 32 CUs of one XCD).
+    auto xcd_order = [&](int first, std::vector<int>& node_of_tile) {
+        const int n = (int)tiles.size() - first;
+        if (a1 - a0 < 8 || n < 16) return;
+        std::vector<std::vector<Tile>> bucket(8);
+        for (int t = 0; t < n; ++t) bucket[(size_t)(node_of_tile[(size_t)t] & 7)].push_back(tiles[(size_t)(first + t)]);
+        size_t longest = 0;
+        for (auto& bk : bucket) longest = std::max(longest, bk.size());
+        Tile idle;
+        memset(&idle, 0, sizeof(idle));
+        idle.store = 3; idle.forward = 2;                     // a tile that returns at once (pads the shorter buckets)
+        tiles.resize((size_t)first);
+        for (size_t r = 0; r < longest; ++r)
+            for (int x = 0; x < 8; ++x) tiles.push_back(r < bucket[(size_t)x].size() ? bucket[(size_t)x][r] : idle);
+    };
+    xcd_order(p.up_first, up_nodes);
+    p.up_tiles = (int)tiles.size() - p.up_first;
+    p.down_first = (int)tiles.size();
+    std::vector<int> down_nodes;
+    for (int64_t i = a0; i < a1; ++i)
+        for (int r = 0; r < T.nd[i].s; r += down_rows) { tiles.push_back(tile_of(i, r, 0)); down_nodes.push_back((int)(i - a0)); }
+    if (lv + 1 < T.levels)      // forward tiles: boundary rows of every node
+        for (int64_t i = a0; i < a1; ++i)
+            for (int r = 0; r < T.nd[i].b; r += WAVE * p.down_nw) { tiles.push_back(tile_of(i, r, 1)); down_nodes.push_back((int)(i - a0)); }
+    xcd_order(p.down_first, down_nodes);
+    p.down_tiles = (int)tiles.size() - p.down_first;
+    return ((size_t)p.s_cap + p.b_cap + 16 * WAVE) * kmax * sizeof(float);
+}
+
+// the static index bytes of every level's launches, and how evenly the tier's subtrees are loaded
+void account_index_bytes(const CreatePlan& T, ls_direct* d) {
+    const int levels = T.levels, arity = T.arity;
+    d->lvl_idx_up.assign((size_t)levels, 0); d->lvl_idx_down.assign((size_t)levels, 0);
+    std::vector<int64_t> fpos((size_t)levels, 0), bsum((size_t)levels + 1, 0);
+    for (int lv = 0; lv < levels; ++lv)
+        for (int64_t i = T.level_off[lv]; i < T.level_off[lv + 1]; ++i)
+            if (T.active(i, lv)) { fpos[(size_t)lv] += T.nd[i].s + T.nd[i].b; bsum[(size_t)lv] += T.nd[i].b; }
+    for (int lv = 0; lv < d->tier_root; ++lv) {
+        const LevelPlan& p = d->plan[lv];
+        // up: tile records, the children mask of every front position, the parent positions of the boundary rows (+ perm when no
+        // tier launch gathered b into the tree's numbering); down: tile records, row pointers of the push lists, the children's targets
+        d->lvl_idx_up[(size_t)lv] = (p.up_p ? (int64_t)p.up_p_tiles * (int64_t)sizeof(PackedTile) : (int64_t)p.up_tiles * (int64_t)sizeof(Tile)) + fpos[(size_t)lv] + 4 * bsum[(size_t)lv];
+        d->lvl_idx_down[(size_t)lv] = (p.down_p ? (int64_t)p.down_p_tiles * (int64_t)sizeof(PackedTile) : (int64_t)p.down_tiles * (int64_t)sizeof(Tile)) + 4 * fpos[(size_t)lv] +
+                                      4 * bsum[(size_t)lv + 1];
+    }
+    if (d->tier_root >= levels) return;
+    const int H = levels - d->tier_root;
+    // item records by the level they belong to: phase ph of the up sweep is level levels - 1 - ph, of the down sweep tier_root + ph
+    for (const TierWG& g : T.wgs)
+        for (int ph = 0; ph < H; ++ph) {
+            d->lvl_idx_up[(size_t)(levels - 1 - ph)] += (int64_t)(g.up_off[ph + 1] - g.up_off[ph]) * (int64_t)sizeof(TierItem);
+            d->lvl_idx_down[(size_t)(d->tier_root + ph)] += (int64_t)(g.down_off[ph + 1] - g.down_off[ph]) * (int64_t)sizeof(TierItem);
+        }
+    d->lvl_idx_up[(size_t)d->tier_root] += (int64_t)T.wgs.size() * (int64_t)sizeof(TierWG);
+    d->lvl_idx_down[(size_t)d->tier_root] += (int64_t)T.wgs.size() * (int64_t)sizeof(TierWG);
+    for (int lv = d->tier_root; lv < levels; ++lv) {
+        const bool inner = lv + 1 < levels;
+        // up: an inner node pulls its children's updates through `arity` indices per front position; the tier's root level and the
+        // leaves read the parent positions of their boundary rows. down: push-list pointers per front position + the children's targets
+        if (inner) d->lvl_idx_up[(size_t)lv] += 4 * (int64_t)arity * fpos[(size_t)lv];
+        if (lv == d->tier_root || !inner) d->lvl_idx_up[(size_t)lv] += 4 * bsum[(size_t)lv];
+        if (inner) d->lvl_idx_down[(size_t)lv] += 4 * fpos[(size_t)lv] + 4 * bsum[(size_t)lv + 1];
+    }
+    // factor words per subtree = per workgroup: with one workgroup per CU the slowest subtree is the launch's time
+    const int64_t q0 = T.sub_lo * T.span(T.cut, d->tier_root);
+    double mx[2] = {0, 0}, sum[2] = {0, 0};
+    for (size_t w = 0; w < T.wgs.size(); ++w) {
+        double wu = 0, wd = 0;
+        int64_t span = 1;
+        for (int lv = d->tier_root; lv < levels; ++lv) {
+            const int64_t first = T.level_off[lv] + (q0 + (int64_t)w) * span;
+            for (int64_t i = first; i < first + span; ++i) {
+                const NodeD& n = T.nd[i];
+                const double s4 = (n.s + 3) & ~3, b4 = (n.b + 3) & ~3, tri_w = ((int64_t)n.s * (n.s + 1) / 2 + 3) & ~(int64_t)3;
+                if (n.flags & NODE_SPARSE) { wu += tri_w + 3.0 * n.b; wd += tri_w + 3.0 * n.b; }      // (+ ~3 words per boundary row of sparse block and pointers)
+                else { wu += s4 * n.b; wd += (s4 + b4) * n.s; }
+            }
+            span *= arity;
+        }
+        mx[0] = std::max(mx[0], wu); mx[1] = std::max(mx[1], wd); sum[0] += wu; sum[1] += wd;
+    }
+    const double nw = (double)std::max<size_t>(T.wgs.size(), 1);
+    d->tier_balance[0] = mx[0]; d->tier_balance[1] = sum[0] / nw; d->tier_balance[2] = mx[1]; d->tier_balance[3] = sum[1] / nw;
+}
+
+}  // namespace
+
+extern "C" int ls_direct_create(const ls_direct_arrays* A, int device, void* stream, ls_direct** out) {
+    LS_REQUIRE(A && out, LS_E_INVALID, "ls_direct_create: null argument");
+    LS_REQUIRE(A->tier_waves == 0 || A->tier_waves == TIER_WAVES || A->tier_waves == TIER_WAVES_WIDE || A->tier_waves == TIER_WAVES_FULL, LS_E_INVALID,
+               "ls_direct_create: tier_waves must be 0 (library's rule), 4, 8 or 16");
+    const int64_t V = A->V, n_bnd = A->n_bnd, n_front = A->n_front;
+    const int levels = A->levels, arity = A->arity;
+    LS_REQUIRE(A->h_nodes && A->h_perm && A->h_push_ptr && V > 0 && levels >= 1 && levels <= 30 && n_bnd >= 0 && n_front >= V &&
+               (arity == 2 || arity == 4 || arity == 8), LS_E_INVALID, "ls_direct_create: bad argument");
+    LS_REQUIRE(V < INT32_MAX && n_bnd < INT32_MAX && n_front * arity < INT32_MAX, LS_E_OVERFLOW, "ls_direct_create: plan exceeds int32 offsets");
+    *out = nullptr;
+    CreatePlan T{levels, arity};
+    T.level_off.resize((size_t)levels + 1);
+    {
+        int64_t cnt = 1, off = 1;
+        for (int lv = 0; lv <= levels; ++lv) {
+            T.level_off[lv] = off; off += cnt; cnt *= arity;
+            LS_REQUIRE(off < ((int64_t)1 << 30), LS_E_OVERFLOW, "ls_direct_create: tree too large");
+        }
+    }
+    DeviceGuard g(device);
+    LS_HIP(g.err);
+    hipStream_t st = (hipStream_t)stream;
+    const bool timing = env_plan_timing();          // host clock only, no synchronisation: where the handle's construction spends its time
+    const NdEnv env = nd_env();
+    const auto t_create = std::chrono::steady_clock::now();
+    auto lap = [&](const char* what) { if (timing) fprintf(stderr, "[ls_direct_create] %-28s %.2f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_create).count()); };
+    std::unique_ptr<ls_direct, int (*)(ls_direct*)> d(new ls_direct(), ls_direct_destroy);
+    d->device = device; d->levels = levels; d->arity = arity; d->n_nodes = (int)(T.level_off[levels] - 1); d->V = V; d->n_bnd = n_bnd; d->n_front = n_front;
+    d->finv = A->d_finv; d->wf = A->d_wf; d->wb = A->d_wb;
+    d->u4 = A->d_u4; d->d4 = A->d_d4;
+    d->tri = A->d_tri; d->sp_ptr = A->d_sp_ptr; d->sp_ent = (const SpEnt*)A->d_sp_ent;
+    // subtree sharding: the cut level is the first one with at least `count` subtrees; rank r takes a contiguous share of them
+    const int n_ranks = std::max(1, (int)A->shard_count), rank = std::min(std::max(0, (int)A->shard_rank), n_ranks - 1);
+    int cut = 0;
+    while (cut + 1 < levels && T.level_off[cut + 1] - T.level_off[cut] < n_ranks) ++cut;
+    if (n_ranks == 1) cut = 0;
+    const int64_t n_sub = T.level_off[cut + 1] - T.level_off[cut];
+    T.sub_lo = n_sub * rank / n_ranks; T.sub_hi = n_sub * (rank + 1) / n_ranks;
+    d->shard_rank = rank; d->shard_count = n_ranks; d->cut = T.cut = cut;
+    T.mask.assign((size_t)n_front, 0);
+    int rc = LS_OK;
+    if ((rc = read_nodes(A, T, d.get())) || (rc = choose_tier(T, A->h_ppos, A->tier_waves, env, d.get()))) return rc;
+    d->upper_lo = (d->tier_root < levels && d->tier_root > 0) ? T.nd[T.level_off[d->tier_root - 1]].own_start : (int)V;
     d->plan.resize(levels);
     size_t lds_max = 0;
     // (measured over 576 .. 1M vertices, tools/tier_sweep.py: the down sweep of levels with s + b of 90 .. 250 runs 5-10 % of a
     //  whole solve faster with the lanes along the reduction; the up sweep of the s = 125 nodes of an 8-level tree loses 2-3 %)
-    const int long_red = env.long_red;                                              // down sweep (reduction s + b)
     const int long_up = env.long_up > 0 ? env.long_up : levels >= 8 ? 256 : 64;      // up sweep (reduction s): small trees gain 1-3 % from 64
-    for (int lv = 0; lv < d->tier_root; ++lv) {
-        LevelPlan& p = d->plan[lv];
-        // this rank's nodes of the level: one contiguous range (all of them above the cut)
-        int64_t a0 = level_off[lv], a1 = level_off[lv + 1];
-        if (lv >= cut) { int64_t span = 1; for (int t = cut; t < lv; ++t) span *= arity; a0 = level_off[lv] + sub_lo * span; a1 = level_off[lv] + sub_hi * span; }
-        int red_up = 0, red_down = 0;
-        for (int64_t i = a0; i < a1; ++i) {
-            p.s_cap = std::max(p.s_cap, nodes[i].s); p.b_cap = std::max(p.b_cap, nodes[i].b);
-            red_up = std::max(red_up, nodes[i].s); red_down = std::max(red_down, nodes[i].s + nodes[i].b);
-        }
-        // long reductions: lanes along the reduction (k_nd_*_b), ND_ROWS * ND_BW rows per tile; short: a row per lane
-        p.up_b = red_up >= long_up; p.down_b = red_down >= long_red;
-        // *_b kernels, shape per level (measured at 1M vertices, profiles/r03_level_kernel_variants.txt):
-        //  * every tile assembles its node's whole reduction vector -- long vectors (the top levels: 2000 entries, four 16-byte slot
-        //    records each) want FEW, FAT workgroups: 8 waves from ~1400 entries on (root 15.0 -> 13.9 us, level 1 15.2 -> 14.3 / 17.3 -> 16.3);
-        //  * below that 4 waves, and as many row chunks per wave (<= 4) as still leave ~500 tiles in the level (two per CU; 1M: level 4 down
-        //    19.6 -> 17.2 us with 4 chunks, level 3 down 18.9 -> 15.7 with 2).
-        // (round 5, docs/measurements.md: 900 or 2100 entries for 8 waves, 250 or 1000 tiles per level: up to 3 % slower at 1M and 4M)
-        const int up_bw = std::min(ND_BW, red_up >= 1400 ? 8 : 4), down_bw = std::min(ND_BW, red_down >= 1400 ? 8 : 4);
-        // (the row-per-lane up kernel: 32 reduction steps per wave; 16 or 64 cost 3-13 % of a 1M-vertex solve, round 5)
-        p.up_nw = p.up_b ? up_bw : pick_nw(red_up, 32); p.down_nw = p.down_b ? down_bw : pick_nw(red_down, env.steps);
-        int64_t rows_up = 0, rows_down = 0;
-        for (int64_t i = a0; i < a1; ++i) { rows_up += nodes[i].b; rows_down += nodes[i].s; }
-        auto pick_chunks = [&](int64_t rows, int bw) {
-            int c = 4;
-            while (c > 1 && rows / (ND_ROWS * bw * c) < 500) --c;
-            return c;
-        };
-        p.up_chunks = pick_chunks(rows_up, up_bw);
-        p.down_chunks = pick_chunks(rows_down, down_bw);
-        const int up_rows = p.up_b ? ND_ROWS * up_bw * p.up_chunks : WAVE, down_rows = p.down_b ? ND_ROWS * down_bw * p.down_chunks : WAVE;
-        // small nodes, up sweep: the whole W staged in 40 KB of LDS at most, one workgroup per node, a row per thread
-        // (measured at 1M: staging pays for the up sweep -- W only, 42 + 18 + 15 us against 45 + 21 + 17 -- but not for the
-        //  down sweep, whose Finv + W footprint left 6 single-wave workgroups per CU: 151 us against 57: the down sweep has no staged kernel)
-        const size_t up_s_bytes = ((size_t)p.s_cap * p.b_cap + (size_t)p.s_cap * d->kmax) * sizeof(float);
-        p.up_s = p.b_cap <= 256 && p.s_cap <= 256 && up_s_bytes <= 40 * 1024 && !env.no_small;
-        if (p.up_s) { p.up_b = 0; p.up_nw = std::max(1, div_up(p.b_cap, WAVE)); }
-        // tiny nodes: several nodes per wave (packed tiles), when at least two nodes of the level fit a wave. Largest row count of a
-        // level that is still packed: a wave up, half a wave down (measured at 1M: packing pairs of ~31-row leaves helps the up
-        // sweep, 42 -> 37 us, while packed down tiles only pay below half a wave)
-        p.up_p = !env.no_pack && p.b_cap <= WAVE && p.s_cap <= 256 && lv > 0;
-        p.down_p = !env.no_pack && p.s_cap <= WAVE / 2;
-        auto pack_level = [&](bool up_sweep, int& first, int& count, int& lds_rows_s, int& lds_rows_b) {
-            first = (int)ptiles.size();
-            lds_rows_s = lds_rows_b = 0;
-            int64_t i = a0;
-            while (i < a1) {
-                PackedTile t;
-                memset(&t, 0, sizeof(t));
-                t.leaf = lv + 1 >= levels; t.arity = arity;
-                int rows = 0;
-                while (i < a1 && t.n < ND_PACK) {
-                    const NodeDesc& nd = nodes[i];
-                    const int r = up_sweep ? nd.b : nd.s;
-                    if (t.n && rows + r > WAVE) break;
-                    NodeP& q = t.d[t.n];
-                    q.s = nd.s; q.b = nd.b; q.own_start = nd.own_start; q.bnd_off = nd.bnd_off; q.front_off = nd.front_off;
-                    q.pfront_off = i > 1 ? nodes[nd.parent].front_off : -1;
-                    q.cix = lv ? (int)((i - level_off[lv]) % arity) : 0; q.pad = 0; q.finv_off = nd.finv_off; q.w_off = nd.w_off;
-                    t.row0[t.n + 1] = t.row0[t.n] + r;
-                    t.sb0[t.n + 1] = t.sb0[t.n] + nd.s;
-                    t.sx0[t.n + 1] = t.sx0[t.n] + nd.b;
-                    rows += r; ++t.n; ++i;
-                }
-                for (int c = t.n + 1; c <= ND_PACK; ++c) { t.row0[c] = t.row0[t.n]; t.sb0[c] = t.sb0[t.n]; t.sx0[c] = t.sx0[t.n]; }
-                lds_rows_s = std::max(lds_rows_s, t.sb0[t.n]); lds_rows_b = std::max(lds_rows_b, t.sx0[t.n]);
-                ptiles.push_back(t);
-            }
-            count = (int)ptiles.size() - first;
-        };
-        int dummy = 0;
-        if (p.up_p) { pack_level(true, p.up_p_first, p.up_p_tiles, p.up_p_lds, dummy); p.up_s = 0; p.up_b = 0; }
-        if (p.down_p) { pack_level(false, p.down_p_first, p.down_p_tiles, p.down_p_s, p.down_p_lds); p.down_b = 0; }
-        p.up_first = (int)tiles.size();
-        const int up_threads = WAVE * p.up_nw;
-        std::vector<int> up_nodes;                                 // node (index within the level) of every tile pushed below
-        for (int64_t i = a0; i < a1; ++i) {
-            // b' of the own rows is kept for the down sweep: by the first compute tile (small nodes, or nodes whose only
-            // tile exists for that purpose), or by store-only tiles of blockDim rows each (large nodes: the one tile
-            // would walk s / blockDim dependent load chains)
-            const bool store_tiles = !p.up_s && nodes[i].s > 2 * up_threads;
-            const int rows = std::max(nodes[i].b, (nodes[i].s && !store_tiles) ? 1 : 0);
-            for (int r = 0; r < rows; r += (p.up_s ? 1 << 30 : up_rows)) {
-                tiles.push_back(tile_of(i, r, lv, 0));
-                tiles.back().store = (r == 0 && !store_tiles) ? 1 : 0;
-                up_nodes.push_back((int)(i - a0));
-            }
-            if (store_tiles)
-                for (int r = 0; r < nodes[i].s; r += up_threads) { tiles.push_back(tile_of(i, r, lv, 0)); tiles.back().store = 2; up_nodes.push_back((int)(i - a0)); }
-        }
-        // XCD-aware order: workgroup b runs on XCD b % 8 (observed placement, speed only) and every tile of a node re-assembles
-        // the node's reduction vector (slots, masks, b) -- with a node's tiles on ONE XCD those reads hit that XCD's L2 instead of
-        // being fetched once per XCD (PMC, round 3: 55 MB per launch of the row-per-lane up kernel for 29 MB of factor). Levels
-        // with fewer than 8 nodes keep the plain order (a node must not be confined to the 32 CUs of one XCD).
-        auto xcd_order = [&](int first, std::vector<int>& node_of_tile) {
-            const int n = (int)tiles.size() - first;
-            if (a1 - a0 < 8 || n < 16) return;
-            std::vector<std::vector<Tile>> bucket(8);
-            for (int t = 0; t < n; ++t) bucket[(size_t)(node_of_tile[(size_t)t] & 7)].push_back(tiles[(size_t)(first + t)]);
-            size_t longest = 0;
-            for (auto& bk : bucket) longest = std::max(longest, bk.size());
-            Tile idle;
-            memset(&idle, 0, sizeof(idle));
-            idle.store = 3; idle.forward = 2;                     // a tile that returns at once (pads the shorter buckets)
-            tiles.resize((size_t)first);
-            for (size_t r = 0; r < longest; ++r)
-                for (int x = 0; x < 8; ++x) tiles.push_back(r < bucket[(size_t)x].size() ? bucket[(size_t)x][r] : idle);
-        };
-        xcd_order(p.up_first, up_nodes);
-        p.up_tiles = (int)tiles.size() - p.up_first;
-        p.down_first = (int)tiles.size();
-        std::vector<int> down_nodes;
-        for (int64_t i = a0; i < a1; ++i)
-            for (int r = 0; r < nodes[i].s; r += down_rows) { tiles.push_back(tile_of(i, r, lv, 0)); down_nodes.push_back((int)(i - a0)); }
-        if (lv + 1 < levels)      // forward tiles: boundary rows of every node
-            for (int64_t i = a0; i < a1; ++i)
-                for (int r = 0; r < nodes[i].b; r += WAVE * p.down_nw) { tiles.push_back(tile_of(i, r, lv, 1)); down_nodes.push_back((int)(i - a0)); }
-        xcd_order(p.down_first, down_nodes);
-        p.down_tiles = (int)tiles.size() - p.down_first;
-        lds_max = std::max(lds_max, ((size_t)p.s_cap + p.b_cap + 16 * WAVE) * d->kmax * sizeof(float));
-    }
-    // ---- accounting (host only): the static index bytes of every level's launches, and how evenly the tier's subtrees are loaded -------
-    {
-        d->lvl_idx_up.assign((size_t)levels, 0); d->lvl_idx_down.assign((size_t)levels, 0);
-        std::vector<int64_t> fpos((size_t)levels, 0), bsum((size_t)levels + 1, 0);
-        for (int lv = 0; lv < levels; ++lv)
-            for (int64_t i = level_off[lv]; i < level_off[lv + 1]; ++i)
-                if (active(i, lv)) { fpos[(size_t)lv] += nodes[i].s + nodes[i].b; bsum[(size_t)lv] += nodes[i].b; }
-        for (int lv = 0; lv < d->tier_root; ++lv) {
-            const LevelPlan& p = d->plan[lv];
-            // up: tile records, the children mask of every front position, the parent positions of the boundary rows (+ perm when no
-            // tier launch gathered b into the tree's numbering); down: tile records, row pointers of the push lists, the children's targets
-            d->lvl_idx_up[(size_t)lv] = (p.up_p ? (int64_t)p.up_p_tiles * (int64_t)sizeof(PackedTile) : (int64_t)p.up_tiles * (int64_t)sizeof(Tile)) + fpos[(size_t)lv] + 4 * bsum[(size_t)lv];
-            d->lvl_idx_down[(size_t)lv] = (p.down_p ? (int64_t)p.down_p_tiles * (int64_t)sizeof(PackedTile) : (int64_t)p.down_tiles * (int64_t)sizeof(Tile)) + 4 * fpos[(size_t)lv] +
-                                          4 * bsum[(size_t)lv + 1];
-        }
-        if (d->tier_root < levels) {
-            const int H = levels - d->tier_root;
-            // item records by the level they belong to: phase ph of the up sweep is level levels - 1 - ph, of the down sweep tier_root + ph
-            for (const TierWG& g : wgs)
-                for (int ph = 0; ph < H; ++ph) {
-                    d->lvl_idx_up[(size_t)(levels - 1 - ph)] += (int64_t)(g.up_off[ph + 1] - g.up_off[ph]) * (int64_t)sizeof(TierItem);
-                    d->lvl_idx_down[(size_t)(d->tier_root + ph)] += (int64_t)(g.down_off[ph + 1] - g.down_off[ph]) * (int64_t)sizeof(TierItem);
-                }
-            d->lvl_idx_up[(size_t)d->tier_root] += (int64_t)wgs.size() * (int64_t)sizeof(TierWG);
-            d->lvl_idx_down[(size_t)d->tier_root] += (int64_t)wgs.size() * (int64_t)sizeof(TierWG);
-            for (int lv = d->tier_root; lv < levels; ++lv) {
-                const bool inner = lv + 1 < levels;
-                // up: an inner node pulls its children's updates through `arity` indices per front position; the tier's root level and the
-                // leaves read the parent positions of their boundary rows. down: push-list pointers per front position + the children's targets
-                if (inner) d->lvl_idx_up[(size_t)lv] += 4 * (int64_t)arity * fpos[(size_t)lv];
-                if (lv == d->tier_root || !inner) d->lvl_idx_up[(size_t)lv] += 4 * bsum[(size_t)lv];
-                if (inner) d->lvl_idx_down[(size_t)lv] += 4 * fpos[(size_t)lv] + 4 * bsum[(size_t)lv + 1];
-            }
-            // factor words per subtree = per workgroup: with one workgroup per CU the slowest subtree is the launch's time
-            int64_t span0 = 1;
-            for (int t = cut; t < d->tier_root; ++t) span0 *= arity;
-            const int64_t q0 = sub_lo * span0;
-            double mx[2] = {0, 0}, sum[2] = {0, 0};
-            for (size_t w = 0; w < wgs.size(); ++w) {
-                double wu = 0, wd = 0;
-                int64_t span = 1;
-                for (int lv = d->tier_root; lv < levels; ++lv) {
-                    const int64_t first = level_off[lv] + (q0 + (int64_t)w) * span;
-                    for (int64_t i = first; i < first + span; ++i) {
-                        const NodeD& n = nd[i];
-                        const double s4 = (n.s + 3) & ~3, b4 = (n.b + 3) & ~3, tri_w = ((int64_t)n.s * (n.s + 1) / 2 + 3) & ~(int64_t)3;
-                        if (n.flags & NODE_SPARSE) { wu += tri_w + 3.0 * n.b; wd += tri_w + 3.0 * n.b; }      // (+ ~3 words per boundary row of sparse block and pointers)
-                        else { wu += s4 * n.b; wd += (s4 + b4) * n.s; }
-                    }
-                    span *= arity;
-                }
-                mx[0] = std::max(mx[0], wu); mx[1] = std::max(mx[1], wd); sum[0] += wu; sum[1] += wd;
-            }
-            const double nw = (double)std::max<size_t>(wgs.size(), 1);
-            d->tier_balance[0] = mx[0]; d->tier_balance[1] = sum[0] / nw; d->tier_balance[2] = mx[1]; d->tier_balance[3] = sum[1] / nw;
-        }
-    }
-    if (lds_max > 150 * 1024) {
-        delete d;
+    for (int lv = 0; lv < d->tier_root; ++lv) lds_max = std::max(lds_max, plan_level(T, lv, long_up, env, d->kmax, d->plan[lv]));
+    account_index_bytes(T, d.get());
+    if (lds_max > LEVEL_LDS) {
         set_error("ls_direct_create: a front needs %zu bytes of LDS (separator too large for this kernel)", lds_max);
         return LS_E_INVALID;
     }
     if (n_ranks > 1 && cut >= 1) {
-        d->exch_f0 = nodes[level_off[cut - 1]].front_off;
-        d->exch_f1 = nodes[level_off[cut]].front_off;
+        d->exch_f0 = T.nd[T.level_off[cut - 1]].front_off;
+        d->exch_f1 = T.nd[T.level_off[cut]].front_off;
     }
     if (n_ranks > 1) {        // designated owner of every row of x: the rank that runs the row's subtree, rank 0 for the replicated levels
         d->owned_rows.assign((size_t)V, 0);
         for (int lv = 0; lv < levels; ++lv)
-            for (int64_t i = level_off[lv]; i < level_off[lv + 1]; ++i)
-                if (lv < cut ? rank == 0 : active(i, lv))
-                    for (int r = 0; r < nodes[i].s; ++r) d->owned_rows[(size_t)h_perm[nodes[i].own_start + r]] = 1;
+            for (int64_t i = T.level_off[lv]; i < T.level_off[lv + 1]; ++i)
+                if (lv < cut ? rank == 0 : T.active(i, lv))
+                    for (int r = 0; r < T.nd[i].s; ++r) d->owned_rows[(size_t)A->h_perm[T.nd[i].own_start + r]] = 1;
     }
-    int rc = LS_OK;
     lap("tables built (host)");
     // The tables go up on a stream of their own: `st` is busy with the factorisation when ls_direct_factor calls this (a copy from
     // pageable memory queued behind it kept the HOST waiting until the last kernel was done, and ~50 MB of index lists then crossed
@@ -1544,53 +1539,44 @@ extern "C" int ls_direct_create(const ls_direct_arrays* A, int device, void* str
         if (n) LS_HIP(hipMemcpyAsync(*dst, src, n * sizeof(**dst), hipMemcpyHostToDevice, su));
         return LS_OK;
     };
-    if (!(rc = up(&d->tiles, tiles.data(), tiles.size())) && !(rc = up(&d->ptiles, ptiles.data(), ptiles.size())) &&
-        !(rc = up(&d->perm, h_perm, (size_t)V)) &&
-        !(rc = up(&d->ppos, h_ppos, (size_t)n_bnd)) && !(rc = up(&d->push_ptr, h_push_ptr, (size_t)n_front + 1)) &&
-        !(rc = up(&d->push_tgt, h_push_tgt, (size_t)n_bnd)) && !(rc = up(&d->mask, mask.data(), mask.size())) &&
-        !(rc = up(&d->d_items, items.data(), items.size())) && !(rc = up(&d->pull, pull.data(), pull.size())) &&
-        !(rc = up(&d->d_wgs, wgs.data(), wgs.size()))) {
-        hipError_t e = table((void**)&d->bp, sizeof(float) * (size_t)V * d->kmax);
-        if (e == hipSuccess) e = table((void**)&d->braw, sizeof(float) * (size_t)V * d->kmax);
-        if (e == hipSuccess) e = table((void**)&d->slots, sizeof(float) * (size_t)n_front * arity * d->kmax);
-        if (e == hipSuccess) e = table((void**)&d->xb, sizeof(float) * (size_t)std::max<int64_t>(n_bnd, 1) * d->kmax);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&d->busy, hipEventDisableTiming);
-        lap("uploads enqueued, vectors allocated");
-        if (e == hipSuccess) e = hipEventRecord(d->busy, su);
-        if (e == hipSuccess) e = hipStreamWaitEvent(st, d->busy, 0);      // whatever follows on the caller's stream sees the tables
-        if (e == hipSuccess) e = hipStreamSynchronize(su);               // the host vectors above go out of scope
-        lap("uploads done");
-        if (e != hipSuccess) rc = hip_fail(e, "ls_direct_create allocations", __FILE__, __LINE__);
-    }
-    if (rc != LS_OK) { ls_direct_destroy(d); return rc; }
+    if ((rc = up(&d->tiles, T.tiles.data(), T.tiles.size())) || (rc = up(&d->ptiles, T.ptiles.data(), T.ptiles.size())) ||
+        (rc = up(&d->perm, A->h_perm, (size_t)V)) ||
+        (rc = up(&d->ppos, A->h_ppos, (size_t)n_bnd)) || (rc = up(&d->push_ptr, A->h_push_ptr, (size_t)n_front + 1)) ||
+        (rc = up(&d->push_tgt, A->h_push_tgt, (size_t)n_bnd)) || (rc = up(&d->mask, T.mask.data(), T.mask.size())) ||
+        (rc = up(&d->d_items, T.items.data(), T.items.size())) || (rc = up(&d->pull, T.pull.data(), T.pull.size())) ||
+        (rc = up(&d->d_wgs, T.wgs.data(), T.wgs.size())))
+        return rc;
+    hipError_t e = table((void**)&d->bp, sizeof(float) * (size_t)V * d->kmax);
+    if (e == hipSuccess) e = table((void**)&d->braw, sizeof(float) * (size_t)V * d->kmax);
+    if (e == hipSuccess) e = table((void**)&d->slots, sizeof(float) * (size_t)n_front * d->arity * d->kmax);
+    if (e == hipSuccess) e = table((void**)&d->xb, sizeof(float) * (size_t)std::max<int64_t>(n_bnd, 1) * d->kmax);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&d->busy, hipEventDisableTiming);
+    lap("uploads enqueued, vectors allocated");
+    if (e == hipSuccess) e = hipEventRecord(d->busy, su);
+    if (e == hipSuccess) e = hipStreamWaitEvent(st, d->busy, 0);      // whatever follows on the caller's stream sees the tables
+    if (e == hipSuccess) e = hipStreamSynchronize(su);               // the host tables go out of scope
+    lap("uploads done");
+    if (e != hipSuccess) return hip_fail(e, "ls_direct_create allocations", __FILE__, __LINE__);
     // kernels of the top levels may need more than 64 KiB of dynamic LDS
-#define LS_OPTIN(KK)                                                                                                   \
-    (void)hipFuncSetAttribute((const void*)k_nd_up<KK, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);       \
-    (void)hipFuncSetAttribute((const void*)k_nd_down<KK, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);     \
-    (void)hipFuncSetAttribute((const void*)k_nd_up_b<KK, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);     \
-    (void)hipFuncSetAttribute((const void*)k_nd_down_b<KK, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);   \
-    (void)hipFuncSetAttribute((const void*)k_nd_up<KK, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);        \
-    (void)hipFuncSetAttribute((const void*)k_nd_down<KK, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);      \
-    (void)hipFuncSetAttribute((const void*)k_nd_up_b<KK, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);      \
-    (void)hipFuncSetAttribute((const void*)k_nd_down_b<KK, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);    \
-    (void)hipFuncSetAttribute((const void*)k_nd_up_s<KK>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    LS_OPTIN(1) LS_OPTIN(2) LS_OPTIN(3) LS_OPTIN(4)
+    static const void* const kernels[] = {
+#define LS_OPTIN(KK)                                                                                                                \
+        (const void*)k_nd_up<KK, false>, (const void*)k_nd_down<KK, false>, (const void*)k_nd_up_b<KK, false>,                      \
+        (const void*)k_nd_down_b<KK, false>, (const void*)k_nd_up<KK, true>, (const void*)k_nd_down<KK, true>,                      \
+        (const void*)k_nd_up_b<KK, true>, (const void*)k_nd_down_b<KK, true>, (const void*)k_nd_up_s<KK>,
+        LS_OPTIN(1) LS_OPTIN(2) LS_OPTIN(3) LS_OPTIN(4)
 #undef LS_OPTIN
-#define LS_OPTIN(KK)                                                                                                       \
-    (void)hipFuncSetAttribute((const void*)k_nd_tier<KK, true, TIER_WAVES, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);   \
-    (void)hipFuncSetAttribute((const void*)k_nd_tier<KK, false, TIER_WAVES, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);  \
-    (void)hipFuncSetAttribute((const void*)k_nd_tier<KK, true, TIER_WAVES, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);    \
-    (void)hipFuncSetAttribute((const void*)k_nd_tier<KK, false, TIER_WAVES, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);   \
-    (void)hipFuncSetAttribute((const void*)k_nd_tier<KK, true, TIER_WAVES_WIDE, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);   \
-    (void)hipFuncSetAttribute((const void*)k_nd_tier<KK, false, TIER_WAVES_WIDE, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);  \
-    (void)hipFuncSetAttribute((const void*)k_nd_tier<KK, true, TIER_WAVES_FULL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);   \
-    (void)hipFuncSetAttribute((const void*)k_nd_tier<KK, false, TIER_WAVES_FULL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);  \
-    (void)hipFuncSetAttribute((const void*)k_nd_tier<KK, true, TIER_WAVES_FULL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);    \
-    (void)hipFuncSetAttribute((const void*)k_nd_tier<KK, false, TIER_WAVES_FULL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    LS_OPTIN(1) LS_OPTIN(2) LS_OPTIN(3) LS_OPTIN(4)
+#define LS_OPTIN(KK)                                                                                                                \
+        (const void*)k_nd_tier<KK, true, TIER_WAVES, false>, (const void*)k_nd_tier<KK, false, TIER_WAVES, false>,                  \
+        (const void*)k_nd_tier<KK, true, TIER_WAVES, true>, (const void*)k_nd_tier<KK, false, TIER_WAVES, true>,                    \
+        (const void*)k_nd_tier<KK, true, TIER_WAVES_WIDE, false>, (const void*)k_nd_tier<KK, false, TIER_WAVES_WIDE, false>,        \
+        (const void*)k_nd_tier<KK, true, TIER_WAVES_FULL, false>, (const void*)k_nd_tier<KK, false, TIER_WAVES_FULL, false>,        \
+        (const void*)k_nd_tier<KK, true, TIER_WAVES_FULL, true>, (const void*)k_nd_tier<KK, false, TIER_WAVES_FULL, true>,
+        LS_OPTIN(1) LS_OPTIN(2) LS_OPTIN(3) LS_OPTIN(4)
 #undef LS_OPTIN
+    };
+    for (const void* k : kernels) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_OPTIN);
     lap("kernel attributes set");
-    *out = d;
+    *out = d.release();
     return LS_OK;
 }
 
@@ -1598,11 +1584,9 @@ extern "C" int ls_direct_destroy(ls_direct* d) {
     if (!d) return LS_OK;
     DeviceGuard g(d->device);
     if (d->busy) (void)hipEventDestroy(d->busy);
-    (void)hipDeviceSynchronize();                                   // (what hipFree did implicitly: nothing of the handle is in flight any more)
-    for (const auto& t : d->tables)                                 // tiles, perm, ppos, push lists, mask, items, pull, wgs; bp, braw, slots, xb
+    if (!d->tables.empty()) (void)hipDeviceSynchronize();           // (what hipFree did implicitly: nothing of the handle is in flight any more)
+    for (const auto& t : d->tables)                                 // tiles, perm, ppos, push lists, mask, items, pull, wgs; bp, braw, slots, xb; factor arrays
         if (!ls::pool_give(d->device, t.first, t.second)) (void)hipFree(t.first);
-    for (size_t i = 0; i < d->owned.size(); ++i)
-        if (!ls::pool_give(d->device, d->owned[i], i < d->owned_bytes.size() ? d->owned_bytes[i] : 0)) (void)hipFree(d->owned[i]);
     ls::refactor_state_free(d->refac);
     for (hipEvent_t e : d->ev) (void)hipEventDestroy(e);
 #ifdef LS_TIER_STAMPS
@@ -1830,17 +1814,11 @@ extern "C" int ls_direct_set(ls_direct* d, const char* name, int value) {
     return LS_E_INVALID;
 }
 
-int ls_direct_adopt(ls_direct* d, void* const* owned, const size_t* owned_bytes, int n_owned, const double* seconds3, const double* quality4) {
-    d->owned.assign(owned, owned + n_owned);
-    d->owned_bytes.assign(owned_bytes, owned_bytes + n_owned);
+int ls_direct_adopt(ls_direct* d, std::vector<std::pair<void*, size_t>> owned, const double* seconds3, const double* quality4, ls::RefactorState* refac) {
+    d->tables.insert(d->tables.end(), owned.begin(), owned.end());
+    d->refac = refac;
     for (int i = 0; i < 3; ++i) d->factor_s[i] = seconds3[i];
     for (int i = 0; i < 4; ++i) d->plan_q[i] = quality4[i];
-    return LS_OK;
-}
-
-int ls_direct_adopt_refactor(ls_direct* d, ls::RefactorState* state) {
-    ls::refactor_state_free(d->refac);
-    d->refac = state;
     return LS_OK;
 }
 

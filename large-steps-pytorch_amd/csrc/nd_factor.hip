@@ -750,8 +750,7 @@ int refactor_run(RefactorState* R, const int32_t* d_rowptr, const int32_t* d_col
 
 // defined in direct.hip: builds the handle from plan + factor arrays and takes ownership of the device arrays
 extern "C" int ls_direct_create(const ls_direct_arrays* A, int device, void* stream, ls_direct** out);
-int ls_direct_adopt(ls_direct* d, void* const* owned, const size_t* owned_bytes, int n_owned, const double* seconds3, const double* quality4);
-int ls_direct_adopt_refactor(ls_direct* d, ls::RefactorState* state);
+int ls_direct_adopt(ls_direct* d, std::vector<std::pair<void*, size_t>> owned, const double* seconds3, const double* quality4, ls::RefactorState* refac);
 namespace ls { extern std::atomic<long long> g_malloc_calls, g_malloc_us, g_malloc_bytes; }
 bool direct_tier_fits(int levels, int arity, const int* s, const int* b, const int* own_start, int tier_levels, bool sparse_leaves, int waves);
 bool direct_tier_full16(int64_t V, int arity, int levels, int tier_levels, int shard_count, int tier_waves);
@@ -793,10 +792,394 @@ extern "C" int ls_direct_pick_tree(int64_t V, int* leaf_size_io, int* arity_io) 
     return LS_OK;
 }
 
+// ---- ls_direct_factor's stages. Its device buffers come in three classes: scratch, the handle's factor arrays, and what a refactorable
+// handle keeps (scratch when it is not: sharded handles never are). Their owner hands the last two over on success; whatever it still
+// owns at the end -- the scratch, or everything after a failure -- goes back to the pool once the stream is idle.
+namespace {
+enum BufClass { BUF_SCRATCH = 0, BUF_HANDLE = 1, BUF_REFACTOR = 2 };
+struct CtorBuffers {
+    using List = std::vector<std::pair<void*, size_t>>;
+    int device;
+    hipStream_t st;
+    bool retain, timing;
+    List lists[3];
+    std::vector<hipEvent_t> events;         // the numeric chain's side-stream ordering (numeric_run)
+    int rc = LS_OK;                         // why the last take() failed
+    hipError_t err = hipSuccess;            // the first failed h2d() copy
+    CtorBuffers(int device, hipStream_t st, bool retain, bool timing) : device(device), st(st), retain(retain), timing(timing) {}
+    CtorBuffers(const CtorBuffers&) = delete;
+    ~CtorBuffers() {
+        (void)hipStreamSynchronize(st);
+        for (const List& l : lists)
+            for (const auto& b : l) if (!pool_give(device, b.first, b.second)) (void)hipFree(b.first);
+        for (hipEvent_t e : events) (void)hipEventDestroy(e);
+    }
+    // `bytes` (at least 16) + 16 from the pool the previous solver's went to (direct.hip), else hipMalloc; zeroed on request
+    template <class T> bool take(T** p, size_t bytes, BufClass c, bool zero) {
+        const double ta = timing ? now_s() : 0.0;
+        const size_t want = std::max<size_t>(bytes, 16) + 16;
+        hipError_t e = hipSuccess;
+        size_t cap = want;
+        *p = (T*)pool_take(device, want, &cap);
+        const bool pooled = *p != nullptr;
+        if (!pooled) e = pool_alloc(device, (void**)p, want);       // (out of memory: the pool is emptied and the call repeated once)
+        const double tb = timing ? now_s() : 0.0;
+        if (e == hipSuccess && zero) e = hipMemsetAsync(*p, 0, std::max<size_t>(bytes, 16) + 16, st);
+        if (timing && bytes > ((size_t)256 << 20)) {
+            (void)hipStreamSynchronize(st);
+            fprintf(stderr, "[ls_direct_factor]   %.2f GB: %s %.1f ms, %s %.1f ms\n", bytes / 1073741824.0, pooled ? "from the pool" : "hipMalloc", (tb - ta) * 1e3, zero ? "zeroed in" : "no memset",
+                    (now_s() - tb) * 1e3);
+        }
+        if (e != hipSuccess) { rc = hip_fail(e, "ls_direct_factor allocation", __FILE__, __LINE__); *p = nullptr; return false; }
+        lists[c == BUF_REFACTOR && !retain ? BUF_SCRATCH : c].emplace_back((void*)*p, cap);
+        return true;
+    }
+    void h2d(void* dst, const void* src, size_t bytes) { if (err == hipSuccess && bytes) err = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st); }
+    List release(BufClass c) { List l; l.swap(lists[c]); return l; }
+};
+
+// The tier's height. tier_levels < 0: chosen here so that about a thousand subtrees (4 workgroups per CU) are left at the tier's root
+// level: levels - 5 at arity 4 -- three at 1M vertices (8 levels), four at 4M (9 levels: 0.795 ms against 0.850 with three), two below
+// 8 levels (a tier of three on a 7-level tree leaves most CUs without a workgroup; tools/tier_sweep.py, 576 .. 4M vertices). *leaves_ok: sparse leaves
+int tier_height(const NdPlan& P, int64_t V, int arity, int tier_levels, bool sparse_leaves, int shard_count, int tier_waves, bool* leaves_ok_out) {
+    const int levels = P.levels;
+    const bool tier_auto = tier_levels < 0;
+    if (tier_levels < 0) {
+        tier_levels = std::max(2, std::min(4, levels - 5));
+        if (shard_count > 1) {                  // the cut (first level with a subtree per rank) must not lie inside the tier
+            int cut = 0;
+            int64_t width = 1;
+            while (width < shard_count && cut < levels) { width *= arity; ++cut; }
+            tier_levels = std::max(0, std::min(tier_levels, levels - cut));
+        }
+    }
+    tier_levels = std::max(0, std::min(std::min(tier_levels, levels), 6));
+    if (tier_auto) {
+        // the tier walks a node with ONE workgroup (a wave per 64-row chunk): right for leaves of <= 64 vertices, fine for the leaf level
+        // alone up to ~200 rows (tools/leaf_sweep.py: arity 8, 70k vertices, leaves of 137: 57 us with a tier of one level, 97 with two,
+        // 74 with none), 10-30x too slow for a leaf of many hundreds or thousands of rows (a caller's large leaf_size; the single dense node of a very small mesh) -- those go
+        // through the level kernels, which spread a node over as many workgroups as it has row tiles
+        int leaf_max = 0;
+        for (int64_t i = P.level_off[levels - 1]; i < P.level_off[levels]; ++i) leaf_max = std::max(leaf_max, P.s[i]);
+        const int64_t n_leaves = P.level_off[levels] - P.level_off[levels - 1];
+        if (leaf_max > 256 || levels == 1) tier_levels = 0;         // (a single node: the root's launch does both sweeps)
+        else if (leaf_max > 64) {                                   // dense leaves
+            // many leaves of up to ~220 rows in a shallow tree: the tier's leaf launch alone (64 leaves of 256 rows are better off in the
+            // level kernels: 16k vertices 28 against 37 us)
+            if (levels <= 4 && n_leaves >= 256 && leaf_max <= 224) tier_levels = std::min(tier_levels, 1);
+            else if (leaf_max > 128) tier_levels = 0;
+        }
+    }
+    bool leaves_ok = tier_levels > 0 && sparse_leaves;
+    for (int64_t i = P.level_off[levels - 1]; i < P.level_off[levels] && leaves_ok; ++i) leaves_ok = P.s[i] <= 64;
+    // a tier the library picked itself never fails for lack of LDS: one level less until its subtrees fit a workgroup
+    // (an explicit tier_levels that does not fit is reported by ls_direct_create: LS_E_WORKSPACE)
+    if (tier_auto) {
+        // large systems: a subtree one level taller per workgroup of sixteen waves, if its leaves and vectors fit the 160 KB of LDS
+        const int taller = levels - 4;
+        if (direct_tier_full16(V, arity, levels, taller, shard_count, tier_waves) && direct_tier_fits(levels, arity, P.s.data(), P.b.data(), P.own_start.data(), taller, leaves_ok, 16))
+            tier_levels = taller;
+        else
+            while (tier_levels > 0 && !direct_tier_fits(levels, arity, P.s.data(), P.b.data(), P.own_start.data(), tier_levels, leaves_ok, 4)) --tier_levels;
+    }
+    *leaves_ok_out = tier_levels > 0 && leaves_ok;
+    return tier_levels;
+}
+
+// Where every node's numbers live: the fp64 scratch of the numeric chain (fronts, xs, ws, work) and the handle's fp32 factor arrays in
+// the level kernels' (finv / w), the tier's quad-interleaved (d4 / u4) or the sparse leaves' (tri) layout; hn = ls_direct_arrays::h_nodes.
+// Then the device arrays themselves (owner: CtorBuffers).
+struct FactorLayout {
+    std::vector<FactorNode> fn;
+    std::vector<int64_t> hn, work_off;
+    int64_t f_tot = 0, x_tot = 0, w_tot = 0, work_tot = 0, o_finv = 0, o_w = 0, o_d4 = 0, o_u4 = 0, o_tri = 0;
+    std::vector<int> off_b, off_s;              // sparse leaves: where a leaf's pointer lists (A_bs by boundary row / by own row) start
+    int64_t n_sp_ptr = 0, n_ent = 0;            // (n_ent: sparse-leaf entries per list)
+    RefactorState dev;                          // the factor arrays, and what a refactorable handle keeps
+    double *fronts = nullptr, *xs = nullptr, *ws = nullptr, *work = nullptr;
+    int32_t* sp_ptr = nullptr; int *rowidx = nullptr, *flag = nullptr;
+    GemmDesc* gemm = nullptr; InvDesc* invd = nullptr;
+};
+
+int lay_out(const NdPlan& P, int tier_levels, bool leaves_ok, FactorLayout& L) {
+    const int n_nodes = P.n_nodes, levels = P.levels, tier_root = levels - tier_levels;
+    L.fn.resize((size_t)n_nodes + 1);
+    memset(L.fn.data(), 0, L.fn.size() * sizeof(FactorNode));
+    L.hn.assign((size_t)(n_nodes + 1) * LS_DIRECT_NODE_COLS, 0);
+    L.work_off.assign((size_t)n_nodes + 1, 0);
+    for (int i = 1; i <= n_nodes; ++i) {
+        FactorNode& n = L.fn[i];
+        const int s = P.s[i], b = P.b[i], lv = P.level_of[i];
+        n.s = s; n.b = b; n.own_start = P.own_start[i]; n.parent = P.parent[i]; n.bnd_off = P.bnd_off[i];
+        n.f_off = L.f_tot; L.f_tot += (int64_t)(s + b) * (s + b);
+        n.x_off = L.x_tot; L.x_tot += (int64_t)s * s;
+        n.w_off = L.w_tot; L.w_tot += (int64_t)s * b;
+        L.work_off[i] = L.work_tot; L.work_tot += ((int64_t)s * s + 1) / 2 + 64;
+        const bool sparse = leaves_ok && lv == levels - 1 && s >= 1;
+        const bool quad = !sparse && lv >= tier_root;
+        n.layout = sparse ? 2 : quad ? 1 : 0; n.pad = lv;
+        int64_t* r = L.hn.data() + (size_t)i * LS_DIRECT_NODE_COLS;
+        r[0] = s; r[1] = b; r[2] = P.own_start[i]; r[3] = P.bnd_off[i]; r[4] = P.front_off[i]; r[7] = P.parent[i];
+        r[8] = -1; r[9] = -1; r[10] = -1; r[11] = quad;
+        const int64_t s4 = (s + 3) & ~3, b4 = (b + 3) & ~3;
+        if (sparse) { n.o_tri = L.o_tri; r[8] = L.o_tri; L.o_tri += ((int64_t)s * (s + 1) / 2 + 3) & ~(int64_t)3; }
+        else if (quad) { n.o_finv = L.o_d4; n.o_w = L.o_u4; r[5] = L.o_d4; r[6] = L.o_u4; L.o_d4 += (s4 + b4) * s; L.o_u4 += s4 * b; }
+        else { n.o_finv = L.o_finv; n.o_w = L.o_w; r[5] = L.o_finv; r[6] = L.o_w; L.o_finv += (int64_t)s * s; L.o_w += (int64_t)s * b; }
+    }
+    LS_REQUIRE(L.o_finv + 2 * L.o_w + L.o_d4 + L.o_u4 + 2 * L.o_tri < (int64_t)4000000000, LS_E_WORKSPACE, "ls_direct_factor: the factor is too large");
+    if (leaves_ok) {        // the lists themselves are built on the device (leaf_lists)
+        const int64_t leaf0 = P.level_off[levels - 1], leaf1 = P.level_off[levels];
+        L.off_b.assign((size_t)(leaf1 - leaf0), -1); L.off_s.assign((size_t)(leaf1 - leaf0), -1);
+        for (int pass = 0; pass < 2; ++pass)                 // boundary rows of all leaves first, then own rows
+            for (int64_t i = leaf0; i < leaf1; ++i) {
+                if (P.s[i] < 1) continue;
+                (pass == 0 ? L.off_b : L.off_s)[(size_t)(i - leaf0)] = (int)L.n_sp_ptr;
+                L.hn[(size_t)i * LS_DIRECT_NODE_COLS + (pass == 0 ? 9 : 10)] = L.n_sp_ptr;
+                L.n_sp_ptr += (pass == 0 ? P.b[i] : P.s[i]) + 1;
+            }
+    }
+    return LS_OK;
+}
+
+// The sparse leaves' two entry lists (A_bs by boundary row / by own row), counted, scanned, filled and sorted on the device; with
+// `retain`, where every value went. Without sparse leaves a 16-byte placeholder.
+int leaf_lists(CtorBuffers& B, const NdPlan& P, FactorLayout& L, const int32_t* d_col, const float* d_val, int64_t V, int64_t nnz, bool leaves_ok,
+               bool retain, hipStream_t st) {
+    if (!leaves_ok) return B.take(&L.dev.sp_ent, 16, BUF_HANDLE, true) ? LS_OK : B.rc;
+    const int levels = P.levels;
+    const int64_t leaf0 = P.level_off[levels - 1], leaf1 = P.level_off[levels];
+    // own rows of the leaves: the tree's numbering [0, rows_s); boundary rows: bnd[bnd0, n_bnd)
+    const int64_t rows_s = levels > 1 ? P.own_start[P.level_off[levels - 2]] : V, bnd0 = P.bnd_off[leaf0], rows_b = P.n_bnd - bnd0;
+    int *cnt_s = nullptr, *cnt_b = nullptr, *ptr_s = nullptr, *ptr_b = nullptr, *bsum = nullptr, *d_off_b = nullptr, *d_off_s = nullptr;
+    if (!(B.take(&cnt_s, sizeof(int) * (rows_s + 1), BUF_SCRATCH, true) && B.take(&cnt_b, sizeof(int) * (rows_b + 1), BUF_SCRATCH, true) &&
+          B.take(&ptr_s, sizeof(int) * (rows_s + 1), BUF_SCRATCH, false) && B.take(&ptr_b, sizeof(int) * (rows_b + 1), BUF_SCRATCH, false) &&
+          B.take(&bsum, sizeof(int) * (scan_blocks(std::max(rows_s, rows_b)) + 2), BUF_SCRATCH, false) &&
+          B.take(&d_off_b, sizeof(int) * L.off_b.size(), BUF_SCRATCH, false) && B.take(&d_off_s, sizeof(int) * L.off_s.size(), BUF_SCRATCH, false)))
+        return B.rc;
+    hipError_t e = hipMemcpyAsync(d_off_b, L.off_b.data(), sizeof(int) * L.off_b.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_off_s, L.off_s.data(), sizeof(int) * L.off_s.size(), hipMemcpyHostToDevice, st);
+    const unsigned eg = (unsigned)div_up(nnz, 256);
+    hipLaunchKernelGGL(k_leaf_entries<0>, dim3(eg), dim3(256), 0, st, nnz, L.rowidx, d_col, d_val, L.dev.inv, L.dev.non, L.dev.nodes, L.dev.bnd, (long long)bnd0, cnt_s,
+                       cnt_b, (const int*)nullptr, (const int*)nullptr, (SpEnt*)nullptr, 0);
+    int tot[2] = {0, 0};
+    int rc = LS_OK;
+    if ((rc = exclusive_scan(cnt_s, rows_s, ptr_s, bsum, st)) != LS_OK || (rc = exclusive_scan(cnt_b, rows_b, ptr_b, bsum, st)) != LS_OK) return rc;
+    if (e == hipSuccess) e = hipMemcpyAsync(&tot[0], ptr_s + rows_s, sizeof(int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&tot[1], ptr_b + rows_b, sizeof(int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemsetAsync(cnt_s, 0, sizeof(int) * (rows_s + 1), st);
+    if (e == hipSuccess) e = hipMemsetAsync(cnt_b, 0, sizeof(int) * (rows_b + 1), st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return hip_fail(e, "ls_direct_factor leaf lists", __FILE__, __LINE__);
+    if (tot[0] != tot[1]) { set_error("ls_direct_factor: the leaf lists disagree (%d own-row entries, %d boundary-row entries)", tot[0], tot[1]); return LS_E_INVALID; }
+    const int64_t n_ent = L.n_ent = tot[0];
+    if (!B.take(&L.dev.sp_ent, sizeof(SpEnt) * 2 * n_ent, BUF_HANDLE, true)) return B.rc;
+    hipLaunchKernelGGL(k_leaf_entries<1>, dim3(eg), dim3(256), 0, st, nnz, L.rowidx, d_col, d_val, L.dev.inv, L.dev.non, L.dev.nodes, L.dev.bnd, (long long)bnd0, cnt_s,
+                       cnt_b, (const int*)ptr_s, (const int*)ptr_b, L.dev.sp_ent, (int)n_ent);
+    if (rows_b) hipLaunchKernelGGL(k_leaf_sort, dim3((unsigned)div_up(rows_b, 256)), dim3(256), 0, st, rows_b, (const int*)ptr_b, 0, L.dev.sp_ent);
+    if (rows_s) hipLaunchKernelGGL(k_leaf_sort, dim3((unsigned)div_up(rows_s, 256)), dim3(256), 0, st, rows_s, (const int*)ptr_s, (int)n_ent, L.dev.sp_ent);
+    hipLaunchKernelGGL(k_leaf_ptrs, dim3((unsigned)(leaf1 - leaf0)), dim3(64), 0, st, (int)leaf0, L.dev.nodes, (long long)bnd0, (const int*)d_off_b,
+                       (const int*)d_off_s, (const int*)ptr_b, (const int*)ptr_s, (int)n_ent, L.sp_ptr);
+    if (retain) {                                           // where every value went, taken after the sort (ls_direct_refactor rewrites them there)
+        if (!B.take(&L.dev.slots, sizeof(LeafSlot) * nnz, BUF_REFACTOR, false)) return B.rc;
+        hipLaunchKernelGGL(k_leaf_slots, dim3(eg), dim3(256), 0, st, nnz, L.rowidx, d_col, L.dev.inv, L.dev.non, L.dev.nodes, L.dev.bnd, (long long)bnd0,
+                           (const int*)ptr_s, (const int*)ptr_b, (const SpEnt*)L.dev.sp_ent, (int)n_ent, L.dev.slots);
+    }
+    return LS_OK;
+}
+
+// The numeric factorisation as a recorded chain of launches (per level the children's extend-adds, the inverses, W and U), then its
+// descriptors on the device; with `retain` also as offsets (in doubles) into [fronts | xs | ws | work], which k_rebase points into a
+// refactorisation's scratch (an operand no region holds belongs to an empty product -- K = 0, never read: offset 0). gemm_off / inv_off:
+// the host copies of the offsets, alive until the stream is synchronised.
+int record_chain(CtorBuffers& B, const NdPlan& P, FactorLayout& L, int arity, bool retain, hipStream_t st, FactorCtx& ctx, std::vector<GemmDesc>& gemm_off,
+                 std::vector<InvDesc>& inv_off) {
+    const int levels = P.levels;
+    std::vector<int> ids;
+    for (int lv = levels - 1; lv >= 0; --lv) {
+        const int64_t first = P.level_off[lv], last = P.level_off[lv + 1];
+        if (lv + 1 < levels) {                                      // children's Schur complements, one sibling index per launch
+            for (int c = 0; c < arity; ++c) {
+                ids.clear();
+                int bmax = 0;
+                for (int64_t ch = P.level_off[lv + 1] + c; ch < P.level_off[lv + 2]; ch += arity)
+                    if (P.b[ch] > 0) { ids.push_back((int)ch); bmax = std::max(bmax, P.b[ch]); }
+                id_launch(ctx, 2, ids, std::min(64, div_up((int64_t)bmax * bmax, 256)));
+            }
+        }
+        int smax = 0;
+        for (int64_t i = first; i < last; ++i) smax = std::max(smax, P.s[i]);
+        int depth = 0;
+        while (((smax + (1 << depth) - 1) >> depth) > INV_N) ++depth;
+        std::vector<Blk> blocks;
+        ids.clear();
+        for (int64_t i = first; i < last; ++i) {
+            if (P.s[i] == 0) continue;
+            const int m = P.s[i] + P.b[i];
+            blocks.push_back(Blk{L.fronts + L.fn[i].f_off, L.xs + L.fn[i].x_off, L.work + L.work_off[i], P.s[i], m, P.s[i]});
+            ids.push_back((int)i);
+        }
+        inverse_rec(ctx, blocks, depth);
+        std::vector<GemmDesc> gd;
+        for (int64_t i = first; i < last; ++i) {                    // W = F_bs Finv
+            const int s = P.s[i], b = P.b[i], m = s + b;
+            if (s && b) gd.push_back(GemmDesc{L.fronts + L.fn[i].f_off + (size_t)s * m, L.xs + L.fn[i].x_off, L.ws + L.fn[i].w_off, b, s, s, m, s, s, 0, 0, 1.0, 0.0});
+        }
+        gemm_batched(ctx, gd);
+        for (int64_t i = first; i < last; ++i) {                    // U = F_bb - W F_sb  (F_sb = F_bs^T)
+            const int s = P.s[i], b = P.b[i], m = s + b;
+            if (s && b) gd.push_back(GemmDesc{L.ws + L.fn[i].w_off, L.fronts + L.fn[i].f_off + (size_t)s * m, L.fronts + L.fn[i].f_off + (size_t)s * m + s,
+                                              b, b, s, s, m, m, 0, 1, -1.0, 1.0, 1, 0});
+        }
+        gemm_batched(ctx, gd);
+        int64_t emax = 0;
+        for (int i : ids) emax = std::max(emax, (int64_t)P.s[i] * (P.s[i] + P.b[i]));
+        id_launch(ctx, 3, ids, std::min(256, div_up(emax, 256)));
+    }
+    if (!(B.take(&L.gemm, sizeof(GemmDesc) * ctx.gemm.size(), BUF_SCRATCH, false) && B.take(&L.invd, sizeof(InvDesc) * ctx.inv.size(), BUF_SCRATCH, false) &&
+          B.take(&L.dev.ids, sizeof(int) * ctx.ids.size(), BUF_REFACTOR, false) &&
+          (!retain || (B.take(&L.dev.gemm, sizeof(GemmDesc) * ctx.gemm.size(), BUF_REFACTOR, false) && B.take(&L.dev.invd, sizeof(InvDesc) * ctx.inv.size(), BUF_REFACTOR, false)))))
+        return B.rc;
+    B.h2d(L.gemm, ctx.gemm.data(), sizeof(GemmDesc) * ctx.gemm.size());
+    B.h2d(L.invd, ctx.inv.data(), sizeof(InvDesc) * ctx.inv.size());
+    B.h2d(L.dev.ids, ctx.ids.data(), sizeof(int) * ctx.ids.size());
+    if (retain) {
+        const uintptr_t base[4] = {(uintptr_t)L.fronts, (uintptr_t)L.xs, (uintptr_t)L.ws, (uintptr_t)L.work};
+        const int64_t len[4] = {L.f_tot, L.x_tot, L.w_tot, L.work_tot};
+        auto off = [&](const double* p) -> double* {
+            const uintptr_t q = (uintptr_t)p;
+            int64_t start = 0;
+            for (int k = 0; k < 4; ++k) {
+                if (q >= base[k] && q < base[k] + sizeof(double) * (size_t)len[k]) return (double*)(uintptr_t)(start + (int64_t)((q - base[k]) / sizeof(double)));
+                start += len[k];
+            }
+            return nullptr;
+        };
+        gemm_off = ctx.gemm;
+        for (GemmDesc& g : gemm_off) { g.A = off(g.A); g.B = off(g.B); g.C = off(g.C); }
+        inv_off = ctx.inv;
+        for (InvDesc& v : inv_off) { v.M = off(v.M); v.X = off(v.X); }
+        B.h2d(L.dev.gemm, gemm_off.data(), sizeof(GemmDesc) * gemm_off.size());
+        B.h2d(L.dev.invd, inv_off.data(), sizeof(InvDesc) * inv_off.size());
+    }
+    return B.err == hipSuccess ? LS_OK : hip_fail(B.err, "ls_direct_factor kernels", __FILE__, __LINE__);
+}
+
+}  // namespace
+
 static int direct_factor_impl(const int32_t* d_rowptr, const int32_t* d_col, const float* d_val, int64_t V, int64_t nnz,
                               const float* d_positions, int leaf_size, int arity, int tier_levels, int sparse_leaves, int shard_rank,
                               int shard_count, int ordering_arg, int tier_waves, int device, void* stream, ls_direct** out,
-                              bool refactorable = false);
+                              bool refactorable = false) {
+    LS_REQUIRE(out && d_rowptr && d_col && d_val && V > 0 && nnz > 0 && nnz < INT32_MAX, LS_E_INVALID, "ls_direct_factor: bad argument");
+    *out = nullptr;
+    { const int rc_pick = ls_direct_pick_tree(V, &leaf_size, &arity); if (rc_pick) return rc_pick; }      // leaf_size / arity <= 0: picked from V
+    DeviceGuard g(device);
+    LS_HIP(g.err);
+    hipStream_t st = (hipStream_t)stream;
+    const double t0 = now_s();
+    const bool timing = env_plan_timing();
+    const NdEnv env = nd_env();
+    auto faults = [] { struct rusage u; getrusage(RUSAGE_SELF, &u); return (long)u.ru_minflt; };
+    const long f0 = timing ? faults() : 0;
+    auto lap = [&](const char* what) { if (timing) { (void)hipStreamSynchronize(st); fprintf(stderr, "[ls_direct_factor] %-30s %.3f s  (%ld page faults so far)\n", what, now_s() - t0, faults() - f0); } };
+    uvec<int32_t> rowptr((size_t)V + 1), col((size_t)nnz);                 // the host's copy of the pattern, filled by the analysis (not zeroed first: 32 MB at 1M)
+    NdPlan P;
+    FactorLayout L;             // (these and the chain: sources of asynchronous copies, declared before the buffers' owner that synchronises)
+    FactorCtx ctx;
+    std::vector<GemmDesc> gemm_off;
+    std::vector<InvDesc> inv_off;
+    // how the cutting directions are chosen: ND_ORDER_AUTO (nd_plan.h) unless the environment says otherwise (LS_ND_ORDER = 0: always
+    // the longest axis of the embedding, 1: always the thinnest of six trial separators -- on the device since round 5: 5-10 % fewer
+    // factor numbers on rough scans for 10-25 ms more constructor at 250k vertices)
+    // an explicit argument (ls_direct_factor_ex) wins; "auto" lets the environment override the library's rule
+    {
+        const std::string err = nd_plan_build_device(d_rowptr, d_col, d_positions, V, nnz, rowptr.data(), col.data(), leaf_size, arity, 4, st, P,
+                                                     ordering_arg != ND_ORDER_AUTO ? ordering_arg : env.order, /* defer_push_lists = */ true);
+        LS_REQUIRE(err.empty(), LS_E_INVALID, "%s", err.c_str());
+    }
+    int max_front = 0;
+    for (int i = 1; i <= P.n_nodes; ++i) max_front = std::max(max_front, P.s[i] + P.b[i]);
+    LS_REQUIRE(max_front <= 8000, LS_E_WORKSPACE, "ls_direct_factor: a front of %d rows exceeds the solver's limit (the mesh does not dissect)", max_front);
+    int rc = LS_OK;
+    const double t1 = now_s();
+    lap("symbolic analysis");
+    bool leaves_ok = false;
+    tier_levels = tier_height(P, V, arity, tier_levels, sparse_leaves != 0, shard_count, tier_waves > 0 ? tier_waves : env.tier_waves.value_or(0), &leaves_ok);
+    if ((rc = lay_out(P, tier_levels, leaves_ok, L))) return rc;
+    lap("layouts");
+    const double t2 = now_s();
+    const bool retain = refactorable && shard_count <= 1;
+    CtorBuffers B(device, st, retain, timing);
+    // (this order, these sizes and classes: the pool's best fit reuses what the previous constructor gave back)
+    if (!(B.take(&L.dev.finv, sizeof(float) * L.o_finv, BUF_HANDLE, false) && B.take(&L.dev.wf, sizeof(float) * L.o_w, BUF_HANDLE, false) &&
+          B.take(&L.dev.wb, sizeof(float) * L.o_w, BUF_HANDLE, false) && B.take(&L.dev.u4, sizeof(float) * L.o_u4, BUF_HANDLE, true) &&
+          B.take(&L.dev.d4, sizeof(float) * L.o_d4, BUF_HANDLE, true) && B.take(&L.dev.tri, sizeof(float) * L.o_tri, BUF_HANDLE, true) &&
+          B.take(&L.sp_ptr, sizeof(int32_t) * L.n_sp_ptr, BUF_HANDLE, false) &&
+          B.take(&L.fronts, sizeof(double) * L.f_tot, BUF_SCRATCH, false) && B.take(&L.xs, sizeof(double) * L.x_tot, BUF_SCRATCH, false) &&
+          B.take(&L.ws, sizeof(double) * L.w_tot, BUF_SCRATCH, false) && B.take(&L.work, sizeof(double) * L.work_tot, BUF_SCRATCH, false) &&
+          B.take(&L.dev.inv, sizeof(int) * V, BUF_REFACTOR, false) && B.take(&L.dev.non, sizeof(int) * V, BUF_REFACTOR, false) &&
+          B.take(&L.dev.bnd, sizeof(int) * P.n_bnd, BUF_REFACTOR, false) && B.take(&L.dev.ppos, sizeof(int) * P.n_bnd, BUF_REFACTOR, false) &&
+          B.take(&L.rowidx, sizeof(int) * nnz, BUF_SCRATCH, false) &&
+          B.take(&L.dev.nodes, sizeof(FactorNode) * (P.n_nodes + 1), BUF_REFACTOR, false) && B.take(&L.flag, sizeof(int), BUF_SCRATCH, true) &&
+          (!retain || (B.take(&L.dev.rowptr, sizeof(int32_t) * (V + 1), BUF_REFACTOR, false) && B.take(&L.dev.col, sizeof(int32_t) * nnz, BUF_REFACTOR, false)))))
+        return B.rc;
+    lap("device allocations");
+    B.h2d(L.dev.inv, P.inv.data(), sizeof(int) * V); B.h2d(L.dev.non, P.node_of_new.data(), sizeof(int) * V);
+    B.h2d(L.dev.bnd, P.bnd.data(), sizeof(int) * P.n_bnd); B.h2d(L.dev.ppos, P.ppos.data(), sizeof(int) * P.n_bnd);
+    B.h2d(L.dev.nodes, L.fn.data(), sizeof(FactorNode) * (P.n_nodes + 1));
+    if (retain && B.err == hipSuccess) B.err = hipMemcpyAsync(L.dev.rowptr, d_rowptr, sizeof(int32_t) * (V + 1), hipMemcpyDeviceToDevice, st);
+    if (retain && B.err == hipSuccess) B.err = hipMemcpyAsync(L.dev.col, d_col, sizeof(int32_t) * nnz, hipMemcpyDeviceToDevice, st);
+    if (B.err != hipSuccess) return hip_fail(B.err, "ls_direct_factor uploads", __FILE__, __LINE__);
+    hipLaunchKernelGGL(k_expand_rows, dim3((unsigned)div_up(V, 256)), dim3(256), 0, st, V, d_rowptr, L.rowidx);
+    if ((rc = leaf_lists(B, P, L, d_col, d_val, V, nnz, leaves_ok, retain, st))) return rc;
+    lap("uploads");
+    // ---- numeric factorisation: recorded (host), uploaded, launched back to back ---------------------------------------------------------
+    if ((rc = record_chain(B, P, L, arity, retain, st, ctx, gemm_off, inv_off))) return rc;
+    const NumericRun run{nnz, L.rowidx, d_col, d_val, L.dev.inv, L.dev.non, L.dev.bnd, L.dev.ppos, L.dev.ids, L.dev.nodes, L.gemm, L.invd, &ctx.cmds,
+                         L.fronts, L.xs, L.ws, L.f_tot, L.dev.finv, L.dev.wf, L.dev.wb, L.dev.u4, L.dev.d4, L.dev.tri, L.flag};
+    hipError_t e = numeric_run(run, device, st, B.events, &ctx.launches);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "ls_direct_factor kernels", __FILE__, __LINE__);
+    // ---- the solver handle: its tables are built on the host WHILE the device factorises (everything above is only enqueued) ------------
+    if (timing) fprintf(stderr, "[ls_direct_factor]   %d launches enqueued %.3f s (host clock)\n", ctx.launches, now_s() - t0);
+    nd_plan_push_lists(P);          // (left out of the analysis: only the solve needs them)
+    if (timing) fprintf(stderr, "[ls_direct_factor]   push lists built %.3f s (host clock)\n", now_s() - t0);
+    ls_direct_arrays A;
+    memset(&A, 0, sizeof(A));
+    A.V = V; A.levels = P.levels; A.arity = arity; A.h_nodes = L.hn.data(); A.h_perm = P.perm.data(); A.h_ppos = P.ppos.data(); A.n_bnd = P.n_bnd;
+    A.h_push_ptr = P.push_ptr.data(); A.h_push_tgt = P.push_tgt.data(); A.n_front = P.n_front;
+    A.d_finv = L.dev.finv; A.d_wf = L.dev.wf; A.d_wb = L.dev.wb; A.d_u4 = L.dev.u4; A.d_d4 = L.dev.d4; A.d_tri = L.dev.tri; A.d_sp_ptr = L.sp_ptr; A.d_sp_ent = L.dev.sp_ent;
+    A.n_sp_ptr = L.n_sp_ptr; A.n_sp_ent = 2 * L.n_ent;
+    A.shard_rank = shard_rank; A.shard_count = shard_count; A.tier_waves = tier_waves;
+    rc = ls_direct_create(&A, device, stream, out);
+    int flag = 0;
+    e = hipMemcpyAsync(&flag, L.flag, sizeof(int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (rc != LS_OK || e != hipSuccess || flag) {
+        if (rc == LS_OK) { (void)ls_direct_destroy(*out); *out = nullptr; }       // (the handle does not own the factor arrays yet)
+        if (rc != LS_OK) return rc;
+        if (e != hipSuccess) return hip_fail(e, "ls_direct_factor kernels", __FILE__, __LINE__);
+        set_error(flag == 2 ? "ls_direct_factor: the matrix pattern is not symmetric" : "ls_direct_factor: a front is not positive definite");
+        return LS_E_INVALID;
+    }
+    RefactorState* refac = nullptr;
+    if (retain) {                       // what a refactorable handle keeps: the refactor-class buffers, the arrays above and the chain
+        RefactorState& R = L.dev;
+        R.device = device; R.V = V; R.nnz = nnz; R.f_tot = L.f_tot; R.x_tot = L.x_tot; R.w_tot = L.w_tot; R.work_tot = L.work_tot;
+        R.cmds = ctx.cmds; R.n_gemm = ctx.gemm.size(); R.n_inv = ctx.inv.size(); R.bufs = B.release(BUF_REFACTOR);
+        refac = new RefactorState(std::move(R));
+    }
+    const double t3 = now_s();
+    lap("numeric factorisation + solve tables (overlapped)");
+    if (timing) {
+        const long long nc = ls::g_malloc_calls.exchange(0), us = ls::g_malloc_us.exchange(0), by = ls::g_malloc_bytes.exchange(0);
+        fprintf(stderr, "[ls_direct_factor]   allocations that missed the pool since the last report: %lld hipMalloc calls, %.1f MB, %.2f ms\n", nc, by / 1048576.0, us / 1e3);
+    }
+    const double secs[3] = {t1 - t0, t2 - t1, t3 - t2};
+    const double quality[4] = {(double)P.ordering, P.words_per_vertex, P.spread, P.words_other};
+    return ls_direct_adopt(*out, B.release(BUF_HANDLE), secs, quality, refac);
+}
 
 extern "C" int ls_direct_factor(const int32_t* d_rowptr, const int32_t* d_col, const float* d_val, int64_t V, int64_t nnz,
                                 const float* d_positions, int leaf_size, int arity, int tier_levels, int sparse_leaves, int shard_rank,
@@ -839,367 +1222,6 @@ extern "C" int ls_direct_options_default(ls_direct_options* o) {
     o->leaf_size = 0; o->arity = 0; o->tier_levels = -1; o->sparse_leaves = 1; o->shard_rank = 0; o->shard_count = 1;
     o->ordering = LS_ND_ORDER_AUTO; o->tier_waves = 0;
     return LS_OK;
-}
-
-static int direct_factor_impl(const int32_t* d_rowptr, const int32_t* d_col, const float* d_val, int64_t V, int64_t nnz,
-                              const float* d_positions, int leaf_size, int arity, int tier_levels, int sparse_leaves, int shard_rank,
-                              int shard_count, int ordering_arg, int tier_waves, int device, void* stream, ls_direct** out,
-                              bool refactorable) {
-    LS_REQUIRE(out && d_rowptr && d_col && d_val && V > 0 && nnz > 0 && nnz < INT32_MAX, LS_E_INVALID, "ls_direct_factor: bad argument");
-    *out = nullptr;
-    { const int rc_pick = ls_direct_pick_tree(V, &leaf_size, &arity); if (rc_pick) return rc_pick; }      // leaf_size / arity <= 0: picked from V
-    DeviceGuard g(device);
-    LS_HIP(g.err);
-    hipStream_t st = (hipStream_t)stream;
-    const double t0 = now_s();
-    const bool timing = env_plan_timing();
-    const NdEnv env = nd_env();
-    auto faults = [] { struct rusage u; getrusage(RUSAGE_SELF, &u); return (long)u.ru_minflt; };
-    const long f0 = timing ? faults() : 0;
-    auto lap = [&](const char* what) { if (timing) { (void)hipStreamSynchronize(st); fprintf(stderr, "[ls_direct_factor] %-30s %.3f s  (%ld page faults so far)\n", what, now_s() - t0, faults() - f0); } };
-    // ---- symbolic analysis: the bisection rounds on the device (nd_bisect.hip), the tree / fronts / index lists on the host ------------
-    uvec<int32_t> rowptr((size_t)V + 1), col((size_t)nnz);                 // the host's copy of the pattern, filled by the analysis (not zeroed first: 32 MB at 1M)
-    NdPlan P;
-    {
-        // how the cutting directions are chosen: ND_ORDER_AUTO (nd_plan.h) unless the environment says otherwise (LS_ND_ORDER = 0: always
-        // the longest axis of the embedding, 1: always the thinnest of six trial separators -- on the device since round 5: 5-10 % fewer
-        // factor numbers on rough scans for 10-25 ms more constructor at 250k vertices)
-        // an explicit argument (ls_direct_factor_ex) wins; "auto" lets the environment override the library's rule
-        const int ordering = ordering_arg != ND_ORDER_AUTO ? ordering_arg : env.order;
-        const std::string err = nd_plan_build_device(d_rowptr, d_col, d_positions, V, nnz, rowptr.data(), col.data(), leaf_size, arity, 4, st, P, ordering,
-                                                     /* defer_push_lists = */ true);
-        LS_REQUIRE(err.empty(), LS_E_INVALID, "%s", err.c_str());
-    }
-    const double t1 = now_s();
-    lap("symbolic analysis");
-    const int n_nodes = P.n_nodes, levels = P.levels;
-    int max_front = 0;
-    for (int i = 1; i <= n_nodes; ++i) max_front = std::max(max_front, P.s[i] + P.b[i]);
-    LS_REQUIRE(max_front <= 8000, LS_E_WORKSPACE, "ls_direct_factor: a front of %d rows exceeds the solver's limit (the mesh does not dissect)", max_front);
-    // ---- layouts -------------------------------------------------------------------------------------------------------------------
-    // tier_levels < 0: chosen here so that about a thousand subtrees (4 workgroups per CU) are left at the tier's root level:
-    // levels - 5 at arity 4 -- three at 1M vertices (8 levels), four at 4M (9 levels: 0.795 ms against 0.850 with three), two
-    // below 8 levels (a tier of three on a 7-level tree leaves most CUs without a workgroup; tools/tier_sweep.py, 576 .. 4M vertices)
-    const bool tier_auto = tier_levels < 0;
-    if (tier_levels < 0) {
-        tier_levels = std::max(2, std::min(4, levels - 5));
-        if (shard_count > 1) {                  // the cut (first level with a subtree per rank) must not lie inside the tier
-            int cut = 0;
-            int64_t width = 1;
-            while (width < shard_count && cut < levels) { width *= arity; ++cut; }
-            tier_levels = std::max(0, std::min(tier_levels, levels - cut));
-        }
-    }
-    tier_levels = std::max(0, std::min(std::min(tier_levels, levels), 6));
-    if (tier_auto) {
-        // the tier walks a node with ONE workgroup (a wave per 64-row chunk): right for leaves of <= 64 vertices, fine for the leaf level
-        // alone up to ~200 rows (tools/leaf_sweep.py: arity 8, 70k vertices, leaves of 137: 57 us with a tier of one level, 97 with two,
-        // 74 with none), 10-30x too slow for a leaf of many hundreds or thousands of rows (a caller's large leaf_size; the single dense node of a very small mesh) -- those go
-        // through the level kernels, which spread a node over as many workgroups as it has row tiles
-        int leaf_max = 0;
-        for (int64_t i = P.level_off[levels - 1]; i < P.level_off[levels]; ++i) leaf_max = std::max(leaf_max, P.s[i]);
-        const int64_t n_leaves = P.level_off[levels] - P.level_off[levels - 1];
-        if (leaf_max > 256 || levels == 1) tier_levels = 0;         // (a single node: the root's launch does both sweeps)
-        else if (leaf_max > 64) {                                   // dense leaves
-            // many leaves of up to ~220 rows in a shallow tree: the tier's leaf launch alone (64 leaves of 256 rows are better off in the
-            // level kernels: 16k vertices 28 against 37 us)
-            if (levels <= 4 && n_leaves >= 256 && leaf_max <= 224) tier_levels = std::min(tier_levels, 1);
-            else if (leaf_max > 128) tier_levels = 0;
-        }
-    }
-    bool leaves_ok = tier_levels > 0 && sparse_leaves;
-    for (int64_t i = P.level_off[levels - 1]; i < P.level_off[levels] && leaves_ok; ++i) leaves_ok = P.s[i] <= 64;
-    // a tier the library picked itself never fails for lack of LDS: one level less until its subtrees fit a workgroup
-    // (an explicit tier_levels that does not fit is reported by ls_direct_create: LS_E_WORKSPACE)
-    if (tier_auto) {
-        // large systems: a subtree one level taller per workgroup of sixteen waves, if its leaves and vectors fit the 160 KB of LDS
-        const int taller = levels - 4;
-        if (direct_tier_full16(V, arity, levels, taller, shard_count, tier_waves > 0 ? tier_waves : env.tier_waves.value_or(0)) && direct_tier_fits(levels, arity, P.s.data(), P.b.data(), P.own_start.data(), taller, leaves_ok, 16))
-            tier_levels = taller;
-        else
-            while (tier_levels > 0 && !direct_tier_fits(levels, arity, P.s.data(), P.b.data(), P.own_start.data(), tier_levels, leaves_ok, 4)) --tier_levels;
-    }
-    if (tier_levels == 0) leaves_ok = false;
-    const int tier_root = levels - tier_levels;
-    std::vector<FactorNode> fn((size_t)n_nodes + 1);
-    memset(fn.data(), 0, fn.size() * sizeof(FactorNode));
-    std::vector<int64_t> hn((size_t)(n_nodes + 1) * LS_DIRECT_NODE_COLS, 0);
-    int64_t f_tot = 0, x_tot = 0, w_tot = 0, o_finv = 0, o_w = 0, o_d4 = 0, o_u4 = 0, o_tri = 0;
-    for (int i = 1; i <= n_nodes; ++i) {
-        FactorNode& n = fn[i];
-        const int s = P.s[i], b = P.b[i], lv = P.level_of[i];
-        n.s = s; n.b = b; n.own_start = P.own_start[i]; n.parent = P.parent[i]; n.bnd_off = P.bnd_off[i];
-        n.f_off = f_tot; f_tot += (int64_t)(s + b) * (s + b);
-        n.x_off = x_tot; x_tot += (int64_t)s * s;
-        n.w_off = w_tot; w_tot += (int64_t)s * b;
-        const bool sparse = leaves_ok && lv == levels - 1 && s >= 1;
-        const bool quad = !sparse && lv >= tier_root;
-        n.layout = sparse ? 2 : quad ? 1 : 0; n.pad = lv;
-        int64_t* r = hn.data() + (size_t)i * LS_DIRECT_NODE_COLS;
-        r[0] = s; r[1] = b; r[2] = P.own_start[i]; r[3] = P.bnd_off[i]; r[4] = P.front_off[i]; r[7] = P.parent[i];
-        r[8] = -1; r[9] = -1; r[10] = -1; r[11] = quad;
-        const int64_t s4 = (s + 3) & ~3, b4 = (b + 3) & ~3;
-        if (sparse) { n.o_tri = o_tri; r[8] = o_tri; o_tri += ((int64_t)s * (s + 1) / 2 + 3) & ~(int64_t)3; }
-        else if (quad) { n.o_finv = o_d4; n.o_w = o_u4; r[5] = o_d4; r[6] = o_u4; o_d4 += (s4 + b4) * s; o_u4 += s4 * b; }
-        else { n.o_finv = o_finv; n.o_w = o_w; r[5] = o_finv; r[6] = o_w; o_finv += (int64_t)s * s; o_w += (int64_t)s * b; }
-    }
-    LS_REQUIRE(o_finv + 2 * o_w + o_d4 + o_u4 + 2 * o_tri < (int64_t)4000000000, LS_E_WORKSPACE, "ls_direct_factor: the factor is too large");
-    lap("layouts");
-    // ---- sparse leaves: where every leaf's two pointer lists (A_bs by boundary row / by own row) start; the lists themselves are
-    // built on the device below
-    std::vector<int> off_b, off_s;
-    int64_t n_sp_ptr = 0;
-    const int64_t leaf0 = P.level_off[levels - 1], leaf1 = P.level_off[levels];
-    if (leaves_ok) {
-        off_b.assign((size_t)(leaf1 - leaf0), -1); off_s.assign((size_t)(leaf1 - leaf0), -1);
-        for (int pass = 0; pass < 2; ++pass)                 // boundary rows of all leaves first, then own rows
-            for (int64_t i = leaf0; i < leaf1; ++i) {
-                if (P.s[i] < 1) continue;
-                (pass == 0 ? off_b : off_s)[(size_t)(i - leaf0)] = (int)n_sp_ptr;
-                hn[(size_t)i * LS_DIRECT_NODE_COLS + (pass == 0 ? 9 : 10)] = n_sp_ptr;
-                n_sp_ptr += (pass == 0 ? P.b[i] : P.s[i]) + 1;
-            }
-    }
-    const double t2 = now_s();
-    // ---- device storage ---------------------------------------------------------------------------------------------------------------
-    // keep: 0 scratch (back to the pool at the end), 1 the handle's (factor arrays), 2 the refactor state's when the handle is refactorable
-    // (sharded handles are not: ls_direct_refactor reports LS_E_STATE for them), scratch otherwise
-    const bool retain = refactorable && shard_count <= 1;
-    std::vector<void*> owned, scratch, kept;
-    std::vector<size_t> owned_bytes, scratch_bytes, kept_bytes;
-    int rc = LS_OK;
-    auto dalloc = [&](void** p, size_t bytes, int keep, bool zero) -> bool {
-        const double ta = timing ? now_s() : 0.0;
-        const size_t want = std::max<size_t>(bytes, 16) + 16;
-        hipError_t e = hipSuccess;
-        size_t cap = want;
-        *p = pool_take(device, want, &cap);                          // large buffers: from the pool the previous solver's went to (direct.hip)
-        const bool pooled = *p != nullptr;
-        if (!pooled) e = pool_alloc(device, p, want);                // (out of memory: the pool is emptied and the call repeated once)
-        const double tb = timing ? now_s() : 0.0;
-        if (e == hipSuccess && zero) e = hipMemsetAsync(*p, 0, std::max<size_t>(bytes, 16) + 16, st);
-        if (timing && bytes > ((size_t)256 << 20)) {
-            (void)hipStreamSynchronize(st);
-            fprintf(stderr, "[ls_direct_factor]   %.2f GB: %s %.1f ms, %s %.1f ms\n", bytes / 1073741824.0, pooled ? "from the pool" : "hipMalloc", (tb - ta) * 1e3, zero ? "zeroed in" : "no memset",
-                    (now_s() - tb) * 1e3);
-        }
-        if (e != hipSuccess) { rc = hip_fail(e, "ls_direct_factor allocation", __FILE__, __LINE__); *p = nullptr; return false; }
-        (keep == 1 ? owned : keep == 2 && retain ? kept : scratch).push_back(*p);
-        (keep == 1 ? owned_bytes : keep == 2 && retain ? kept_bytes : scratch_bytes).push_back(cap);
-        return true;
-    };
-    float *finv = nullptr, *wf = nullptr, *wb = nullptr, *u4 = nullptr, *d4 = nullptr, *tri = nullptr;
-    int32_t* d_sp_ptr = nullptr; SpEnt* d_sp_ent = nullptr;
-    double *fronts = nullptr, *xs = nullptr, *ws = nullptr, *work = nullptr;
-    int *d_inv = nullptr, *d_non = nullptr, *d_bnd = nullptr, *d_ppos = nullptr, *d_rowidx = nullptr, *d_ids = nullptr;
-    FactorNode* d_nodes = nullptr;
-    FactorCtx ctx;
-    int* d_flag = nullptr;
-    GemmDesc *d_gemm = nullptr, *d_gemm_off = nullptr; InvDesc *d_invd = nullptr, *d_invd_off = nullptr;
-    int32_t *d_rowptr_kept = nullptr, *d_col_kept = nullptr;
-    LeafSlot* d_slots = nullptr;
-    int64_t work_tot = 0;
-    for (int i = 1; i <= n_nodes; ++i) work_tot += ((int64_t)P.s[i] * P.s[i] + 1) / 2 + 64;
-    bool ok = dalloc((void**)&finv, sizeof(float) * o_finv, true, false) && dalloc((void**)&wf, sizeof(float) * o_w, true, false) &&
-              dalloc((void**)&wb, sizeof(float) * o_w, true, false) && dalloc((void**)&u4, sizeof(float) * o_u4, true, true) &&
-              dalloc((void**)&d4, sizeof(float) * o_d4, true, true) && dalloc((void**)&tri, sizeof(float) * o_tri, true, true) &&
-              dalloc((void**)&d_sp_ptr, sizeof(int32_t) * n_sp_ptr, true, false) &&
-              dalloc((void**)&fronts, sizeof(double) * f_tot, false, false) && dalloc((void**)&xs, sizeof(double) * x_tot, false, false) &&
-              dalloc((void**)&ws, sizeof(double) * w_tot, false, false) && dalloc((void**)&work, sizeof(double) * work_tot, false, false) &&
-              dalloc((void**)&d_inv, sizeof(int) * V, 2, false) && dalloc((void**)&d_non, sizeof(int) * V, 2, false) &&
-              dalloc((void**)&d_bnd, sizeof(int) * P.n_bnd, 2, false) && dalloc((void**)&d_ppos, sizeof(int) * P.n_bnd, 2, false) &&
-              dalloc((void**)&d_rowidx, sizeof(int) * nnz, false, false) &&
-              dalloc((void**)&d_nodes, sizeof(FactorNode) * (n_nodes + 1), 2, false) && dalloc((void**)&d_flag, sizeof(int), false, true) &&
-              (!retain || (dalloc((void**)&d_rowptr_kept, sizeof(int32_t) * (V + 1), 2, false) && dalloc((void**)&d_col_kept, sizeof(int32_t) * nnz, 2, false)));
-    auto cleanup = [&](bool all) {
-        (void)hipStreamSynchronize(st);
-        for (size_t i = 0; i < scratch.size(); ++i) if (!pool_give(device, scratch[i], scratch_bytes[i])) (void)hipFree(scratch[i]);
-        scratch.clear(); scratch_bytes.clear();
-        if (all) {
-            for (size_t i = 0; i < owned.size(); ++i) if (!pool_give(device, owned[i], owned_bytes[i])) (void)hipFree(owned[i]);
-            owned.clear(); owned_bytes.clear();
-            for (size_t i = 0; i < kept.size(); ++i) if (!pool_give(device, kept[i], kept_bytes[i])) (void)hipFree(kept[i]);
-            kept.clear(); kept_bytes.clear();
-        }
-    };
-    if (!ok) { cleanup(true); return rc; }
-    lap("device allocations");
-    hipError_t e = hipSuccess;
-    auto h2d = [&](void* dst, const void* src, size_t bytes) { if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st); };
-    h2d(d_inv, P.inv.data(), sizeof(int) * V); h2d(d_non, P.node_of_new.data(), sizeof(int) * V);
-    h2d(d_bnd, P.bnd.data(), sizeof(int) * P.n_bnd); h2d(d_ppos, P.ppos.data(), sizeof(int) * P.n_bnd);
-    h2d(d_nodes, fn.data(), sizeof(FactorNode) * (n_nodes + 1));
-    if (retain && e == hipSuccess) e = hipMemcpyAsync(d_rowptr_kept, d_rowptr, sizeof(int32_t) * (V + 1), hipMemcpyDeviceToDevice, st);
-    if (retain && e == hipSuccess) e = hipMemcpyAsync(d_col_kept, d_col, sizeof(int32_t) * nnz, hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) { cleanup(true); return hip_fail(e, "ls_direct_factor uploads", __FILE__, __LINE__); }
-    hipLaunchKernelGGL(k_expand_rows, dim3((unsigned)div_up(V, 256)), dim3(256), 0, st, V, d_rowptr, d_rowidx);
-    int64_t n_ent = 0;
-    if (leaves_ok) {
-        // own rows of the leaves: the tree's numbering [0, rows_s); boundary rows: bnd[bnd0, n_bnd)
-        const int64_t rows_s = levels > 1 ? P.own_start[P.level_off[levels - 2]] : V, bnd0 = P.bnd_off[leaf0], rows_b = P.n_bnd - bnd0;
-        int *cnt_s = nullptr, *cnt_b = nullptr, *ptr_s = nullptr, *ptr_b = nullptr, *bsum = nullptr, *d_off_b = nullptr, *d_off_s = nullptr;
-        ok = dalloc((void**)&cnt_s, sizeof(int) * (rows_s + 1), false, true) && dalloc((void**)&cnt_b, sizeof(int) * (rows_b + 1), false, true) &&
-             dalloc((void**)&ptr_s, sizeof(int) * (rows_s + 1), false, false) && dalloc((void**)&ptr_b, sizeof(int) * (rows_b + 1), false, false) &&
-             dalloc((void**)&bsum, sizeof(int) * (scan_blocks(std::max(rows_s, rows_b)) + 2), false, false) &&
-             dalloc((void**)&d_off_b, sizeof(int) * off_b.size(), false, false) && dalloc((void**)&d_off_s, sizeof(int) * off_s.size(), false, false);
-        if (!ok) { cleanup(true); return rc; }
-        h2d(d_off_b, off_b.data(), sizeof(int) * off_b.size()); h2d(d_off_s, off_s.data(), sizeof(int) * off_s.size());
-        const unsigned eg = (unsigned)div_up(nnz, 256);
-        hipLaunchKernelGGL(k_leaf_entries<0>, dim3(eg), dim3(256), 0, st, nnz, d_rowidx, d_col, d_val, d_inv, d_non, d_nodes, d_bnd, (long long)bnd0, cnt_s,
-                           cnt_b, (const int*)nullptr, (const int*)nullptr, (SpEnt*)nullptr, 0);
-        int tot[2] = {0, 0};
-        if ((rc = exclusive_scan(cnt_s, rows_s, ptr_s, bsum, st)) != LS_OK || (rc = exclusive_scan(cnt_b, rows_b, ptr_b, bsum, st)) != LS_OK) { cleanup(true); return rc; }
-        if (e == hipSuccess) e = hipMemcpyAsync(&tot[0], ptr_s + rows_s, sizeof(int), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(&tot[1], ptr_b + rows_b, sizeof(int), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemsetAsync(cnt_s, 0, sizeof(int) * (rows_s + 1), st);
-        if (e == hipSuccess) e = hipMemsetAsync(cnt_b, 0, sizeof(int) * (rows_b + 1), st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) { cleanup(true); return hip_fail(e, "ls_direct_factor leaf lists", __FILE__, __LINE__); }
-        if (tot[0] != tot[1]) { cleanup(true); set_error("ls_direct_factor: the leaf lists disagree (%d own-row entries, %d boundary-row entries)", tot[0], tot[1]); return LS_E_INVALID; }
-        n_ent = tot[0];
-        if (!dalloc((void**)&d_sp_ent, sizeof(SpEnt) * 2 * n_ent, true, true)) { cleanup(true); return rc; }
-        hipLaunchKernelGGL(k_leaf_entries<1>, dim3(eg), dim3(256), 0, st, nnz, d_rowidx, d_col, d_val, d_inv, d_non, d_nodes, d_bnd, (long long)bnd0, cnt_s,
-                           cnt_b, (const int*)ptr_s, (const int*)ptr_b, d_sp_ent, (int)n_ent);
-        if (rows_b) hipLaunchKernelGGL(k_leaf_sort, dim3((unsigned)div_up(rows_b, 256)), dim3(256), 0, st, rows_b, (const int*)ptr_b, 0, d_sp_ent);
-        if (rows_s) hipLaunchKernelGGL(k_leaf_sort, dim3((unsigned)div_up(rows_s, 256)), dim3(256), 0, st, rows_s, (const int*)ptr_s, (int)n_ent, d_sp_ent);
-        hipLaunchKernelGGL(k_leaf_ptrs, dim3((unsigned)(leaf1 - leaf0)), dim3(64), 0, st, (int)leaf0, d_nodes, (long long)bnd0, (const int*)d_off_b,
-                           (const int*)d_off_s, (const int*)ptr_b, (const int*)ptr_s, (int)n_ent, d_sp_ptr);
-        if (retain) {                                           // where every value went, taken after the sort (ls_direct_refactor rewrites them there)
-            if (!dalloc((void**)&d_slots, sizeof(LeafSlot) * nnz, 2, false)) { cleanup(true); return rc; }
-            hipLaunchKernelGGL(k_leaf_slots, dim3(eg), dim3(256), 0, st, nnz, d_rowidx, d_col, d_inv, d_non, d_nodes, d_bnd, (long long)bnd0,
-                               (const int*)ptr_s, (const int*)ptr_b, (const SpEnt*)d_sp_ent, (int)n_ent, d_slots);
-        }
-    } else if (!dalloc((void**)&d_sp_ent, 16, true, true)) { cleanup(true); return rc; }
-    if (e != hipSuccess) { cleanup(true); return hip_fail(e, "ls_direct_factor uploads", __FILE__, __LINE__); }
-    lap("uploads");
-    // ---- numeric factorisation: recorded (host), uploaded, launched back to back ---------------------------------------------------------
-    std::vector<int> ids;
-    std::vector<int64_t> work_off((size_t)n_nodes + 1, 0);
-    { int64_t o = 0; for (int i = 1; i <= n_nodes; ++i) { work_off[i] = o; o += ((int64_t)P.s[i] * P.s[i] + 1) / 2 + 64; } }
-    for (int lv = levels - 1; lv >= 0; --lv) {
-        const int64_t first = P.level_off[lv], last = P.level_off[lv + 1];
-        if (lv + 1 < levels) {                                      // children's Schur complements, one sibling index per launch
-            for (int c = 0; c < arity; ++c) {
-                ids.clear();
-                int bmax = 0;
-                for (int64_t ch = P.level_off[lv + 1] + c; ch < P.level_off[lv + 2]; ch += arity)
-                    if (P.b[ch] > 0) { ids.push_back((int)ch); bmax = std::max(bmax, P.b[ch]); }
-                id_launch(ctx, 2, ids, std::min(64, div_up((int64_t)bmax * bmax, 256)));
-            }
-        }
-        int smax = 0;
-        for (int64_t i = first; i < last; ++i) smax = std::max(smax, P.s[i]);
-        int depth = 0;
-        while (((smax + (1 << depth) - 1) >> depth) > INV_N) ++depth;
-        std::vector<Blk> blocks;
-        ids.clear();
-        for (int64_t i = first; i < last; ++i) {
-            if (P.s[i] == 0) continue;
-            const int m = P.s[i] + P.b[i];
-            blocks.push_back(Blk{fronts + fn[i].f_off, xs + fn[i].x_off, work + work_off[i], P.s[i], m, P.s[i]});
-            ids.push_back((int)i);
-        }
-        inverse_rec(ctx, blocks, depth);
-        std::vector<GemmDesc> gd;
-        for (int64_t i = first; i < last; ++i) {                    // W = F_bs Finv
-            const int s = P.s[i], b = P.b[i], m = s + b;
-            if (s && b) gd.push_back(GemmDesc{fronts + fn[i].f_off + (size_t)s * m, xs + fn[i].x_off, ws + fn[i].w_off, b, s, s, m, s, s, 0, 0, 1.0, 0.0});
-        }
-        gemm_batched(ctx, gd);
-        for (int64_t i = first; i < last; ++i) {                    // U = F_bb - W F_sb  (F_sb = F_bs^T)
-            const int s = P.s[i], b = P.b[i], m = s + b;
-            if (s && b) gd.push_back(GemmDesc{ws + fn[i].w_off, fronts + fn[i].f_off + (size_t)s * m, fronts + fn[i].f_off + (size_t)s * m + s,
-                                              b, b, s, s, m, m, 0, 1, -1.0, 1.0, 1, 0});
-        }
-        gemm_batched(ctx, gd);
-        int64_t emax = 0;
-        for (int i : ids) emax = std::max(emax, (int64_t)P.s[i] * (P.s[i] + P.b[i]));
-        id_launch(ctx, 3, ids, std::min(256, div_up(emax, 256)));
-    }
-    ok = dalloc((void**)&d_gemm, sizeof(GemmDesc) * ctx.gemm.size(), false, false) && dalloc((void**)&d_invd, sizeof(InvDesc) * ctx.inv.size(), false, false) &&
-         dalloc((void**)&d_ids, sizeof(int) * ctx.ids.size(), 2, false) &&
-         (!retain || (dalloc((void**)&d_gemm_off, sizeof(GemmDesc) * ctx.gemm.size(), 2, false) && dalloc((void**)&d_invd_off, sizeof(InvDesc) * ctx.inv.size(), 2, false)));
-    if (!ok) { cleanup(true); return rc; }
-    h2d(d_gemm, ctx.gemm.data(), sizeof(GemmDesc) * ctx.gemm.size());
-    h2d(d_invd, ctx.inv.data(), sizeof(InvDesc) * ctx.inv.size());
-    h2d(d_ids, ctx.ids.data(), sizeof(int) * ctx.ids.size());
-    std::vector<GemmDesc> gemm_off;
-    std::vector<InvDesc> inv_off;
-    if (retain) {
-        // the descriptors as offsets (in doubles) into [fronts | xs | ws | work]: k_rebase points them into a refactorisation's scratch.
-        // An operand no region holds belongs to an empty product (K = 0, never read): offset 0.
-        const uintptr_t base[4] = {(uintptr_t)fronts, (uintptr_t)xs, (uintptr_t)ws, (uintptr_t)work};
-        const int64_t len[4] = {f_tot, x_tot, w_tot, work_tot};
-        auto off = [&](const double* p) -> double* {
-            const uintptr_t q = (uintptr_t)p;
-            int64_t start = 0;
-            for (int k = 0; k < 4; ++k) {
-                if (q >= base[k] && q < base[k] + sizeof(double) * (size_t)len[k]) return (double*)(uintptr_t)(start + (int64_t)((q - base[k]) / sizeof(double)));
-                start += len[k];
-            }
-            return nullptr;
-        };
-        gemm_off = ctx.gemm;
-        for (GemmDesc& g : gemm_off) { g.A = off(g.A); g.B = off(g.B); g.C = off(g.C); }
-        inv_off = ctx.inv;
-        for (InvDesc& v : inv_off) { v.M = off(v.M); v.X = off(v.X); }
-        h2d(d_gemm_off, gemm_off.data(), sizeof(GemmDesc) * gemm_off.size());
-        h2d(d_invd_off, inv_off.data(), sizeof(InvDesc) * inv_off.size());
-    }
-    std::vector<hipEvent_t> evs;
-    if (e == hipSuccess) {
-        const NumericRun run{nnz, d_rowidx, d_col, d_val, d_inv, d_non, d_bnd, d_ppos, d_ids, d_nodes, d_gemm, d_invd, &ctx.cmds,
-                             fronts, xs, ws, f_tot, finv, wf, wb, u4, d4, tri, d_flag};
-        e = numeric_run(run, device, st, evs, &ctx.launches);
-    }
-    struct EventGuard { std::vector<hipEvent_t>& v; ~EventGuard() { for (hipEvent_t x : v) (void)hipEventDestroy(x); } } ev_guard{evs};
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) { cleanup(true); return hip_fail(e, "ls_direct_factor kernels", __FILE__, __LINE__); }
-    // ---- the solver handle: its tables are built on the host WHILE the device factorises (everything above is only enqueued) ------------
-    if (timing) fprintf(stderr, "[ls_direct_factor]   %d launches enqueued %.3f s (host clock)\n", ctx.launches, now_s() - t0);
-    nd_plan_push_lists(P);          // (left out of the analysis: only the solve needs them)
-    if (timing) fprintf(stderr, "[ls_direct_factor]   push lists built %.3f s (host clock)\n", now_s() - t0);
-    ls_direct_arrays A;
-    memset(&A, 0, sizeof(A));
-    A.V = V; A.levels = levels; A.arity = arity; A.h_nodes = hn.data(); A.h_perm = P.perm.data(); A.h_ppos = P.ppos.data(); A.n_bnd = P.n_bnd;
-    A.h_push_ptr = P.push_ptr.data(); A.h_push_tgt = P.push_tgt.data(); A.n_front = P.n_front;
-    A.d_finv = finv; A.d_wf = wf; A.d_wb = wb; A.d_u4 = u4; A.d_d4 = d4; A.d_tri = tri; A.d_sp_ptr = d_sp_ptr; A.d_sp_ent = d_sp_ent;
-    A.n_sp_ptr = n_sp_ptr; A.n_sp_ent = 2 * n_ent;
-    A.shard_rank = shard_rank; A.shard_count = shard_count; A.tier_waves = tier_waves;
-    rc = ls_direct_create(&A, device, stream, out);
-    int flag = 0;
-    e = hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (rc != LS_OK || e != hipSuccess || flag) {
-        if (rc == LS_OK) { (void)ls_direct_destroy(*out); *out = nullptr; }       // (the handle does not own the factor arrays yet)
-        cleanup(true);
-        if (rc != LS_OK) return rc;
-        if (e != hipSuccess) return hip_fail(e, "ls_direct_factor kernels", __FILE__, __LINE__);
-        set_error(flag == 2 ? "ls_direct_factor: the matrix pattern is not symmetric" : "ls_direct_factor: a front is not positive definite");
-        return LS_E_INVALID;
-    }
-    cleanup(false);
-    if (retain) {
-        RefactorState* R = new RefactorState;
-        R->device = device; R->V = V; R->nnz = nnz; R->f_tot = f_tot; R->x_tot = x_tot; R->w_tot = w_tot; R->work_tot = work_tot;
-        R->rowptr = d_rowptr_kept; R->col = d_col_kept; R->inv = d_inv; R->non = d_non; R->bnd = d_bnd; R->ppos = d_ppos; R->ids = d_ids;
-        R->nodes = d_nodes; R->gemm = d_gemm_off; R->invd = d_invd_off; R->slots = d_slots;
-        R->cmds = ctx.cmds; R->n_gemm = ctx.gemm.size(); R->n_inv = ctx.inv.size();
-        R->finv = finv; R->wf = wf; R->wb = wb; R->u4 = u4; R->d4 = d4; R->tri = tri; R->sp_ent = d_sp_ent;
-        for (size_t i = 0; i < kept.size(); ++i) R->bufs.emplace_back(kept[i], kept_bytes[i]);
-        kept.clear(); kept_bytes.clear();
-        ls_direct_adopt_refactor(*out, R);
-    }
-    const double t3 = now_s();
-    lap("numeric factorisation + solve tables (overlapped)");
-    if (timing) {
-        const long long nc = ls::g_malloc_calls.exchange(0), us = ls::g_malloc_us.exchange(0), by = ls::g_malloc_bytes.exchange(0);
-        fprintf(stderr, "[ls_direct_factor]   allocations that missed the pool since the last report: %lld hipMalloc calls, %.1f MB, %.2f ms\n", nc, by / 1048576.0, us / 1e3);
-    }
-    const double secs[3] = {t1 - t0, t2 - t1, t3 - t2};
-    const double quality[4] = {(double)P.ordering, P.words_per_vertex, P.spread, P.words_other};
-    return ls_direct_adopt(*out, owned.data(), owned_bytes.data(), (int)owned.size(), secs, quality);
 }
 
 // ---- is a CSR matrix symmetric (pattern and values)? Replaces a sort-based check on the host side of the solver -------------------

@@ -33,6 +33,12 @@ constexpr int TIER_WAVES = 4;            // waves per tier workgroup: 4 (four wo
 constexpr int TIER_WAVES_WIDE = 8;       // (<= 768 workgroups -- the arity-8 trees of 105k-300k vertices have 512: with 4 waves each that is half a
                                          //  CU's waves; 8 waves per workgroup, two workgroups per CU: -5 %)
 constexpr int TIER_WAVES_FULL = 16;      // one workgroup per CU on a subtree one level taller (direct_tier_full16, direct.hip: from 800k vertices)
+// dynamic LDS budgets in bytes (host side: what the planner lets a workgroup ask for)
+constexpr int TIER_LDS_FULL = 160 * 1024;  // a 16-wave tier workgroup: one per CU, the whole 160 KB
+constexpr int TIER_LDS = 150 * 1024;       // a 4-wave tier workgroup
+constexpr int TIER_LDS_WIDE = 80 * 1024;   // an 8-wave tier workgroup: two per CU
+constexpr int LEVEL_LDS = 150 * 1024;      // a level kernel's front (the tiles above the tier)
+constexpr int LDS_OPTIN = 160 * 1024;      // the dynamic-LDS limit every tier and level kernel is opted in to
 constexpr int TIER_TRI4 = 9;             // 16-byte loads per lane that hold a leaf triangle (s <= 64: 2080 floats = 520 float4)
 constexpr int TIER_SPE = 4;              // sparse entries per row prefetched to registers (longer rows: loop)
 

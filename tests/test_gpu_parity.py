@@ -459,6 +459,50 @@ def test_factor_and_solve_through_the_c_abi_only(golden, dev, name):
     assert rc != 0 and not h.value
 
 
+def test_refused_constructions_leave_no_device_memory(dev):
+    """A construction refused half way gives back every device buffer it took: three of a matrix that is not positive definite (refused
+    after the numeric factorisation) and one whose explicit tier -- six levels of an arity-8 tree on the 1M plane -- does not fit the tier
+    kernels' LDS (refused by ls_direct_create). With the pool emptied the device's free memory is what it was."""
+    import ctypes
+    from largesteps import _native, synthetic
+    from largesteps.geometry import compute_matrix
+    from largesteps.solvers import release_scratch
+    v, f, c = synthetic.config_mesh("cfg4_plane1m")
+    tv = _t(v, dev).contiguous()
+    csr = _native.csr_of(compute_matrix(tv, _t(f, dev), lambda_=c["lambda_"]))
+    bad = csr.val.clone()
+    bad[csr.rowptr[:-1].long()] = -1.0                              # first stored entry of every row (vertex 0: its diagonal)
+    lib = _native.lib()
+
+    def factor(val, **options):
+        opt = _native.DirectOptions()
+        _native.check(lib.ls_direct_options_default(ctypes.byref(opt)))
+        for k, x in options.items():
+            setattr(opt, k, x)
+        h = ctypes.c_void_p()
+        rc = lib.ls_direct_factor_ex(_native.ptr(csr.rowptr), _native.ptr(csr.col), _native.ptr(val), csr.V, csr.nnz, _native.ptr(tv),
+                                     ctypes.byref(opt), dev.index, _native.stream_of(dev), ctypes.byref(h))
+        return rc, h
+
+    def free():
+        torch.cuda.synchronize(dev)
+        release_scratch(dev)
+        torch.cuda.empty_cache()
+        return torch.cuda.mem_get_info(dev)[0]
+
+    rc, h = factor(csr.val)                                         # kernels loaded, side streams created
+    assert rc == 0, _native.last_error()
+    _native.check(lib.ls_direct_destroy(h))
+    f0 = free()
+    for _ in range(3):
+        rc, h = factor(bad)
+        assert rc != 0 and not h.value and "not positive definite" in _native.last_error(), _native.last_error()
+    rc, h = factor(csr.val, arity=8, leaf_size=64, tier_levels=6)
+    assert rc != 0 and not h.value and "does not fit" in _native.last_error(), _native.last_error()
+    f1 = free()
+    assert abs(f1 - f0) <= (2 << 20), (f0, f1)
+
+
 def test_python_array_handle_matches_native_factorisation(dev):
     """ls_direct_create (plan and factor handed over as arrays: here the numpy plan + torch factorisation STATEMENTS of
     tests/) and ls_direct_factor (everything native) solve the same system to the same accuracy."""
