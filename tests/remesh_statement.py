@@ -393,12 +393,88 @@ def point_triangle(p, a, b, c):
     return r
 
 
-def project(V, F, V0, F0):
+def _dt(a, b):
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def point_triangle_torch(p, a, b, c):
+    """point_triangle in torch, fp64 on any device: the same operations in the same order, so the same bits as numpy"""
+    import torch
+    ab, ac, ap = b - a, c - a, p - a
+    d1, d2 = _dt(ab, ap), _dt(ac, ap)
+    bp = p - b
+    d3, d4 = _dt(ab, bp), _dt(ac, bp)
+    vc = d1 * d4 - d3 * d2
+    cp = p - c
+    d5, d6 = _dt(ab, cp), _dt(ac, cp)
+    vb = d5 * d2 - d1 * d6
+    va = d3 * d6 - d5 * d4
+    v_ab = d1 / (d1 - d3)
+    w_ac = d2 / (d2 - d6)
+    w_bc = (d4 - d3) / ((d4 - d3) + (d5 - d6))
+    den = torch.ones_like(va) / ((va + vb) + vc)
+    v, w = vb * den, vc * den
+    r = (a + ab * v[..., None]) + ac * w[..., None]
+    r = torch.where(((va <= 0) & (d4 - d3 >= 0) & (d5 - d6 >= 0))[..., None], b + (c - b) * w_bc[..., None], r)
+    r = torch.where(((vb <= 0) & (d2 >= 0) & (d6 <= 0))[..., None], a + ac * w_ac[..., None], r)
+    r = torch.where(((d6 >= 0) & (d5 <= d6))[..., None], c, r)
+    r = torch.where(((vc <= 0) & (d1 >= 0) & (d3 <= 0))[..., None], a + ab * v_ab[..., None], r)
+    r = torch.where(((d3 >= 0) & (d4 <= d3))[..., None], b, r)
+    r = torch.where(((d1 <= 0) & (d2 <= 0))[..., None], a, r)
+    return r
+
+
+def closest_points_torch(P, V0, F0, device="cpu", pchunk=1024, tchunk=4096):
+    """closest_points on a torch device, in chunks of points and triangles: (closest points (n, 3), their squared distances (n,)),
+    fp64 tensors on `device`. Same bits as closest_points: its region tests and order, and the first minimum over all triangles (a
+    later chunk replaces the running best only when strictly closer; a NaN distance counts as the smallest, as in np.argmin)."""
+    import torch
+
+    def f64(x):
+        return (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x))).to(device=device, dtype=torch.float64)
+
+    P, V0 = f64(P), f64(V0)
+    F0 = (F0 if isinstance(F0, torch.Tensor) else torch.from_numpy(np.asarray(F0, dtype=np.int64))).to(device=device, dtype=torch.int64)
+    A, B, C = (V0[F0[:, k]] for k in range(3))
+    T = F0.shape[0]
+    q_out = torch.empty_like(P)
+    d_out = torch.empty(P.shape[0], dtype=torch.float64, device=device)
+    for s in range(0, P.shape[0], pchunk):
+        p = P[s:s + pchunk, None, :]
+        rows = torch.arange(p.shape[0], device=device)
+        best_k = torch.full((p.shape[0],), float("inf"), dtype=torch.float64, device=device)
+        best_q = p[:, 0, :].clone()
+        best_d = best_k.clone()
+        for t in range(0, T, tchunk):
+            q = point_triangle_torch(p, A[None, t:t + tchunk], B[None, t:t + tchunk], C[None, t:t + tchunk])
+            dd = p - q
+            d2 = (dd[..., 0] * dd[..., 0] + dd[..., 1] * dd[..., 1]) + dd[..., 2] * dd[..., 2]
+            k = torch.where(torch.isnan(d2), float("-inf"), d2)
+            m = k.min(dim=1).values
+            ids = torch.arange(k.shape[1], device=device)
+            j = torch.where(k == m[:, None], ids, k.shape[1]).min(dim=1).values           # first minimum of the chunk
+            better = m < best_k
+            best_k = torch.where(better, m, best_k)
+            best_d = torch.where(better, d2[rows, j], best_d)
+            best_q = torch.where(better[:, None], q[rows, j], best_q)
+        q_out[s:s + pchunk] = best_q
+        d_out[s:s + pchunk] = best_d
+    return q_out, d_out
+
+
+def closest_on(device, **chunks):
+    """a `closest=` argument for project / iteration / remesh_botsch: closest_points computed by closest_points_torch on `device`"""
+    def closest(P, V0, F0):
+        return closest_points_torch(P, V0, F0, device, **chunks)[0].cpu().numpy()
+    return closest
+
+
+def project(V, F, V0, F0, closest=closest_points):
     t = Topo(V, F)
     move = (~t.bnd) & (t.cnt > 0)
     out = V.copy()
     if move.any():
-        out[move] = closest_points(V[move], V0, F0).astype(F32)
+        out[move] = closest(V[move], V0, F0).astype(F32)
     return out, F, int(move.sum())
 
 
@@ -414,22 +490,30 @@ def run_phase(fn, cap, V, F, h):
     return V, F, rounds, ops
 
 
-def iteration(V, F, h, project_to=None):
-    V, F, _, _ = run_phase(split_round, SPLIT_ROUNDS, V, F, h)
-    V, F, _, _ = run_phase(collapse_round, COLLAPSE_ROUNDS, V, F, h)
-    V, F, _, _ = run_phase(flip_round, FLIP_ROUNDS, V, F, h)
+def iteration(V, F, h, project_to=None, closest=closest_points, stats=None):
+    """one iteration; `stats` (a dict, optional) accumulates the rounds and operations of each phase (the device's info() counters)"""
+    for name, fn, cap in (("split", split_round, SPLIT_ROUNDS), ("collapse", collapse_round, COLLAPSE_ROUNDS), ("flip", flip_round, FLIP_ROUNDS)):
+        V, F, rounds, ops = run_phase(fn, cap, V, F, h)
+        if stats is not None:
+            stats.setdefault("rounds", {}).setdefault(name, 0)
+            stats.setdefault("ops", {}).setdefault(name, 0)
+            stats["rounds"][name] += rounds
+            stats["ops"][name] += ops
     V, F, _ = relax(V, F)
     if project_to is not None:
-        V, F, _ = project(V, F, *project_to)
+        V, F, _ = project(V, F, *project_to, closest=closest)
     return V, F
 
 
-def remesh_botsch(V, F, iters, h, project=True):
+def remesh_botsch(V, F, iters, h, project=True, closest=closest_points, stats=None):
     V = np.asarray(V, dtype=F32)
     F = np.asarray(F, dtype=np.int64)
     validate(V, F)
     V, F = drop_unreferenced(V, F)
     V0, F0 = V.copy(), F.copy()
+    if stats is not None:
+        for k in ("rounds", "ops"):
+            stats.setdefault(k, {}).update({name: stats.get(k, {}).get(name, 0) for name in ("split", "collapse", "flip")})
     for _ in range(iters):
-        V, F = iteration(V, F, h, (V0, F0) if project else None)
+        V, F = iteration(V, F, h, (V0, F0) if project else None, closest, stats)
     return V, F

@@ -196,3 +196,36 @@ def test_projection_is_the_closest_point():
     samples = np.einsum("sk,fkd->fsd", w, v[f].astype(np.float64)).reshape(-1, 3)
     dd = np.linalg.norm(p[:, None, :] - samples[None], axis=2).min(axis=1)
     assert (d <= dd + 1e-9).all()
+
+
+def probe_points(v, f, n, seed):
+    """points around a mesh: vertices and shared-edge midpoints exactly, and points near (0.02 of the box) and far (3 boxes) from it"""
+    rng = np.random.default_rng(seed)
+    v64 = v.astype(np.float64)
+    span = float(np.linalg.norm(v64.max(0) - v64.min(0)))
+    e = edges(f)
+    on_v = v64[rng.choice(v.shape[0], n)]
+    on_e = e[rng.choice(e.shape[0], n)]
+    on_e = (v64[on_e[:, 0]] + v64[on_e[:, 1]]) * 0.5
+    near = v64[rng.choice(v.shape[0], n)] + rng.normal(scale=0.02 * span, size=(n, 3))
+    far = rng.normal(scale=3.0 * span, size=(n, 3))
+    return np.concatenate([on_v, on_e, near, far])
+
+
+@pytest.mark.parametrize("name", ["icosphere_perturbed", "torus"])
+def test_torch_closest_points_is_the_statement_bitwise(name):
+    """closest_points_torch (the device brute force of the GPU tests) on torch CPU: the bits of closest_points, with chunk sizes that
+    cut the triangle list inside vertex fans, so ties across chunks follow the first-minimum rule"""
+    v, f = MESHES[name]
+    p = probe_points(v, f, 60, seed=3)
+    want = rs.closest_points(p, v, f)
+    got, d2 = rs.closest_points_torch(p, v, f, "cpu", pchunk=97, tchunk=61)
+    got = got.numpy()
+    assert np.array_equal(got.view(np.int64), want.view(np.int64))
+    dd = p - want
+    assert np.array_equal(d2.numpy(), (dd[:, 0] * dd[:, 0] + dd[:, 1] * dd[:, 1]) + dd[:, 2] * dd[:, 2])
+    # through project(): the default and the torch port give the same vertices
+    V, F, _ = rs.relax(v, f)
+    a = rs.project(V, F, v, f)[0]
+    b = rs.project(V, F, v, f, closest=rs.closest_on("cpu", pchunk=128, tchunk=100))[0]
+    assert np.array_equal(a.view(np.int32), b.view(np.int32))

@@ -1,7 +1,10 @@
 """
 largesteps.remesh.remesh_botsch on the device (csrc/remesh.hip) against tests/remesh_statement.py: every phase on its own (identical
-faces, positions within 2 ulp, int32 and int64 faces), the full call on the 70k and 250k configs (invariants, reproducibility,
-numpy vs tensor entry, distance to the input surface), scripts/main.py's remesh block end to end, and the argument errors.
+faces, positions within 2 ulp, int32 and int64 faces), single rounds at 70k, the full call (ls_remesh_run) on a grid of meshes and
+settings with the handle's counters, the handle's runs and phases composed, the projection against a brute-force closest point on
+meshes up to 1M vertices (folded sheets, a thin tube, graded and collapsed meshes, a mesh far from the origin), the full call on the
+70k and 250k configs (invariants, reproducibility, numpy vs tensor entry, distance to the input surface), scripts/main.py's remesh
+block end to end, and the argument errors.
 """
 import numpy as np
 import pytest
@@ -199,3 +202,221 @@ def test_argument_errors(dev):
         remesh_botsch(tv.to(dev), torch.from_numpy(g).to(dev), 1, 0.1, True)
     with pytest.raises(ValueError):
         remesh_botsch(v.astype(np.float64), np.concatenate([f, [[0, 0, 1]]]).astype(np.int32), 1, 0.1, True)
+
+
+# ---- the full call against the statement -----------------------------------------------------------------------------------------
+def _ico(n):
+    v, f = synthetic.icosphere(n)
+    return synthetic.perturb(v, radial=0.05, seed=n).astype(F32), f
+
+
+def translated(v, f):
+    """the mesh moved to about 1000 diagonals from the origin (a part in scanner units): its coordinates' ulps exceed 1e-5 diagonals"""
+    diag = float(np.linalg.norm(v.astype(np.float64).max(0) - v.astype(np.float64).min(0)))
+    return (v.astype(np.float64) + 1000.0 * diag).astype(F32), f
+
+
+def call_meshes():
+    out = {f"ico{n}": _ico(n) for n in (6, 7, 8, 9, 12)}
+    out["torus"] = torus()
+    out["plane"] = synthetic.plane(10)
+    sv, sf = out["ico6"]
+    tv, tf = torus()
+    out["sphere_torus"] = (np.concatenate([sv, tv + F32(3.0)]).astype(F32), np.concatenate([sf, tf + sv.shape[0]]))
+    # 40 vertices no face references, before, among and after the used ones
+    rng = np.random.default_rng(5)
+    extra = np.sort(rng.choice(sv.shape[0] + 40, 40, replace=False))
+    used = np.setdiff1d(np.arange(sv.shape[0] + 40), extra)
+    uv = np.zeros((sv.shape[0] + 40, 3), F32)
+    uv[used] = sv
+    uv[extra] = rng.normal(size=(40, 3)).astype(F32)
+    out["unreferenced"] = (uv, used[sf])
+    out["translated"] = translated(sv, sf)
+    return out
+
+
+CALL_MESHES = call_meshes()
+
+# every mesh, every h / avg in {0.15, 0.5, 1, 2, 4}, i in {0, 1, 5}, project on and off, int32 and int64 faces, numpy and tensor entry
+CALLS = [("torus", 0.15, 1, True, np.int32, "tensor"), ("ico8", 0.5, 5, True, np.int64, "numpy"), ("ico12", 0.5, 5, True, np.int32, "tensor"),
+         ("ico7", 2.0, 5, True, np.int64, "tensor"), ("ico6", 4.0, 5, True, np.int32, "numpy"), ("ico9", 1.0, 1, True, np.int64, "tensor"),
+         ("ico7", 0.5, 5, False, np.int32, "tensor"), ("torus", 1.0, 5, False, np.int64, "tensor"), ("torus", 0.5, 0, True, np.int32, "numpy"),
+         ("torus", 0.5, 5, True, np.int32, "tensor"), ("plane", 0.5, 5, True, np.int32, "numpy"), ("plane", 2.0, 1, False, np.int64, "tensor"),
+         ("sphere_torus", 1.0, 5, True, np.int64, "tensor"), ("unreferenced", 0.5, 1, True, np.int32, "numpy"),
+         ("unreferenced", 1.0, 0, False, np.int64, "tensor"), ("translated", 0.5, 5, True, np.int32, "tensor"),
+         ("translated", 2.0, 1, False, np.int64, "numpy")]
+
+
+@pytest.mark.parametrize("mesh,scale,iters,project,idx,entry", CALLS, ids=lambda x: getattr(x, "__name__", str(x)))
+def test_full_call_matches_the_statement(dev, mesh, scale, iters, project, idx, entry):
+    """remesh_botsch (ls_remesh_run: the iteration loop, the round caps, the buffers' growth over rounds, one BVH for all
+    projections) against rs.remesh_botsch: identical faces, positions within 2 ulp, and the handle's round and operation counters
+    equal to the statement's sums over the call"""
+    from largesteps.remesh import RemeshHandle, remesh_botsch
+    v, f = CALL_MESHES[mesh]
+    h = F32(scale * avg_edge(v, f))
+    stats = {}
+    ev, ef = rs.remesh_botsch(v, f, iters, h, project, closest=rs.closest_on(dev), stats=stats)
+    tv, tf = torch.from_numpy(v).to(dev), torch.from_numpy(f.astype(idx)).to(dev)
+    if entry == "numpy":
+        gv, gf = remesh_botsch(v.astype(np.float64), f.astype(idx), iters, h, project)
+        assert gv.dtype == np.float64 and gf.dtype == np.int32
+        gv = gv.astype(F32)
+    else:
+        tgv, tgf = remesh_botsch(tv, tf, iters, h, project)
+        assert tgv.dtype == torch.float32 and tgf.dtype == tf.dtype
+        gv, gf = tgv.cpu().numpy(), tgf.cpu().numpy()
+    assert np.array_equal(gf.astype(np.int64), ef), "faces differ from the statement"
+    assert gv.shape == ev.shape and ulps(gv, ev) <= 2
+    with RemeshHandle(tv, tf, h, project) as r:
+        r.run(iters)
+        info = r.info()
+        hv, hf = r.result()
+    assert info["rounds"] == stats["rounds"] and info["ops"] == stats["ops"]
+    assert np.array_equal(hf.cpu().numpy(), gf) and np.array_equal(hv.cpu().numpy().view(np.int32), gv.view(np.int32))
+
+
+def _handle_state(r):
+    V, F = r.result()
+    return V.cpu().numpy().view(np.int32), F.cpu().numpy(), (r.info()["rounds"], r.info()["ops"])
+
+
+def test_handle_runs_compose(dev):
+    """run(2) then run(3) is run(5) bit for bit, counters included; the five phases called one by one are run(1)"""
+    from largesteps.remesh import RemeshHandle
+    v, f = CALL_MESHES["ico8"]
+    h = F32(0.5 * avg_edge(v, f))
+    tv, tf = torch.from_numpy(v).to(dev), torch.from_numpy(f).to(dev)
+    with RemeshHandle(tv, tf, h, True) as a, RemeshHandle(tv, tf, h, True) as b:
+        a.run(5)
+        b.run(2)
+        b.run(3)
+        sa, sb = _handle_state(a), _handle_state(b)
+    assert np.array_equal(sa[0], sb[0]) and np.array_equal(sa[1], sb[1]) and sa[2] == sb[2]
+    with RemeshHandle(tv, tf, h, True) as a, RemeshHandle(tv, tf, h, True) as b:
+        a.run(1)
+        for p, cap in (("split", rs.SPLIT_ROUNDS), ("collapse", rs.COLLAPSE_ROUNDS), ("flip", rs.FLIP_ROUNDS), ("relax", 1), ("project", 1)):
+            b.phase(p, cap)
+        sa, sb = _handle_state(a), _handle_state(b)
+    assert np.array_equal(sa[0], sb[0]) and np.array_equal(sa[1], sb[1]) and sa[2] == sb[2]
+
+
+def test_device_brute_force_is_the_statement_bitwise(dev):
+    """closest_points_torch on the device gives the bits of numpy closest_points (so it may stand in for it below)"""
+    from test_remesh_cpu import probe_points
+    v, f = SMALL["torus"]
+    p = probe_points(v, f, 64, seed=4)
+    want = rs.closest_points(p, v, f)
+    got, _ = rs.closest_points_torch(p, v, f, dev, pchunk=100, tchunk=70)
+    assert np.array_equal(got.cpu().numpy().view(np.int64), want.view(np.int64))
+
+
+# ---- single rounds at 70k --------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def bunny():
+    v, f, _ = synthetic.config_mesh("cfg2_bunny70k")
+    return v.astype(F32), f
+
+
+@pytest.mark.parametrize("phase", ["split", "flip", "relax", "collapse"])
+def test_one_round_at_scale_matches_the_statement(dev, bunny, phase):
+    """one round on the 70k config (collapse: on a 10k-face sphere at h = 2 avg; the statement's collapse round takes minutes at 70k)"""
+    v, f = bunny
+    h = F32(0.5 * avg_edge(v, f))
+    if phase == "flip":                      # an irregular input: one split round of the statement
+        v, f, _ = rs.split_round(v, f, h)
+    if phase == "collapse":
+        v, f = _ico(22)
+        h = F32(2.0 * avg_edge(v, f))
+    fn = {"split": rs.split_round, "collapse": rs.collapse_round, "flip": rs.flip_round, "relax": rs.relax}[phase]
+    ev, ef, n = fn(v, f, h)
+    gv, gf, info = device_phase(dev, v, f, h, np.int32, [phase])
+    if phase != "relax":
+        assert n > (50 if phase == "collapse" else 1000), "the case must exercise the phase"
+        assert info["ops"][phase] == n and info["rounds"][phase] == 1
+    assert np.array_equal(gf, ef)
+    assert gv.shape == ev.shape and ulps(gv, ev) <= 2
+
+
+# ---- the projection at scale against the brute force ----------------------------------------------------------------------------
+def tube(m=6000, k=12, radius=1e-3):
+    """an open tube of length 1 and radius 1e-3 along x: m rings of k vertices"""
+    x = np.arange(m) / (m - 1)
+    w = np.arange(k) * 2 * np.pi / k
+    X, W = np.meshgrid(x, w, indexing="ij")
+    v = np.stack([X, radius * np.cos(W), radius * np.sin(W)], -1).reshape(-1, 3).astype(F32)
+    i, j = np.meshgrid(np.arange(m - 1), np.arange(k), indexing="ij")
+    a, b, c, d = i * k + j, (i + 1) * k + j, (i + 1) * k + (j + 1) % k, i * k + (j + 1) % k
+    return v, np.concatenate([np.stack([a, b, c], -1).reshape(-1, 3), np.stack([a, c, d], -1).reshape(-1, 3)])
+
+
+def projection_mesh(name):
+    if name in ("cfg2_bunny70k", "cfg3_dragon250k", "cfg4b_sphere1m"):
+        v, f, _ = synthetic.config_mesh(name)
+    elif name == "folded":
+        v, f = synthetic.folded_sheet(120)
+    elif name == "scroll":
+        v, f = synthetic.scroll(120, 10)
+    elif name == "shells":
+        v, f = synthetic.shells(40)
+    elif name == "tube":
+        v, f = tube()
+    elif name in ("graded", "collapsed"):
+        from test_ordering_cpu import _hard_mesh
+        v, f = _hard_mesh(name)
+    else:
+        v, f, _ = synthetic.config_mesh("cfg2_bunny70k")
+        v, f = translated(v.astype(F32), f)
+    v, f = np.asarray(v, dtype=F32), np.asarray(f, dtype=np.int64)
+    rs.validate(v, f)
+    return v, f
+
+
+PROJECTION_MESHES = {"cfg2_bunny70k": None, "folded": None, "scroll": None, "shells": None, "cfg3_dragon250k": 16384,
+                     "cfg4b_sphere1m": 16384, "tube": None, "graded": None, "collapsed": None, "bunny_translated": None}
+
+
+@pytest.mark.parametrize("iters", [0, 4])
+@pytest.mark.parametrize("name", list(PROJECTION_MESHES))
+def test_projection_is_the_brute_force_closest_point(dev, name, iters):
+    """after run(iters), split / collapse / flip to their caps and relax: the projection moves every interior vertex to the fp32
+    rounding of the brute-force fp64 closest point of its pre-projection position (the LBVH walk prunes nothing it should not), and
+    its fp64 squared distance is at most the brute-force minimum plus the slack of that rounding. The fp64 test is the statement's
+    and the tie rule the same, so the answer is exact: the same bits, not only within 2 ulp. On the largest meshes: a fixed sample of
+    the interior vertices and the 1024 that relax moved most."""
+    from largesteps.remesh import RemeshHandle
+    v, f = projection_mesh(name)
+    avg = avg_edge(v, f)
+    h = F32(0.5 * avg) if avg > 0 else F32(1e-2)
+    with RemeshHandle(torch.from_numpy(v).to(dev), torch.from_numpy(f).to(dev), h, True) as r:
+        r.run(iters)
+        for p, cap in (("split", rs.SPLIT_ROUNDS), ("collapse", rs.COLLAPSE_ROUNDS), ("flip", rs.FLIP_ROUNDS)):
+            r.phase(p, cap)
+        P_flip, _ = r.result()
+        r.phase("relax")
+        P_pre, F_pre = r.result()
+        r.phase("project")
+        P_post, F_post = r.result()
+    assert torch.equal(F_pre, F_post)
+    F_np = F_post.cpu().numpy().astype(np.int64)
+    t = rs.Topo(np.zeros((P_post.shape[0], 3), F32), F_np)
+    interior = np.nonzero(~t.bnd & (t.cnt > 0))[0]
+    pre, post = P_pre.cpu().numpy(), P_post.cpu().numpy()
+    fixed = np.setdiff1d(np.arange(pre.shape[0]), interior)
+    assert np.array_equal(pre[fixed].view(np.int32), post[fixed].view(np.int32)), "a boundary vertex moved"
+    idx = interior
+    sample = PROJECTION_MESHES[name]
+    if sample is not None and interior.size > sample:
+        moved = torch.linalg.vector_norm((P_pre - P_flip).double(), dim=1).cpu().numpy()[interior]
+        top = interior[np.argsort(-moved, kind="stable")[:1024]]
+        rng = np.random.default_rng(0)
+        idx = np.union1d(rng.choice(interior, sample, replace=False), top)
+    q, d2 = rs.closest_points_torch(torch.from_numpy(pre[idx]), v, f, dev, pchunk=256, tchunk=65536)
+    want = q.float().cpu().numpy()
+    got = post[idx]
+    n_off = int((got.view(np.int32) != want.view(np.int32)).any(axis=1).sum())
+    assert n_off == 0, f"{n_off} of {idx.size} vertices are not the brute force's (largest difference {ulps(got, want)} ulp)"
+    e = torch.linalg.vector_norm(q - q.float().double(), dim=1)
+    dpost = ((torch.from_numpy(post[idx]).to(dev).double() - torch.from_numpy(pre[idx]).to(dev).double()) ** 2).sum(1)
+    bound = (torch.sqrt(d2) + e) ** 2 * (1 + 1e-12)
+    assert bool((dpost <= bound).all()), "a vertex is farther from the input surface than the brute force's nearest point"
