@@ -22,13 +22,18 @@ N > 1 (one rank per GPU, RCCL; largesteps.distributed), strong scaling (total wo
   halo             : N contiguous vertex blocks of the Chebyshev / PCG iteration with ghost layers (neighbour exchanges);
   replicas         : every rank solves its own copy of the system (independent meshes), weak scaling, no communication.
 
-Prints ONE JSON line on rank 0 (contract: see the task description): metric/value/unit/... plus
+Prints ONE JSON line on rank 0 (contract: see the task description): metric/value/unit/n_gpus/steps/warmup/ms_per_step/...
+N = 1 without --full (the plain run): set up, warm up, time the K steps, --dump-outputs, print the line -- nothing that takes runs of
+its own; "config" then holds only what setup and the timed steps already measured, "roofline" and "cpu_baseline" are null.
+N = 1 with --full, after the timed region and --dump-outputs:
   "roofline":     HBM roofline of the dominant kernel group (the down sweep of the direct solver: its algorithmic bytes /
                   its duration from HIP events on the solve's own stream, in an extra profiled pass right after the timed
-                  region, same workload)
+                  region, same workload), with per-launch, assembly, to_differential and constructor-repeat figures in "config"
   "cpu_baseline": the oracle's CPU "factor once / re-solve" direct solver (scipy SuperLU, fp64, 1 thread) on
-                  the same 1M-vertex system, rank 0 at N = 1 only (bounded: 1 factorisation + 3 solves); "extra": the
-                  reference's CG algorithm on the host (70k config) and in stock torch ops on the device (B2 / B3)
+                  the same 1M-vertex system, rank 0 at N = 1 only (bounded: 1 factorisation + 3 solves), and the forward error of
+                  the timed solve against it (config.tolerance); "extra": the reference's CG algorithm on the host (70k config) and in
+                  stock torch ops on the device (B2 / B3)
+N > 1 runs the same with or without --full (largesteps.distributed.bench_sharded: per-rank profile and self-check included).
 """
 import argparse
 import json
@@ -254,6 +259,26 @@ def dump_output(out_dir, name, t):
     np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
+def headline(args, ms):
+    """the keys every N = 1 line starts with, in this order"""
+    return dict(metric="from_differential_solves_per_sec", value=1e3 / ms, unit="solves/s", n_gpus=1, steps=args.steps,
+                warmup=args.warmup, ms_per_step=ms, higher_is_better=True, scaling="strong", vs_baseline=None, dtype="f32",
+                data="synthetic")
+
+
+def report_plain(args, solver, info, ms, workload, t_assemble):
+    """JSON line of a plain N = 1 run: what setup and the timed steps already measured, no further device or host work (--full adds
+    the profiled passes, the roofline, the constructor repeats, the CPU baselines and the forward error against the fp64 oracle)."""
+    direct = info["method"] == "nested-dissection"
+    config = dict(workload=workload + (", factor once (not timed), re-solve timed" if direct else ", cold start, residual reduction 1e-6"),
+                  method=info["method"], iterations=0 if direct else info["iterations"], assemble_ms=t_assemble * 1e3,
+                  factor_seconds=getattr(solver, "build_seconds", None) if direct else None,
+                  device=torch.cuda.get_device_name(0))
+    if not direct:
+        config["converged"] = info["converged"]
+    print(json.dumps(dict(headline(args, ms), config=config, roofline=None, cpu_baseline=None)), flush=True)
+
+
 def run_single(args):
     from largesteps.geometry import compute_matrix
     from largesteps.parameterize import to_differential, from_differential
@@ -306,6 +331,8 @@ def run_single(args):
     info = dict(solver.last_info)
     ms = elapsed / args.steps * 1e3
     method = info["method"]
+    if not args.full:
+        return report_plain(args, solver, info, ms, describe(args.workload, cfg, V, nnz), t_assemble)
     if method == "nested-dissection":
         return report_direct(args, solver, M, u, x, tv, v, f, cfg, ms, t_assemble)
 
@@ -364,9 +391,7 @@ def run_single(args):
         kernel_desc = "k_spmv_dot<3> (K1: Ap = M p on SELL-64, partial p.Ap)"
         kernel_us = dict(k1_spmv_dot=k_ms[0] * 1e3, k2_update=k_ms[1] * 1e3, k3_direction=k_ms[2] * 1e3)
     out = dict(
-        metric="from_differential_solves_per_sec", value=1e3 / ms, unit="solves/s", n_gpus=1, steps=args.steps,
-        warmup=args.warmup, ms_per_step=ms, higher_is_better=True, scaling="strong", vs_baseline=None, dtype="f32",
-        data="synthetic",
+        headline(args, ms),
         config=dict(workload=describe(args.workload, cfg, V, nnz) + ", cold start, residual reduction 1e-6", solver=solver_desc, method=method,
                     iterations=info["iterations"], converged=info["converged"],
                     tolerance=dict(kind="relative residual ||r|| / ||b|| per column at which the iteration stops (SURVEY 8d)", rel=1e-6,
@@ -544,9 +569,7 @@ def report_direct(args, solver, M, u, x, tv, v, f, cfg, ms, t_assemble):
         except Exception:
             steady_seconds = None
     out = dict(
-        metric="from_differential_solves_per_sec", value=1e3 / ms, unit="solves/s", n_gpus=1, steps=args.steps,
-        warmup=args.warmup, ms_per_step=ms, higher_is_better=True, scaling="strong", vs_baseline=None, dtype="f32",
-        data="synthetic",
+        headline(args, ms),
         config=dict(workload=describe(args.workload, cfg, V, nnz) + ", factor once (not timed), re-solve timed",
                     solver=(f"HIP nested-dissection multifrontal direct solver behind ls_direct_factor: {inf['levels']} tree levels, "
                             f"symbolic analysis (bisection rounds on the device, tree and index lists on host threads), fp64 factorisation with hand-written kernels (once), fp32 factor "
@@ -717,8 +740,12 @@ def main():
     ap.add_argument("--block", type=int, default=None, help="threads per PCG workgroup (256 or 1024; default: auto)")
     ap.add_argument("--grid", type=int, default=0)
     ap.add_argument("--check-every", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-baselines", action="store_true", help="skip the B2 / B3 legs (reference CG on the host / in stock torch ops)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the timed steps also measure the roofline, per-launch, assembly, to_differential and constructor-repeat "
+                         "figures, the CPU baselines and the forward error against the fp64 oracle (a plain run prints the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines (and the oracle's forward error)")
+    ap.add_argument("--no-extra-baselines", action="store_true",
+                    help="--full: skip the B2 / B3 legs (reference CG on the host / in stock torch ops) and the constructor repeats")
     ap.add_argument("--pcg", action="store_true", help="time the Jacobi-PCG instead of the default (Chebyshev) solver")
     ap.add_argument("--iterative", action="store_true",
                     help="'Cholesky' through the Chebyshev-Jacobi iteration instead of the nested-dissection direct solver (A/B)")
