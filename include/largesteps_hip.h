@@ -638,6 +638,49 @@ int ls_adam_uniform_step(float* param, const float* grad, float* g1, float* g2, 
 int ls_adam_uniform_step_device(float* param, const float* grad, float* g1, float* g2, int64_t n, float lr, float beta1,
                                 float beta2, int32_t* d_step, void* scratch, int device, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Differentiable rasterizer (largesteps/render.py; the rules are stated in csrc/raster.hip and DESIGN.md section 2.7, restated in
+ * numpy by tests/render_statement.py). pos (B, V, 4) fp32 clip-space positions, tri (F, 3) int32 whose indices lie in [0, V) (the
+ * caller range-checks them: ls_corner_ranks does), resolution H x W up to 4096 each; rast (B, H, W, 4) fp32 = (u, v, z/w, id + 1), 0 for
+ * background. vptr / corner_order: the corner ranking of ls_corner_ranks for tri (corner_order = rank -> corner, "order" above). No entry
+ * point allocates or synchronises, none uses float atomics: outputs and gradients are bitwise reproducible. ASYNC.
+ *   ls_raster_workspace_bytes       workspace of every entry point below for these sizes and C attribute / colour channels.
+ *   ls_raster_forward               rast. Coverage: homogeneous edge functions in fp64 with a top-left rule, z/w in [-1, 1].
+ *   ls_raster_pixel_order           order (B H W) = the pixels sorted stably by b F + face (background last), seg (B F + 1) = the first
+ *                                   sorted position of each key: the order every backward sums in. Reads only rast's id channel.
+ *   ls_raster_backward              grad_pos (B, V, 4) = d (sum grad_rast[..., 0:2] * (u, v)) / d pos; the z/w channel's gradient is
+ *                                   dropped, grad_pos[..., 2] = 0. Overwritten.
+ *   ls_raster_interpolate           out (B, H, W, C) = u a0 + v a1 + (1 - u - v) a2, 0 for background; attr (attr_batch, V, C) with
+ *                                   attr_batch 1 (shared by every image) or B.
+ *   ls_raster_interpolate_backward  grad_rast (B, H, W, 4) (channels 2, 3 zero) and grad_attr (attr_batch, V, C); either may be NULL.
+ *   ls_raster_adjacency             adj (3 F): the face across edge (corner e, corner e + 1) of face f at adj[3 f + e], -1 when the
+ *                                   edge has one face or more than two. Radix sort of the half-edges.
+ *   ls_raster_antialias             out (B, H, W, C): the colour blended across silhouette edges between neighbouring pixels.
+ *   ls_raster_antialias_backward    grad_color (B, H, W, C) and grad_pos (B, V, 4) (scaled by boost, [..., 2] = 0); either may be NULL.
+ * --------------------------------------------------------------------------------------------- */
+int ls_raster_workspace_bytes(int64_t B, int64_t F, int H, int W, int C, size_t* bytes);
+int ls_raster_forward(const float* pos, int64_t B, int64_t V, const int32_t* tri, int64_t F, int H, int W, float* rast, void* ws,
+                      size_t ws_bytes, int device, void* stream);
+int ls_raster_pixel_order(const float* rast, int64_t B, int64_t F, int H, int W, int32_t* order, int32_t* seg, void* ws, size_t ws_bytes,
+                          int device, void* stream);
+int ls_raster_backward(const float* pos, int64_t B, int64_t V, const int32_t* tri, int64_t F, int H, int W, const float* grad_rast,
+                       const int32_t* order, const int32_t* seg, const int32_t* vptr, const int32_t* corner_order, float* grad_pos,
+                       void* ws, size_t ws_bytes, int device, void* stream);
+int ls_raster_interpolate(const float* attr, int64_t attr_batch, int64_t V, int C, const float* rast, int64_t B, int H, int W,
+                          const int32_t* tri, int64_t F, float* out, int device, void* stream);
+int ls_raster_interpolate_backward(const float* attr, int64_t attr_batch, int64_t V, int C, const float* rast, int64_t B, int H, int W,
+                                   const int32_t* tri, int64_t F, const float* grad_out, const int32_t* order, const int32_t* seg,
+                                   const int32_t* vptr, const int32_t* corner_order, float* grad_attr, float* grad_rast, void* ws,
+                                   size_t ws_bytes, int device, void* stream);
+int ls_raster_adjacency_workspace_bytes(int64_t F, size_t* bytes);
+int ls_raster_adjacency(const int32_t* tri, int64_t F, int32_t* adj, void* ws, size_t ws_bytes, int device, void* stream);
+int ls_raster_antialias(const float* color, int C, const float* rast, const float* pos, int64_t B, int64_t V, int H, int W,
+                        const int32_t* tri, int64_t F, const int32_t* adj, float* out, int device, void* stream);
+int ls_raster_antialias_backward(const float* color, int C, const float* rast, const float* pos, int64_t B, int64_t V, int H, int W,
+                                 const int32_t* tri, int64_t F, const int32_t* adj, const float* grad_out, float boost,
+                                 const int32_t* order, const int32_t* seg, const int32_t* vptr, const int32_t* corner_order,
+                                 float* grad_color, float* grad_pos, void* ws, size_t ws_bytes, int device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,21 @@ _SIGNATURES = {
                                      c_void_p, c_int, c_void_p]),
     "ls_adam_uniform_step_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_float, c_float, c_float, c_void_p,
                                             c_void_p, c_int, c_void_p]),
+    "ls_raster_workspace_bytes": (c_int, [c_i64, c_i64, c_int, c_int, c_int, ctypes.POINTER(c_size_t)]),
+    "ls_raster_forward": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_int, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "ls_raster_pixel_order": (c_int, [c_void_p, c_i64, c_i64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "ls_raster_backward": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "ls_raster_interpolate": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_i64, c_int, c_int, c_void_p, c_i64, c_void_p, c_int, c_void_p]),
+    "ls_raster_interpolate_backward": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_i64, c_int, c_int, c_void_p, c_i64, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "ls_raster_adjacency_workspace_bytes": (c_int, [c_i64, ctypes.POINTER(c_size_t)]),
+    "ls_raster_adjacency": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "ls_raster_antialias": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_void_p, c_i64, c_void_p, c_void_p, c_int,
+                                    c_void_p]),
+    "ls_raster_antialias_backward": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_void_p, c_i64, c_void_p, c_void_p,
+                                             c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int,
+                                             c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

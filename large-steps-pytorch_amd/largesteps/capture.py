@@ -12,7 +12,7 @@ function:
     def body():
         v = from_differential(M, u, 'Cholesky')
         n = compute_vertex_normals(v, f, compute_face_normals(v, f))
-        loss = (render(v, n) - target).abs().mean()
+        loss = (renderer.render(v, n, f) - target).abs().mean()     # renderer = largesteps.render.NVDRenderer(scene_params)
         opt.zero_grad(set_to_none=True)        # (set_to_none=True: the gradient tensors are then graph-private and reused)
         loss.backward()
         opt.step()

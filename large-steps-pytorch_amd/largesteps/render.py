@@ -1,0 +1,500 @@
+"""
+Differentiable rasterizer on the MI355X, in the shape of the nvdiffrast calls the reference's renderer makes
+(rgl-epfl/large-steps-pytorch scripts/render.py): `import nvdiffrast.torch as dr` becomes `import largesteps.render as dr`.
+
+Primitives (autograd Functions over hand-written HIP, csrc/raster.hip; the rules are DESIGN.md section 2.7, restated in numpy by
+tests/render_statement.py):
+
+    rast, rast_db = rasterize(ctx, pos, tri, resolution)       pos (B, V, 4) clip space, tri (F, 3) int32 / int64, resolution (H, W)
+    out, _ = interpolate(attr, rast, tri)                      attr (V, C), (1, V, C) or (B, V, C)
+    color_aa = antialias(color, rast, pos, tri, pos_gradient_boost=1.0)
+    texture(tex, uv)                                           bilinear, wrapping, forward only (plain torch: backgrounds only)
+
+plus the renderer built on them: `persp_proj`, `SphericalHarmonics`, `NVDRenderer` (same constructor keys, same values as the
+reference's). Conventions: rast = (u, v, z/w, id + 1), 0 for background; an attribute interpolates as u a0 + v a1 + (1 - u - v) a2;
+row 0 of an image is NDC y = -1, pixel (x, y) has its centre at NDC ((2x + 1) / W - 1, (2y + 1) / H - 1). Gradients: rasterize passes
+the gradients of u and v to pos (the z/w channel's gradient is dropped), interpolate to attr and to rast[..., :2], antialias to color
+and (scaled by pos_gradient_boost) to pos. No float atomics anywhere: images and gradients are bitwise reproducible, and no call
+synchronises with the host once a face tensor has been seen (its edge adjacency and corner ranking are cached per tensor object), so
+the whole render can sit inside `CapturedStep`. There is no CPU path.
+"""
+import ctypes
+import weakref
+
+import numpy as np
+import torch
+from torch.autograd import Function
+
+from . import _native
+from .normals import _plan as _corner_plan
+
+__all__ = ["RasterizeContext", "RasterizeGLContext", "RasterizeCudaContext", "rasterize", "interpolate", "antialias", "texture",
+           "persp_proj", "SphericalHarmonics", "NVDRenderer"]
+
+
+class RasterizeContext:
+    """Accepted and ignored: the rasterizer keeps no per-context state (nvdiffrast's GL / CUDA contexts hold buffers)."""
+
+    def __init__(self, *args, **kwargs):
+        pass
+
+
+RasterizeGLContext = RasterizeContext
+RasterizeCudaContext = RasterizeContext
+
+
+# ---- per face tensor: range check + corner ranking (normals.py's cache) and the edge adjacency ------------------------------------------
+_adjacency = {}
+
+
+def _faces(tri, V):
+    _native.require_device(tri, "tri")
+    if tri.dim() != 2 or tri.shape[1] != 3:
+        raise ValueError(f"tri must be (F, 3), got {tuple(tri.shape)}")
+    if tri.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"tri must be int32 or int64, got {tri.dtype}")
+    f = tri if tri.is_contiguous() else tri.contiguous()
+    vptr, _, narrow, order = _corner_plan(f, V)       # range check: an index outside [0, V) raises IndexError
+    if narrow.dtype != torch.int32:
+        raise OverflowError("tri needs indices below 2**31")
+    return f, narrow, vptr, order
+
+
+def _adjacent(f, narrow):
+    key = id(f)
+    hit = _adjacency.get(key)
+    if hit is not None:
+        ref, version, ptr, adj = hit
+        if ref() is f and version == f._version and ptr == f.data_ptr():
+            return adj
+        del _adjacency[key]
+    F = narrow.shape[0]
+    n = ctypes.c_size_t(0)
+    _native.check(_native.lib().ls_raster_adjacency_workspace_bytes(F, ctypes.byref(n)))
+    ws = torch.empty(n.value, dtype=torch.uint8, device=f.device)
+    adj = torch.empty(max(3 * F, 1), dtype=torch.int32, device=f.device)
+    with torch.cuda.device(f.device):
+        _native.check(_native.lib().ls_raster_adjacency(_native.ptr(narrow), F, _native.ptr(adj), _native.ptr(ws), ws.numel(), f.device.index,
+                                                        _native.stream_of(f.device)))
+    for k in [k for k, h in _adjacency.items() if h[0]() is None]:
+        del _adjacency[k]
+    if len(_adjacency) >= 8:
+        _adjacency.clear()
+    try:
+        _adjacency[key] = (weakref.ref(f), f._version, f.data_ptr(), adj)
+    except TypeError:
+        pass
+    return adj
+
+
+def _workspace(B, F, H, W, C, dev):
+    n = ctypes.c_size_t(0)
+    _native.check(_native.lib().ls_raster_workspace_bytes(B, F, H, W, C, ctypes.byref(n)))
+    return torch.empty(n.value, dtype=torch.uint8, device=dev)
+
+
+def _pos(pos):
+    _native.require_device(pos, "pos")
+    if pos.dim() != 3 or pos.shape[2] != 4:
+        raise ValueError(f"pos must be (B, V, 4) clip-space positions (instanced mode), got {tuple(pos.shape)}")
+    p = pos.detach()
+    if p.dtype != torch.float32 or not p.is_contiguous():
+        p = p.to(torch.float32).contiguous()
+    return p
+
+
+def _rast(rast):
+    _native.require_device(rast, "rast")
+    if rast.dim() != 4 or rast.shape[3] != 4:
+        raise ValueError(f"rast must be (B, H, W, 4), got {tuple(rast.shape)}")
+    r = rast.detach()
+    return r if (r.dtype == torch.float32 and r.is_contiguous()) else r.to(torch.float32).contiguous()
+
+
+class _PixelOrder:
+    """The pixels of one rasterized frame sorted by (image, face) -- the order every backward sums in. Made at most once per frame, by
+    the first backward that needs it, and shared through the rast tensor."""
+    __slots__ = ("version", "F", "order", "seg")
+
+    def __init__(self, version, F):
+        self.version, self.F, self.order, self.seg = version, F, None, None
+
+    def get(self, r):
+        if self.order is None:
+            B, H, W, _ = r.shape
+            dev = r.device
+            order = torch.empty(B * H * W, dtype=torch.int32, device=dev)
+            seg = torch.empty(B * self.F + 1, dtype=torch.int32, device=dev)
+            ws = _workspace(B, self.F, H, W, 0, dev)
+            with torch.cuda.device(dev):
+                _native.check(_native.lib().ls_raster_pixel_order(_native.ptr(r), B, self.F, H, W, _native.ptr(order), _native.ptr(seg),
+                                                                  _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
+            self.order, self.seg = order, seg
+        return self.order, self.seg
+
+
+def _order_slot(rast, F):
+    slot = getattr(rast, "_largesteps_order", None)
+    if slot is not None and slot.version == rast._version and slot.F == F:
+        return slot
+    return _PixelOrder(rast._version, F)
+
+
+class _Rasterize(Function):
+    @staticmethod
+    def forward(ctx, pos, tri, H, W, slot):
+        p = _pos(pos)
+        B, V = p.shape[0], p.shape[1]
+        f, narrow, vptr, order = _faces(tri, V)
+        F, dev = narrow.shape[0], p.device
+        rast = torch.empty((B, H, W, 4), dtype=torch.float32, device=dev)
+        ws = _workspace(B, F, H, W, 0, dev)
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().ls_raster_forward(_native.ptr(p), B, V, _native.ptr(narrow), F, H, W, _native.ptr(rast), _native.ptr(ws),
+                                                          ws.numel(), dev.index, _native.stream_of(dev)))
+        rast_db = torch.zeros((B, H, W, 4), dtype=torch.float32, device=dev)
+        ctx.mark_non_differentiable(rast_db)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(p, narrow, vptr, order, rast)
+        ctx.slot = slot
+        ctx.HW = (H, W)
+        return rast, rast_db
+
+    @staticmethod
+    def backward(ctx, g_rast, g_db):
+        if g_rast is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        p, narrow, vptr, corner_order, rast = ctx.saved_tensors
+        B, V = p.shape[0], p.shape[1]
+        F, dev = narrow.shape[0], p.device
+        H, W = ctx.HW
+        g = g_rast.to(torch.float32).contiguous()
+        order, seg = ctx.slot.get(rast)
+        ws = _workspace(B, F, H, W, 0, dev)
+        gp = torch.empty_like(p)
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().ls_raster_backward(_native.ptr(p), B, V, _native.ptr(narrow), F, H, W, _native.ptr(g), _native.ptr(order),
+                                                           _native.ptr(seg), _native.ptr(vptr), _native.ptr(corner_order), _native.ptr(gp),
+                                                           _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
+        return gp, None, None, None, None
+
+
+@_native.retry_on_oom
+def rasterize(glctx, pos, tri, resolution, ranges=None, grad_db=True):
+    """
+    Rasterize triangles (nvdiffrast.torch.rasterize, instanced mode). Returns (rast, rast_db).
+
+    glctx : RasterizeContext (ignored)
+    pos : (B, V, 4) fp32 clip-space positions on a HIP device
+    tri : (F, 3) int32 or int64
+    resolution : (H, W), each in [1, 4096]
+    ranges : must be None (range mode is not supported)
+    grad_db : ignored; rast_db is returned only so that `rasterize(...)[0]` keeps working. It holds zeros (no image-space derivatives
+              are computed) and asking for its gradient raises.
+
+    rast (B, H, W, 4) = (u, v, z/w, triangle id + 1), 0 for background pixels. Coverage: a pixel is covered iff its centre lies in the
+    projected triangle (top-left rule, watertight along shared edges) and z/w is in [-1, 1] (near and far clipping); the nearest
+    covering triangle wins (ties: the lower id). The gradient of rast[..., 0:2] flows to pos; the gradient of the z/w channel is dropped.
+    """
+    if ranges is not None:
+        raise NotImplementedError("largesteps.render.rasterize: range mode (ranges=...) is not supported; pass pos as (B, V, 4)")
+    H, W = (int(resolution[0]), int(resolution[1]))
+    if not (1 <= H <= 4096 and 1 <= W <= 4096):
+        raise ValueError(f"resolution must be (H, W) with each in [1, 4096], got {tuple(resolution)}")
+    F = tri.shape[0] if isinstance(tri, torch.Tensor) and tri.dim() == 2 else 0
+    slot = _PixelOrder(0, F)
+    rast, rast_db = _Rasterize.apply(pos, tri, H, W, slot)
+    slot.version = rast._version
+    _attach_order(rast, slot)
+    return rast, rast_db
+
+
+def _attach_order(rast, slot):
+    rast._largesteps_order = slot
+
+
+class _Interpolate(Function):
+    @staticmethod
+    def forward(ctx, attr, rast, tri, slot):
+        _native.require_device(attr, "attr")
+        r = _rast(rast)
+        B, H, W, _ = r.shape
+        if attr.dim() == 2:
+            a3 = attr.unsqueeze(0)
+        elif attr.dim() == 3:
+            a3 = attr
+        else:
+            raise ValueError(f"attr must be (V, C), (1, V, C) or (B, V, C), got {tuple(attr.shape)}")
+        if a3.shape[0] not in (1, B):
+            raise ValueError(f"attr has {a3.shape[0]} batches for {B} images")
+        a = a3.detach()
+        if a.dtype != torch.float32 or not a.is_contiguous():
+            a = a.to(torch.float32).contiguous()
+        Ba, V, C = a.shape
+        f, narrow, vptr, order = _faces(tri, V)
+        F, dev = narrow.shape[0], r.device
+        out = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().ls_raster_interpolate(_native.ptr(a), Ba, V, C, _native.ptr(r), B, H, W, _native.ptr(narrow), F,
+                                                              _native.ptr(out), dev.index, _native.stream_of(dev)))
+        ctx.save_for_backward(a, r, narrow, vptr, order)
+        ctx.slot = slot
+        ctx.attr_shape = tuple(attr.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        need_attr, need_rast = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_attr or need_rast):
+            return None, None, None, None
+        a, r, narrow, vptr, corner_order = ctx.saved_tensors
+        B, H, W, _ = r.shape
+        Ba, V, C = a.shape
+        F, dev = narrow.shape[0], r.device
+        g = g.to(torch.float32).contiguous()
+        ga = torch.empty_like(a) if need_attr else None
+        gr = torch.empty((B, H, W, 4), dtype=torch.float32, device=dev) if need_rast else None
+        order = seg = ws = None
+        if need_attr:
+            order, seg = ctx.slot.get(r)
+            ws = _workspace(B, F, H, W, C, dev)
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().ls_raster_interpolate_backward(
+                _native.ptr(a), Ba, V, C, _native.ptr(r), B, H, W, _native.ptr(narrow), F, _native.ptr(g), _native.ptr(order), _native.ptr(seg),
+                _native.ptr(vptr), _native.ptr(corner_order), _native.ptr(ga), _native.ptr(gr), _native.ptr(ws), 0 if ws is None else ws.numel(),
+                dev.index, _native.stream_of(dev)))
+        return (ga.view(ctx.attr_shape) if need_attr else None), gr, None, None
+
+
+@_native.retry_on_oom
+def interpolate(attr, rast, tri, rast_db=None, diff_attrs=None):
+    """
+    Interpolate vertex attributes over the rasterized images (nvdiffrast.torch.interpolate). Returns (out, None).
+
+    attr : (V, C), (1, V, C) (shared by every image, as the reference passes it) or (B, V, C) fp32
+    rast : the first output of `rasterize`
+    tri : the faces given to `rasterize`
+    rast_db, diff_attrs : must be None (attribute pixel differentials are not computed)
+
+    out (B, H, W, C) = u a0 + v a1 + (1 - u - v) a2 per covered pixel, 0 for background. Gradients flow to attr and to rast[..., :2].
+    """
+    if diff_attrs is not None:
+        raise NotImplementedError("largesteps.render.interpolate: diff_attrs (attribute pixel differentials) is not supported")
+    F = tri.shape[0] if isinstance(tri, torch.Tensor) and tri.dim() == 2 else 0
+    slot = _order_slot(rast, F)
+    out = _Interpolate.apply(attr, rast, tri, slot)
+    _attach_order(rast, slot)
+    return out, None
+
+
+class _Antialias(Function):
+    @staticmethod
+    def forward(ctx, color, rast, pos, tri, boost, slot):
+        _native.require_device(color, "color")
+        r = _rast(rast)
+        p = _pos(pos)
+        B, H, W, _ = r.shape
+        if color.dim() != 4 or tuple(color.shape[:3]) != (B, H, W):
+            raise ValueError(f"color must be ({B}, {H}, {W}, C), got {tuple(color.shape)}")
+        if p.shape[0] != B:
+            raise ValueError(f"pos has {p.shape[0]} batches for {B} images")
+        c = color.detach()
+        if c.dtype != torch.float32 or not c.is_contiguous():
+            c = c.to(torch.float32).contiguous()
+        C, V = c.shape[3], p.shape[1]
+        f, narrow, vptr, order = _faces(tri, V)
+        adj = _adjacent(f, narrow)
+        F, dev = narrow.shape[0], r.device
+        out = torch.empty_like(c)
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().ls_raster_antialias(_native.ptr(c), C, _native.ptr(r), _native.ptr(p), B, V, H, W, _native.ptr(narrow), F,
+                                                            _native.ptr(adj), _native.ptr(out), dev.index, _native.stream_of(dev)))
+        ctx.save_for_backward(c, r, p, narrow, adj, vptr, order)
+        ctx.boost = float(boost)
+        ctx.slot = slot
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        need_color, need_pos = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
+        if not (need_color or need_pos):
+            return None, None, None, None, None, None
+        c, r, p, narrow, adj, vptr, corner_order = ctx.saved_tensors
+        B, H, W, C = c.shape
+        V, F, dev = p.shape[1], narrow.shape[0], c.device
+        g = g.to(torch.float32).contiguous()
+        gc = torch.empty_like(c) if need_color else None
+        gp = torch.empty_like(p) if need_pos else None
+        order = seg = ws = None
+        if need_pos:
+            order, seg = ctx.slot.get(r)
+            ws = _workspace(B, F, H, W, 0, dev)
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().ls_raster_antialias_backward(
+                _native.ptr(c), C, _native.ptr(r), _native.ptr(p), B, V, H, W, _native.ptr(narrow), F, _native.ptr(adj), _native.ptr(g), ctx.boost,
+                _native.ptr(order), _native.ptr(seg), _native.ptr(vptr), _native.ptr(corner_order), _native.ptr(gc), _native.ptr(gp), _native.ptr(ws),
+                0 if ws is None else ws.numel(), dev.index, _native.stream_of(dev)))
+        return gc, None, gp, None, None, None
+
+
+@_native.retry_on_oom
+def antialias(color, rast, pos, tri, topology_hash=None, pos_gradient_boost=1.0):
+    """
+    Analytic silhouette antialiasing (nvdiffrast.torch.antialias; Laine et al. 2020). Returns the blended (B, H, W, C) image.
+
+    For every horizontally or vertically adjacent pixel pair with different triangle ids, the triangle t of the nearer pixel
+    (background is infinitely far) is searched for a silhouette edge -- a mesh-boundary edge, or one whose neighbour triangle has the
+    opposite screen-space winding in this view -- whose projection crosses the segment between the two pixel centres, at distance
+    alpha (pixels) from the nearer centre. Then, with c_n / c_o the colours of the nearer / other pixel:
+        alpha > 1/2: other += (alpha - 1/2) (c_n - c_o)        alpha < 1/2: nearer += (1/2 - alpha) (c_o - c_n)
+    which makes the image continuous in the vertex positions. Gradients flow to color and to pos (the latter scaled by
+    pos_gradient_boost). topology_hash is accepted and ignored (the edge adjacency is cached per face tensor).
+    """
+    F = tri.shape[0] if isinstance(tri, torch.Tensor) and tri.dim() == 2 else 0
+    slot = _order_slot(rast, F)
+    out = _Antialias.apply(color, rast, pos, tri, float(pos_gradient_boost), slot)
+    _attach_order(rast, slot)
+    return out
+
+
+def texture(tex, uv, uv_da=None, mip_level_bias=None, mip=None, filter_mode='linear', boundary_mode='wrap', max_mip_level=None):
+    """
+    Bilinear texture lookup (nvdiffrast.torch.texture, forward only): tex (1 or B, Ht, Wt, C), uv (B, H, W, 2) -> (B, H, W, C).
+    Texel (i, j) has its centre at ((i + 0.5) / Wt, (j + 0.5) / Ht); coordinates wrap around. The reference calls it once per
+    renderer, to build the backgrounds, so it is plain torch and carries no gradient.
+    """
+    if filter_mode not in ('linear', 'auto') or boundary_mode != 'wrap':
+        raise NotImplementedError("largesteps.render.texture: only filter_mode='linear' with boundary_mode='wrap' is supported")
+    with torch.no_grad():
+        Ht, Wt = tex.shape[1], tex.shape[2]
+        x = uv[..., 0] * Wt - 0.5
+        y = uv[..., 1] * Ht - 0.5
+        x0, y0 = torch.floor(x), torch.floor(y)
+        fx, fy = (x - x0)[..., None], (y - y0)[..., None]
+        i0 = torch.remainder(x0.long(), Wt)
+        j0 = torch.remainder(y0.long(), Ht)
+        i1, j1 = torch.remainder(i0 + 1, Wt), torch.remainder(j0 + 1, Ht)
+        B = uv.shape[0]
+        t = tex if tex.shape[0] == B else tex.expand(B, *tex.shape[1:])
+        bi = torch.arange(B, device=uv.device).view(B, *([1] * (uv.dim() - 2)))
+        t00, t10 = t[bi, j0, i0], t[bi, j0, i1]
+        t01, t11 = t[bi, j1, i0], t[bi, j1, i1]
+        top = t00 + (t10 - t00) * fx
+        bot = t01 + (t11 - t01) * fx
+        return top + (bot - top) * fy
+
+
+def persp_proj(fov_x=45, ar=1, near=0.1, far=100, device=None):
+    """OpenGL-style perspective projection with the reference's sign conventions (x mirrored, w = view-space z): a (4, 4) fp32 tensor.
+    fov_x: horizontal field of view in degrees, ar = width / height."""
+    t = np.tan(np.deg2rad(fov_x) / 2.0)
+    P = np.zeros((4, 4), dtype=np.float64)
+    P[0, 0] = -1.0 / t
+    P[1, 1] = float(np.float32(ar)) / t
+    P[2, 2] = (far + near) / (far - near)
+    P[2, 3] = 2.0 * far * near / (near - far)
+    P[3, 2] = 1.0
+    return torch.tensor(P, dtype=torch.float32, device=device)
+
+
+class SphericalHarmonics:
+    """
+    Order-2 spherical-harmonic irradiance of an environment map (Ramamoorthi and Hanrahan 2001, "An efficient representation for
+    irradiance environment maps"), with Y as the up axis. `M` is (3, 4, 4), one quadratic form per colour channel;
+    `eval(n)` returns n_h^T M n_h for n_h = (n, 1).
+    """
+
+    # normalisation constants of the real spherical harmonics up to l = 2, and the irradiance-filter constants c1..c5 of the paper
+    _K00, _K1, _K2a, _K2b, _K2c = 0.282095, 0.488603, 1.092548, 0.315392, 0.546274
+    _C1, _C2, _C3, _C4, _C5 = 0.429043, 0.511664, 0.743125, 0.886227, 0.247708
+
+    def __init__(self, envmap):
+        h, w = envmap.shape[:2]
+        dev = envmap.device
+        theta = torch.linspace(0, np.pi, h, device=dev)[:, None].expand(h, w)            # polar angle per row
+        phi = torch.linspace(3 * np.pi, np.pi, w, device=dev)[None, :].expand(h, w)      # azimuth per column
+        st = torch.sin(theta)
+        dx, dy, dz = st * torch.cos(phi), torch.cos(theta), -st * torch.sin(phi)
+        # the nine basis functions: constant; z, x, y; 3 z^2 - 1, x z, x^2 - y^2, x y, y z
+        basis = [None, self._K1 * dz, self._K1 * dx, self._K1 * dy,
+                 self._K2b * (3 * dz.square() - 1), self._K2a * dx * dz, self._K2c * (dx.square() - dy.square()), self._K2a * dx * dy,
+                 self._K2a * dy * dz]
+        rad = envmap[..., :3]
+        dw = 2.0 * np.pi ** 2 / (w * h)                        # solid-angle weight per texel (times sin theta)
+
+        def coeff(y):
+            if y is None:
+                return (rad * self._K00 * st[..., None] * dw).sum(dim=(0, 1))
+            return (rad * (y * st)[..., None] * dw).sum(dim=(0, 1))
+
+        # projections of the radiance on the basis functions, named after their polynomial (zz: 3 z^2 - 1, xxyy: x^2 - y^2)
+        Lc, Lz, Lx, Ly, Lzz, Lxz, Lxxyy, Lxy, Lyz = [coeff(y) for y in basis]
+        # Ramamoorthi-Hanrahan eq. 12, with their z axis played by this frame's z and the (x, y, z, 1) ordering of n_h
+        c1, c2, c3, c4, c5 = self._C1, self._C2, self._C3, self._C4, self._C5
+        rows = [
+            [c1 * Lxxyy, c1 * Lxy, c1 * Lxz, c2 * Lx],
+            [c1 * Lxy, -c1 * Lxxyy, c1 * Lyz, c2 * Ly],
+            [c1 * Lxz, c1 * Lyz, c3 * Lzz, c2 * Lz],
+            [c2 * Lx, c2 * Ly, c2 * Lz, c4 * Lc - c5 * Lzz],
+        ]
+        self.M = torch.stack([torch.stack(r) for r in rows]).movedim(2, 0)
+
+    def eval(self, n):
+        nh = torch.nn.functional.pad(n.reshape(-1, 3), (0, 1), 'constant', 1.0).t()           # (4, N)
+        return (nh * (self.M @ nh)).sum(dim=1).t().reshape(n.shape)
+
+
+class NVDRenderer:
+    """
+    The reference's renderer (scripts/render.py) on this package's primitives: the same constructor keys (res_x, res_y, fov,
+    near_clip, far_clip, view_mats, envmap, envmap_scale), the same images. Tensors stay on the device of the scene's tensors.
+
+    shading : shade with the environment's SH irradiance over a background of the environment; otherwise white silhouettes
+    boost : pos_gradient_boost of the antialiasing
+    """
+
+    def __init__(self, scene_params, shading=True, boost=1.0):
+        near, far = scene_params["near_clip"], scene_params["far_clip"]
+        self.fov_x = scene_params["fov"]
+        w, h = scene_params["res_x"], scene_params["res_y"]
+        self.res = (h, w)
+        self.view_mats = torch.stack(list(scene_params["view_mats"]))
+        dev = self.view_mats.device
+        self.proj_mat = persp_proj(self.fov_x, w / h, near, far, device=dev)
+        self.mvps = self.proj_mat @ self.view_mats
+        self.boost = boost
+        self.shading = shading
+        self.glctx = RasterizeContext()
+        envmap = scene_params['envmap_scale'] * scene_params['envmap']
+        self.sh = SphericalHarmonics(envmap)
+        self.render_backgrounds(envmap)
+
+    def background_uvs(self):
+        """the envmap coordinates of every pixel's view ray, (n_views, H, W, 2), before the vertical flip of the backgrounds"""
+        h, w = self.res
+        dev = self.view_mats.device
+        idx = torch.arange(w * h, dtype=torch.int32, device=dev)
+        pix = 0.5 - torch.stack((idx % w, idx // w), dim=1) / torch.tensor((w, h), device=dev)
+        half = np.deg2rad(self.fov_x) / 2
+        scale = torch.tensor((2 * np.tan(half), 2 * np.tan(half) / (w / h)), device=dev, dtype=torch.float32)
+        rays = torch.cat((pix * scale, torch.ones((w * h, 1), device=dev), torch.zeros((w * h, 1), device=dev)), dim=1)
+        rays = rays / torch.norm(rays, dim=1, keepdim=True)
+        world = torch.matmul(rays, self.view_mats.inverse().transpose(1, 2)).reshape((self.view_mats.shape[0], h, w, -1))
+        theta = torch.acos(world[..., 1])
+        phi = torch.atan2(world[..., 0], world[..., 2])
+        return torch.stack([0.75 - phi / (2 * np.pi), theta / np.pi], dim=-1)
+
+    def render_backgrounds(self, envmap):
+        self.bgs = texture(envmap[None, ...], self.background_uvs(), filter_mode='linear').flip(1)
+        self.bgs[..., -1] = 0
+
+    def render(self, v, n, f):
+        """Images (n_views, H, W, 4) of the mesh (v, n, f) from every view, differentiable in v (and n when shading)."""
+        v_ndc = torch.matmul(torch.nn.functional.pad(v, (0, 1), 'constant', 1.0), self.mvps.transpose(1, 2))
+        rast = rasterize(self.glctx, v_ndc, f, self.res)[0]
+        if self.shading:
+            light = interpolate(self.sh.eval(n).contiguous()[None, ...], rast, f)[0]
+            col = torch.cat((light / np.pi, torch.ones((*light.shape[:-1], 1), device=v.device)), dim=-1)
+            return antialias(torch.where(rast[..., -1:] != 0, col, self.bgs), rast, v_ndc, f, pos_gradient_boost=self.boost)
+        col = interpolate(torch.ones_like(v)[None, ...], rast, f)[0]
+        return antialias(col, rast, v_ndc, f, pos_gradient_boost=self.boost)
