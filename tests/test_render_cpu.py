@@ -18,6 +18,7 @@ for p in (ROOT, os.path.join(ROOT, "large-steps-pytorch_amd"), HERE):
         sys.path.insert(0, p)
 
 import render_statement as rs  # noqa: E402
+from render_scenes import grid_mesh as _grid_mesh  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -87,25 +88,6 @@ def test_texture_is_bilinear_with_texel_centres_and_wrap():
 
 
 # ---- the statement ---------------------------------------------------------------------------------------------------------------------
-def _grid_mesh(n, lo, hi, jitter=0.0, seed=0, wscale=False, coords=None):
-    """an n x n vertex grid spanning [lo, hi]^2 in NDC (w = 1), two triangles per cell; optional dyadic jitter of interior vertices and
-    a per-vertex power-of-two homogeneous scale (same projection)"""
-    t = np.linspace(lo, hi, n) if coords is None else coords
-    X, Y = np.meshgrid(t, t, indexing="xy")
-    rng = np.random.default_rng(seed)
-    if jitter:
-        J = np.round(rng.uniform(-jitter, jitter, X.shape) * 1024) / 1024
-        X[1:-1, 1:-1] += J[1:-1, 1:-1]
-        J = np.round(rng.uniform(-jitter, jitter, X.shape) * 1024) / 1024
-        Y[1:-1, 1:-1] += J[1:-1, 1:-1]
-    v = np.stack([X.ravel(), Y.ravel(), np.zeros(n * n), np.ones(n * n)], 1)
-    if wscale:
-        v *= 2.0 ** rng.integers(-2, 3, (n * n, 1))
-    i = (np.arange(n - 1)[:, None] * n + np.arange(n - 1)[None, :]).ravel()
-    f = np.concatenate([np.stack([i, i + 1, i + n + 1], 1), np.stack([i, i + n + 1, i + n], 1)])
-    return v.astype(np.float32)[None], f
-
-
 def _coverage_count(pos, f, H, W):
     py, px = np.meshgrid(rs.centres(H), rs.centres(W), indexing="ij")
     cnt = np.zeros((H, W), dtype=np.int64)

@@ -15,64 +15,10 @@ for p in (ROOT, os.path.join(ROOT, "large-steps-pytorch_amd"), os.path.dirname(o
         sys.path.insert(0, p)
 
 import render_statement as rs  # noqa: E402
+from render_scenes import SCENES, look_at, scene  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0) if torch.cuda.is_available() else None
-
-
-def look_at(eye, target=(0.0, 0.0, 0.0), up=(0.0, 1.0, 0.0)):
-    """world -> view (4, 4) with the camera looking along +z of the view (w = view z under persp_proj)"""
-    eye, target, up = (np.asarray(a, dtype=np.float64) for a in (eye, target, up))
-    z = target - eye
-    z /= np.linalg.norm(z)
-    x = np.cross(up, z)
-    x /= np.linalg.norm(x)
-    y = np.cross(z, x)
-    M = np.eye(4)
-    M[0, :3], M[1, :3], M[2, :3] = x, y, z
-    M[:3, 3] = -M[:3, :3] @ eye
-    return M
-
-
-def clip(v, views, fov=45.0, ar=1.0, near=0.1, far=100.0):
-    from largesteps.render import persp_proj
-    P = persp_proj(fov, ar, near, far).double().numpy()
-    vh = np.concatenate([v.astype(np.float64), np.ones((v.shape[0], 1))], 1)
-    return np.stack([(vh @ (P @ M).T) for M in views]).astype(np.float32)
-
-
-def scene(name):
-    """(pos (B, V, 4) fp32, tri (F, 3) int64, H, W)"""
-    from largesteps import synthetic
-    if name == "sphere":
-        v, f = synthetic.icosphere(4)
-        return clip(v, [look_at((0.3, 0.4, -3.0))], ar=32 / 24), f, 24, 32
-    if name == "sphere_b3":
-        v, f = synthetic.icosphere(3)
-        v = synthetic.perturb(v, radial=0.05, seed=1)
-        return clip(v, [look_at((0, 0, -3.0)), look_at((3.0, 0.5, 0)), look_at((-1.5, 2.0, 2.0))]), f, 20, 20
-    if name == "folded":
-        v, f = synthetic.folded_sheet(6, gap=0.05)
-        v = v - np.array([0.25, 0.5, 0.0], np.float32)
-        return clip(v, [look_at((0.6, 0.3, -1.5))], ar=2.0), f, 16, 32
-    if name == "near_plane":                     # a floor through the eye's plane: crosses near and w = 0
-        v = np.array([[-3, -0.5, -2], [3, -0.5, -2], [3, -0.5, 6], [-3, -0.5, 6]], np.float32)
-        f = np.array([[0, 1, 2], [0, 2, 3]])
-        return clip(v, [look_at((0, 0, -0.5), (0, -0.2, 1.0))], near=0.5, far=10.0, ar=24 / 16), f, 16, 24
-    if name == "sheet":                          # a tilted plane facing the camera: its silhouette is its boundary
-        v, f = synthetic.plane(6)
-        v = v - np.array([0.5, 0.5, 0.0], np.float32)
-        return clip(v, [look_at((0.3, 0.2, -1.6))], ar=32 / 24), f, 24, 32
-    if name == "quad":                           # full-screen 2-triangle quad, w = 1: the cooperative path
-        pos = np.array([[[-1, -1, 0.5, 1], [1, -1, 0.5, 1], [1, 1, 0.5, 1], [-1, 1, 0.5, 1]]], np.float32)
-        return pos, np.array([[0, 1, 2], [0, 2, 3]]), 40, 48
-    if name == "empty":                          # everything behind the camera
-        v, f = synthetic.icosphere(2)
-        return clip(v + np.array([0, 0, -5], np.float32), [look_at((0, 0, 0), (0, 0, 1))]), f, 12, 12
-    raise KeyError(name)
-
-
-SCENES = ["sphere", "sphere_b3", "folded", "near_plane", "quad", "empty"]
 
 
 def to_dev(pos, f, dtype=torch.int64):
