@@ -33,6 +33,7 @@
  *                        scripts/main.py:146) and its autograd gradient
  *   ls_massmatrix_voronoi*    scripts/geometry.py:35-89 (massmatrix_voronoi: Voronoi area per vertex, obtuse-triangle rule)
  *                        and its autograd gradient
+ *   ls_mesh_distance_*   igl.point_mesh_squared_distance / igl.hausdorff (figures/comparison/generate_data.py: the error column)
  */
 #ifndef LARGESTEPS_HIP_H
 #define LARGESTEPS_HIP_H
@@ -624,6 +625,26 @@ int ls_remesh_phase(void* handle, int phase, int max_rounds);
 int ls_remesh_info(void* handle, int64_t* V, int64_t* F, int64_t* counters, double* seconds);
 int ls_remesh_copy_out(void* handle, float* verts, void* faces, int idx_bytes);
 int ls_remesh_destroy(void* handle);
+
+/* ------------------------------------------------------------------------------------------------
+ * Point-to-mesh squared distance (libigl's point_mesh_squared_distance and hausdorff, which figures/comparison/generate_data.py and
+ * the notebooks call on every recorded step; largesteps/distance.py). The rules are stated in csrc/distance.hip and DESIGN.md
+ * section 2.8, restated in numpy / torch by tests/distance_statement.py: fp64 arithmetic from the fp32 coordinates, a degenerate
+ * triangle measured as its closest segment, ties of the squared distance to the lowest triangle id. Bitwise reproducible.
+ *   ls_mesh_distance_create   copies verts (V, 3) fp32 and faces (F, 3) int32 / int64 (idx_bytes 4 / 8) of the device and builds the
+ *                             LBVH over the faces. LS_E_INDEX for an index outside [0, V); LS_E_INVALID for F = 0, V = 0, a null
+ *                             pointer or another idx_bytes. SYNC.
+ *   ls_mesh_distance_query    for n query points P (n, 3) fp32: sqrD (n) fp64 squared distance to the nearest face, I (n) int64 its
+ *                             face id, C (n, 3) fp64 the closest point. Any of the three may be NULL. ASYNC on `stream`.
+ *   ls_mesh_distance_max      out_sqd[0] (fp64, device) = max over the n points of their squared distance (0 for n = 0). ASYNC.
+ *   ls_mesh_distance_destroy  synchronises the device (queries may run on any stream), then gives the handle's buffer back to the
+ *                             scratch pool (ls_release_scratch empties it). NULL is accepted.
+ * --------------------------------------------------------------------------------------------- */
+int ls_mesh_distance_create(const float* verts, int64_t V, const void* faces, int idx_bytes, int64_t F, int device, void* stream,
+                            void** handle);
+int ls_mesh_distance_query(void* handle, const float* P, int64_t n, double* sqrD, int64_t* I, double* C, void* stream);
+int ls_mesh_distance_max(void* handle, const float* P, int64_t n, double* out_sqd, void* stream);
+int ls_mesh_distance_destroy(void* handle);
 
 /* ------------------------------------------------------------------------------------------------
  * AdamUniform step (optimize.py:18-41) on n contiguous fp32 elements, two kernels, no host sync:

@@ -11,11 +11,11 @@
 //   twin                   the opposite half-edge or -1 (boundary); edge id = min(h, twin)
 //   bnd                    1 for a vertex with a boundary half-edge; valence = cnt + bnd
 // Winners of collapse / flip: a 64-bit key (value bits << 32 | edge id) min-propagated with integer atomicMin (order independent).
-// Projection: an LBVH over the call's input triangles (30-bit Morton codes, the stable radix sort of radix.h, Karras' hierarchy,
-// a bottom-up refit of boxes inflated by 1e-5 of the box diagonal) walked stacklessly through escape links; the point-triangle
-// test is fp64 and ties of the squared distance go to the lower triangle id, so the BVH answers what a brute-force scan answers.
+// Projection: the LBVH of lbvh.h over the call's input triangles (boxes inflated by 1e-5 of the box diagonal) walked stacklessly
+// through escape links; the point-triangle test is fp64 and ties of the squared distance go to the lower triangle id, so the BVH
+// answers what a brute-force scan answers.
 #include "common.h"
-#include "radix.h"
+#include "lbvh.h"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -371,150 +371,12 @@ __global__ __launch_bounds__(BLOCK) void k_rm_relax(const float* __restrict__ P,
     rm_st(Pn, v, make_float3(q.x + s * u.x, q.y + s * u.y, q.z + s * u.z));
 }
 
-// ---- projection: LBVH ----------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned rm_key_inv(unsigned k) { return (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k; }
-__global__ __launch_bounds__(BLOCK) void k_rm_bbox(const float* __restrict__ P, int V, unsigned* __restrict__ box /* 6: min keys, max keys */) {
-    __shared__ unsigned s[6];
-    if (threadIdx.x < 6) s[threadIdx.x] = threadIdx.x < 3 ? 0xffffffffu : 0u;
-    __syncthreads();
-    unsigned mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
-    for (int v = blockIdx.x * BLOCK + threadIdx.x; v < V; v += gridDim.x * BLOCK)
-        for (int q = 0; q < 3; ++q) { const unsigned k = key_of(P[3 * (size_t)v + q]); mn[q] = min(mn[q], k); mx[q] = max(mx[q], k); }
-    for (int q = 0; q < 3; ++q) { atomicMin(&s[q], mn[q]); atomicMax(&s[3 + q], mx[q]); }
-    __syncthreads();
-    if (threadIdx.x < 3) atomicMin(&box[threadIdx.x], s[threadIdx.x]);
-    else if (threadIdx.x < 6) atomicMax(&box[threadIdx.x], s[threadIdx.x]);
-}
-__device__ __forceinline__ unsigned rm_expand(unsigned x) {
-    x = (x | (x << 16)) & 0x030000FFu;
-    x = (x | (x << 8)) & 0x0300F00Fu;
-    x = (x | (x << 4)) & 0x030C30C3u;
-    x = (x | (x << 2)) & 0x09249249u;
-    return x;
-}
-__global__ __launch_bounds__(BLOCK) void k_rm_morton(const float* __restrict__ P, const int* __restrict__ faces, int T, const unsigned* __restrict__ box,
-                                                     int* __restrict__ code) {
-    const int f = blockIdx.x * BLOCK + threadIdx.x;
-    if (f >= T) return;
-    const float3 a = rm_ld(P, faces[3 * f]), b = rm_ld(P, faces[3 * f + 1]), c = rm_ld(P, faces[3 * f + 2]);
-    const float cen[3] = {((a.x + b.x) + c.x) / 3.0f, ((a.y + b.y) + c.y) / 3.0f, ((a.z + b.z) + c.z) / 3.0f};
-    unsigned q[3];
-    for (int k = 0; k < 3; ++k) {
-        const float lo = __uint_as_float(rm_key_inv(box[k])), hi = __uint_as_float(rm_key_inv(box[3 + k]));
-        const float ext = hi - lo > 0.0f ? hi - lo : 1.0f;
-        q[k] = (unsigned)min(max((int)((cen[k] - lo) / ext * 1024.0f), 0), 1023);
-    }
-    code[f] = (int)((rm_expand(q[0]) << 2) | (rm_expand(q[1]) << 1) | rm_expand(q[2]));
-}
-__global__ __launch_bounds__(BLOCK) void k_rm_sorted_codes(const int* __restrict__ order, const int* __restrict__ code, int T, int* __restrict__ tri,
-                                                           unsigned* __restrict__ scode) {
-    const int i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i < T) { tri[i] = order[i]; scode[i] = (unsigned)code[order[i]]; }
-}
-__device__ __forceinline__ int rm_delta(const unsigned* __restrict__ k, int T, int i, int j) {
-    if (j < 0 || j >= T) return -1;
-    const unsigned a = k[i], b = k[j];
-    return a == b ? 32 + __clz((unsigned)(i ^ j)) : __clz(a ^ b);
-}
-// Karras (2012): internal node i of T - 1, leaves at T - 1 + i
-__global__ __launch_bounds__(BLOCK) void k_rm_karras(const unsigned* __restrict__ k, int T, int* __restrict__ left, int* __restrict__ right,
-                                                     int* __restrict__ parent) {
-    const int i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= T - 1) return;
-    const int d = rm_delta(k, T, i, i + 1) - rm_delta(k, T, i, i - 1) >= 0 ? 1 : -1;
-    const int dmin = rm_delta(k, T, i, i - d);
-    int lmax = 2;
-    while (rm_delta(k, T, i, i + lmax * d) > dmin) lmax *= 2;
-    int l = 0;
-    for (int t = lmax / 2; t >= 1; t /= 2)
-        if (rm_delta(k, T, i, i + (l + t) * d) > dmin) l += t;
-    const int j = i + l * d, dnode = rm_delta(k, T, i, j);
-    int s = 0, t = l;
-    do {
-        t = (t + 1) >> 1;
-        if (rm_delta(k, T, i, i + (s + t) * d) > dnode) s += t;
-    } while (t > 1);
-    const int gamma = i + s * d + min(d, 0);
-    const int L = min(i, j) == gamma ? T - 1 + gamma : gamma, R = max(i, j) == gamma + 1 ? T - 1 + gamma + 1 : gamma + 1;
-    left[i] = L; right[i] = R;
-    parent[L] = i; parent[R] = i;
-}
-__global__ __launch_bounds__(BLOCK) void k_rm_refit(const float* __restrict__ P, const int* __restrict__ faces, const int* __restrict__ tri, int T,
-                                                    float margin, const int* __restrict__ left, const int* __restrict__ right,
-                                                    const int* __restrict__ parent, int* __restrict__ flag, float* __restrict__ box) {
-    const int i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= T) return;
-    const int f = tri[i];
-    const float3 a = rm_ld(P, faces[3 * f]), b = rm_ld(P, faces[3 * f + 1]), c = rm_ld(P, faces[3 * f + 2]);
-    int node = T - 1 + i;
-    float* bx = box + 6 * (size_t)node;
-    bx[0] = fminf(fminf(a.x, b.x), c.x) - margin; bx[1] = fminf(fminf(a.y, b.y), c.y) - margin; bx[2] = fminf(fminf(a.z, b.z), c.z) - margin;
-    bx[3] = fmaxf(fmaxf(a.x, b.x), c.x) + margin; bx[4] = fmaxf(fmaxf(a.y, b.y), c.y) + margin; bx[5] = fmaxf(fmaxf(a.z, b.z), c.z) + margin;
-    if (T == 1) return;
-    node = parent[node];
-    while (node >= 0) {
-        __threadfence();
-        if (atomicAdd(&flag[node], 1) == 0) return;       // the sibling's subtree is not done yet: its last thread goes on
-        __threadfence();
-        const volatile float* l = box + 6 * (size_t)left[node];
-        const volatile float* r = box + 6 * (size_t)right[node];
-        float* o = box + 6 * (size_t)node;
-        for (int q = 0; q < 3; ++q) { o[q] = fminf(l[q], r[q]); o[3 + q] = fmaxf(l[3 + q], r[3 + q]); }
-        node = parent[node];
-    }
-}
-// escape link: the node that follows a node's subtree in the pre-order (left first), -1 past the end
-__global__ __launch_bounds__(BLOCK) void k_rm_escape(const int* __restrict__ left, const int* __restrict__ right, const int* __restrict__ parent, int N,
-                                                     int* __restrict__ esc) {
-    const int i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= N) return;
-    int x = i, e = -1;
-    while (x != 0) {
-        const int p = parent[x];
-        if (left[p] == x) { e = right[p]; break; }
-        x = p;
-    }
-    esc[i] = e;
-}
-__device__ __forceinline__ double rm_dd(double ax, double ay, double az, double bx, double by, double bz) { return (ax * bx + ay * by) + az * bz; }
-// closest point of p on triangle (a, b, c) in fp64 (the region tests of tests/remesh_statement.py:point_triangle)
-__device__ void rm_point_tri(const double p[3], const double a[3], const double b[3], const double c[3], double r[3]) {
-    const double ab[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, ac[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
-    const double ap[3] = {p[0] - a[0], p[1] - a[1], p[2] - a[2]};
-    const double d1 = rm_dd(ab[0], ab[1], ab[2], ap[0], ap[1], ap[2]), d2 = rm_dd(ac[0], ac[1], ac[2], ap[0], ap[1], ap[2]);
-    if (d1 <= 0.0 && d2 <= 0.0) { r[0] = a[0]; r[1] = a[1]; r[2] = a[2]; return; }
-    const double bp[3] = {p[0] - b[0], p[1] - b[1], p[2] - b[2]};
-    const double d3 = rm_dd(ab[0], ab[1], ab[2], bp[0], bp[1], bp[2]), d4 = rm_dd(ac[0], ac[1], ac[2], bp[0], bp[1], bp[2]);
-    if (d3 >= 0.0 && d4 <= d3) { r[0] = b[0]; r[1] = b[1]; r[2] = b[2]; return; }
-    const double vc = d1 * d4 - d3 * d2;
-    if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {
-        const double v = d1 / (d1 - d3);
-        for (int q = 0; q < 3; ++q) r[q] = a[q] + ab[q] * v;
-        return;
-    }
-    const double cp[3] = {p[0] - c[0], p[1] - c[1], p[2] - c[2]};
-    const double d5 = rm_dd(ab[0], ab[1], ab[2], cp[0], cp[1], cp[2]), d6 = rm_dd(ac[0], ac[1], ac[2], cp[0], cp[1], cp[2]);
-    if (d6 >= 0.0 && d5 <= d6) { r[0] = c[0]; r[1] = c[1]; r[2] = c[2]; return; }
-    const double vb = d5 * d2 - d1 * d6;
-    if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {
-        const double w = d2 / (d2 - d6);
-        for (int q = 0; q < 3; ++q) r[q] = a[q] + ac[q] * w;
-        return;
-    }
-    const double va = d3 * d6 - d5 * d4;
-    if (va <= 0.0 && d4 - d3 >= 0.0 && d5 - d6 >= 0.0) {
-        const double w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
-        for (int q = 0; q < 3; ++q) r[q] = b[q] + (c[q] - b[q]) * w;
-        return;
-    }
-    const double den = 1.0 / ((va + vb) + vc), v = vb * den, w = vc * den;
-    for (int q = 0; q < 3; ++q) r[q] = (a[q] + ab[q] * v) + ac[q] * w;
-}
+// ---- projection: the LBVH of lbvh.h over the input mesh -----------------------------------------------------------------------
 struct RmBest { double d2, r[3]; int tri; };
 __device__ __forceinline__ void rm_test_leaf(const float* __restrict__ P0, const int* __restrict__ F0, int f, const double p[3], RmBest& best) {
     double a[3], b[3], c[3], r[3];
     for (int q = 0; q < 3; ++q) { a[q] = P0[3 * (size_t)F0[3 * f] + q]; b[q] = P0[3 * (size_t)F0[3 * f + 1] + q]; c[q] = P0[3 * (size_t)F0[3 * f + 2] + q]; }
-    rm_point_tri(p, a, b, c, r);
+    lbvh_point_tri(p, a, b, c, r);
     const double dx = p[0] - r[0], dy = p[1] - r[1], dz = p[2] - r[2];
     const double d2 = (dx * dx + dy * dy) + dz * dz;
     if (d2 < best.d2 || (d2 == best.d2 && f < best.tri)) { best.d2 = d2; best.tri = f; best.r[0] = r[0]; best.r[1] = r[1]; best.r[2] = r[2]; }
@@ -525,6 +387,19 @@ __device__ __forceinline__ float rm_box_d2(const float* __restrict__ bx, float p
     const float z = fmaxf(fmaxf(bx[2] - pz, 0.0f), pz - bx[5]);
     return (x * x + y * y) + z * z;
 }
+// the projection's query of lbvh_walk: fp32 box distances (boxes inflated by the margin of rm_build_bvh), the fp64 leaf test
+struct RmProject {
+    const float* __restrict__ P0;
+    const int* __restrict__ F0;
+    const int* __restrict__ tri;
+    const float* __restrict__ box;
+    float px, py, pz;
+    double p[3];
+    RmBest b;
+    __device__ __forceinline__ float bound(int node) const { return rm_box_d2(box + 6 * (size_t)node, px, py, pz); }
+    __device__ __forceinline__ double best() const { return b.d2; }
+    __device__ __forceinline__ void leaf(int i) { rm_test_leaf(P0, F0, tri[i], p, b); }
+};
 __global__ __launch_bounds__(BLOCK) void k_rm_project(float* __restrict__ P, const int* __restrict__ vptr, const int* __restrict__ bnd, int V,
                                                       const float* __restrict__ P0, const int* __restrict__ F0, int T, const int* __restrict__ tri,
                                                       const float* __restrict__ box, const int* __restrict__ left, const int* __restrict__ right,
@@ -533,23 +408,12 @@ __global__ __launch_bounds__(BLOCK) void k_rm_project(float* __restrict__ P, con
     if (v >= V || bnd[v] || vptr[v + 1] == vptr[v]) return;
     const float px = P[3 * (size_t)v], py = P[3 * (size_t)v + 1], pz = P[3 * (size_t)v + 2];
     const double p[3] = {px, py, pz};
-    RmBest best;
-    best.d2 = __longlong_as_double(0x7ff0000000000000ll);
-    best.tri = 0x7fffffff;
-    best.r[0] = p[0]; best.r[1] = p[1]; best.r[2] = p[2];
-    const int leaf0 = T - 1;
-    int node = 0;                                  // a first bound: the greedy descent to one leaf
-    while (node < leaf0) {
-        const int l = left[node], r = right[node];
-        node = rm_box_d2(box + 6 * (size_t)r, px, py, pz) < rm_box_d2(box + 6 * (size_t)l, px, py, pz) ? r : l;
-    }
-    rm_test_leaf(P0, F0, tri[node - leaf0], p, best);
-    node = 0;
-    while (node >= 0) {
-        if ((double)rm_box_d2(box + 6 * (size_t)node, px, py, pz) > best.d2) { node = esc[node]; continue; }
-        if (node >= leaf0) { rm_test_leaf(P0, F0, tri[node - leaf0], p, best); node = esc[node]; }
-        else node = left[node];
-    }
+    RmProject q{P0, F0, tri, box, px, py, pz, {p[0], p[1], p[2]}, {}};
+    q.b.d2 = __longlong_as_double(0x7ff0000000000000ll);
+    q.b.tri = 0x7fffffff;
+    q.b.r[0] = p[0]; q.b.r[1] = p[1]; q.b.r[2] = p[2];
+    lbvh_walk(left, right, esc, T, q);
+    const RmBest& best = q.b;
     P[3 * (size_t)v] = (float)best.r[0]; P[3 * (size_t)v + 1] = (float)best.r[1]; P[3 * (size_t)v + 2] = (float)best.r[2];
 }
 
@@ -773,38 +637,14 @@ static int rm_build_bvh(RemeshHandle* H) {
     RM_TRY(rm_ensure(H, H->esc, sizeof(int) * N));
     RM_TRY(rm_ensure(H, H->rflag, sizeof(int) * T));
     RM_TRY(rm_ensure(H, H->box, sizeof(float) * 6 * (size_t)N));
-    unsigned* bb = (unsigned*)(rp<int>(H->small) + 16);
-    const unsigned init[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
-    LS_HIP(hipMemcpyAsync(bb, init, sizeof(init), hipMemcpyHostToDevice, H->st));
-    hipLaunchKernelGGL(k_rm_bbox, dim3(std::min(div_up(V0, BLOCK), 1024)), dim3(BLOCK), 0, H->st, (const float*)rp<float>(H->pos0), V0, bb);
-    unsigned hb[6];
-    LS_HIP(hipMemcpyAsync(hb, bb, sizeof(hb), hipMemcpyDeviceToHost, H->st));
-    LS_HIP(hipStreamSynchronize(H->st));
+    const Lbvh a{rp<int>(H->code), rp<int>(H->ord_a), rp<int>(H->ord_b), rp<int>(H->hist), rp<int>(H->offs), rp<int>(H->bsum), rp<int>(H->tri),
+                 rp<unsigned>(H->scode), rp<int>(H->left), rp<int>(H->right), rp<int>(H->parent), rp<int>(H->esc), rp<int>(H->rflag),
+                 rp<float>(H->box), (unsigned*)(rp<int>(H->small) + 16)};
     float lo[3], hi[3];
-    for (int q = 0; q < 3; ++q) {
-        unsigned k = hb[q];
-        k = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-        memcpy(&lo[q], &k, 4);
-        k = hb[3 + q];
-        k = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-        memcpy(&hi[q], &k, 4);
-    }
+    RM_TRY(lbvh_bounds(rp<float>(H->pos0), V0, a, H->st, lo, hi));
     const double diag = sqrt((double)(hi[0] - lo[0]) * (hi[0] - lo[0]) + (double)(hi[1] - lo[1]) * (hi[1] - lo[1]) + (double)(hi[2] - lo[2]) * (hi[2] - lo[2]));
     const float margin = (float)(1e-5 * diag) + 1e-30f;
-    hipLaunchKernelGGL(k_rm_morton, RM_GRID(T), (const float*)rp<float>(H->pos0), (const int*)rp<int>(H->faces0), T, (const unsigned*)bb, rp<int>(H->code));
-    const int* order = nullptr;
-    RM_TRY(radix_argsort(KeyInt{(const int*)rp<int>(H->code)}, T, 4, rp<int>(H->ord_a), rp<int>(H->ord_b), rp<int>(H->hist), rp<int>(H->offs),
-                         rp<int>(H->bsum), H->st, &order));
-    hipLaunchKernelGGL(k_rm_sorted_codes, RM_GRID(T), order, (const int*)rp<int>(H->code), T, rp<int>(H->tri), rp<unsigned>(H->scode));
-    LS_HIP(hipMemsetAsync(H->parent.p, 0xff, sizeof(int) * N, H->st));
-    LS_HIP(hipMemsetAsync(H->rflag.p, 0, sizeof(int) * T, H->st));
-    if (T > 1) hipLaunchKernelGGL(k_rm_karras, RM_GRID(T - 1), (const unsigned*)rp<unsigned>(H->scode), T, rp<int>(H->left), rp<int>(H->right),
-                                  rp<int>(H->parent));
-    hipLaunchKernelGGL(k_rm_refit, RM_GRID(T), (const float*)rp<float>(H->pos0), (const int*)rp<int>(H->faces0), (const int*)rp<int>(H->tri), T, margin,
-                       (const int*)rp<int>(H->left), (const int*)rp<int>(H->right), (const int*)rp<int>(H->parent), rp<int>(H->rflag), rp<float>(H->box));
-    hipLaunchKernelGGL(k_rm_escape, RM_GRID(N), (const int*)rp<int>(H->left), (const int*)rp<int>(H->right), (const int*)rp<int>(H->parent), N,
-                       rp<int>(H->esc));
-    LS_HIP(hipGetLastError());
+    RM_TRY(lbvh_build(rp<float>(H->pos0), rp<int>(H->faces0), T, margin, a, H->st));
     H->bvh = true;
     return LS_OK;
 }

@@ -102,6 +102,10 @@ _SIGNATURES = {
     "ls_remesh_info": (c_int, [c_void_p, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64 * 6), ctypes.POINTER(c_double * 5)]),
     "ls_remesh_copy_out": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     "ls_remesh_destroy": (c_int, [c_void_p]),
+    "ls_mesh_distance_create": (c_int, [c_void_p, c_i64, c_void_p, c_int, c_i64, c_int, c_void_p, ctypes.POINTER(c_void_p)]),
+    "ls_mesh_distance_query": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ls_mesh_distance_max": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p]),
+    "ls_mesh_distance_destroy": (c_int, [c_void_p]),
     "ls_shard_plan_create": (c_int, [c_i64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
     "ls_shard_plan_destroy": (c_int, [c_void_p]),
     "ls_shard_plan_info": (c_int, [c_void_p] + [ctypes.POINTER(c_i64)] * 5 + [ctypes.POINTER(c_int)] * 2 + [ctypes.POINTER(c_i64)]),
