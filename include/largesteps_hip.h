@@ -33,6 +33,7 @@
  *                        scripts/main.py:146) and its autograd gradient
  *   ls_massmatrix_voronoi*    scripts/geometry.py:35-89 (massmatrix_voronoi: Voronoi area per vertex, obtuse-triangle rule)
  *                        and its autograd gradient
+ *   ls_texture_*         nvdiffrast.torch.texture as scripts/render.py calls it (the backgrounds), with gradients to tex and uv
  *   ls_mesh_distance_*   igl.point_mesh_squared_distance / igl.hausdorff (figures/comparison/generate_data.py: the error column)
  */
 #ifndef LARGESTEPS_HIP_H
@@ -701,6 +702,39 @@ int ls_raster_antialias_backward(const float* color, int C, const float* rast, c
                                  const int32_t* tri, int64_t F, const int32_t* adj, const float* grad_out, float boost,
                                  const int32_t* order, const int32_t* seg, const int32_t* vptr, const int32_t* corner_order,
                                  float* grad_color, float* grad_pos, void* ws, size_t ws_bytes, int device, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Differentiable 2D texture lookup (largesteps/render.py: texture; the rules are stated in csrc/texture.hip and DESIGN.md section 2.7,
+ * restated in numpy by tests/texture_statement.py). tex (Bt, Ht, Wt, C) fp32 with Bt 1 (shared by every image) or B, 1 <= Ht, Wt <= 8192,
+ * 1 <= C <= 32; uv (B, H, W, 2) fp32, 8-byte aligned; out (B, H, W, C). filter: LS_TEXTURE_NEAREST / _LINEAR; boundary: LS_TEXTURE_WRAP /
+ * _CLAMP / _ZERO, applied per tap index. A non-finite uv gives output 0 and no gradient; every texel index is made range-safe before an
+ * address is formed (saturating conversion, then integer remainder, clamp or range test). LS_E_INVALID for bad sizes or modes,
+ * LS_E_OVERFLOW when B H W or Bt (Ht + 1) (Wt + 1) + 1 does not fit int32. No entry point allocates or synchronises, none uses float
+ * atomics: outputs and gradients are bitwise reproducible. ASYNC.
+ *   ls_texture_workspace_bytes   workspace of ls_texture_order for B H W pixels.
+ *   ls_texture_forward           out.
+ *   ls_texture_order             order (B H W) = the pixels sorted stably by their base tap (after the part of the boundary rule that does
+ *                                not change which texels it touches; pixels without a gradient last), seg (Bt (Ht + 1) (Wt + 1) + 1) = the
+ *                                first sorted position of each key: the order grad_tex sums in. Depends on uv, the texture's SHAPE and the
+ *                                two modes only.
+ *   ls_texture_backward          grad_tex (Bt, Ht, Wt, C) (summed over the images when Bt = 1) and grad_uv (B, H, W, 2) (zero for
+ *                                LS_TEXTURE_NEAREST); either may be NULL, both are overwritten. order / seg: what ls_texture_order returned
+ *                                for the same uv, shapes and modes (needed for grad_tex only; the kernels index pixels through them
+ *                                without a range check).
+ * --------------------------------------------------------------------------------------------- */
+#define LS_TEXTURE_NEAREST 0
+#define LS_TEXTURE_LINEAR 1
+#define LS_TEXTURE_WRAP 0
+#define LS_TEXTURE_CLAMP 1
+#define LS_TEXTURE_ZERO 2
+int ls_texture_workspace_bytes(int64_t B, int H, int W, size_t* bytes);
+int ls_texture_forward(const float* tex, int64_t Bt, int Ht, int Wt, int C, const float* uv, int64_t B, int H, int W, int filter,
+                       int boundary, float* out, int device, void* stream);
+int ls_texture_order(const float* uv, int64_t B, int H, int W, int64_t Bt, int Ht, int Wt, int filter, int boundary, int32_t* order,
+                     int32_t* seg, void* ws, size_t ws_bytes, int device, void* stream);
+int ls_texture_backward(const float* tex, int64_t Bt, int Ht, int Wt, int C, const float* uv, int64_t B, int H, int W, int filter,
+                        int boundary, const float* grad_out, const int32_t* order, const int32_t* seg, float* grad_tex, float* grad_uv,
+                        int device, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,498 @@
+// texture.hip -- differentiable 2D texture lookup (gfx950, wave64): the fourth nvdiffrast primitive the reference's renderer calls
+// (rgl-epfl/large-steps-pytorch scripts/render.py: dr.texture), restated in numpy by tests/texture_statement.py and described in
+// DESIGN.md section 2.7.
+//
+// Rules. tex (Bt, Ht, Wt, C) fp32 with Bt in {1, B}, uv (B, H, W, 2) fp32, out (B, H, W, C). Texel (i, j) has its centre at
+// ((i + 0.5) / Wt, (j + 0.5) / Ht). Linear: x = u Wt - 0.5, y = v Ht - 0.5 (one fp32 multiply, one fp32 subtract: the build has
+// -ffp-contract=off), i0 = floor(x), fx = x - i0, likewise j0, fy; top = t00 + (t10 - t00) fx, bot = t01 + (t11 - t01) fx,
+// out = top + (bot - top) fy -- the operation order of the plain-torch lookup this kernel replaced, so the results are the same bits.
+// Nearest: the texel (floor(u Wt), floor(v Ht)). Boundary per tap index: wrap = modulo the size, clamp = clamped to [0, size - 1],
+// zero = a tap outside reads 0 and receives no gradient. A non-finite u or v gives output 0 and no gradient.
+//
+// Range safety. floor(x) becomes an int32 through tx_sat (clamped IN FLOAT to [-2^31, 2^31 - 128], both representable, before the
+// conversion; a NaN never reaches it) and is then reduced by tx_fold (integer remainder made non-negative, or an integer clamp) to
+// [0, size) -- or, in zero mode, compared against [0, size) and the tap dropped. No address is formed from anything else.
+//
+// Gradient to uv (linear only; zero for nearest): per pixel, d out / d u = Wt ((t10 - t00)(1 - fy) + (t11 - t01) fy), likewise v.
+//
+// Gradient to tex: a many-to-one sum, without float atomics. ls_texture_order sorts the N = B H W pixels stably (radix.h) by ONE key
+// each, the pixel's base tap after the part of the boundary rule that cannot change which texels it touches:
+//     linear   wrap: (i0 mod Wt, j0 mod Ht)   clamp: (clamp(i0, -1, Wt - 1), clamp(j0, -1, Ht - 1))   zero: (i0, j0) if both lie
+//              in [-1, size - 1], else none
+//     nearest  the texel itself after wrap / clamp; zero: none when outside
+// as key = (bt (Ht + 1) + j + 1) (Wt + 1) + i + 1, "none" (and non-finite uv) = Bt (Ht + 1) (Wt + 1), sorted last; seg[k] = the first
+// sorted position with key >= k. The order depends on uv alone. ls_texture_backward then runs one thread per texel: it walks the base
+// positions whose taps fall on it -- per axis (i, tap 0) and (i - 1, tap 1) (wrapped in wrap mode), plus (-1, tap 0) for texel 0 and
+// (size - 1, tap 1) for the last texel in clamp mode -- and adds g (wx wy) over each position's pixels in sorted order. A texel with
+// more than 64 pixels in all is summed by its whole wave, lane-strided per position, then an xor butterfly: a fixed order either way,
+// so every gradient is bitwise reproducible. No entry point allocates or synchronises.
+#include "common.h"
+#include "radix.h"
+#include <algorithm>
+
+namespace ls {
+
+constexpr int TX_LINEAR = 1, TX_NEAREST = 0;                 // LS_TEXTURE_* of the header
+constexpr int TX_WRAP = 0, TX_CLAMP = 1, TX_ZERO = 2;
+constexpr int TX_MAX_SIZE = 8192, TX_MAX_C = 32;
+
+struct TxShape {
+    int Bt, Ht, Wt, C;          // texture
+    int64_t N, HW;              // pixels in all, per image
+    int filter, boundary;
+    int vec4;                   // C == 4 and every channel-row pointer of the call is 16-byte aligned: rows move as one float4
+};
+
+// float -> int32, saturating: the clamp happens on the float, whose bounds are exactly representable; x is finite
+__device__ __forceinline__ int tx_sat(float x) { return (int)fminf(fmaxf(x, -2147483648.0f), 2147483520.0f); }
+
+// tap index -> [0, n) by the boundary rule; zero mode: returns false when the tap lies outside (i is then unused)
+__device__ __forceinline__ bool tx_fold(int& i, int n, int boundary) {
+    if (boundary == TX_WRAP) {
+        int r = i % n;
+        i = r < 0 ? r + n : r;
+        return true;
+    }
+    if (boundary == TX_CLAMP) {
+        i = min(max(i, 0), n - 1);
+        return true;
+    }
+    return i >= 0 && i < n;
+}
+
+// the texel after tap `i` (already in [0, n)) by the boundary rule: i + 1 without overflow
+__device__ __forceinline__ bool tx_next(int i, int n, int boundary, int& i1) {
+    if (boundary == TX_WRAP) { i1 = i + 1 == n ? 0 : i + 1; return true; }
+    if (boundary == TX_CLAMP) { i1 = min(i + 1, n - 1); return true; }
+    i1 = i + 1;
+    return i1 < n;
+}
+
+struct TxCoord {
+    bool finite;
+    int i0, j0;                 // saturated floor
+    float fx, fy;
+};
+
+__device__ __forceinline__ TxCoord tx_coord(const float* __restrict__ uv, int64_t pix, const TxShape& s) {
+    const float2 c = *reinterpret_cast<const float2*>(uv + 2 * (size_t)pix);
+    TxCoord t;
+    float x = c.x * (float)s.Wt, y = c.y * (float)s.Ht;
+    if (s.filter == TX_LINEAR) { x = x - 0.5f; y = y - 0.5f; }
+    t.finite = isfinite(x) && isfinite(y);
+    const float x0 = floorf(x), y0 = floorf(y);
+    t.fx = x - x0;
+    t.fy = y - y0;
+    t.i0 = t.finite ? tx_sat(x0) : 0;
+    t.j0 = t.finite ? tx_sat(y0) : 0;
+    return t;
+}
+
+template <int CT>
+__device__ __forceinline__ void tx_load(const float* __restrict__ p, bool vec4, float (&t)[CT]) {
+    if constexpr (CT == 4) {
+        if (vec4) {
+            const float4 v = *reinterpret_cast<const float4*>(p);
+            t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
+            return;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < CT; ++c) t[c] = p[c];
+}
+
+template <int CT>
+__device__ __forceinline__ void tx_store(float* __restrict__ p, bool vec4, const float (&t)[CT]) {
+    if constexpr (CT == 4) {
+        if (vec4) {
+            *reinterpret_cast<float4*>(p) = make_float4(t[0], t[1], t[2], t[3]);
+            return;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < CT; ++c) p[c] = t[c];
+}
+
+// the four taps of a pixel (linear) or its one texel (nearest: only t[0][0], ok[0][0]); a tap that is not ok reads 0
+template <int CT>
+struct TxTaps {
+    float t[2][2][CT];          // [dy][dx]
+    bool ok[2][2];
+};
+
+template <int CT>
+__device__ __forceinline__ TxTaps<CT> tx_taps(const float* __restrict__ tex, const TxCoord& q, int64_t pix, const TxShape& s, int c0) {
+    TxTaps<CT> r;
+    const int bt = s.Bt == 1 ? 0 : (int)(pix / s.HW);
+    const bool vec4 = s.vec4 != 0;
+    int ix[2], jy[2];
+    bool okx[2], oky[2];
+    ix[0] = q.i0; jy[0] = q.j0;
+    okx[0] = tx_fold(ix[0], s.Wt, s.boundary);
+    oky[0] = tx_fold(jy[0], s.Ht, s.boundary);
+    if (s.filter == TX_LINEAR) {
+        if (s.boundary == TX_ZERO) {         // i0 + 1: no overflow, tx_sat stops below 2^31 - 1
+            ix[1] = q.i0 + 1; jy[1] = q.j0 + 1;
+            okx[1] = ix[1] >= 0 && ix[1] < s.Wt;
+            oky[1] = jy[1] >= 0 && jy[1] < s.Ht;
+        } else if (s.boundary == TX_CLAMP) {
+            ix[1] = min(max(q.i0 + 1, 0), s.Wt - 1); jy[1] = min(max(q.j0 + 1, 0), s.Ht - 1);
+            okx[1] = oky[1] = true;
+        } else {
+            okx[1] = tx_next(ix[0], s.Wt, TX_WRAP, ix[1]);
+            oky[1] = tx_next(jy[0], s.Ht, TX_WRAP, jy[1]);
+        }
+    } else {
+        ix[1] = jy[1] = 0;
+        okx[1] = oky[1] = false;
+    }
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) {
+            const bool ok = q.finite && okx[dx] && oky[dy];
+            r.ok[dy][dx] = ok;
+            if (ok) tx_load<CT>(tex + (((size_t)bt * s.Ht + jy[dy]) * s.Wt + ix[dx]) * s.C + c0, vec4, r.t[dy][dx]);
+            else {
+#pragma unroll
+                for (int c = 0; c < CT; ++c) r.t[dy][dx][c] = 0.0f;
+            }
+        }
+    return r;
+}
+
+// ---- forward: one thread per pixel, CT channels from c0 -------------------------------------------------------------------------------
+template <int CT>
+__global__ __launch_bounds__(256) void k_tx_forward(const float* __restrict__ tex, const float* __restrict__ uv, TxShape s, int c0,
+                                                    float* __restrict__ out) {
+    const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (pix >= s.N) return;
+    const TxCoord q = tx_coord(uv, pix, s);
+    const TxTaps<CT> a = tx_taps<CT>(tex, q, pix, s, c0);
+    float o[CT];
+    if (s.filter == TX_LINEAR) {
+#pragma unroll
+        for (int c = 0; c < CT; ++c) {
+            const float top = a.t[0][0][c] + (a.t[0][1][c] - a.t[0][0][c]) * q.fx;
+            const float bot = a.t[1][0][c] + (a.t[1][1][c] - a.t[1][0][c]) * q.fx;
+            o[c] = q.finite ? top + (bot - top) * q.fy : 0.0f;
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < CT; ++c) o[c] = a.t[0][0][c];
+    }
+    tx_store<CT>(out + (size_t)pix * s.C + c0, s.vec4 != 0, o);
+}
+
+// ---- backward to uv: one thread per pixel; gu (N, 2) accumulates over the channel groups (first = the group that starts at channel 0) ----
+template <int CT>
+__global__ __launch_bounds__(256) void k_tx_backward_uv(const float* __restrict__ tex, const float* __restrict__ uv, const float* __restrict__ g,
+                                                        TxShape s, int c0, float* __restrict__ guv) {
+    const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (pix >= s.N) return;
+    float2 acc = c0 == 0 ? make_float2(0.0f, 0.0f) : *reinterpret_cast<const float2*>(guv + 2 * (size_t)pix);
+    if (s.filter == TX_LINEAR) {
+        const TxCoord q = tx_coord(uv, pix, s);
+        if (q.finite) {
+            const TxTaps<CT> a = tx_taps<CT>(tex, q, pix, s, c0);
+            float go[CT];
+            tx_load<CT>(g + (size_t)pix * s.C + c0, s.vec4 != 0, go);
+            const float ofx = 1.0f - q.fx, ofy = 1.0f - q.fy;
+            float su = 0.0f, sv = 0.0f;
+#pragma unroll
+            for (int c = 0; c < CT; ++c) {
+                const float du = (a.t[0][1][c] - a.t[0][0][c]) * ofy + (a.t[1][1][c] - a.t[1][0][c]) * q.fy;
+                const float dv = (a.t[1][0][c] - a.t[0][0][c]) * ofx + (a.t[1][1][c] - a.t[0][1][c]) * q.fx;
+                su += go[c] * du;
+                sv += go[c] * dv;
+            }
+            acc.x += (float)s.Wt * su;
+            acc.y += (float)s.Ht * sv;
+        }
+    }
+    *reinterpret_cast<float2*>(guv + 2 * (size_t)pix) = acc;
+}
+
+// ---- the pixel order -------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int64_t tx_nkeys(const TxShape& s) { return (int64_t)s.Bt * (s.Ht + 1) * (s.Wt + 1); }
+
+__global__ __launch_bounds__(256) void k_tx_keys(const float* __restrict__ uv, TxShape s, int* __restrict__ keys) {
+    const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (pix >= s.N) return;
+    const TxCoord q = tx_coord(uv, pix, s);
+    int i = q.i0, j = q.j0;
+    bool ok = q.finite;
+    if (s.filter == TX_NEAREST) {
+        ok = tx_fold(i, s.Wt, s.boundary) && ok;
+        ok = tx_fold(j, s.Ht, s.boundary) && ok;
+    } else if (s.boundary == TX_WRAP) {
+        tx_fold(i, s.Wt, TX_WRAP);
+        tx_fold(j, s.Ht, TX_WRAP);
+    } else if (s.boundary == TX_CLAMP) {
+        i = min(max(i, -1), s.Wt - 1);
+        j = min(max(j, -1), s.Ht - 1);
+    } else {
+        ok = ok && i >= -1 && i < s.Wt && j >= -1 && j < s.Ht;
+    }
+    const int bt = s.Bt == 1 ? 0 : (int)(pix / s.HW);
+    keys[pix] = ok ? (int)(((int64_t)bt * (s.Ht + 1) + (j + 1)) * (s.Wt + 1) + (i + 1)) : (int)tx_nkeys(s);
+}
+
+__global__ __launch_bounds__(256) void k_tx_sorted_keys(const int* __restrict__ keys, const int* __restrict__ order, int64_t N, int* __restrict__ sk) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < N) sk[i] = keys[order[i]];
+}
+
+// seg[k] = first sorted position whose key is >= k, k in [0, nk]
+__global__ __launch_bounds__(256) void k_tx_segments(const int* __restrict__ sk, int64_t N, int64_t nk, int* __restrict__ seg) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k > nk) return;
+    int64_t lo = 0, hi = N;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (sk[mid] < k) lo = mid + 1; else hi = mid;
+    }
+    seg[k] = (int)lo;
+}
+
+// ---- backward to tex: one thread per texel ------------------------------------------------------------------------------------------------
+// slot q < 4 of the base positions along one axis whose tap falls on texel i of n: (base, tap); false = the slot is empty
+__device__ __forceinline__ bool tx_slot(int q, int i, int n, int filter, int boundary, int& base, int& tap) {
+    if (q == 0) { base = i; tap = 0; return true; }
+    if (filter == TX_NEAREST) return false;
+    if (q == 1) { base = (boundary == TX_WRAP && i == 0) ? n - 1 : i - 1; tap = 1; return true; }
+    if (boundary != TX_CLAMP) return false;
+    if (q == 2) { base = -1; tap = 0; return i == 0; }
+    base = n - 1; tap = 1;
+    return i == n - 1;
+}
+
+struct TxTexel { int bt, j, i; };
+
+// the pixels of the texel's base positions: their number (COUNT) or their weighted gradients added to acc, pixels start, start + step, ...
+// of every position
+template <int CT, bool COUNT>
+__device__ __forceinline__ int64_t tx_texel_walk(const TxTexel& t, const TxShape& s, const float* __restrict__ uv, const float* __restrict__ g,
+                                             const int* __restrict__ order, const int* __restrict__ seg, int c0, int start, int step, float (&acc)[CT]) {
+    int64_t total = 0;
+#pragma unroll
+    for (int qy = 0; qy < 4; ++qy) {
+        int by, ty;
+        if (!tx_slot(qy, t.j, s.Ht, s.filter, s.boundary, by, ty)) continue;
+#pragma unroll
+        for (int qx = 0; qx < 4; ++qx) {
+            int bx, tx;
+            if (!tx_slot(qx, t.i, s.Wt, s.filter, s.boundary, bx, tx)) continue;
+            const int64_t key = ((int64_t)t.bt * (s.Ht + 1) + (by + 1)) * (s.Wt + 1) + (bx + 1);
+            const int b = seg[key], e = seg[key + 1];
+            if constexpr (COUNT) total += e - b;
+            else {
+                for (int p = b + start; p < e; p += step) {
+                    const int pix = order[p];
+                    float w = 1.0f;
+                    if (s.filter == TX_LINEAR) {
+                        const TxCoord q = tx_coord(uv, pix, s);
+                        w = (tx ? q.fx : 1.0f - q.fx) * (ty ? q.fy : 1.0f - q.fy);
+                    }
+                    float go[CT];
+                    tx_load<CT>(g + (size_t)pix * s.C + c0, s.vec4 != 0, go);
+#pragma unroll
+                    for (int c = 0; c < CT; ++c) acc[c] += go[c] * w;
+                }
+            }
+        }
+    }
+    return total;
+}
+
+template <int CT>
+__global__ __launch_bounds__(256) void k_tx_backward_tex(const float* __restrict__ uv, const float* __restrict__ g, const int* __restrict__ order,
+                                                         const int* __restrict__ seg, TxShape s, int c0, float* __restrict__ gtex) {
+    const int64_t T = (int64_t)s.Bt * s.Ht * s.Wt;
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool ok = k < T;
+    auto texel = [&](int64_t kk) {
+        TxTexel t;
+        const int64_t row = kk / s.Wt;
+        t.i = (int)(kk - row * s.Wt);
+        t.bt = (int)(row / s.Ht);
+        t.j = (int)(row - (int64_t)t.bt * s.Ht);
+        return t;
+    };
+    float acc[CT];
+#pragma unroll
+    for (int c = 0; c < CT; ++c) acc[c] = 0.0f;
+    int64_t count = 0;
+    if (ok) count = tx_texel_walk<CT, true>(texel(k), s, uv, g, order, seg, c0, 0, 1, acc);
+    const bool lng = count > 64;
+    if (ok && !lng) {
+        tx_texel_walk<CT, false>(texel(k), s, uv, g, order, seg, c0, 0, 1, acc);
+        tx_store<CT>(gtex + (size_t)k * s.C + c0, s.vec4 != 0, acc);
+    }
+    unsigned long long m = __ballot(ok && lng);
+    while (m) {                                       // (wave-uniform)
+        const int src = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const int64_t kk = (int64_t)blockIdx.x * 256 + (threadIdx.x & ~63) + src;
+        float part[CT];
+#pragma unroll
+        for (int c = 0; c < CT; ++c) part[c] = 0.0f;
+        tx_texel_walk<CT, false>(texel(kk), s, uv, g, order, seg, c0, lane, 64, part);
+#pragma unroll
+        for (int c = 0; c < CT; ++c) {
+#pragma unroll
+            for (int x = 32; x >= 1; x >>= 1) part[c] += __shfl_xor(part[c], x, 64);
+        }
+        if (lane == 0) tx_store<CT>(gtex + (size_t)kk * s.C + c0, s.vec4 != 0, part);
+    }
+}
+
+}  // namespace ls
+
+using namespace ls;
+
+namespace {
+
+struct TxWs {
+    size_t keys, ord_b, keys_a, keys_b, hist, offs, bsum, total;
+};
+
+TxWs tx_layout(int64_t N) {
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const int64_t nb = div_up(N, rs_chunk(N));
+    TxWs w;
+    size_t o = 0;
+    w.keys = o; o += al(4 * (size_t)N);
+    w.ord_b = o; o += al(4 * (size_t)N);
+    w.keys_a = o; o += al(4 * (size_t)N);
+    w.keys_b = o; o += al(4 * (size_t)N);
+    w.hist = o; o += al(4 * (size_t)(256 * nb + 16));
+    w.offs = o; o += al(4 * (size_t)(256 * nb + 16));
+    w.bsum = o; o += al(4 * (size_t)(scan_blocks(256 * nb) + 2));
+    w.total = o;
+    return w;
+}
+
+int tx_check(int64_t Bt, int Ht, int Wt, int C, int64_t B, int H, int W, int filter, int boundary, const char* who, TxShape* s) {
+    LS_REQUIRE(B >= 1 && H >= 1 && W >= 1 && (Bt == 1 || Bt == B) && Ht >= 1 && Wt >= 1 && Ht <= TX_MAX_SIZE && Wt <= TX_MAX_SIZE && C >= 1 &&
+                   C <= TX_MAX_C,
+               LS_E_INVALID, "%s: bad sizes (tex %lld x %d x %d x %d, uv %lld x %d x %d)", who, (long long)Bt, Ht, Wt, C, (long long)B, H, W);
+    LS_REQUIRE((filter == TX_NEAREST || filter == TX_LINEAR) && (boundary == TX_WRAP || boundary == TX_CLAMP || boundary == TX_ZERO), LS_E_INVALID,
+               "%s: unknown filter mode %d or boundary mode %d", who, filter, boundary);
+    const int64_t N = B * (int64_t)H * W;
+    LS_REQUIRE(N < ((int64_t)1 << 31) - 1 && Bt * (int64_t)(Ht + 1) * (Wt + 1) < ((int64_t)1 << 31) - 2, LS_E_OVERFLOW,
+               "%s: the problem does not fit the int32 index space (tex %lld x %d x %d, uv %lld x %d x %d)", who, (long long)Bt, Ht, Wt,
+               (long long)B, H, W);
+    *s = TxShape{(int)Bt, Ht, Wt, C, N, (int64_t)H * W, filter, boundary, 0};
+    return LS_OK;
+}
+
+// the channels in groups of at most four: one launch per group
+template <class Launch>
+void tx_groups(int C, Launch launch) {
+    if (C <= 4) { launch(0, C); return; }
+    for (int c0 = 0; c0 < C; c0 += 4) launch(c0, std::min(4, C - c0));
+}
+
+bool tx_aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+}  // namespace
+
+extern "C" int ls_texture_workspace_bytes(int64_t B, int H, int W, size_t* bytes) {
+    LS_REQUIRE(bytes && B >= 1 && H >= 1 && W >= 1, LS_E_INVALID, "ls_texture_workspace_bytes: bad argument");
+    LS_REQUIRE(B * (int64_t)H * W < ((int64_t)1 << 31) - 1, LS_E_OVERFLOW, "ls_texture_workspace_bytes: B H W does not fit int32");
+    *bytes = tx_layout(B * (int64_t)H * W).total;
+    return LS_OK;
+}
+
+extern "C" int ls_texture_forward(const float* tex, int64_t Bt, int Ht, int Wt, int C, const float* uv, int64_t B, int H, int W, int filter,
+                                  int boundary, float* out, int device, void* stream) {
+    TxShape s;
+    int rc = tx_check(Bt, Ht, Wt, C, B, H, W, filter, boundary, "ls_texture_forward", &s);
+    if (rc) return rc;
+    LS_REQUIRE(tex && uv && out, LS_E_INVALID, "ls_texture_forward: null argument");
+    LS_REQUIRE(tx_aligned(uv, 8), LS_E_INVALID, "ls_texture_forward: uv must be 8-byte aligned");
+    s.vec4 = C == 4 && tx_aligned(tex, 16) && tx_aligned(out, 16);
+    DeviceGuard g(device);
+    LS_HIP(g.err);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(div_up(s.N, 256)), block(256);
+    tx_groups(C, [&](int c0, int ct) {
+        switch (ct) {
+        case 1: hipLaunchKernelGGL(k_tx_forward<1>, grid, block, 0, st, tex, uv, s, c0, out); break;
+        case 2: hipLaunchKernelGGL(k_tx_forward<2>, grid, block, 0, st, tex, uv, s, c0, out); break;
+        case 3: hipLaunchKernelGGL(k_tx_forward<3>, grid, block, 0, st, tex, uv, s, c0, out); break;
+        default: hipLaunchKernelGGL(k_tx_forward<4>, grid, block, 0, st, tex, uv, s, c0, out); break;
+        }
+    });
+    LS_HIP(hipGetLastError());
+    return LS_OK;
+}
+
+extern "C" int ls_texture_order(const float* uv, int64_t B, int H, int W, int64_t Bt, int Ht, int Wt, int filter, int boundary, int32_t* order,
+                                int32_t* seg, void* ws, size_t ws_bytes, int device, void* stream) {
+    TxShape s;
+    int rc = tx_check(Bt, Ht, Wt, 1, B, H, W, filter, boundary, "ls_texture_order", &s);
+    if (rc) return rc;
+    const TxWs L = tx_layout(s.N);
+    LS_REQUIRE(uv && order && seg && ws, LS_E_INVALID, "ls_texture_order: null argument");
+    LS_REQUIRE(tx_aligned(uv, 8), LS_E_INVALID, "ls_texture_order: uv must be 8-byte aligned");
+    LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_texture_order: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
+    DeviceGuard g(device);
+    LS_HIP(g.err);
+    hipStream_t st = (hipStream_t)stream;
+    char* w = (char*)ws;
+    const int64_t N = s.N, nk = (int64_t)s.Bt * (s.Ht + 1) * (s.Wt + 1);
+    int* keys = (int*)(w + L.keys);
+    hipLaunchKernelGGL(k_tx_keys, dim3(div_up(N, 256)), dim3(256), 0, st, uv, s, keys);
+    const int passes = nk < 256 ? 1 : nk < 65536 ? 2 : nk < (1 << 24) ? 3 : 4;         // the largest key is nk itself
+    const int* sorted = nullptr;
+    rc = radix_argsort_words(KeyInt{keys}, N, 1, order, (int*)(w + L.ord_b), (unsigned*)(w + L.keys_a), (unsigned*)(w + L.keys_b), (int*)(w + L.hist),
+                             (int*)(w + L.offs), (int*)(w + L.bsum), st, &sorted, passes);
+    if (rc) return rc;
+    if (sorted != order) LS_HIP(hipMemcpyAsync(order, sorted, 4 * (size_t)N, hipMemcpyDeviceToDevice, st));
+    int* sk = (int*)(w + L.keys_a);
+    hipLaunchKernelGGL(k_tx_sorted_keys, dim3(div_up(N, 256)), dim3(256), 0, st, (const int*)keys, (const int*)order, N, sk);
+    hipLaunchKernelGGL(k_tx_segments, dim3(div_up(nk + 1, 256)), dim3(256), 0, st, (const int*)sk, N, nk, seg);
+    LS_HIP(hipGetLastError());
+    return LS_OK;
+}
+
+extern "C" int ls_texture_backward(const float* tex, int64_t Bt, int Ht, int Wt, int C, const float* uv, int64_t B, int H, int W, int filter,
+                                   int boundary, const float* grad_out, const int32_t* order, const int32_t* seg, float* grad_tex, float* grad_uv,
+                                   int device, void* stream) {
+    TxShape s;
+    int rc = tx_check(Bt, Ht, Wt, C, B, H, W, filter, boundary, "ls_texture_backward", &s);
+    if (rc) return rc;
+    LS_REQUIRE(tex && uv && grad_out && (!grad_tex || (order && seg)), LS_E_INVALID, "ls_texture_backward: null argument");
+    LS_REQUIRE(tx_aligned(uv, 8) && (!grad_uv || tx_aligned(grad_uv, 8)), LS_E_INVALID, "ls_texture_backward: uv and grad_uv must be 8-byte aligned");
+    s.vec4 = C == 4 && tx_aligned(tex, 16) && tx_aligned(grad_out, 16) && (!grad_tex || tx_aligned(grad_tex, 16));
+    DeviceGuard g(device);
+    LS_HIP(g.err);
+    hipStream_t st = (hipStream_t)stream;
+    if (grad_uv) {
+        const dim3 grid(div_up(s.N, 256)), block(256);
+        tx_groups(C, [&](int c0, int ct) {
+            switch (ct) {
+            case 1: hipLaunchKernelGGL(k_tx_backward_uv<1>, grid, block, 0, st, tex, uv, grad_out, s, c0, grad_uv); break;
+            case 2: hipLaunchKernelGGL(k_tx_backward_uv<2>, grid, block, 0, st, tex, uv, grad_out, s, c0, grad_uv); break;
+            case 3: hipLaunchKernelGGL(k_tx_backward_uv<3>, grid, block, 0, st, tex, uv, grad_out, s, c0, grad_uv); break;
+            default: hipLaunchKernelGGL(k_tx_backward_uv<4>, grid, block, 0, st, tex, uv, grad_out, s, c0, grad_uv); break;
+            }
+        });
+    }
+    if (grad_tex) {
+        const dim3 grid(div_up((int64_t)s.Bt * s.Ht * s.Wt, 256)), block(256);
+        tx_groups(C, [&](int c0, int ct) {
+            switch (ct) {
+            case 1: hipLaunchKernelGGL(k_tx_backward_tex<1>, grid, block, 0, st, uv, grad_out, order, seg, s, c0, grad_tex); break;
+            case 2: hipLaunchKernelGGL(k_tx_backward_tex<2>, grid, block, 0, st, uv, grad_out, order, seg, s, c0, grad_tex); break;
+            case 3: hipLaunchKernelGGL(k_tx_backward_tex<3>, grid, block, 0, st, uv, grad_out, order, seg, s, c0, grad_tex); break;
+            default: hipLaunchKernelGGL(k_tx_backward_tex<4>, grid, block, 0, st, uv, grad_out, order, seg, s, c0, grad_tex); break;
+            }
+        });
+    }
+    LS_HIP(hipGetLastError());
+    return LS_OK;
+}

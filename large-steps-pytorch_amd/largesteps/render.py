@@ -8,15 +8,17 @@ tests/render_statement.py):
     rast, rast_db = rasterize(ctx, pos, tri, resolution)       pos (B, V, 4) clip space, tri (F, 3) int32 / int64, resolution (H, W)
     out, _ = interpolate(attr, rast, tri)                      attr (V, C), (1, V, C) or (B, V, C)
     color_aa = antialias(color, rast, pos, tri, pos_gradient_boost=1.0)
-    texture(tex, uv)                                           bilinear, wrapping, forward only (plain torch: backgrounds only)
+    texture(tex, uv, filter_mode='linear', boundary_mode='wrap')    tex (1 or B, Ht, Wt, C), uv (B, H, W, 2); nearest / linear, wrap / clamp /
+                                                               zero (csrc/texture.hip, restated by tests/texture_statement.py)
 
 plus the renderer built on them: `persp_proj`, `SphericalHarmonics`, `NVDRenderer` (same constructor keys, same values as the
 reference's). Conventions: rast = (u, v, z/w, id + 1), 0 for background; an attribute interpolates as u a0 + v a1 + (1 - u - v) a2;
 row 0 of an image is NDC y = -1, pixel (x, y) has its centre at NDC ((2x + 1) / W - 1, (2y + 1) / H - 1). Gradients: rasterize passes
 the gradients of u and v to pos (the z/w channel's gradient is dropped), interpolate to attr and to rast[..., :2], antialias to color
-and (scaled by pos_gradient_boost) to pos. No float atomics anywhere: images and gradients are bitwise reproducible, and no call
+and (scaled by pos_gradient_boost) to pos, texture to tex and (linear filtering) to uv -- so interpolate(uv attribute) -> texture ->
+antialias learns a texture and moves the geometry under it. No float atomics anywhere: images and gradients are bitwise reproducible, and no call
 synchronises with the host once a face tensor has been seen (its edge adjacency and corner ranking are cached per tensor object), so
-the whole render can sit inside `CapturedStep`. There is no CPU path.
+the whole render can sit inside `CapturedStep`. There is no CPU path (but a plain-torch `texture` forward, linear + wrap, for CPU tensors).
 """
 import ctypes
 import weakref
@@ -357,14 +359,99 @@ def antialias(color, rast, pos, tri, topology_hash=None, pos_gradient_boost=1.0)
     return out
 
 
-def texture(tex, uv, uv_da=None, mip_level_bias=None, mip=None, filter_mode='linear', boundary_mode='wrap', max_mip_level=None):
-    """
-    Bilinear texture lookup (nvdiffrast.torch.texture, forward only): tex (1 or B, Ht, Wt, C), uv (B, H, W, 2) -> (B, H, W, C).
-    Texel (i, j) has its centre at ((i + 0.5) / Wt, (j + 0.5) / Ht); coordinates wrap around. The reference calls it once per
-    renderer, to build the backgrounds, so it is plain torch and carries no gradient.
-    """
-    if filter_mode not in ('linear', 'auto') or boundary_mode != 'wrap':
-        raise NotImplementedError("largesteps.render.texture: only filter_mode='linear' with boundary_mode='wrap' is supported")
+_FILTER_MODES = {'nearest': 0, 'linear': 1, 'auto': 1}                  # LS_TEXTURE_* of the header
+_BOUNDARY_MODES = {'wrap': 0, 'clamp': 1, 'zero': 2}
+_MIP_FILTER_MODES = ('linear-mipmap-nearest', 'linear-mipmap-linear')
+TEXTURE_MAX_SIZE = 8192                                                 # texels per side
+TEXTURE_MAX_CHANNELS = 32
+
+
+class _TexelOrder:
+    """The pixels of one uv image sorted by their base tap -- the order the texture gradient sums in. It depends on uv, the texture's
+    shape and the two modes, not on the texture's values: made at most once per uv tensor and version, by the first backward that
+    needs it, and shared through the uv tensor (a fixed uv -- backgrounds, texture fitting on fixed geometry -- sorts once)."""
+    __slots__ = ("key", "order", "seg")
+
+    def __init__(self, key):
+        self.key, self.order, self.seg = key, None, None
+
+    def get(self, u, Bt, Ht, Wt, filt, bnd):
+        if self.order is None:
+            B, H, W, _ = u.shape
+            dev = u.device
+            n = ctypes.c_size_t(0)
+            _native.check(_native.lib().ls_texture_workspace_bytes(B, H, W, ctypes.byref(n)))
+            ws = torch.empty(n.value, dtype=torch.uint8, device=dev)
+            order = torch.empty(B * H * W, dtype=torch.int32, device=dev)
+            seg = torch.empty(Bt * (Ht + 1) * (Wt + 1) + 1, dtype=torch.int32, device=dev)
+            with torch.cuda.device(dev):
+                _native.check(_native.lib().ls_texture_order(_native.ptr(u), B, H, W, Bt, Ht, Wt, filt, bnd, _native.ptr(order), _native.ptr(seg),
+                                                             _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
+            self.order, self.seg = order, seg
+        return self.order, self.seg
+
+
+def _texel_order_slot(uv, Bt, Ht, Wt, filt, bnd):
+    key = (uv._version, uv.data_ptr(), tuple(uv.shape), tuple(uv.stride()), Bt, Ht, Wt, filt, bnd)
+    # while a graph is being captured the order is neither taken from the tensor nor left on it: a replay must sort the uv it finds
+    # (a captured body may read a uv that is updated in place between replays), and memory of the graph's pool must not outlive it
+    if torch.cuda.is_current_stream_capturing():
+        return _TexelOrder(None)
+    slot = getattr(uv, "_largesteps_texel_order", None)
+    if slot is not None and slot.key == key:
+        return slot
+    return _TexelOrder(key)
+
+
+def _aligned(t):
+    """float2 / float4 rows: torch's allocations are 256-byte aligned, a view into one need not be"""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class _Texture(Function):
+    @staticmethod
+    def forward(ctx, tex, uv, filt, bnd, slot):
+        t, u = tex.detach(), uv.detach()
+        t = _aligned(t if t.is_contiguous() else t.contiguous())
+        u = _aligned(u if u.is_contiguous() else u.contiguous())
+        Bt, Ht, Wt, C = t.shape
+        B, H, W, _ = u.shape
+        dev = u.device
+        out = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().ls_texture_forward(_native.ptr(t), Bt, Ht, Wt, C, _native.ptr(u), B, H, W, filt, bnd, _native.ptr(out),
+                                                           dev.index, _native.stream_of(dev)))
+        ctx.save_for_backward(t, u)
+        ctx.modes = (filt, bnd)
+        ctx.slot = slot
+        ctx.shapes = (tuple(tex.shape), tuple(uv.shape))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        need_tex, need_uv = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_tex or need_uv):
+            return None, None, None, None, None
+        t, u = ctx.saved_tensors
+        filt, bnd = ctx.modes
+        Bt, Ht, Wt, C = t.shape
+        B, H, W, _ = u.shape
+        dev = u.device
+        g = _aligned(g.to(torch.float32).contiguous())
+        gt = torch.empty_like(t) if need_tex else None
+        gu = torch.empty_like(u) if need_uv else None
+        order = seg = None
+        if need_tex:
+            order, seg = ctx.slot.get(u, Bt, Ht, Wt, filt, bnd)
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().ls_texture_backward(_native.ptr(t), Bt, Ht, Wt, C, _native.ptr(u), B, H, W, filt, bnd, _native.ptr(g),
+                                                            _native.ptr(order), _native.ptr(seg), _native.ptr(gt), _native.ptr(gu), dev.index,
+                                                            _native.stream_of(dev)))
+        return (gt.view(ctx.shapes[0]) if need_tex else None), (gu.view(ctx.shapes[1]) if need_uv else None), None, None, None
+
+
+def _texture_cpu(tex, uv):
+    """the lookup in plain torch, linear + wrap, forward only: what a CPU tensor gets (the device kernel keeps this operation order)"""
     with torch.no_grad():
         Ht, Wt = tex.shape[1], tex.shape[2]
         x = uv[..., 0] * Wt - 0.5
@@ -382,6 +469,69 @@ def texture(tex, uv, uv_da=None, mip_level_bias=None, mip=None, filter_mode='lin
         top = t00 + (t10 - t00) * fx
         bot = t01 + (t11 - t01) * fx
         return top + (bot - top) * fy
+
+
+@_native.retry_on_oom
+def texture(tex, uv, uv_da=None, mip_level_bias=None, mip=None, filter_mode='linear', boundary_mode='wrap', max_mip_level=None):
+    """
+    2D texture lookup (nvdiffrast.torch.texture without mipmaps): tex (1 or B, Ht, Wt, C), uv (B, H, W, 2) -> (B, H, W, C), all fp32.
+
+    filter_mode : 'linear' (bilinear), 'nearest', 'auto' (= 'linear': no mipmaps). The mipmap modes raise NotImplementedError.
+    boundary_mode : 'wrap', 'clamp' or 'zero', applied to each tap index: modulo the size; clamped to [0, size - 1]; a tap outside
+                    reads 0 and receives no gradient. 'cube' raises NotImplementedError.
+    uv_da, mip_level_bias, mip, max_mip_level : accepted and ignored.
+
+    Texel (i, j) has its centre at ((i + 0.5) / Wt, (j + 0.5) / Ht). Linear: x = u Wt - 0.5, i0 = floor(x), fx = x - i0 (likewise y),
+    out = top + (bot - top) fy with top = t00 + (t10 - t00) fx, bot = t01 + (t11 - t01) fx. Nearest: the texel (floor(u Wt), floor(v Ht)).
+    A non-finite uv gives 0 and no gradient. Sizes: 1 <= Ht, Wt <= 8192, C <= 32, B H W < 2^31.
+
+    Gradients flow to tex in every mode (summed over the images when tex has one batch entry) and to uv in linear mode (zero for
+    'nearest'), without float atomics: bitwise reproducible. The pixel order the texture gradient sums in is cached per uv tensor
+    and version. Tensors on a HIP device take the native path whether or not a gradient is wanted; CPU tensors get a plain-torch
+    forward without gradient, for 'linear' + 'wrap' only.
+    """
+    if filter_mode in _MIP_FILTER_MODES:
+        raise NotImplementedError(f"largesteps.render.texture: filter_mode={filter_mode!r} (mipmaps) is not supported")
+    if boundary_mode == 'cube':
+        raise NotImplementedError("largesteps.render.texture: boundary_mode='cube' (cube maps) is not supported")
+    if filter_mode not in _FILTER_MODES:
+        raise ValueError(f"filter_mode must be one of {sorted(_FILTER_MODES)}, got {filter_mode!r}")
+    if boundary_mode not in _BOUNDARY_MODES:
+        raise ValueError(f"boundary_mode must be one of {sorted(_BOUNDARY_MODES)}, got {boundary_mode!r}")
+    for t, what in ((tex, "tex"), (uv, "uv")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what} must be a torch.Tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{what} must be float32, got {t.dtype}")
+    if tex.dim() != 4:
+        raise ValueError(f"tex must be (1 or B, Ht, Wt, C), got {tuple(tex.shape)}")
+    if uv.dim() != 4 or uv.shape[3] != 2:
+        raise ValueError(f"uv must be (B, H, W, 2), got {tuple(uv.shape)}")
+    Bt, Ht, Wt, C = tex.shape
+    B, H, W, _ = uv.shape
+    if Bt not in (1, B):
+        raise ValueError(f"tex has {Bt} batches for {B} images")
+    if not (1 <= Ht <= TEXTURE_MAX_SIZE and 1 <= Wt <= TEXTURE_MAX_SIZE):
+        raise ValueError(f"the texture must be between 1 and {TEXTURE_MAX_SIZE} texels a side, got {Ht} x {Wt}")
+    if not 1 <= C <= TEXTURE_MAX_CHANNELS:
+        raise ValueError(f"the texture must have between 1 and {TEXTURE_MAX_CHANNELS} channels, got {C}")
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError(f"uv must not be empty, got {tuple(uv.shape)}")
+    if B * H * W >= 2 ** 31 - 1:
+        raise OverflowError(f"uv has {B * H * W} pixels: the kernels index them with int32")
+    if tex.device != uv.device:
+        raise ValueError(f"tex is on {tex.device}, uv on {uv.device}")
+    filt, bnd = _FILTER_MODES[filter_mode], _BOUNDARY_MODES[boundary_mode]
+    if not uv.is_cuda:
+        if (filt, bnd) != (1, 0):
+            raise NotImplementedError("largesteps.render.texture: CPU tensors get filter_mode='linear' with boundary_mode='wrap' only; "
+                                      "every other mode needs a HIP device")
+        return _texture_cpu(tex, uv)
+    slot = _texel_order_slot(uv, Bt, Ht, Wt, filt, bnd)
+    out = _Texture.apply(tex, uv, filt, bnd, slot)
+    if slot.key is not None:
+        uv._largesteps_texel_order = slot
+    return out
 
 
 def persp_proj(fov_x=45, ar=1, near=0.1, far=100, device=None):
