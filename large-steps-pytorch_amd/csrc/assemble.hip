@@ -52,7 +52,7 @@ struct AsmLayout {
 // exclusive scan of int32 (three kernels; the middle one is a single workgroup)
 // ------------------------------------------------------------------------------------------------
 constexpr int SCAN_ITEMS = 8;
-constexpr int SCAN_CHUNK = BLOCK * SCAN_ITEMS;   // 2048 elements per workgroup
+static_assert(SCAN_CHUNK == BLOCK * SCAN_ITEMS, "scan_scratch_ints (common.h) counts workgroups of BLOCK * SCAN_ITEMS elements");
 
 __device__ __forceinline__ int wave_inclusive_scan(int x) {
     const int lane = threadIdx.x & (WAVE - 1);
@@ -829,11 +829,27 @@ __global__ __launch_bounds__(256) void k_dedup_faces(const IdxT* __restrict__ fa
 
 }  // namespace ls
 
+namespace {
+
+// The workspaces of the three users of the radix sort below: the caller's own regions as named byte offsets behind a 256-byte aligned
+// base (the + 256 of `total`), then the sort's scratch (radix.h), whose bsum also serves the entry point's own scan over V elements.
+struct DedupWs { size_t ord_a, flag, uid, sort, total; };
+DedupWs dedup_layout(int64_t V) {
+    const size_t n = 4 * (size_t)V;
+    return {0, n, 2 * n, 3 * n + 4, 3 * n + 4 + sort_scratch_bytes(V, true, V) + 256};          // uid: V + 1
+}
+// n ids ranked by keys in [0, V): ord_a, the key counts (V + 1, the last one the range flag), `own` more ints of the caller, the sort's scratch
+struct RankWs { size_t ord_a, cnt, own, sort, total; };
+RankWs rank_layout(int64_t n, int64_t V, int64_t own) {
+    const size_t cnt = 4 * (size_t)n, o = cnt + 4 * (size_t)(V + 1), sort = o + 4 * (size_t)own;
+    return {0, cnt, o, sort, sort + sort_scratch_bytes(n, false, V) + 256};
+}
+
+}  // namespace
+
 extern "C" int ls_remove_duplicates_workspace_bytes(int64_t V, size_t* h_bytes) {
     LS_REQUIRE(h_bytes && V >= 0, LS_E_INVALID, "ls_remove_duplicates_workspace_bytes: bad argument");
-    const size_t nb = (size_t)div_up(std::max<int64_t>(V, 1), rs_chunk(V));
-    // order a / b, flags, uid (V + 1), carried keys a / b, histogram + its scan (256 nb + 1 each), scan block sums
-    *h_bytes = sizeof(int) * ((size_t)V * 6 + 16 + 2 * (256 * nb + 16) + (size_t)div_up(std::max<int64_t>(std::max<int64_t>(V, 256 * (int64_t)nb), 1), SCAN_CHUNK) + 64) + 256;
+    *h_bytes = dedup_layout(V).total;
     return LS_OK;
 }
 
@@ -842,34 +858,27 @@ extern "C" int ls_remove_duplicates(const float* verts, int64_t V, const void* f
                                     void* stream) {
     LS_REQUIRE(h_n_unique && V >= 0 && F >= 0 && V < INT32_MAX && (V == 0 || (verts && unique_verts && inverse)) &&
                (F == 0 || (faces && new_faces && (idx_bytes == 4 || idx_bytes == 8))), LS_E_INVALID, "ls_remove_duplicates: bad argument");
-    size_t need = 0;
-    ls_remove_duplicates_workspace_bytes(V, &need);
-    LS_REQUIRE(workspace && ws_bytes >= need, LS_E_WORKSPACE, "ls_remove_duplicates: workspace too small (%zu < %zu bytes)", ws_bytes, need);
+    const DedupWs L = dedup_layout(V);
+    LS_REQUIRE(workspace && ws_bytes >= L.total, LS_E_WORKSPACE, "ls_remove_duplicates: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
     *h_n_unique = 0;
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
     if (V == 0) { LS_REQUIRE(F == 0, LS_E_INDEX, "ls_remove_duplicates: faces without vertices"); return LS_OK; }
-    const int nb = div_up(V, rs_chunk(V));
-    int* w = (int*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    int* ord_a = w;
-    int* ord_b = ord_a + V;
-    int* flag = ord_b + V;
-    int* uid = flag + V;                       // V + 1
-    unsigned* keys_a = (unsigned*)(uid + V + 16);
-    unsigned* keys_b = keys_a + V;
-    int* hist = (int*)(keys_b + V);            // 256 nb
-    int* offs = hist + 256 * (size_t)nb + 16;  // 256 nb + 1
-    int* bsum = offs + 256 * (size_t)nb + 16;
+    char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    int* ord_a = (int*)(w + L.ord_a);
+    int* flag = (int*)(w + L.flag);
+    int* uid = (int*)(w + L.uid);              // V + 1
+    const SortScratch ss = sort_scratch_carve(w + L.sort, V, true);
     const int* src = nullptr;
     {
         KeyVerts key{verts};                   // three 32-bit key words (z, y, x), each gathered once and carried through its four byte passes
-        const int rc0 = radix_argsort_words(key, V, 3, ord_a, ord_b, keys_a, keys_b, hist, offs, bsum, st, &src);
+        const int rc0 = radix_argsort_words(key, V, 3, ord_a, ss, st, &src);
         if (rc0) return rc0;
     }
     const int vg = div_up(V, 256);
     hipLaunchKernelGGL(k_dedup_flags, dim3(vg), dim3(256), 0, st, verts, src, V, flag);
-    int rc = exclusive_scan(flag, V, uid, bsum, st);
+    int rc = exclusive_scan(flag, V, uid, ss.bsum, st);
     if (rc) return rc;
     hipLaunchKernelGGL(k_dedup_emit, dim3(vg), dim3(256), 0, st, verts, src, V, (const int*)flag, (const int*)uid, unique_verts, inverse);
     int* bad = flag;                           // flags are consumed: reuse one word as the range-check flag
@@ -924,40 +933,31 @@ __global__ __launch_bounds__(256) void k_invert_order(const int* __restrict__ or
 }
 }  // namespace ls
 
-static size_t argsort_ws_ints(int64_t n, int64_t nkeys) {
-    const size_t nb = (size_t)div_up(std::max<int64_t>(n, 1), rs_chunk(n));
-    return (size_t)n * 3 + (size_t)nkeys + 64 + 2 * (256 * nb + 16) + (size_t)div_up(std::max<int64_t>(std::max<int64_t>(std::max<int64_t>(n, nkeys), 256 * (int64_t)nb), 1), SCAN_CHUNK) + 64;
-}
-
 extern "C" int ls_csr_transpose_workspace_bytes(int64_t V, int64_t nnz, size_t* h_bytes) {
     LS_REQUIRE(h_bytes && V >= 0 && nnz >= 0, LS_E_INVALID, "ls_csr_transpose_workspace_bytes: bad argument");
-    *h_bytes = sizeof(int) * argsort_ws_ints(nnz, V + 1) + 256;
+    *h_bytes = rank_layout(nnz, V, 0).total;
     return LS_OK;
 }
 
 extern "C" int ls_csr_transpose(const int32_t* rowptr, const int32_t* col, const float* val, int64_t V, int64_t nnz, int32_t* t_rowptr,
                                 int32_t* t_col, float* t_val, void* workspace, size_t ws_bytes, int device, void* stream) {
     LS_REQUIRE(rowptr && t_rowptr && V > 0 && nnz >= 0 && nnz < INT32_MAX && (nnz == 0 || (col && val && t_col && t_val)), LS_E_INVALID, "ls_csr_transpose: bad argument");
-    size_t need = 0;
-    ls_csr_transpose_workspace_bytes(V, nnz, &need);
-    LS_REQUIRE(workspace && ws_bytes >= need, LS_E_WORKSPACE, "ls_csr_transpose: workspace too small (%zu < %zu bytes)", ws_bytes, need);
+    const RankWs L = rank_layout(nnz, V, 0);
+    LS_REQUIRE(workspace && ws_bytes >= L.total, LS_E_WORKSPACE, "ls_csr_transpose: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
-    const size_t nb = (size_t)div_up(std::max<int64_t>(nnz, 1), rs_chunk(nnz));
-    int* w = (int*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    int *ord_a = w, *ord_b = ord_a + nnz, *cnt = ord_b + nnz;          // cnt: V + 1 (last = range flag)
-    int *hist = cnt + V + 16 + nnz, *offs = hist + 256 * nb + 16, *bsum = offs + 256 * nb + 16;
+    char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    int *ord_a = (int*)(w + L.ord_a), *cnt = (int*)(w + L.cnt);
+    const SortScratch ss = sort_scratch_carve(w + L.sort, nnz, false);
     LS_HIP(hipMemsetAsync(cnt, 0, sizeof(int) * (V + 1), st));
     if (nnz) hipLaunchKernelGGL(k_count_keys, dim3(div_up(nnz, 256)), dim3(256), 0, st, (const int*)col, nnz, V, cnt, cnt + V);
-    int rc = exclusive_scan(cnt, V, t_rowptr, bsum, st);
+    int rc = exclusive_scan(cnt, V, t_rowptr, ss.bsum, st);
     if (rc) return rc;
     if (nnz) {
         const int* src = nullptr;
-        int passes = 1;
-        while (passes < 4 && (V - 1) >> (8 * passes)) ++passes;
         KeyInt key{(const int*)col};
-        rc = radix_argsort(key, nnz, passes, ord_a, ord_b, hist, offs, bsum, st, &src);
+        rc = radix_argsort(key, nnz, radix_passes(V - 1), ord_a, ss, st, &src);
         if (rc) return rc;
         hipLaunchKernelGGL(k_transpose_emit, dim3(div_up(nnz, 256)), dim3(256), 0, st, src, nnz, (const int*)rowptr, V, val, (int*)t_col, t_val);
     }
@@ -971,7 +971,7 @@ extern "C" int ls_csr_transpose(const int32_t* rowptr, const int32_t* col, const
 
 extern "C" int ls_corner_ranks_workspace_bytes(int64_t F, int64_t V, size_t* h_bytes) {
     LS_REQUIRE(h_bytes && F >= 0 && V >= 0, LS_E_INVALID, "ls_corner_ranks_workspace_bytes: bad argument");
-    *h_bytes = sizeof(int) * (argsort_ws_ints(3 * F, V + 1) + (size_t)3 * F) + 256;
+    *h_bytes = rank_layout(3 * F, V, 3 * F).total;
     return LS_OK;
 }
 
@@ -979,25 +979,22 @@ extern "C" int ls_corner_ranks(const void* faces, int idx_bytes, int64_t F, int6
                                size_t ws_bytes, int device, void* stream) {
     LS_REQUIRE(vptr && V >= 0 && F >= 0 && 3 * F < INT32_MAX && (F == 0 || (faces && cpos && (idx_bytes == 4 || idx_bytes == 8))), LS_E_INVALID,
                "ls_corner_ranks: bad argument");
-    size_t need = 0;
-    ls_corner_ranks_workspace_bytes(F, V, &need);
-    LS_REQUIRE(workspace && ws_bytes >= need, LS_E_WORKSPACE, "ls_corner_ranks: workspace too small (%zu < %zu bytes)", ws_bytes, need);
+    const int64_t n = 3 * F;
+    const RankWs L = rank_layout(n, V, n);
+    LS_REQUIRE(workspace && ws_bytes >= L.total, LS_E_WORKSPACE, "ls_corner_ranks: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
-    const int64_t n = 3 * F;
-    const size_t nb = (size_t)div_up(std::max<int64_t>(n, 1), rs_chunk(n));
-    int* w = (int*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    int *ord_a = w, *ord_b = ord_a + n, *cnt = ord_b + n;
-    int *hist = cnt + V + 16 + n, *offs = hist + 256 * nb + 16, *bsum = offs + 256 * nb + 16;
-    int* keys = bsum + div_up(std::max<int64_t>(std::max<int64_t>(std::max<int64_t>(n, V + 1), 256 * (int64_t)nb), 1), SCAN_CHUNK) + 64;
+    char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    int *ord_a = (int*)(w + L.ord_a), *cnt = (int*)(w + L.cnt), *keys = (int*)(w + L.own);        // keys: the face corners as int32
+    const SortScratch ss = sort_scratch_carve(w + L.sort, n, false);
     LS_HIP(hipMemsetAsync(cnt, 0, sizeof(int) * (V + 1), st));
     if (n) {
         if (idx_bytes == 4) hipLaunchKernelGGL(k_faces_to_i32<int32_t>, dim3(div_up(n, 256)), dim3(256), 0, st, (const int32_t*)faces, n, V, keys);
         else hipLaunchKernelGGL(k_faces_to_i32<int64_t>, dim3(div_up(n, 256)), dim3(256), 0, st, (const int64_t*)faces, n, V, keys);
         hipLaunchKernelGGL(k_count_keys, dim3(div_up(n, 256)), dim3(256), 0, st, (const int*)keys, n, V, cnt, cnt + V);
     }
-    int rc = exclusive_scan(cnt, V, (int*)vptr, bsum, st);
+    int rc = exclusive_scan(cnt, V, (int*)vptr, ss.bsum, st);
     if (rc) return rc;
     int bad = 0;
     LS_HIP(hipMemcpyAsync(&bad, cnt + V, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -1005,10 +1002,8 @@ extern "C" int ls_corner_ranks(const void* faces, int idx_bytes, int64_t F, int6
     LS_REQUIRE(!bad, LS_E_INDEX, "face index out of range for %lld vertices", (long long)V);
     if (n) {
         const int* src = nullptr;
-        int passes = 1;
-        while (passes < 4 && (std::max<int64_t>(V, 1) - 1) >> (8 * passes)) ++passes;
         KeyInt key{(const int*)keys};
-        rc = radix_argsort(key, n, passes, ord_a, ord_b, hist, offs, bsum, st, &src);
+        rc = radix_argsort(key, n, radix_passes(std::max<int64_t>(V, 1) - 1), ord_a, ss, st, &src);
         if (rc) return rc;
         hipLaunchKernelGGL(k_invert_order, dim3(div_up(n, 256)), dim3(256), 0, st, src, n, (int*)cpos);
     }

@@ -54,9 +54,11 @@ void* pool_take(int device, size_t bytes, size_t* capacity);
 bool pool_give(int device, void* p, size_t bytes);
 hipError_t pool_alloc(int device, void** p, size_t bytes);      // hipMalloc; out of memory: the pool of `device` is emptied and the call repeated once
 constexpr size_t POOL_FROM = (size_t)256 << 10, POOL_SLACK = (size_t)1 << 20;      // smallest pooled buffer; a taken buffer is at most 1.5 x the request + POOL_SLACK
-// assemble.hip: out[0 .. n] = exclusive scan of the int32 in[0 .. n), out[n] = total; bsum: scan_blocks(n) + 1 ints of scratch
+// assemble.hip: out[0 .. n] = exclusive scan of the int32 in[0 .. n), out[n] = total; bsum: scan_scratch_ints(n) ints of scratch
 int exclusive_scan(const int* in, int64_t n, int* out, int* bsum, hipStream_t st);
-inline int64_t scan_blocks(int64_t n) { return (n + 2047) / 2048; }
+constexpr int SCAN_CHUNK = 2048;   // elements per workgroup of the scan
+// one sum per workgroup and the grand total behind them: every bsum is sized by this
+inline int64_t scan_scratch_ints(int64_t n) { return (n + SCAN_CHUNK - 1) / SCAN_CHUNK + 1; }
 
 // ---- device side ---------------------------------------------------------------------------------
 #ifdef __HIPCC__
@@ -120,6 +122,14 @@ __device__ __forceinline__ T wave_sum(T x) {
 #pragma unroll
     for (int off = WAVE / 2; off > 0; off >>= 1) x += __shfl_down(x, off, WAVE);
     return x;   // valid in lane 0
+}
+
+// The same sum by an xor butterfly (32, 16, ... 1), returned in EVERY lane. The segmented sum of groupby.h is pinned to this order of
+// additions (bitwise-reproducible gradients): it is not interchangeable with wave_sum above.
+__device__ __forceinline__ float wave_sum_xor(float v) {
+#pragma unroll
+    for (int m = WAVE / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, WAVE);
+    return v;
 }
 
 __device__ __forceinline__ float wave_max(float x) {

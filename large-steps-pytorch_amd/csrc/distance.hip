@@ -133,11 +133,12 @@ using namespace ls;
 // carves the handle's arrays out of one buffer (256-byte aligned) of the scratch pool
 static int md_alloc(MeshDistanceHandle* H) {
     const int64_t T = H->T, N = 2 * T - 1;
-    void** slot[] = {(void**)&H->pos, (void**)&H->faces, (void**)&H->small, (void**)&H->bvh.code, (void**)&H->bvh.ord_a, (void**)&H->bvh.ord_b,
-                     (void**)&H->bvh.hist, (void**)&H->bvh.offs, (void**)&H->bvh.bsum, (void**)&H->bvh.tri, (void**)&H->bvh.scode, (void**)&H->bvh.left,
-                     (void**)&H->bvh.right, (void**)&H->bvh.parent, (void**)&H->bvh.esc, (void**)&H->bvh.rflag, (void**)&H->bvh.box};
-    const int64_t bytes[] = {12 * (int64_t)H->V, 12 * T, 4 * 16, 4 * T, 4 * T, 4 * T, 4 * lbvh_hist_ints((int)T), 4 * lbvh_hist_ints((int)T),
-                             4 * lbvh_bsum_ints((int)T), 4 * T, 4 * T, 4 * T, 4 * T, 4 * N, 4 * N, 4 * T, 24 * N};
+    void* sort = nullptr;
+    void** slot[] = {(void**)&H->pos, (void**)&H->faces, (void**)&H->small, (void**)&H->bvh.code, (void**)&H->bvh.ord_a, &sort,
+                     (void**)&H->bvh.tri, (void**)&H->bvh.scode, (void**)&H->bvh.left, (void**)&H->bvh.right, (void**)&H->bvh.parent,
+                     (void**)&H->bvh.esc, (void**)&H->bvh.rflag, (void**)&H->bvh.box};
+    const int64_t bytes[] = {12 * (int64_t)H->V, 12 * T, 4 * 16, 4 * T, 4 * T, (int64_t)sort_scratch_bytes(T, false),
+                             4 * T, 4 * T, 4 * T, 4 * T, 4 * N, 4 * N, 4 * T, 24 * N};
     size_t total = 0;
     for (int64_t b : bytes) total += ((size_t)b + 255) & ~(size_t)255;
     void* p = pool_take(H->device, total, &H->cap);
@@ -148,6 +149,7 @@ static int md_alloc(MeshDistanceHandle* H) {
         *slot[k] = (char*)p + off;
         off += ((size_t)bytes[k] + 255) & ~(size_t)255;
     }
+    H->bvh.sort = sort_scratch_carve(sort, T, false);
     H->bvh.bb = (unsigned*)(H->small + 8);
     return LS_OK;
 }

@@ -16,17 +16,17 @@
 namespace ls {
 
 // the device arrays of one hierarchy over T triangles (N = 2 T - 1 nodes); the caller owns them. Sizes in ints unless said:
-//   code, ord_a, ord_b: T; hist, offs: lbvh_hist_ints(T); bsum: lbvh_bsum_ints(T); tri, scode (unsigned), left, right: T;
+//   code, ord_a: T; sort: sort_scratch_bytes(T, false) bytes, carved by sort_scratch_carve; tri, scode (unsigned), left, right: T;
 //   parent, esc: N; rflag: T; box: 6 N floats (min xyz, max xyz of node i at box[6 i]); bb: 6 unsigned (the vertex box's keys)
 struct Lbvh {
-    int *code, *ord_a, *ord_b, *hist, *offs, *bsum, *tri;
+    int *code, *ord_a;
+    SortScratch sort;
+    int* tri;
     unsigned* scode;
     int *left, *right, *parent, *esc, *rflag;
     float* box;
     unsigned* bb;
 };
-static inline int64_t lbvh_hist_ints(int T) { return 256 * (int64_t)div_up(T > 1 ? T : 1, rs_chunk(T)) + 16; }
-static inline int64_t lbvh_bsum_ints(int T) { return scan_blocks(T > lbvh_hist_ints(T) ? T : lbvh_hist_ints(T)) + 1; }
 
 __device__ __forceinline__ float3 lbvh_ld(const float* __restrict__ P, int v) { return make_float3(P[3 * (size_t)v], P[3 * (size_t)v + 1], P[3 * (size_t)v + 2]); }
 __device__ __forceinline__ unsigned lbvh_key_inv(unsigned k) { return (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k; }
@@ -166,7 +166,7 @@ static inline int lbvh_build(const float* P, const int* faces, int T, float marg
     const dim3 grid_t(div_up(std::max(T, 1), BLOCK)), grid_n(div_up(std::max(N, 1), BLOCK)), block(BLOCK);
     hipLaunchKernelGGL(k_lbvh_morton<0>, grid_t, block, 0, st, P, faces, T, (const unsigned*)a.bb, a.code);
     const int* order = nullptr;
-    int rc = radix_argsort(KeyInt{(const int*)a.code}, T, 4, a.ord_a, a.ord_b, a.hist, a.offs, a.bsum, st, &order);
+    int rc = radix_argsort(KeyInt{(const int*)a.code}, T, 4, a.ord_a, a.sort, st, &order);
     if (rc) return rc;
     hipLaunchKernelGGL(k_lbvh_sorted_codes<0>, grid_t, block, 0, st, order, (const int*)a.code, T, a.tri, a.scode);
     LS_HIP(hipMemsetAsync(a.parent, 0xff, sizeof(int) * N, st));

@@ -552,7 +552,6 @@ std::string nd_bisect_device(void* ctx, int64_t V, int D, int smooth, const doub
     if (!has_pos && !embedded) return "nd_bisect_device: neither positions nor an embedding";
     const int NA = (minsep && has_pos && embedded) ? 6 : 3;
     const int max_dom = 1 << (D - 1), nb = div_up(V, BCH);
-    const size_t nbr = (size_t)div_up(V, rs_chunk(V));
     // one allocation: positions (two copies), 3 x 2 lists, state, node, end-point flags, per-domain tables, scan scratch, sort scratch
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
@@ -566,9 +565,7 @@ std::string nd_bisect_device(void* ctx, int64_t V, int D, int smooth, const doub
                  o_use1 = take(sizeof(int) * max_dom), o_b0 = take(sizeof(int) * max_dom), o_b1 = take(sizeof(int) * max_dom);
     const size_t o_bsum = take(sizeof(unsigned long long) * NA * (size_t)nb);
     const size_t o_sideb = minsep ? take(sizeof(unsigned) * V) : 0, o_cutb = minsep ? take(V) : 0, o_ecnt6 = minsep ? take(sizeof(int) * 2 * NAX * (size_t)max_dom) : 0;
-    const size_t o_keys = take(sizeof(unsigned) * 2 * (size_t)V);            // carried key words of the coordinate sorts
-    const size_t o_hist = take(sizeof(int) * (256 * nbr + 16)), o_offs = take(sizeof(int) * (256 * nbr + 16)),
-                 o_sb = take(sizeof(int) * ((size_t)scan_blocks(256 * (int64_t)nbr) + 64));
+    const size_t o_sort = take(sort_scratch_bytes(V, true));                 // the coordinate sorts carry their key words
     int dev = 0;
     (void)hipGetDevice(&dev);
     size_t cap = off;
@@ -582,6 +579,7 @@ std::string nd_bisect_device(void* ctx, int64_t V, int D, int smooth, const doub
     double* pos2 = (double*)(base + o_pos2);
     int* L[2 * NAX];
     for (int k = 0; k < 2 * NA; ++k) L[k] = (int*)(base + o_L[k]);
+    const SortScratch ss = sort_scratch_carve(base + o_sort, V, true);
     long long* state = (long long*)(base + o_state);
     long long* d_node = (long long*)(base + o_node);
     int* seg[2] = {(int*)(base + o_seg0), (int*)(base + o_seg1)};
@@ -613,8 +611,8 @@ std::string nd_bisect_device(void* ctx, int64_t V, int D, int smooth, const doub
     int* Lo[NAX];
     for (int k = 0; k < NA; ++k) {
         const int* res = nullptr;
-        const int rc = radix_argsort_words(KeyF64{k < 3 ? pos : posB, k < 3 ? k : k - 3}, V, 2, L[2 * k], L[2 * k + 1], (unsigned*)(base + o_keys), (unsigned*)(base + o_keys) + V, (int*)(base + o_hist),
-                                           (int*)(base + o_offs), (int*)(base + o_sb), st, &res);
+        // both lists of an axis live on (the result is one, the rounds' scratch the other): the axis' own second list is the sort's second id buffer
+        const int rc = radix_argsort_words(KeyF64{k < 3 ? pos : posB, k < 3 ? k : k - 3}, V, 2, L[2 * k], sort_scratch_onto(ss, L[2 * k + 1]), st, &res);
         if (rc) return "nd_bisect_device: sort failed";
         Lc[k] = res;
         Lo[k] = res == L[2 * k] ? L[2 * k + 1] : L[2 * k];

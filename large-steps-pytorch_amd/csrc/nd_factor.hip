@@ -953,7 +953,7 @@ int leaf_lists(CtorBuffers& B, const NdPlan& P, FactorLayout& L, const int32_t* 
     int *cnt_s = nullptr, *cnt_b = nullptr, *ptr_s = nullptr, *ptr_b = nullptr, *bsum = nullptr, *d_off_b = nullptr, *d_off_s = nullptr;
     if (!(B.take(&cnt_s, sizeof(int) * (rows_s + 1), BUF_SCRATCH, true) && B.take(&cnt_b, sizeof(int) * (rows_b + 1), BUF_SCRATCH, true) &&
           B.take(&ptr_s, sizeof(int) * (rows_s + 1), BUF_SCRATCH, false) && B.take(&ptr_b, sizeof(int) * (rows_b + 1), BUF_SCRATCH, false) &&
-          B.take(&bsum, sizeof(int) * (scan_blocks(std::max(rows_s, rows_b)) + 2), BUF_SCRATCH, false) &&
+          B.take(&bsum, sizeof(int) * scan_scratch_ints(std::max(rows_s, rows_b)), BUF_SCRATCH, false) &&
           B.take(&d_off_b, sizeof(int) * L.off_b.size(), BUF_SCRATCH, false) && B.take(&d_off_s, sizeof(int) * L.off_s.size(), BUF_SCRATCH, false)))
         return B.rc;
     hipError_t e = hipMemcpyAsync(d_off_b, L.off_b.data(), sizeof(int) * L.off_b.size(), hipMemcpyHostToDevice, st);

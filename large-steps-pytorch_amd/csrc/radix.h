@@ -1,9 +1,13 @@
 // radix.h -- stable LSD radix sort of row ids by a key policy (hand-written: per pass a histogram kernel, the scan of assemble.hip
 // and a scatter kernel in which ONE wave walks its chunk in order and ranks equal digits inside every 64-element tile with ballots:
-// stable by construction, no atomics in the scatter). Used by remove_duplicates, the CSR transpose, the corner ranking
-// (assemble.hip) and the coordinate orders of the device bisection (nd_bisect.hip).
+// stable by construction, no atomics in the scatter), and the one description of the scratch it needs (SortScratch below).
+// Users: remove_duplicates, the CSR transpose and the corner ranking (assemble.hip); the coordinate orders of the device bisection
+// (nd_bisect.hip); the Morton order of the LBVH (lbvh.h: the remesher's projection in remesh.hip, the point-to-mesh distance in
+// distance.hip); the edge adjacency of the rasterizer (raster.hip); and, through the group-by of groupby.h, the pixel orders of the
+// rasterizer and of the texture lookup (raster.hip, texture.hip).
 #pragma once
 #include "common.h"
+#include <algorithm>
 #include <utility>
 
 namespace ls {
@@ -215,49 +219,81 @@ __global__ __launch_bounds__(64) void k_rs_scatter32(const unsigned* __restrict_
 
 }  // namespace ls
 
-// order = the ids 0..n-1 sorted stably by `passes` key bytes; tmp: n ints; hist / offs: 256 nb + 16 ints each; returns where the result is
+// ---- the scratch of one sort, described once ---------------------------------------------------------------------------------------
+// The second id buffer, the histogram (256 counters per workgroup of rs_chunk(n) rows) and its scan with the total behind it, the scan's
+// own scratch and, for the sort with carried keys, two key buffers. Every user sizes and carves its scratch here and nowhere else: kernels
+// whose grids follow rs_chunk and SCAN_CHUNK write these arrays, so a formula restated elsewhere is an out-of-bounds write in waiting.
+struct SortScratch {
+    int *ord_b, *hist, *offs, *bsum;
+    unsigned *keys_a, *keys_b;          // null without carried keys
+};
+static inline int64_t sort_table_ints(int64_t n) { return 256 * (int64_t)ls::div_up(n > 1 ? n : 1, ls::rs_chunk(n)) + 16; }      // hist, offs: 256 nb + 16 each
+// scan_n: the largest exclusive_scan the CALLER runs through .bsum between sorts, 0 for none
+static inline size_t sort_scratch_bytes(int64_t n, bool carried, int64_t scan_n = 0) {
+    const int64_t table = sort_table_ints(n);
+    return sizeof(int) * (size_t)((carried ? 3 : 1) * n + 2 * table + ls::scan_scratch_ints(std::max(table - 16, scan_n)));
+}
+// the regions of sort_scratch_bytes(n, carried, scan_n) at base (4-byte aligned). bsum comes last, so its extent is whatever scan_n the
+// bytes were asked with: a caller that borrows .bsum for a scan of its own must have passed that scan's length there.
+static inline SortScratch sort_scratch_carve(void* base, int64_t n, bool carried) {
+    int* ord_b = (int*)base;
+    unsigned* keys = (unsigned*)(ord_b + n);
+    int* hist = (int*)(keys + (carried ? 2 * n : 0));
+    const int64_t table = sort_table_ints(n);
+    return {ord_b, hist, hist + table, hist + 2 * table, carried ? keys : nullptr, carried ? keys + n : nullptr};
+}
+
+// the same scratch with the CALLER's second id buffer (n ints) in place of its own, for a caller that keeps both buffers afterwards
+static inline SortScratch sort_scratch_onto(SortScratch s, int* ord_b) { s.ord_b = ord_b; return s; }
+
+// byte passes that sort keys in [0, max_key]
+static inline int radix_passes(int64_t max_key) {
+    int passes = 1;
+    while (passes < 4 && (max_key >> (8 * passes))) ++passes;
+    return passes;
+}
+
+// order = the ids 0..n-1 sorted stably by `passes` key bytes, n >= 1; ord_a: n ints; returns where the result is (ord_a or s.ord_b)
 template <typename Key>
-static inline int radix_argsort(Key key, int64_t n, int passes, int* ord_a, int* ord_b, int* hist, int* offs, int* bsum, hipStream_t st, const int** result) {
+static inline int radix_argsort(Key key, int64_t n, int passes, int* ord_a, const SortScratch& s, hipStream_t st, const int** result) {
     const int nb = ls::div_up(n, ls::rs_chunk(n));
     const int* src = nullptr;                  // pass 0 reads the identity order
     int* dst = ord_a;
     for (int pass = 0; pass < passes; ++pass) {
-        hipLaunchKernelGGL(ls::k_rs_hist<Key>, dim3(nb), dim3(256), 0, st, key, src, n, pass, nb, hist);
-        int rc = ls::exclusive_scan(hist, 256 * (int64_t)nb, offs, bsum, st);
+        hipLaunchKernelGGL(ls::k_rs_hist<Key>, dim3(nb), dim3(256), 0, st, key, src, n, pass, nb, s.hist);
+        int rc = ls::exclusive_scan(s.hist, 256 * (int64_t)nb, s.offs, s.bsum, st);
         if (rc) return rc;
-        hipLaunchKernelGGL(ls::k_rs_scatter<Key>, dim3(nb), dim3(64), 0, st, key, src, n, pass, nb, (const int*)offs, dst);
+        hipLaunchKernelGGL(ls::k_rs_scatter<Key>, dim3(nb), dim3(64), 0, st, key, src, n, pass, nb, (const int*)s.offs, dst);
         src = dst;
-        dst = (dst == ord_a) ? ord_b : ord_a;
+        dst = (dst == ord_a) ? s.ord_b : ord_a;
     }
     *result = src;
     return LS_OK;
 }
 
-// the same order (bit for bit) by `words` 32-bit key words, keys carried; keys_a / keys_b: n unsigned each; last_bytes: byte passes of the LAST word
-// (keys known to be small: fewer passes)
+// the same order (bit for bit) by `words` 32-bit key words, keys carried (a scratch carved with carried = true); last_bytes: byte passes of
+// the LAST word (keys known to be small: fewer passes)
 template <typename Key>
-static inline int radix_argsort_words(Key key, int64_t n, int words, int* ord_a, int* ord_b, unsigned* keys_a, unsigned* keys_b, int* hist, int* offs, int* bsum,
-                                      hipStream_t st, const int** result, int last_bytes = 4) {
+static inline int radix_argsort_words(Key key, int64_t n, int words, int* ord_a, const SortScratch& s, hipStream_t st, const int** result, int last_bytes = 4) {
     const int nb = ls::div_up(n, ls::rs_chunk(n));
     const int* src = nullptr;                  // word 0 is loaded in the identity order
     int* dst = ord_a;
     for (int w = 0; w < words; ++w) {
-        hipLaunchKernelGGL(ls::k_rs_load<Key>, dim3(ls::div_up(n, 256)), dim3(256), 0, st, key, src, n, w, keys_a);
-        unsigned* kin = keys_a;
-        unsigned* kout = keys_b;
+        hipLaunchKernelGGL(ls::k_rs_load<Key>, dim3(ls::div_up(n, 256)), dim3(256), 0, st, key, src, n, w, s.keys_a);
+        unsigned* kin = s.keys_a;
+        unsigned* kout = s.keys_b;
         const int nbytes = w + 1 == words ? last_bytes : 4;
         for (int byte = 0; byte < nbytes; ++byte) {
-            hipLaunchKernelGGL(ls::k_rs_hist32<0>, dim3(nb), dim3(256), 0, st, (const unsigned*)kin, n, 8 * byte, nb, hist);
-            int rc = ls::exclusive_scan(hist, 256 * (int64_t)nb, offs, bsum, st);
+            hipLaunchKernelGGL(ls::k_rs_hist32<0>, dim3(nb), dim3(256), 0, st, (const unsigned*)kin, n, 8 * byte, nb, s.hist);
+            int rc = ls::exclusive_scan(s.hist, 256 * (int64_t)nb, s.offs, s.bsum, st);
             if (rc) return rc;
-            hipLaunchKernelGGL(ls::k_rs_scatter32<0>, dim3(nb), dim3(64), 0, st, (const unsigned*)kin, src, n, 8 * byte, nb, (const int*)offs,
+            hipLaunchKernelGGL(ls::k_rs_scatter32<0>, dim3(nb), dim3(64), 0, st, (const unsigned*)kin, src, n, 8 * byte, nb, (const int*)s.offs,
                                byte + 1 < nbytes ? kout : (unsigned*)nullptr, dst);
             src = dst;
-            dst = (dst == ord_a) ? ord_b : ord_a;
+            dst = (dst == ord_a) ? s.ord_b : ord_a;
             std::swap(kin, kout);
         }
     }
     *result = src;
     return LS_OK;
 }
-

@@ -25,7 +25,7 @@
 // [B F][9] (the x, y, w gradient of each corner) or [B F][C][3] (attribute gradients). A per-vertex pass adds a vertex's face rows in the
 // corner ranking of the normals (ls_corner_ranks): every output and gradient is bitwise reproducible.
 #include "common.h"
-#include "radix.h"
+#include "groupby.h"
 #include <algorithm>
 
 namespace ls {
@@ -217,67 +217,28 @@ __global__ __launch_bounds__(256) void k_rs_keys(const float* __restrict__ rast,
     keys[pix] = id ? (int)((pix / HW) * F + id - 1) : (int)((int64_t)B * F);
 }
 
-__global__ __launch_bounds__(256) void k_rs_sorted_keys(const int* __restrict__ keys, const int* __restrict__ order, int64_t N, int* __restrict__ sk) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < N) sk[i] = keys[order[i]];
-}
-
-// seg[k] = first sorted position whose key is >= k, k in [0, nk]
-__global__ __launch_bounds__(256) void k_rs_segments(const int* __restrict__ sk, int64_t N, int64_t nk, int* __restrict__ seg) {
-    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k > nk) return;
-    int64_t lo = 0, hi = N;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (sk[mid] < k) lo = mid + 1; else hi = mid;
-    }
-    seg[k] = (int)lo;
-}
-
 // ---- sums in pixel order ---------------------------------------------------------------------------------------------------------
-// rows[key * stride + off + q] (q < K) = the sum of R::add over the pixels of `key` in sorted order (one thread per key; keys with more
-// than 64 pixels: lane-strided over the wave, then an xor butterfly -- a fixed order either way)
-template <int K>
-__device__ __forceinline__ float rs_wave_sum(float v) {
+// rows[key * stride + off + q] (q < K) = the sum of R::add over the pixels of `key` in sorted order, by seg_sum of groupby.h (a fixed
+// order of additions)
+template <class R>
+struct RsRows {
+    R r;
+    const int* __restrict__ order; const int* __restrict__ seg; int stride, off; float* __restrict__ rows;
+    __device__ __forceinline__ int count(int64_t key) const { return seg[key + 1] - seg[key]; }
+    __device__ __forceinline__ void walk(int64_t key, int start, int step, float (&acc)[R::K]) const {
+        const int e = seg[key + 1];
+        for (int i = seg[key] + start; i < e; i += step) r.add(order[i], key, acc);
+    }
+    __device__ __forceinline__ void store(int64_t key, const float (&acc)[R::K]) const {
 #pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
+        for (int q = 0; q < R::K; ++q) rows[key * stride + off + q] = acc[q];
+    }
+};
 
 template <class R>
 __global__ __launch_bounds__(256) void k_rs_seg_sum(R r, const int* __restrict__ order, const int* __restrict__ seg, int64_t nk, int stride, int off,
                                                     float* __restrict__ rows) {
-    constexpr int K = R::K;
-    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int lane = threadIdx.x & 63;
-    const bool ok = k < nk;
-    const int s = ok ? seg[k] : 0, e = ok ? seg[k + 1] : 0;
-    const bool lng = e - s > 64;
-    if (ok && !lng) {
-        float acc[K];
-#pragma unroll
-        for (int q = 0; q < K; ++q) acc[q] = 0.0f;
-        for (int i = s; i < e; ++i) r.add(order[i], k, acc);
-#pragma unroll
-        for (int q = 0; q < K; ++q) rows[k * stride + off + q] = acc[q];
-    }
-    unsigned long long m = __ballot(ok && lng);
-    while (m) {
-        const int src = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        const int64_t kk = (int64_t)blockIdx.x * 256 + (threadIdx.x & ~63) + src;
-        const int ss = __shfl(s, src, 64), ee = __shfl(e, src, 64);
-        float acc[K];
-#pragma unroll
-        for (int q = 0; q < K; ++q) acc[q] = 0.0f;
-        for (int i = ss + lane; i < ee; i += 64) r.add(order[i], kk, acc);
-#pragma unroll
-        for (int q = 0; q < K; ++q) acc[q] = rs_wave_sum<K>(acc[q]);
-        if (lane == 0) {
-#pragma unroll
-            for (int q = 0; q < K; ++q) rows[kk * stride + off + q] = acc[q];
-        }
-    }
+    seg_sum<R::K>(nk, RsRows<R>{r, order, seg, stride, off, rows});
 }
 
 // rasterize backward: d (gu u + gv v) / d (x, y, w) of the three corners, u = E_0 / S, v = E_1 / S
@@ -590,25 +551,20 @@ using namespace ls;
 namespace {
 
 struct RsWs {          // the workspace's regions (sized from the shapes alone)
-    size_t depth, tiles, toff, bsum, keys, ord_b, sk, hist, offs, rbsum, rows, total;
+    size_t depth, tiles, toff, bsum, keys, sort, rows, total;
 };
 
 RsWs rs_layout(int64_t B, int64_t F, int64_t H, int64_t W, int64_t C) {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const int64_t N = B * H * W, nk = B * F;
-    const int64_t nb = div_up(N, rs_chunk(N));
     RsWs w;
     size_t o = 0;
     w.depth = o; o += al(8 * (size_t)N);
     w.tiles = o; o += al(4 * (size_t)(nk + 1));
     w.toff = o; o += al(4 * (size_t)(nk + 2));
-    w.bsum = o; o += al(4 * (size_t)(scan_blocks(std::max<int64_t>(nk, 256 * nb)) + 2));
+    w.bsum = o; o += al(4 * (size_t)scan_scratch_ints(nk));
     w.keys = o; o += al(4 * (size_t)N);
-    w.ord_b = o; o += al(4 * (size_t)N);
-    w.sk = o; o += al(4 * (size_t)N);
-    w.hist = o; o += al(4 * (size_t)(256 * nb + 16));
-    w.offs = o; o += al(4 * (size_t)(256 * nb + 16));
-    w.rbsum = o; o += al(4 * (size_t)(scan_blocks(256 * nb) + 2));
+    w.sort = o; o += al(sort_scratch_bytes(N, false));         // the pixel order sorts by gathered key bytes
     w.rows = o; o += al(4 * (size_t)nk * (size_t)std::max<int64_t>(9, 3 * C));
     w.total = o;
     return w;
@@ -674,16 +630,7 @@ extern "C" int ls_raster_pixel_order(const float* rast, int64_t B, int64_t F, in
     const int64_t N = B * H * W, nk = B * F;
     int* keys = (int*)(w + L.keys);
     hipLaunchKernelGGL(k_rs_keys, dim3(div_up(N, 256)), dim3(256), 0, st, rast, N, (int64_t)H * W, F, (int)B, keys);
-    const int passes = nk < 256 ? 1 : nk < 65536 ? 2 : nk < (1 << 24) ? 3 : 4;
-    const int* sorted = nullptr;
-    rc = radix_argsort(KeyInt{keys}, N, passes, order, (int*)(w + L.ord_b), (int*)(w + L.hist), (int*)(w + L.offs), (int*)(w + L.rbsum), st, &sorted);
-    if (rc) return rc;
-    if (sorted != order) LS_HIP(hipMemcpyAsync(order, sorted, 4 * (size_t)N, hipMemcpyDeviceToDevice, st));
-    int* sk = (int*)(w + L.sk);
-    hipLaunchKernelGGL(k_rs_sorted_keys, dim3(div_up(N, 256)), dim3(256), 0, st, (const int*)keys, (const int*)order, N, sk);
-    hipLaunchKernelGGL(k_rs_segments, dim3(div_up(nk + 1, 256)), dim3(256), 0, st, (const int*)sk, N, nk, seg);
-    LS_HIP(hipGetLastError());
-    return LS_OK;
+    return group_by_key<false>(keys, N, nk, order, seg, sort_scratch_carve(w + L.sort, N, false), st);
 }
 
 extern "C" int ls_raster_backward(const float* pos, int64_t B, int64_t V, const int32_t* tri, int64_t F, int H, int W, const float* grad_rast,
@@ -764,8 +711,7 @@ extern "C" int ls_raster_interpolate_backward(const float* attr, int64_t attr_ba
 
 extern "C" int ls_raster_adjacency_workspace_bytes(int64_t F, size_t* bytes) {
     LS_REQUIRE(bytes && F >= 0 && 3 * F < ((int64_t)1 << 31) - 1, LS_E_INVALID, "ls_raster_adjacency_workspace_bytes: bad argument");
-    const int64_t n = 3 * F, nb = div_up(std::max<int64_t>(n, 1), rs_chunk(n));
-    *bytes = 4 * (size_t)(4 * std::max<int64_t>(n, 1) + 2 * (256 * nb + 16) + scan_blocks(256 * nb) + 2);
+    *bytes = 4 * (size_t)(3 * F) + sort_scratch_bytes(3 * F, true);       // the half-edge ids, the sort's scratch behind them
     return LS_OK;
 }
 
@@ -779,14 +725,11 @@ extern "C" int ls_raster_adjacency(const int32_t* tri, int64_t F, int32_t* adj, 
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
-    const int64_t n = 3 * F, nb = div_up(n, rs_chunk(n));
-    int* w = (int*)ws;
-    int* ord_a = w; int* ord_b = w + n;
-    unsigned* ka = (unsigned*)(w + 2 * n); unsigned* kb = (unsigned*)(w + 3 * n);
-    int* hist = w + 4 * n; int* offs = hist + 256 * nb + 16; int* bsum = offs + 256 * nb + 16;
+    const int64_t n = 3 * F;
+    int* ord_a = (int*)ws;
     const int* sorted = nullptr;
     KeyEdge key{tri};
-    rc = radix_argsort_words(key, n, 2, ord_a, ord_b, ka, kb, hist, offs, bsum, st, &sorted);
+    rc = radix_argsort_words(key, n, 2, ord_a, sort_scratch_carve(ord_a + n, n, true), st, &sorted);
     if (rc) return rc;
     hipLaunchKernelGGL(k_rs_adjacency, dim3(div_up(n, 256)), dim3(256), 0, st, key, sorted, n, adj);
     LS_HIP(hipGetLastError());

@@ -434,10 +434,10 @@ struct RemeshHandle {
     double seconds[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
     // mesh (ping-pong), tables of a round, the input mesh and its BVH
     RmBuf pos, pos_b, faces, faces_b, cnt, vptr, cursor, vcorner, twin, bnd, flag, scan, key, mA, mB, remap, vkeep, vscan, fkeep, fscan,
-        bsum, small, pos0, faces0, code, ord_a, ord_b, hist, offs, tri, scode, left, right, parent, esc, rflag, box;
+        bsum, small, pos0, faces0, code, ord_a, sort, tri, scode, left, right, parent, esc, rflag, box;
     std::vector<RmBuf*> all() {
         return {&pos, &pos_b, &faces, &faces_b, &cnt, &vptr, &cursor, &vcorner, &twin, &bnd, &flag, &scan, &key, &mA, &mB, &remap, &vkeep,
-                &vscan, &fkeep, &fscan, &bsum, &small, &pos0, &faces0, &code, &ord_a, &ord_b, &hist, &offs, &tri, &scode, &left, &right,
+                &vscan, &fkeep, &fscan, &bsum, &small, &pos0, &faces0, &code, &ord_a, &sort, &tri, &scode, &left, &right,
                 &parent, &esc, &rflag, &box};
     }
 };
@@ -481,7 +481,7 @@ static int rm_topo(RemeshHandle* H) {
     RM_TRY(rm_ensure(H, H->vcorner, sizeof(int) * (n + 1)));
     RM_TRY(rm_ensure(H, H->twin, sizeof(int) * (n + 1)));
     RM_TRY(rm_ensure(H, H->bnd, sizeof(int) * (V + 1)));
-    RM_TRY(rm_ensure(H, H->bsum, sizeof(int) * (scan_blocks(std::max(n, V) + 1) + 1)));
+    RM_TRY(rm_ensure(H, H->bsum, sizeof(int) * scan_scratch_ints(std::max(n, V))));
     LS_HIP(hipMemsetAsync(H->cnt.p, 0, sizeof(int) * (V + 1), H->st));
     LS_HIP(hipMemsetAsync(H->cursor.p, 0, sizeof(int) * (V + 1), H->st));
     const int* fc = rp<int>(H->faces);
@@ -622,13 +622,9 @@ static int rm_relax(RemeshHandle* H) {
 
 static int rm_build_bvh(RemeshHandle* H) {
     const int T = H->F0, V0 = H->V0, N = 2 * T - 1;
-    const int nb = div_up(std::max(T, 1), rs_chunk(T));
     RM_TRY(rm_ensure(H, H->code, sizeof(int) * T));
     RM_TRY(rm_ensure(H, H->ord_a, sizeof(int) * T));
-    RM_TRY(rm_ensure(H, H->ord_b, sizeof(int) * T));
-    RM_TRY(rm_ensure(H, H->hist, sizeof(int) * (256 * (size_t)nb + 16)));
-    RM_TRY(rm_ensure(H, H->offs, sizeof(int) * (256 * (size_t)nb + 16)));
-    RM_TRY(rm_ensure(H, H->bsum, sizeof(int) * (scan_blocks(std::max<int64_t>(std::max(T, 256 * nb), 3 * (int64_t)H->F) + 1) + 1)));
+    RM_TRY(rm_ensure(H, H->sort, sort_scratch_bytes(T, false)));
     RM_TRY(rm_ensure(H, H->tri, sizeof(int) * T));
     RM_TRY(rm_ensure(H, H->scode, sizeof(unsigned) * T));
     RM_TRY(rm_ensure(H, H->left, sizeof(int) * T));
@@ -637,7 +633,7 @@ static int rm_build_bvh(RemeshHandle* H) {
     RM_TRY(rm_ensure(H, H->esc, sizeof(int) * N));
     RM_TRY(rm_ensure(H, H->rflag, sizeof(int) * T));
     RM_TRY(rm_ensure(H, H->box, sizeof(float) * 6 * (size_t)N));
-    const Lbvh a{rp<int>(H->code), rp<int>(H->ord_a), rp<int>(H->ord_b), rp<int>(H->hist), rp<int>(H->offs), rp<int>(H->bsum), rp<int>(H->tri),
+    const Lbvh a{rp<int>(H->code), rp<int>(H->ord_a), sort_scratch_carve(H->sort.p, T, false), rp<int>(H->tri),
                  rp<unsigned>(H->scode), rp<int>(H->left), rp<int>(H->right), rp<int>(H->parent), rp<int>(H->esc), rp<int>(H->rflag),
                  rp<float>(H->box), (unsigned*)(rp<int>(H->small) + 16)};
     float lo[3], hi[3];

@@ -27,8 +27,9 @@
 // more than 64 pixels in all is summed by its whole wave, lane-strided per position, then an xor butterfly: a fixed order either way,
 // so every gradient is bitwise reproducible. No entry point allocates or synchronises.
 #include "common.h"
-#include "radix.h"
+#include "groupby.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace ls {
 
@@ -238,23 +239,6 @@ __global__ __launch_bounds__(256) void k_tx_keys(const float* __restrict__ uv, T
     keys[pix] = ok ? (int)(((int64_t)bt * (s.Ht + 1) + (j + 1)) * (s.Wt + 1) + (i + 1)) : (int)tx_nkeys(s);
 }
 
-__global__ __launch_bounds__(256) void k_tx_sorted_keys(const int* __restrict__ keys, const int* __restrict__ order, int64_t N, int* __restrict__ sk) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < N) sk[i] = keys[order[i]];
-}
-
-// seg[k] = first sorted position whose key is >= k, k in [0, nk]
-__global__ __launch_bounds__(256) void k_tx_segments(const int* __restrict__ sk, int64_t N, int64_t nk, int* __restrict__ seg) {
-    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k > nk) return;
-    int64_t lo = 0, hi = N;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (sk[mid] < k) lo = mid + 1; else hi = mid;
-    }
-    seg[k] = (int)lo;
-}
-
 // ---- backward to tex: one thread per texel ------------------------------------------------------------------------------------------------
 // slot q < 4 of the base positions along one axis whose tap falls on texel i of n: (base, tap); false = the slot is empty
 __device__ __forceinline__ bool tx_slot(int q, int i, int n, int filter, int boundary, int& base, int& tap) {
@@ -305,47 +289,33 @@ __device__ __forceinline__ int64_t tx_texel_walk(const TxTexel& t, const TxShape
     return total;
 }
 
+// the gradient of one texel per key, summed by seg_sum of groupby.h: a texel's items are the pixels of up to 16 base positions
 template <int CT>
-__global__ __launch_bounds__(256) void k_tx_backward_tex(const float* __restrict__ uv, const float* __restrict__ g, const int* __restrict__ order,
-                                                         const int* __restrict__ seg, TxShape s, int c0, float* __restrict__ gtex) {
-    const int64_t T = (int64_t)s.Bt * s.Ht * s.Wt;
-    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int lane = threadIdx.x & 63;
-    const bool ok = k < T;
-    auto texel = [&](int64_t kk) {
+struct TxTexelSum {
+    const float* __restrict__ uv; const float* __restrict__ g; const int* __restrict__ order; const int* __restrict__ seg;
+    TxShape s; int c0; float* __restrict__ gtex;
+    __device__ __forceinline__ TxTexel texel(int64_t k) const {
         TxTexel t;
-        const int64_t row = kk / s.Wt;
-        t.i = (int)(kk - row * s.Wt);
+        const int64_t row = k / s.Wt;
+        t.i = (int)(k - row * s.Wt);
         t.bt = (int)(row / s.Ht);
         t.j = (int)(row - (int64_t)t.bt * s.Ht);
         return t;
-    };
-    float acc[CT];
-#pragma unroll
-    for (int c = 0; c < CT; ++c) acc[c] = 0.0f;
-    int64_t count = 0;
-    if (ok) count = tx_texel_walk<CT, true>(texel(k), s, uv, g, order, seg, c0, 0, 1, acc);
-    const bool lng = count > 64;
-    if (ok && !lng) {
-        tx_texel_walk<CT, false>(texel(k), s, uv, g, order, seg, c0, 0, 1, acc);
-        tx_store<CT>(gtex + (size_t)k * s.C + c0, s.vec4 != 0, acc);
     }
-    unsigned long long m = __ballot(ok && lng);
-    while (m) {                                       // (wave-uniform)
-        const int src = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        const int64_t kk = (int64_t)blockIdx.x * 256 + (threadIdx.x & ~63) + src;
-        float part[CT];
-#pragma unroll
-        for (int c = 0; c < CT; ++c) part[c] = 0.0f;
-        tx_texel_walk<CT, false>(texel(kk), s, uv, g, order, seg, c0, lane, 64, part);
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-#pragma unroll
-            for (int x = 32; x >= 1; x >>= 1) part[c] += __shfl_xor(part[c], x, 64);
-        }
-        if (lane == 0) tx_store<CT>(gtex + (size_t)kk * s.C + c0, s.vec4 != 0, part);
+    __device__ __forceinline__ int64_t count(int64_t k) const {
+        float none[CT];
+        return tx_texel_walk<CT, true>(texel(k), s, uv, g, order, seg, c0, 0, 1, none);
     }
+    __device__ __forceinline__ void walk(int64_t k, int start, int step, float (&acc)[CT]) const {
+        tx_texel_walk<CT, false>(texel(k), s, uv, g, order, seg, c0, start, step, acc);
+    }
+    __device__ __forceinline__ void store(int64_t k, const float (&acc)[CT]) const { tx_store<CT>(gtex + (size_t)k * s.C + c0, s.vec4 != 0, acc); }
+};
+
+template <int CT>
+__global__ __launch_bounds__(256) void k_tx_backward_tex(const float* __restrict__ uv, const float* __restrict__ g, const int* __restrict__ order,
+                                                         const int* __restrict__ seg, TxShape s, int c0, float* __restrict__ gtex) {
+    seg_sum<CT>((int64_t)s.Bt * s.Ht * s.Wt, TxTexelSum<CT>{uv, g, order, seg, s, c0, gtex});
 }
 
 }  // namespace ls
@@ -355,21 +325,15 @@ using namespace ls;
 namespace {
 
 struct TxWs {
-    size_t keys, ord_b, keys_a, keys_b, hist, offs, bsum, total;
+    size_t keys, sort, total;
 };
 
 TxWs tx_layout(int64_t N) {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const int64_t nb = div_up(N, rs_chunk(N));
     TxWs w;
     size_t o = 0;
     w.keys = o; o += al(4 * (size_t)N);
-    w.ord_b = o; o += al(4 * (size_t)N);
-    w.keys_a = o; o += al(4 * (size_t)N);
-    w.keys_b = o; o += al(4 * (size_t)N);
-    w.hist = o; o += al(4 * (size_t)(256 * nb + 16));
-    w.offs = o; o += al(4 * (size_t)(256 * nb + 16));
-    w.bsum = o; o += al(4 * (size_t)(scan_blocks(256 * nb) + 2));
+    w.sort = o; o += al(sort_scratch_bytes(N, true));          // the pixel order sorts with carried keys
     w.total = o;
     return w;
 }
@@ -388,11 +352,16 @@ int tx_check(int64_t Bt, int Ht, int Wt, int C, int64_t B, int H, int W, int fil
     return LS_OK;
 }
 
-// the channels in groups of at most four: one launch per group
+// the channels in groups of at most four: one launch per group, launch(c0, std::integral_constant<int, CT>) for its CT channels from c0
 template <class Launch>
 void tx_groups(int C, Launch launch) {
-    if (C <= 4) { launch(0, C); return; }
-    for (int c0 = 0; c0 < C; c0 += 4) launch(c0, std::min(4, C - c0));
+    for (int c0 = 0; c0 < C; c0 += 4)
+        switch (std::min(4, C - c0)) {
+        case 1: launch(c0, std::integral_constant<int, 1>()); break;
+        case 2: launch(c0, std::integral_constant<int, 2>()); break;
+        case 3: launch(c0, std::integral_constant<int, 3>()); break;
+        default: launch(c0, std::integral_constant<int, 4>()); break;
+        }
 }
 
 bool tx_aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
@@ -418,14 +387,7 @@ extern "C" int ls_texture_forward(const float* tex, int64_t Bt, int Ht, int Wt, 
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(div_up(s.N, 256)), block(256);
-    tx_groups(C, [&](int c0, int ct) {
-        switch (ct) {
-        case 1: hipLaunchKernelGGL(k_tx_forward<1>, grid, block, 0, st, tex, uv, s, c0, out); break;
-        case 2: hipLaunchKernelGGL(k_tx_forward<2>, grid, block, 0, st, tex, uv, s, c0, out); break;
-        case 3: hipLaunchKernelGGL(k_tx_forward<3>, grid, block, 0, st, tex, uv, s, c0, out); break;
-        default: hipLaunchKernelGGL(k_tx_forward<4>, grid, block, 0, st, tex, uv, s, c0, out); break;
-        }
-    });
+    tx_groups(C, [&](int c0, auto ct) { hipLaunchKernelGGL(k_tx_forward<decltype(ct)::value>, grid, block, 0, st, tex, uv, s, c0, out); });
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
@@ -446,17 +408,7 @@ extern "C" int ls_texture_order(const float* uv, int64_t B, int H, int W, int64_
     const int64_t N = s.N, nk = (int64_t)s.Bt * (s.Ht + 1) * (s.Wt + 1);
     int* keys = (int*)(w + L.keys);
     hipLaunchKernelGGL(k_tx_keys, dim3(div_up(N, 256)), dim3(256), 0, st, uv, s, keys);
-    const int passes = nk < 256 ? 1 : nk < 65536 ? 2 : nk < (1 << 24) ? 3 : 4;         // the largest key is nk itself
-    const int* sorted = nullptr;
-    rc = radix_argsort_words(KeyInt{keys}, N, 1, order, (int*)(w + L.ord_b), (unsigned*)(w + L.keys_a), (unsigned*)(w + L.keys_b), (int*)(w + L.hist),
-                             (int*)(w + L.offs), (int*)(w + L.bsum), st, &sorted, passes);
-    if (rc) return rc;
-    if (sorted != order) LS_HIP(hipMemcpyAsync(order, sorted, 4 * (size_t)N, hipMemcpyDeviceToDevice, st));
-    int* sk = (int*)(w + L.keys_a);
-    hipLaunchKernelGGL(k_tx_sorted_keys, dim3(div_up(N, 256)), dim3(256), 0, st, (const int*)keys, (const int*)order, N, sk);
-    hipLaunchKernelGGL(k_tx_segments, dim3(div_up(nk + 1, 256)), dim3(256), 0, st, (const int*)sk, N, nk, seg);
-    LS_HIP(hipGetLastError());
-    return LS_OK;
+    return group_by_key<true>(keys, N, nk, order, seg, sort_scratch_carve(w + L.sort, N, true), st);
 }
 
 extern "C" int ls_texture_backward(const float* tex, int64_t Bt, int Ht, int Wt, int C, const float* uv, int64_t B, int H, int W, int filter,
@@ -473,25 +425,11 @@ extern "C" int ls_texture_backward(const float* tex, int64_t Bt, int Ht, int Wt,
     hipStream_t st = (hipStream_t)stream;
     if (grad_uv) {
         const dim3 grid(div_up(s.N, 256)), block(256);
-        tx_groups(C, [&](int c0, int ct) {
-            switch (ct) {
-            case 1: hipLaunchKernelGGL(k_tx_backward_uv<1>, grid, block, 0, st, tex, uv, grad_out, s, c0, grad_uv); break;
-            case 2: hipLaunchKernelGGL(k_tx_backward_uv<2>, grid, block, 0, st, tex, uv, grad_out, s, c0, grad_uv); break;
-            case 3: hipLaunchKernelGGL(k_tx_backward_uv<3>, grid, block, 0, st, tex, uv, grad_out, s, c0, grad_uv); break;
-            default: hipLaunchKernelGGL(k_tx_backward_uv<4>, grid, block, 0, st, tex, uv, grad_out, s, c0, grad_uv); break;
-            }
-        });
+        tx_groups(C, [&](int c0, auto ct) { hipLaunchKernelGGL(k_tx_backward_uv<decltype(ct)::value>, grid, block, 0, st, tex, uv, grad_out, s, c0, grad_uv); });
     }
     if (grad_tex) {
         const dim3 grid(div_up((int64_t)s.Bt * s.Ht * s.Wt, 256)), block(256);
-        tx_groups(C, [&](int c0, int ct) {
-            switch (ct) {
-            case 1: hipLaunchKernelGGL(k_tx_backward_tex<1>, grid, block, 0, st, uv, grad_out, order, seg, s, c0, grad_tex); break;
-            case 2: hipLaunchKernelGGL(k_tx_backward_tex<2>, grid, block, 0, st, uv, grad_out, order, seg, s, c0, grad_tex); break;
-            case 3: hipLaunchKernelGGL(k_tx_backward_tex<3>, grid, block, 0, st, uv, grad_out, order, seg, s, c0, grad_tex); break;
-            default: hipLaunchKernelGGL(k_tx_backward_tex<4>, grid, block, 0, st, uv, grad_out, order, seg, s, c0, grad_tex); break;
-            }
-        });
+        tx_groups(C, [&](int c0, auto ct) { hipLaunchKernelGGL(k_tx_backward_tex<decltype(ct)::value>, grid, block, 0, st, uv, grad_out, order, seg, s, c0, grad_tex); });
     }
     LS_HIP(hipGetLastError());
     return LS_OK;
