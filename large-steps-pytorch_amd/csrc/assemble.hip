@@ -13,6 +13,7 @@
 // The fp32 operation order of the cotangents is the one of oracle/laplacian.py (explicit fma chain
 // in the edge norm, everything else unfused): this file is compiled with -ffp-contract=off.
 #include "common.h"
+#include "meshface.h"
 #include "radix.h"
 #include <algorithm>
 
@@ -343,8 +344,8 @@ __global__ __launch_bounds__(BLOCK) void k_count(const IdxT* __restrict__ faces,
 
 // fp32 cotangents of one face in the reference's operation order (geometry.py:20-41, oracle/laplacian.py)
 __device__ __forceinline__ float edge_norm(float ax, float ay, float az, float bx, float by, float bz) {
-    const float x = ax - bx, y = ay - by, z = az - bz;
-    return sqrtf(fmaf(z, z, fmaf(y, y, x * x)));
+    const float a[3] = {ax, ay, az}, b[3] = {bx, by, bz};
+    return edge_norm(a, b);
 }
 
 __device__ __forceinline__ void face_cot(const float* __restrict__ verts, int64_t i0, int64_t i1, int64_t i2,

@@ -15,6 +15,7 @@
 // bit order is the value order, so the result does not depend on the schedule.
 #include "common.h"
 #include "lbvh.h"
+#include "meshface.h"
 #include <algorithm>
 #include <cmath>
 #include <new>
@@ -24,15 +25,6 @@ namespace ls {
 
 typedef unsigned long long u64;
 constexpr double MD_SLACK = 0x1p-40, MD_SHRINK = 1.0 - 0x1p-40;
-
-template <typename IDX>
-__global__ __launch_bounds__(BLOCK) void k_md_faces_in(const IDX* __restrict__ in, int64_t n, int64_t V, int* __restrict__ out, int* __restrict__ bad) {
-    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const IDX x = in[i];
-    if (x < 0 || (int64_t)x >= V) { atomicOr(bad, 1); out[i] = 0; }
-    else out[i] = (int)x;
-}
 
 __device__ __forceinline__ double md_d2(const double p[3], const double r[3]) {
     const double dx = p[0] - r[0], dy = p[1] - r[1], dz = p[2] - r[2];
@@ -176,11 +168,8 @@ extern "C" int ls_mesh_distance_create(const float* verts, int64_t V, const void
     if (hipMemsetAsync(H->small, 0, sizeof(int) * 16, st) != hipSuccess ||
         hipMemcpyAsync(H->pos, verts, sizeof(float) * 3 * V, hipMemcpyDeviceToDevice, st) != hipSuccess)
         return fail(hip_fail(hipGetLastError(), "ls_mesh_distance_create copies", __FILE__, __LINE__));
-    const dim3 grid(div_up(n, BLOCK)), block(BLOCK);
-    if (idx_bytes == 8) hipLaunchKernelGGL(k_md_faces_in<int64_t>, grid, block, 0, st, (const int64_t*)faces, (int64_t)n, V, H->faces, H->small);
-    else hipLaunchKernelGGL(k_md_faces_in<int32_t>, grid, block, 0, st, (const int32_t*)faces, (int64_t)n, V, H->faces, H->small);
     int bad = 0;
-    if (hipMemcpyAsync(&bad, H->small, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    if (!faces_in(faces, idx_bytes, n, V, H->faces, H->small, st, &bad))
         return fail(hip_fail(hipGetLastError(), "ls_mesh_distance_create", __FILE__, __LINE__));
     if (bad) { set_error("mesh distance: a face index is outside [0, %lld)", (long long)V); return fail(LS_E_INDEX); }
     float lo[3], hi[3];

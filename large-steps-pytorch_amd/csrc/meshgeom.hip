@@ -10,7 +10,7 @@
 //                                corner slot j, then .sum(dim=1). An unreferenced vertex gets 0, a face with a zero-length
 //                                edge NaN cells.
 // The forward cells follow the reference's fp32 operation order (the library is built with -ffp-contract=off; the edge length
-// is torch's CPU norm, sqrt(fma(z, z, fma(y, y, x * x))), as edge_norm in assemble.hip), and the per-vertex sum follows its
+// is torch's CPU norm, edge_norm of meshface.h), and the per-vertex sum follows its
 // reduction: s_j = the vertex's slot-j corners in ascending face id, mass = (s0 + s1) + s2.
 //
 // Launch structure (bytes at the 1M-vertex sphere, F = 2V, 4-byte indices):
@@ -20,35 +20,14 @@
 //                        + faces 12 F + verts 12 V + mass 4 V = 20 V + 24 F (~68 MB); the 3 corner loads of a face re-read
 //                        faces and verts that neighbouring threads share (L2).
 //   massmatrix backward  per face: the 9 coordinates' gradient (reverse pass of the reference's torch graph, op by op) written
-//                        at the corners' ranks, then a per-vertex gather in rank order (2 launches, no atomics).
+//                        at the corners' ranks, then gather_corners of meshface.h (2 launches).
 //   average forward      per face l0 + l1 + l2 in fp32, fp64 partial sums per workgroup (grid fixed by F), one workgroup sums
 //                        the partials in a fixed order and applies / F / 3 in fp32: bitwise reproducible, no host sync.
 //   average backward     g read from device memory: each edge adds (g / 3 / F) (p_a - p_b) / |p_a - p_b| to its ends (0 for a
 //                        zero-length edge), written per corner and gathered as above.
-#include "common.h"
-#include <algorithm>
+#include "meshface.h"
 
 namespace ls {
-
-constexpr int MG_MAXG = 1024;       // partial sums of the average edge length (the reduction grid is capped to this)
-
-template <typename IDX>
-__device__ __forceinline__ void mg_load_face(const IDX* __restrict__ faces, int64_t f, const float* __restrict__ verts, int (&id)[3],
-                                             float (&p)[3][3]) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) id[c] = (int)faces[f * 3 + c];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) p[c][q] = verts[(size_t)id[c] * 3 + q];
-    }
-}
-
-// torch's CPU norm(dim=1) of a 3-vector a - b
-__device__ __forceinline__ float mg_edge_norm(const float (&a)[3], const float (&b)[3]) {
-    const float x = a[0] - b[0], y = a[1] - b[1], z = a[2] - b[2];
-    return sqrtf(fmaf(z, z, fmaf(y, y, x * x)));
-}
 
 // every intermediate of one face in the reference's fp32 order; l[k] = |p[k1] - p[k2]| (k1 = k + 1, k2 = k + 2 mod 3)
 struct VoronoiFace {
@@ -57,9 +36,9 @@ struct VoronoiFace {
 };
 __device__ __forceinline__ VoronoiFace voronoi_face(const float (&p)[3][3]) {
     VoronoiFace t;
-    t.l[0] = mg_edge_norm(p[1], p[2]);
-    t.l[1] = mg_edge_norm(p[2], p[0]);
-    t.l[2] = mg_edge_norm(p[0], p[1]);
+    t.l[0] = edge_norm(p[1], p[2]);
+    t.l[1] = edge_norm(p[2], p[0]);
+    t.l[2] = edge_norm(p[0], p[1]);
     const float sq[3] = {t.l[0] * t.l[0], t.l[1] * t.l[1], t.l[2] * t.l[2]};
     float braw[3];
 #pragma unroll
@@ -93,13 +72,6 @@ __device__ __forceinline__ VoronoiFace voronoi_face(const float (&p)[3][3]) {
     return t;
 }
 
-// a 3-vector at a 4-byte aligned address as one 12-byte access
-typedef float f3_mg __attribute__((ext_vector_type(3), aligned(4)));
-__device__ __forceinline__ void mg_ld3(const float* __restrict__ base, size_t row, float (&v)[3]) {
-    const f3_mg t = *reinterpret_cast<const f3_mg*>(base + row * 3);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z;
-}
-
 // mass[v] = (s0 + s1) + s2, s_j = the cells of v's slot-j corners in rank order (= ascending face id); VG corners are requested
 // together (clamped addresses), then summed in rank order
 template <typename IDX, int VG>
@@ -123,7 +95,7 @@ __global__ __launch_bounds__(BLOCK) void k_voronoi_mass_gather(const float* __re
 #pragma unroll
         for (int t = 0; t < VG; ++t) {
 #pragma unroll
-            for (int c = 0; c < 3; ++c) mg_ld3(verts, (size_t)id[t][c], p[t][c]);
+            for (int c = 0; c < 3; ++c) ld3(verts, (size_t)id[t][c], p[t][c]);
         }
 #pragma unroll
         for (int t = 0; t < VG; ++t) {
@@ -212,7 +184,7 @@ __global__ __launch_bounds__(BLOCK) void k_voronoi_mass_bwd(const float* __restr
     if (f >= F) return;
     int id[3];
     float p[3][3], gv[3][3];
-    mg_load_face(faces, f, verts, id, p);
+    load_face(faces, f, verts, id, p);
     const float gc[3] = {g_mass[id[0]], g_mass[id[1]], g_mass[id[2]]};
     voronoi_face_bwd(p, gc, gv);
 #pragma unroll
@@ -232,8 +204,8 @@ __global__ __launch_bounds__(BLOCK) void k_edge_length_partials(const float* __r
     for (int64_t f = (int64_t)blockIdx.x * BLOCK + threadIdx.x; f < F; f += (int64_t)gridDim.x * BLOCK) {
         int id[3];
         float p[3][3];
-        mg_load_face(faces, f, verts, id, p);
-        acc[0] += (double)((mg_edge_norm(p[1], p[2]) + mg_edge_norm(p[0], p[2])) + mg_edge_norm(p[0], p[1]));
+        load_face(faces, f, verts, id, p);
+        acc[0] += (double)((edge_norm(p[1], p[2]) + edge_norm(p[0], p[2])) + edge_norm(p[0], p[1]));
     }
     block_sum<1>(acc, smem);
     if (threadIdx.x == 0) part[blockIdx.x] = acc[0];
@@ -266,7 +238,7 @@ __global__ __launch_bounds__(BLOCK) void k_edge_length_bwd(const float* __restri
     const float c = (g_out[0] / 3.0f) / (float)F;
     int id[3];
     float p[3][3], gv[3][3];
-    mg_load_face(faces, f, verts, id, p);
+    load_face(faces, f, verts, id, p);
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
 #pragma unroll
@@ -275,7 +247,7 @@ __global__ __launch_bounds__(BLOCK) void k_edge_length_bwd(const float* __restri
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const int k1 = (k + 1) % 3, k2 = (k + 2) % 3;
-        const float l = mg_edge_norm(p[k1], p[k2]);
+        const float l = edge_norm(p[k1], p[k2]);
         const float w = l == 0.0f ? 0.0f : c / l;
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
@@ -292,55 +264,27 @@ __global__ __launch_bounds__(BLOCK) void k_edge_length_bwd(const float* __restri
     }
 }
 
-// dst[v] = sum of the 3-vectors at v's ranks [vptr[v], vptr[v + 1]), in rank order
-__global__ __launch_bounds__(BLOCK) void k_mg_gather_corners(const int* __restrict__ vptr, const float* __restrict__ corner, int64_t V,
-                                                             float* __restrict__ dst) {
-    const int64_t v = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (v >= V) return;
-    const int e0 = vptr[v], e1 = vptr[v + 1];
-    float x = 0.0f, y = 0.0f, z = 0.0f;
-    for (int e = e0; e < e1; ++e) {
-        float c[3];
-        mg_ld3(corner, (size_t)e, c);
-        x += c[0]; y += c[1]; z += c[2];
-    }
-    dst[v * 3] = x; dst[v * 3 + 1] = y; dst[v * 3 + 2] = z;
-}
-
-static int mg_reduce_grid(int64_t F) { return (int)std::min<int64_t>(MG_MAXG, std::max<int64_t>(1, div_up(F, BLOCK))); }
-
 }  // namespace ls
 
 using namespace ls;
 
-#define LS_MG_IDX(bytes, ...)                                                                  \
-    do {                                                                                       \
-        if ((bytes) == 8) { typedef int64_t IDX; __VA_ARGS__; } else { typedef int32_t IDX; __VA_ARGS__; } \
-    } while (0)
-
-static int check_meshgeom_args(const float* verts, const void* faces, int idx_bytes, int64_t F, int64_t V, const char* who) {
-    LS_REQUIRE(verts && (faces || F == 0) && (idx_bytes == 4 || idx_bytes == 8) && F >= 0 && V > 0 && V < INT32_MAX && 3 * F < INT32_MAX,
-               LS_E_INVALID, "%s: bad argument (faces must be int32 or int64, V and 3 F < 2^31)", who);
-    return LS_OK;
-}
-
 extern "C" int ls_meshgeom_workspace_bytes(int64_t F, int64_t V, size_t* h_bytes) {
     LS_REQUIRE(h_bytes && F >= 0 && V >= 0, LS_E_INVALID, "ls_meshgeom_workspace_bytes: bad argument");
     // the partial sums of the average edge length | one 3-vector per corner (backward passes)
-    *h_bytes = sizeof(double) * MG_MAXG + sizeof(float) * 9 * (size_t)std::max<int64_t>(F, 1);
+    *h_bytes = sizeof(double) * MESH_MAXG + sizeof(float) * 9 * (size_t)std::max<int64_t>(F, 1);
     return LS_OK;
 }
 
 extern "C" int ls_massmatrix_voronoi(const float* verts, const void* faces, int idx_bytes, int64_t F, int64_t V, const int32_t* vptr,
                                      const int32_t* order, float* mass, int device, void* stream) {
-    int rc = check_meshgeom_args(verts, faces, idx_bytes, F, V, "ls_massmatrix_voronoi");
+    int rc = check_mesh_args(verts, faces, idx_bytes, F, V, "ls_massmatrix_voronoi");
     if (rc) return rc;
     LS_REQUIRE(mass && vptr && (order || F == 0), LS_E_INVALID, "ls_massmatrix_voronoi: null argument");
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
-    LS_MG_IDX(idx_bytes, hipLaunchKernelGGL((k_voronoi_mass_gather<IDX, 4>), dim3(div_up(V, BLOCK)), dim3(BLOCK), 0, st, verts, (const IDX*)faces, V,
-                                            vptr, order, mass));
+    LS_IDX(idx_bytes, hipLaunchKernelGGL((k_voronoi_mass_gather<IDX, 4>), dim3(div_up(V, BLOCK)), dim3(BLOCK), 0, st, verts, (const IDX*)faces, V,
+                                         vptr, order, mass));
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
@@ -348,39 +292,35 @@ extern "C" int ls_massmatrix_voronoi(const float* verts, const void* faces, int 
 extern "C" int ls_massmatrix_voronoi_backward(const float* verts, const void* faces, int idx_bytes, int64_t F, int64_t V, const int32_t* vptr,
                                               const int32_t* cpos, const float* g_mass, float* grad_verts, void* workspace, size_t ws_bytes,
                                               int device, void* stream) {
-    int rc = check_meshgeom_args(verts, faces, idx_bytes, F, V, "ls_massmatrix_voronoi_backward");
+    int rc = check_mesh_args(verts, faces, idx_bytes, F, V, "ls_massmatrix_voronoi_backward");
     if (rc) return rc;
-    size_t need = 0;
-    ls_meshgeom_workspace_bytes(F, V, &need);
     LS_REQUIRE(g_mass && grad_verts && vptr && workspace && (cpos || F == 0), LS_E_INVALID, "ls_massmatrix_voronoi_backward: null argument");
-    LS_REQUIRE(ws_bytes >= need, LS_E_WORKSPACE, "ls_massmatrix_voronoi_backward: workspace too small (%zu < %zu bytes)", ws_bytes, need);
+    if ((rc = require_workspace("ls_massmatrix_voronoi_backward", ls_meshgeom_workspace_bytes, F, V, ws_bytes))) return rc;
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
-    float* corner = (float*)((double*)workspace + MG_MAXG);
+    float* corner = (float*)((double*)workspace + MESH_MAXG);
     if (F > 0)
-        LS_MG_IDX(idx_bytes, hipLaunchKernelGGL(k_voronoi_mass_bwd<IDX>, dim3(div_up(F, BLOCK)), dim3(BLOCK), 0, st, verts, (const IDX*)faces, F,
-                                                g_mass, cpos, corner));
-    hipLaunchKernelGGL(k_mg_gather_corners, dim3(div_up(V, BLOCK)), dim3(BLOCK), 0, st, vptr, (const float*)corner, V, grad_verts);
+        LS_IDX(idx_bytes, hipLaunchKernelGGL(k_voronoi_mass_bwd<IDX>, dim3(div_up(F, BLOCK)), dim3(BLOCK), 0, st, verts, (const IDX*)faces, F,
+                                             g_mass, cpos, corner));
+    gather_corners(vptr, corner, V, grad_verts, nullptr, st);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
 
 extern "C" int ls_average_edge_length(const float* verts, const void* faces, int idx_bytes, int64_t F, int64_t V, float* out, void* workspace,
                                       size_t ws_bytes, int device, void* stream) {
-    int rc = check_meshgeom_args(verts, faces, idx_bytes, F, V, "ls_average_edge_length");
+    int rc = check_mesh_args(verts, faces, idx_bytes, F, V, "ls_average_edge_length");
     if (rc) return rc;
-    size_t need = 0;
-    ls_meshgeom_workspace_bytes(F, V, &need);
     LS_REQUIRE(out && workspace, LS_E_INVALID, "ls_average_edge_length: null argument");
-    LS_REQUIRE(ws_bytes >= need, LS_E_WORKSPACE, "ls_average_edge_length: workspace too small (%zu < %zu bytes)", ws_bytes, need);
+    if ((rc = require_workspace("ls_average_edge_length", ls_meshgeom_workspace_bytes, F, V, ws_bytes))) return rc;
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
     double* part = (double*)workspace;
-    const int G = F > 0 ? mg_reduce_grid(F) : 0;
+    const int G = F > 0 ? reduce_grid(F) : 0;
     if (G > 0)
-        LS_MG_IDX(idx_bytes, hipLaunchKernelGGL(k_edge_length_partials<IDX>, dim3(G), dim3(BLOCK), 0, st, verts, (const IDX*)faces, F, part));
+        LS_IDX(idx_bytes, hipLaunchKernelGGL(k_edge_length_partials<IDX>, dim3(G), dim3(BLOCK), 0, st, verts, (const IDX*)faces, F, part));
     hipLaunchKernelGGL(k_edge_length_finish, dim3(1), dim3(MG_FIN), 0, st, (const double*)part, G, F, out);
     LS_HIP(hipGetLastError());
     return LS_OK;
@@ -389,20 +329,18 @@ extern "C" int ls_average_edge_length(const float* verts, const void* faces, int
 extern "C" int ls_average_edge_length_backward(const float* verts, const void* faces, int idx_bytes, int64_t F, int64_t V, const int32_t* vptr,
                                                const int32_t* cpos, const float* g_out, float* grad_verts, void* workspace, size_t ws_bytes,
                                                int device, void* stream) {
-    int rc = check_meshgeom_args(verts, faces, idx_bytes, F, V, "ls_average_edge_length_backward");
+    int rc = check_mesh_args(verts, faces, idx_bytes, F, V, "ls_average_edge_length_backward");
     if (rc) return rc;
-    size_t need = 0;
-    ls_meshgeom_workspace_bytes(F, V, &need);
     LS_REQUIRE(g_out && grad_verts && vptr && workspace && (cpos || F == 0), LS_E_INVALID, "ls_average_edge_length_backward: null argument");
-    LS_REQUIRE(ws_bytes >= need, LS_E_WORKSPACE, "ls_average_edge_length_backward: workspace too small (%zu < %zu bytes)", ws_bytes, need);
+    if ((rc = require_workspace("ls_average_edge_length_backward", ls_meshgeom_workspace_bytes, F, V, ws_bytes))) return rc;
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
-    float* corner = (float*)((double*)workspace + MG_MAXG);
+    float* corner = (float*)((double*)workspace + MESH_MAXG);
     if (F > 0)
-        LS_MG_IDX(idx_bytes, hipLaunchKernelGGL(k_edge_length_bwd<IDX>, dim3(div_up(F, BLOCK)), dim3(BLOCK), 0, st, verts, (const IDX*)faces, F,
-                                                g_out, cpos, corner));
-    hipLaunchKernelGGL(k_mg_gather_corners, dim3(div_up(V, BLOCK)), dim3(BLOCK), 0, st, vptr, (const float*)corner, V, grad_verts);
+        LS_IDX(idx_bytes, hipLaunchKernelGGL(k_edge_length_bwd<IDX>, dim3(div_up(F, BLOCK)), dim3(BLOCK), 0, st, verts, (const IDX*)faces, F,
+                                             g_out, cpos, corner));
+    gather_corners(vptr, corner, V, grad_verts, nullptr, st);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }

@@ -12,32 +12,11 @@
 //                                    normals[f_i] += n_f * angle; result normalised per vertex, (V, 3); an unreferenced
 //                                    vertex gives NaN (0 / 0), as in the reference.
 // Three distinct global norms exist: ||E01||, ||E02||, ||E12|| (E_ab = all faces' edges v_b - v_a), each used by two corners.
-// No atomics: per-face kernels write one 3-vector per CORNER (coalesced), a per-vertex kernel sums the corners of a vertex
-// through a vertex-major corner ranking built once per face tensor (measured at 2M faces: 18M fp32 atomics took 0.44 ms per
-// scatter, the two-pass form ~0.05 ms) -- and the result is bitwise reproducible, unlike the reference's index_add_.
-#include "common.h"
-#include <algorithm>
+// No atomics: the per-vertex sums go through the corner ranking of meshface.h (measured at 2M faces: 18M fp32 atomics took 0.44 ms
+// per scatter, the two-pass form ~0.05 ms) -- and the result is bitwise reproducible, unlike the reference's index_add_.
+#include "meshface.h"
 
 namespace ls {
-
-constexpr int NRM_MAXG = 1024;      // partial sums per reduction (grid of the reducing kernels is capped to this)
-
-template <typename IDX>
-__device__ __forceinline__ void load_face(const IDX* __restrict__ faces, int64_t f, const float* __restrict__ verts,
-                                          int (&id)[3], float (&p)[3][3]) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        id[c] = (int)faces[f * 3 + c];
-#pragma unroll
-        for (int q = 0; q < 3; ++q) p[c][q] = verts[(size_t)id[c] * 3 + q];
-    }
-}
-
-__device__ __forceinline__ void cross3(const float (&a)[3], const float (&b)[3], float (&c)[3]) {
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
-}
 
 template <typename IDX>
 __global__ __launch_bounds__(BLOCK) void k_face_normals(const float* __restrict__ verts, const IDX* __restrict__ faces, int64_t F,
@@ -85,45 +64,6 @@ __global__ __launch_bounds__(BLOCK) void k_face_normals_bwd(const float* __restr
     }
 }
 
-// dst[v] = sum of the corner vectors of vertex v: the per-face kernels store the vector of corner 3 f + i at slot
-// cpos[3 f + i], the corner's rank in vertex-major order, so a vertex's vectors are the contiguous slots
-// [vptr[v], vptr[v + 1]) -- consecutive threads read consecutive memory. normalize: also writes the unit vector to `out`.
-__global__ __launch_bounds__(BLOCK) void k_gather_corners(const int* __restrict__ vptr, const float* __restrict__ corner, int64_t V,
-                                                          float* __restrict__ dst, float* __restrict__ out) {
-    const int64_t v = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (v >= V) return;
-    const int e0 = vptr[v], e1 = vptr[v + 1];
-    // the first GC corners (a vertex of a triangle mesh has ~6) are requested together, from clamped addresses (no branch between
-    // the loads); the sum runs over them in rank order as before
-    constexpr int GC = 8;
-    float c[GC][3];
-    const int last = max(e1 - 1, e0);            // e1 == e0 (unreferenced vertex): a valid address, the value is not used
-#pragma unroll
-    for (int t = 0; t < GC; ++t) {
-        const size_t e = (size_t)min(e0 + t, last);
-#pragma unroll
-        for (int q = 0; q < 3; ++q) c[t][q] = corner[e * 3 + q];
-    }
-    float x = 0.0f, y = 0.0f, z = 0.0f;
-#pragma unroll
-    for (int t = 0; t < GC; ++t) {
-        if (e0 + t < e1) { x += c[t][0]; y += c[t][1]; z += c[t][2]; }
-    }
-    for (int e = e0 + GC; e < e1; ++e) {
-        x += corner[(size_t)e * 3]; y += corner[(size_t)e * 3 + 1]; z += corner[(size_t)e * 3 + 2];
-    }
-    dst[v * 3] = x; dst[v * 3 + 1] = y; dst[v * 3 + 2] = z;
-    if (out) {
-        const float len = sqrtf(x * x + y * y + z * z);
-        out[v * 3] = x / len; out[v * 3 + 1] = y / len; out[v * 3 + 2] = z / len;
-    }
-}
-
-// sum over the workgroup of three doubles (result in thread 0)
-__device__ __forceinline__ void block_sum3(double (&x)[3], double* smem) {
-    block_sum<3>(x, smem);
-}
-
 // partial sums of |e01|^2, |e02|^2, |e12|^2 over the faces of this workgroup's stride
 template <typename IDX>
 __global__ __launch_bounds__(BLOCK) void k_edge_norm_partials(const float* __restrict__ verts, const IDX* __restrict__ faces, int64_t F,
@@ -140,10 +80,10 @@ __global__ __launch_bounds__(BLOCK) void k_edge_norm_partials(const float* __res
             acc[0] += (double)(e01 * e01); acc[1] += (double)(e02 * e02); acc[2] += (double)(e12 * e12);
         }
     }
-    block_sum3(acc, smem);
+    block_sum<3>(acc, smem);
     if (threadIdx.x == 0) {
 #pragma unroll
-        for (int i = 0; i < 3; ++i) part[(size_t)i * NRM_MAXG + blockIdx.x] = acc[i];
+        for (int i = 0; i < 3; ++i) part[(size_t)i * MESH_MAXG + blockIdx.x] = acc[i];
     }
 }
 
@@ -285,10 +225,10 @@ __global__ __launch_bounds__(BLOCK) void k_vertex_normals_bwd1(const float* __re
 #pragma unroll
         for (int q = 0; q < 3; ++q) grad_fn[(size_t)q * F + f] = gf[q];
     }
-    block_sum3(gN, smem);
+    block_sum<3>(gN, smem);
     if (threadIdx.x == 0) {
 #pragma unroll
-        for (int i = 0; i < 3; ++i) part[(size_t)i * NRM_MAXG + blockIdx.x] = gN[i];
+        for (int i = 0; i < 3; ++i) part[(size_t)i * MESH_MAXG + blockIdx.x] = gN[i];
     }
 }
 
@@ -398,7 +338,7 @@ __global__ __launch_bounds__(BLOCK) void k_face_normals_norms(const float* __res
             }
         }
     }
-    block_sum3(acc, smem);
+    block_sum<3>(acc, smem);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int i = 0; i < 3; ++i) part[(size_t)i * P + blk] = acc[i];
@@ -469,7 +409,7 @@ __global__ __launch_bounds__(BLOCK) void k_pair_bwd_face(const float* __restrict
             for (int q = 0; q < 3; ++q) grad_fn[(size_t)q * F + f] = gf[q];
         }
     }
-    block_sum3(gN, smem);
+    block_sum<3>(gN, smem);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int i = 0; i < 3; ++i) part[(size_t)i * P + blk] = gN[i];
@@ -552,22 +492,6 @@ __global__ __launch_bounds__(BLOCK) void k_pair_bwd_verts(const float* __restric
 // trips per thread, 96 VGPRs): 12-byte loads and 3 / 4 / 8 corners in flight change nothing. The BACKWARD built the same way (the
 // whole face gradient recomputed per corner, 120 VGPRs) takes 58 us against 35.5 + 14.4 and was not kept.
 
-// a 3-vector at a 4-byte aligned address as ONE 12-byte access (global_load_dwordx3): 24 gather instructions per thread instead of 72
-typedef float f3_nrm __attribute__((ext_vector_type(3), aligned(4)));
-typedef int i3_nrm __attribute__((ext_vector_type(3), aligned(4)));
-__device__ __forceinline__ void ld3(const float* __restrict__ base, size_t row, float (&v)[3]) {
-    const f3_nrm t = *reinterpret_cast<const f3_nrm*>(base + row * 3);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z;
-}
-__device__ __forceinline__ void ld_ids(const int32_t* __restrict__ faces, int64_t f, int (&id)[3]) {
-    const i3_nrm t = *reinterpret_cast<const i3_nrm*>(faces + f * 3);
-    id[0] = t.x; id[1] = t.y; id[2] = t.z;
-}
-__device__ __forceinline__ void ld_ids(const int64_t* __restrict__ faces, int64_t f, int (&id)[3]) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) id[c] = (int)faces[f * 3 + c];
-}
-
 __device__ __forceinline__ float sel3(int i, float a, float b, float c) { return i == 0 ? a : (i == 1 ? b : c); }
 
 // theta of corner i (known at run time only) of a face: corner_of's arithmetic on operands picked by selects (no indexed registers)
@@ -621,30 +545,18 @@ __global__ __launch_bounds__(BLOCK) void k_vertex_normals_gather_geo(const float
     out[v * 3] = x / len; out[v * 3 + 1] = y / len; out[v * 3 + 2] = z / len;
 }
 
-static int reduce_grid(int64_t F) { return (int)std::min<int64_t>(NRM_MAXG, std::max<int64_t>(1, div_up(F, BLOCK))); }
-// slots per row of the partial-sum array: the looping reductions use NRM_MAXG, the per-block ones one per block of faces
-static int64_t part_slots(int64_t F) { return std::max<int64_t>(NRM_MAXG, div_up(std::max<int64_t>(F, 1), BLOCK)); }
+// slots per row of the partial-sum array: the looping reductions use MESH_MAXG, the per-block ones one per block of faces
+static int64_t part_slots(int64_t F) { return std::max<int64_t>(MESH_MAXG, div_up(std::max<int64_t>(F, 1), BLOCK)); }
 
 }  // namespace ls
 
 using namespace ls;
-
-#define LS_IDX(bytes, ...)                                                                     \
-    do {                                                                                       \
-        if ((bytes) == 8) { typedef int64_t IDX; __VA_ARGS__; } else { typedef int32_t IDX; __VA_ARGS__; } \
-    } while (0)
 
 extern "C" int ls_normals_workspace_bytes(int64_t F, int64_t V, size_t* h_bytes) {
     LS_REQUIRE(h_bytes && F >= 0 && V >= 0, LS_E_INVALID, "ls_normals_workspace_bytes: bad argument");
     // reduction partials (one slot per block of faces) | 4 floats | g_raw (V, 3) | one 3-vector per corner (3 F, 3)
     *h_bytes = sizeof(double) * 3 * (size_t)part_slots(F) + sizeof(float) * 4 + sizeof(float) * 3 * (size_t)std::max<int64_t>(V, 1) +
                sizeof(float) * 9 * (size_t)std::max<int64_t>(F, 1);
-    return LS_OK;
-}
-
-static int check_mesh_args(const void* verts, const void* faces, int idx_bytes, int64_t F, int64_t V, const char* who) {
-    LS_REQUIRE(verts && (faces || F == 0) && (idx_bytes == 4 || idx_bytes == 8) && F >= 0 && V > 0 && V < INT32_MAX && 3 * F < INT32_MAX,
-               LS_E_INVALID, "%s: bad argument (faces must be int32 or int64, V and 3 F < 2^31)", who);
     return LS_OK;
 }
 
@@ -677,10 +589,8 @@ extern "C" int ls_face_normals_backward(const float* verts, const void* faces, i
                                         int device, void* stream) {
     int rc = check_mesh_args(verts, faces, idx_bytes, F, V, "ls_face_normals_backward");
     if (rc) return rc;
-    size_t need = 0;
-    ls_normals_workspace_bytes(F, V, &need);
     LS_REQUIRE(grad_verts && vptr && workspace && ((g_fn && cpos) || F == 0), LS_E_INVALID, "ls_face_normals_backward: null argument");
-    LS_REQUIRE(ws_bytes >= need, LS_E_WORKSPACE, "ls_face_normals_backward: workspace too small (%zu < %zu bytes)", ws_bytes, need);
+    if ((rc = require_workspace("ls_face_normals_backward", ls_normals_workspace_bytes, F, V, ws_bytes))) return rc;
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
@@ -688,8 +598,7 @@ extern "C" int ls_face_normals_backward(const float* verts, const void* faces, i
     if (F > 0)
         LS_IDX(idx_bytes, hipLaunchKernelGGL(k_face_normals_bwd<IDX>, dim3(div_up(F, BLOCK)), dim3(BLOCK), 0, st, verts, (const IDX*)faces, F, g_fn,
                                              cpos, w.corner));
-    hipLaunchKernelGGL(k_gather_corners, dim3(div_up(V, BLOCK)), dim3(BLOCK), 0, st, vptr, (const float*)w.corner, V, grad_verts,
-                       (float*)nullptr);
+    gather_corners(vptr, w.corner, V, grad_verts, nullptr, st);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
@@ -699,10 +608,8 @@ extern "C" int ls_vertex_normals(const float* verts, const void* faces, int idx_
                                  size_t ws_bytes, int device, void* stream) {
     int rc = check_mesh_args(verts, faces, idx_bytes, F, V, "ls_vertex_normals");
     if (rc) return rc;
-    size_t need = 0;
-    ls_normals_workspace_bytes(F, V, &need);
     LS_REQUIRE(out && raw && norms && workspace && vptr && ((fn && cpos) || F == 0), LS_E_INVALID, "ls_vertex_normals: null argument");
-    LS_REQUIRE(ws_bytes >= need, LS_E_WORKSPACE, "ls_vertex_normals: workspace too small (%zu < %zu bytes)", ws_bytes, need);
+    if ((rc = require_workspace("ls_vertex_normals", ls_normals_workspace_bytes, F, V, ws_bytes))) return rc;
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
@@ -710,13 +617,13 @@ extern "C" int ls_vertex_normals(const float* verts, const void* faces, int idx_
     if (F > 0) {
         const int G = reduce_grid(F);
         LS_IDX(idx_bytes, hipLaunchKernelGGL(k_edge_norm_partials<IDX>, dim3(G), dim3(BLOCK), 0, st, verts, (const IDX*)faces, F, w.part));
-        hipLaunchKernelGGL(k_finish3, dim3(1), dim3(FIN), 0, st, (const double*)w.part, G, NRM_MAXG, 1, norms);
+        hipLaunchKernelGGL(k_finish3, dim3(1), dim3(FIN), 0, st, (const double*)w.part, G, MESH_MAXG, 1, norms);
         LS_IDX(idx_bytes, hipLaunchKernelGGL(k_vertex_normals_scatter<IDX>, dim3(div_up(F, BLOCK)), dim3(BLOCK), 0, st, verts, (const IDX*)faces,
                                              F, fn, (const float*)norms, cpos, w.corner));
     } else {
         LS_HIP(hipMemsetAsync(norms, 0, sizeof(float) * 3, st));
     }
-    hipLaunchKernelGGL(k_gather_corners, dim3(div_up(V, BLOCK)), dim3(BLOCK), 0, st, vptr, (const float*)w.corner, V, raw, out);
+    gather_corners(vptr, w.corner, V, raw, out, st);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
@@ -726,11 +633,9 @@ extern "C" int ls_vertex_normals_backward(const float* verts, const void* faces,
                                           float* grad_verts, float* grad_fn, void* workspace, size_t ws_bytes, int device, void* stream) {
     int rc = check_mesh_args(verts, faces, idx_bytes, F, V, "ls_vertex_normals_backward");
     if (rc) return rc;
-    size_t need = 0;
-    ls_normals_workspace_bytes(F, V, &need);
     LS_REQUIRE(raw && norms && g_out && grad_verts && workspace && vptr && ((fn && grad_fn && cpos) || F == 0), LS_E_INVALID,
                "ls_vertex_normals_backward: null argument");
-    LS_REQUIRE(ws_bytes >= need, LS_E_WORKSPACE, "ls_vertex_normals_backward: workspace too small (%zu < %zu bytes)", ws_bytes, need);
+    if ((rc = require_workspace("ls_vertex_normals_backward", ls_normals_workspace_bytes, F, V, ws_bytes))) return rc;
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
@@ -740,12 +645,11 @@ extern "C" int ls_vertex_normals_backward(const float* verts, const void* faces,
         const int G = reduce_grid(F);
         LS_IDX(idx_bytes, hipLaunchKernelGGL(k_vertex_normals_bwd1<IDX>, dim3(G), dim3(BLOCK), 0, st, verts, (const IDX*)faces, F, fn, norms,
                                              (const float*)w.g_raw, grad_fn, w.part));
-        hipLaunchKernelGGL(k_finish3, dim3(1), dim3(FIN), 0, st, (const double*)w.part, G, NRM_MAXG, 0, w.gN);
+        hipLaunchKernelGGL(k_finish3, dim3(1), dim3(FIN), 0, st, (const double*)w.part, G, MESH_MAXG, 0, w.gN);
         LS_IDX(idx_bytes, hipLaunchKernelGGL(k_vertex_normals_bwd2<IDX>, dim3(div_up(F, BLOCK)), dim3(BLOCK), 0, st, verts, (const IDX*)faces, F, fn,
                                              norms, (const float*)w.g_raw, (const float*)w.gN, cpos, w.corner));
     }
-    hipLaunchKernelGGL(k_gather_corners, dim3(div_up(V, BLOCK)), dim3(BLOCK), 0, st, vptr, (const float*)w.corner, V, grad_verts,
-                       (float*)nullptr);
+    gather_corners(vptr, w.corner, V, grad_verts, nullptr, st);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
@@ -755,10 +659,8 @@ extern "C" int ls_face_normals_with_norms(const float* verts, const void* faces,
                                           void* workspace, size_t ws_bytes, int device, void* stream) {
     int rc = check_mesh_args(verts, faces, idx_bytes, F, V, "ls_face_normals_with_norms");
     if (rc) return rc;
-    size_t need = 0;
-    ls_normals_workspace_bytes(F, V, &need);
     LS_REQUIRE((fn || F == 0) && norms && workspace, LS_E_INVALID, "ls_face_normals_with_norms: null argument");
-    LS_REQUIRE(ws_bytes >= need, LS_E_WORKSPACE, "ls_face_normals_with_norms: workspace too small (%zu < %zu bytes)", ws_bytes, need);
+    if ((rc = require_workspace("ls_face_normals_with_norms", ls_normals_workspace_bytes, F, V, ws_bytes))) return rc;
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
@@ -776,10 +678,8 @@ extern "C" int ls_vertex_normals_from_norms(const float* verts, const void* face
                                             size_t ws_bytes, int device, void* stream) {
     int rc = check_mesh_args(verts, faces, idx_bytes, F, V, "ls_vertex_normals_from_norms");
     if (rc) return rc;
-    size_t need = 0;
-    ls_normals_workspace_bytes(F, V, &need);
     LS_REQUIRE(out && raw && norms && workspace && vptr && (cpos || F == 0), LS_E_INVALID, "ls_vertex_normals_from_norms: null argument");
-    LS_REQUIRE(ws_bytes >= need, LS_E_WORKSPACE, "ls_vertex_normals_from_norms: workspace too small (%zu < %zu bytes)", ws_bytes, need);
+    if ((rc = require_workspace("ls_vertex_normals_from_norms", ls_normals_workspace_bytes, F, V, ws_bytes))) return rc;
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
@@ -787,7 +687,7 @@ extern "C" int ls_vertex_normals_from_norms(const float* verts, const void* face
     if (F > 0)
         LS_IDX(idx_bytes, hipLaunchKernelGGL(k_vertex_normals_scatter_geo<IDX>, dim3(div_up(F, BLOCK)), dim3(BLOCK), 0, st, verts, (const IDX*)faces,
                                              F, norms, cpos, w.corner));
-    hipLaunchKernelGGL(k_gather_corners, dim3(div_up(V, BLOCK)), dim3(BLOCK), 0, st, vptr, (const float*)w.corner, V, raw, out);
+    gather_corners(vptr, w.corner, V, raw, out, st);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
@@ -797,11 +697,9 @@ extern "C" int ls_normals_pair_backward_faces(const float* verts, const void* fa
                                               void* workspace, size_t ws_bytes, int device, void* stream) {
     int rc = check_mesh_args(verts, faces, idx_bytes, F, V, "ls_normals_pair_backward_faces");
     if (rc) return rc;
-    size_t need = 0;
-    ls_normals_workspace_bytes(F, V, &need);
     LS_REQUIRE(raw && norms && g_out && g_raw && gN && workspace && (grad_fn || F == 0), LS_E_INVALID,
                "ls_normals_pair_backward_faces: null argument");
-    LS_REQUIRE(ws_bytes >= need, LS_E_WORKSPACE, "ls_normals_pair_backward_faces: workspace too small (%zu < %zu bytes)", ws_bytes, need);
+    if ((rc = require_workspace("ls_normals_pair_backward_faces", ls_normals_workspace_bytes, F, V, ws_bytes))) return rc;
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
@@ -825,11 +723,9 @@ extern "C" int ls_normals_pair_backward_verts(const float* verts, const void* fa
                                               void* stream) {
     int rc = check_mesh_args(verts, faces, idx_bytes, F, V, "ls_normals_pair_backward_verts");
     if (rc) return rc;
-    size_t need = 0;
-    ls_normals_workspace_bytes(F, V, &need);
     LS_REQUIRE(norms && g_raw && gN && grad_verts && workspace && vptr && (cpos || F == 0), LS_E_INVALID,
                "ls_normals_pair_backward_verts: null argument");
-    LS_REQUIRE(ws_bytes >= need, LS_E_WORKSPACE, "ls_normals_pair_backward_verts: workspace too small (%zu < %zu bytes)", ws_bytes, need);
+    if ((rc = require_workspace("ls_normals_pair_backward_verts", ls_normals_workspace_bytes, F, V, ws_bytes))) return rc;
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
@@ -837,8 +733,7 @@ extern "C" int ls_normals_pair_backward_verts(const float* verts, const void* fa
     if (F > 0)
         LS_IDX(idx_bytes, hipLaunchKernelGGL(k_pair_bwd_verts<IDX>, dim3(div_up(F, BLOCK)), dim3(BLOCK), 0, st, verts, (const IDX*)faces, F, norms,
                                              g_raw, gN, g_fn, cpos, w.corner));
-    hipLaunchKernelGGL(k_gather_corners, dim3(div_up(V, BLOCK)), dim3(BLOCK), 0, st, vptr, (const float*)w.corner, V, grad_verts,
-                       (float*)nullptr);
+    gather_corners(vptr, w.corner, V, grad_verts, nullptr, st);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }

@@ -16,6 +16,7 @@
 // answers what a brute-force scan answers.
 #include "common.h"
 #include "lbvh.h"
+#include "meshface.h"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -45,14 +46,6 @@ __device__ __forceinline__ int rm_next(int h) { return 3 * (h / 3) + (h % 3 + 1)
 __device__ __forceinline__ int rm_prev(int h) { return 3 * (h / 3) + (h % 3 + 2) % 3; }
 
 // ---- input ---------------------------------------------------------------------------------------------------------------------
-template <typename IDX>
-__global__ __launch_bounds__(BLOCK) void k_rm_faces_in(const IDX* __restrict__ in, int64_t n, int64_t V, int* __restrict__ out, int* __restrict__ bad) {
-    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const IDX x = in[i];
-    if (x < 0 || (int64_t)x >= V) { atomicOr(&bad[0], 1); out[i] = 0; }
-    else out[i] = (int)x;
-}
 template <typename IDX>
 __global__ __launch_bounds__(BLOCK) void k_rm_faces_out(const int* __restrict__ in, int64_t n, IDX* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -707,10 +700,8 @@ extern "C" int ls_remesh_create(const float* verts, int64_t V, const void* faces
     if (hipMemsetAsync(H->small.p, 0, sizeof(int) * 64, H->st) != hipSuccess ||
         hipMemcpyAsync(H->pos.p, verts, sizeof(float) * 3 * V, hipMemcpyDeviceToDevice, H->st) != hipSuccess)
         return fail(hip_fail(hipGetLastError(), "ls_remesh_create copies", __FILE__, __LINE__));
-    if (idx_bytes == 8) hipLaunchKernelGGL(k_rm_faces_in<int64_t>, RM_GRID(n), (const int64_t*)faces, (int64_t)n, V, rp<int>(H->faces), rp<int>(H->small));
-    else hipLaunchKernelGGL(k_rm_faces_in<int32_t>, RM_GRID(n), (const int32_t*)faces, (int64_t)n, V, rp<int>(H->faces), rp<int>(H->small));
     int bad[4] = {0, 0, 0, 0};
-    if (hipMemcpyAsync(bad, H->small.p, sizeof(bad), hipMemcpyDeviceToHost, H->st) != hipSuccess || hipStreamSynchronize(H->st) != hipSuccess)
+    if (!faces_in(faces, idx_bytes, n, V, rp<int>(H->faces), rp<int>(H->small), H->st, &bad[0]))
         return fail(hip_fail(hipGetLastError(), "ls_remesh_create", __FILE__, __LINE__));
     if (bad[0]) { set_error("remesh_botsch: a face index is outside [0, %lld)", (long long)V); return fail(LS_E_INDEX); }
     if ((rc = rm_topo<true>(H))) return fail(rc);

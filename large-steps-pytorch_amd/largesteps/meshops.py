@@ -26,7 +26,7 @@ import torch
 from torch.autograd import Function
 
 from . import _native
-from .normals import _on, _prep
+from .normals import _mesh, _on, _prep, _tail, _workspace_of
 
 
 def remove_duplicates(v, f):
@@ -60,24 +60,11 @@ def remove_duplicates(v, f):
     nu = ctypes.c_int64(0)
     with torch.cuda.device(dev):
         _native.check(lib.ls_remove_duplicates(_native.ptr(vc), V, _native.ptr(fc), fc.element_size(), F, _native.ptr(unique), _native.ptr(inverse),
-                                               _native.ptr(new_faces), ctypes.byref(nu), _native.ptr(ws), ws.numel(), dev.index,
-                                               _native.stream_of(dev)))
+                                               _native.ptr(new_faces), ctypes.byref(nu), *_tail(ws, dev)))
     return unique[: nu.value], new_faces, inverse
 
 
-
-_ws_bytes = {}
-
-
-def _workspace(F, V, dev):
-    n = _ws_bytes.get((F, V))
-    if n is None:
-        c = ctypes.c_size_t(0)
-        _native.check(_native.lib().ls_meshgeom_workspace_bytes(F, V, ctypes.byref(c)))
-        if len(_ws_bytes) > 64:
-            _ws_bytes.clear()
-        n = _ws_bytes[(F, V)] = c.value
-    return torch.empty(n, dtype=torch.uint8, device=dev)
+_workspace = _workspace_of("ls_meshgeom_workspace_bytes")
 
 
 # Both Functions validate the faces through the corner ranking of normals._prep (built once per face tensor: the range check
@@ -90,8 +77,7 @@ class _AverageEdgeLength(Function):
         out = torch.empty((), dtype=torch.float32, device=dev)
         ws = _workspace(F, V, dev)
         with _on(dev):
-            _native.check(_native.lib().ls_average_edge_length(_native.ptr(v), _native.ptr(f), f.element_size(), F, V, _native.ptr(out),
-                                                               _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
+            _native.check(_native.lib().ls_average_edge_length(*_mesh(v, f), _native.ptr(out), *_tail(ws, dev)))
         ctx.save_for_backward(v, f, vptr, vcorner)
         return out
 
@@ -105,9 +91,8 @@ class _AverageEdgeLength(Function):
         gv = torch.empty_like(v)
         ws = _workspace(F, V, dev)
         with _on(dev):
-            _native.check(_native.lib().ls_average_edge_length_backward(_native.ptr(v), _native.ptr(f), f.element_size(), F, V, _native.ptr(vptr),
-                                                                        _native.ptr(vcorner), _native.ptr(g), _native.ptr(gv), _native.ptr(ws),
-                                                                        ws.numel(), dev.index, _native.stream_of(dev)))
+            _native.check(_native.lib().ls_average_edge_length_backward(*_mesh(v, f), _native.ptr(vptr), _native.ptr(vcorner), _native.ptr(g),
+                                                                        _native.ptr(gv), *_tail(ws, dev)))
         return gv, None
 
 
@@ -118,8 +103,8 @@ class _MassmatrixVoronoi(Function):
         F, V, dev = f.shape[0], v.shape[0], v.device
         mass = torch.empty(V, dtype=torch.float32, device=dev)
         with _on(dev):
-            _native.check(_native.lib().ls_massmatrix_voronoi(_native.ptr(v), _native.ptr(f), f.element_size(), F, V, _native.ptr(vptr),
-                                                              _native.ptr(order), _native.ptr(mass), dev.index, _native.stream_of(dev)))
+            _native.check(_native.lib().ls_massmatrix_voronoi(*_mesh(v, f), _native.ptr(vptr), _native.ptr(order), _native.ptr(mass), dev.index,
+                                                              _native.stream_of(dev)))
         ctx.save_for_backward(v, f, vptr, vcorner)
         return mass
 
@@ -133,9 +118,8 @@ class _MassmatrixVoronoi(Function):
         gv = torch.empty_like(v)
         ws = _workspace(F, V, dev)
         with _on(dev):
-            _native.check(_native.lib().ls_massmatrix_voronoi_backward(_native.ptr(v), _native.ptr(f), f.element_size(), F, V, _native.ptr(vptr),
-                                                                       _native.ptr(vcorner), _native.ptr(g), _native.ptr(gv), _native.ptr(ws),
-                                                                       ws.numel(), dev.index, _native.stream_of(dev)))
+            _native.check(_native.lib().ls_massmatrix_voronoi_backward(*_mesh(v, f), _native.ptr(vptr), _native.ptr(vcorner), _native.ptr(g),
+                                                                       _native.ptr(gv), *_tail(ws, dev)))
         return gv, None
 
 

@@ -80,18 +80,33 @@ def _prep(verts, faces):
     return v, narrow, vptr, vcorner, order
 
 
-_ws_bytes = {}
+def _workspace_of(size_fn):
+    """`workspace(F, V, dev)`: a byte buffer of the size the library's `size_fn` (the name of an ls_*_workspace_bytes) asks for"""
+    known = {}
+
+    def workspace(F, V, dev):
+        n = known.get((F, V))
+        if n is None:
+            c = ctypes.c_size_t(0)
+            _native.check(getattr(_native.lib(), size_fn)(F, V, ctypes.byref(c)))
+            if len(known) > 64:
+                known.clear()
+            n = known[(F, V)] = c.value
+        return torch.empty(n, dtype=torch.uint8, device=dev)
+    return workspace
 
 
-def _workspace(F, V, dev):
-    n = _ws_bytes.get((F, V))
-    if n is None:
-        c = ctypes.c_size_t(0)
-        _native.check(_native.lib().ls_normals_workspace_bytes(F, V, ctypes.byref(c)))
-        if len(_ws_bytes) > 64:
-            _ws_bytes.clear()
-        n = _ws_bytes[(F, V)] = c.value
-    return torch.empty(n, dtype=torch.uint8, device=dev)
+_workspace = _workspace_of("ls_normals_workspace_bytes")
+
+
+def _mesh(v, f):
+    """what every entry point of csrc/normals.hip and csrc/meshgeom.hip takes first: verts, faces, idx_bytes, F, V"""
+    return _native.ptr(v), _native.ptr(f), f.element_size(), f.shape[0], v.shape[0]
+
+
+def _tail(ws, dev):
+    """... and last, when it takes a workspace: workspace, ws_bytes, device, stream"""
+    return _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)
 
 
 class _Here:
@@ -161,9 +176,7 @@ class _FaceNormals(Function):
         norms = torch.empty(3, dtype=torch.float32, device=dev)
         ws = _workspace(F, V, dev)
         with _on(dev):
-            _native.check(_native.lib().ls_face_normals_with_norms(_native.ptr(v), _native.ptr(f), f.element_size(), F, V, _native.ptr(fn),
-                                                                   _native.ptr(norms), _native.ptr(ws), ws.numel(), dev.index,
-                                                                   _native.stream_of(dev)))
+            _native.check(_native.lib().ls_face_normals_with_norms(*_mesh(v, f), _native.ptr(fn), _native.ptr(norms), *_tail(ws, dev)))
         ctx.save_for_backward(v, f, vptr, vcorner)
         ctx.set_materialize_grads(False)
         ctx.tag = _PairTag(verts, faces, norms)
@@ -186,17 +199,15 @@ class _FaceNormals(Function):
         with _on(dev):
             if not mine:
                 gv = torch.empty_like(v)
-                _native.check(lib.ls_face_normals_backward(_native.ptr(v), _native.ptr(f), f.element_size(), F, V, _native.ptr(vptr),
-                                                           _native.ptr(vcorner), _native.ptr(g), _native.ptr(gv), _native.ptr(ws),
-                                                           ws.numel(), dev.index, _native.stream_of(dev)))
+                _native.check(lib.ls_face_normals_backward(*_mesh(v, f), _native.ptr(vptr), _native.ptr(vcorner), _native.ptr(g), _native.ptr(gv),
+                                                           *_tail(ws, dev)))
                 return gv, None
             total = None
             for k, (_, g_raw, gN) in enumerate(mine):          # one entry unless several vertex-normal nodes share these face normals
                 gv = torch.empty_like(v)
-                _native.check(lib.ls_normals_pair_backward_verts(_native.ptr(v), _native.ptr(f), f.element_size(), F, V, _native.ptr(vptr),
-                                                                 _native.ptr(vcorner), _native.ptr(ctx.tag.norms), _native.ptr(g_raw),
-                                                                 _native.ptr(gN), _native.ptr(g if k == 0 else None), _native.ptr(gv),
-                                                                 _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
+                _native.check(lib.ls_normals_pair_backward_verts(*_mesh(v, f), _native.ptr(vptr), _native.ptr(vcorner), _native.ptr(ctx.tag.norms),
+                                                                 _native.ptr(g_raw), _native.ptr(gN), _native.ptr(g if k == 0 else None),
+                                                                 _native.ptr(gv), *_tail(ws, dev)))
                 total = gv if total is None else total + gv
         return total, None
 
@@ -219,17 +230,15 @@ class _VertexNormals(Function):
             with _on(dev):
                 # vertex-major: each vertex recomputes the contributions of its corners in rank order -- the bits of
                 # ls_vertex_normals_from_norms without its corner buffer (tests/test_gpu_parity.py compares the two)
-                _native.check(lib.ls_vertex_normals_gathered(_native.ptr(v), _native.ptr(f), f.element_size(), F, V, _native.ptr(vptr),
-                                                             _native.ptr(order), _native.ptr(tag.norms), _native.ptr(out), _native.ptr(raw),
-                                                             dev.index, _native.stream_of(dev)))
+                _native.check(lib.ls_vertex_normals_gathered(*_mesh(v, f), _native.ptr(vptr), _native.ptr(order), _native.ptr(tag.norms),
+                                                             _native.ptr(out), _native.ptr(raw), dev.index, _native.stream_of(dev)))
             ctx.save_for_backward(v, f, raw, vptr, vcorner)
             return out
         fn = face_normals.detach().to(torch.float32).contiguous()
         norms = torch.empty(3, dtype=torch.float32, device=dev)
         with _on(dev):
-            _native.check(lib.ls_vertex_normals(_native.ptr(v), _native.ptr(f), f.element_size(), F, V, _native.ptr(vptr),
-                                                _native.ptr(vcorner), _native.ptr(fn), _native.ptr(out), _native.ptr(raw),
-                                                _native.ptr(norms), _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
+            _native.check(lib.ls_vertex_normals(*_mesh(v, f), _native.ptr(vptr), _native.ptr(vcorner), _native.ptr(fn), _native.ptr(out),
+                                                _native.ptr(raw), _native.ptr(norms), *_tail(ws, dev)))
         ctx.save_for_backward(v, f, fn, raw, norms, vptr, vcorner)
         return out
 
@@ -253,20 +262,17 @@ class _VertexNormals(Function):
             # (and only if the face normals really hang on that node: ctx.can_defer, decided in compute_vertex_normals)
             defer = task >= 0 and ctx.needs_input_grad[0] and ctx.needs_input_grad[2] and ctx.can_defer
             with _on(dev):
-                _native.check(lib.ls_normals_pair_backward_faces(_native.ptr(v), _native.ptr(f), f.element_size(), F, V, _native.ptr(raw),
-                                                                 _native.ptr(tag.norms), _native.ptr(g), _native.ptr(g_raw), _native.ptr(gN),
-                                                                 _native.ptr(gfn), _native.ptr(ws), ws.numel(), dev.index,
-                                                                 _native.stream_of(dev)))
+                _native.check(lib.ls_normals_pair_backward_faces(*_mesh(v, f), _native.ptr(raw), _native.ptr(tag.norms), _native.ptr(g),
+                                                                 _native.ptr(g_raw), _native.ptr(gN), _native.ptr(gfn), *_tail(ws, dev)))
                 if defer:
                     tag.pending[id(ctx)] = (task, g_raw, gN)
                     return None, None, gfn, None, None
                 gv = None
                 if ctx.needs_input_grad[0]:
                     gv = torch.empty_like(v)
-                    _native.check(lib.ls_normals_pair_backward_verts(_native.ptr(v), _native.ptr(f), f.element_size(), F, V, _native.ptr(vptr),
-                                                                     _native.ptr(vcorner), _native.ptr(tag.norms), _native.ptr(g_raw),
-                                                                     _native.ptr(gN), _native.ptr(None), _native.ptr(gv), _native.ptr(ws),
-                                                                     ws.numel(), dev.index, _native.stream_of(dev)))
+                    _native.check(lib.ls_normals_pair_backward_verts(*_mesh(v, f), _native.ptr(vptr), _native.ptr(vcorner), _native.ptr(tag.norms),
+                                                                     _native.ptr(g_raw), _native.ptr(gN), _native.ptr(None), _native.ptr(gv),
+                                                                     *_tail(ws, dev)))
             return gv, None, (gfn if ctx.needs_input_grad[2] else None), None, None
         v, f, fn, raw, norms, vptr, vcorner = ctx.saved_tensors
         F, V, dev = f.shape[0], v.shape[0], v.device
@@ -274,11 +280,8 @@ class _VertexNormals(Function):
         gfn = torch.empty_like(fn)
         ws = _workspace(F, V, dev)
         with _on(dev):
-            _native.check(lib.ls_vertex_normals_backward(_native.ptr(v), _native.ptr(f), f.element_size(), F, V, _native.ptr(vptr),
-                                                         _native.ptr(vcorner), _native.ptr(fn),
-                                                         _native.ptr(raw), _native.ptr(norms), _native.ptr(g), _native.ptr(gv),
-                                                         _native.ptr(gfn), _native.ptr(ws), ws.numel(), dev.index,
-                                                         _native.stream_of(dev)))
+            _native.check(lib.ls_vertex_normals_backward(*_mesh(v, f), _native.ptr(vptr), _native.ptr(vcorner), _native.ptr(fn), _native.ptr(raw),
+                                                         _native.ptr(norms), _native.ptr(g), _native.ptr(gv), _native.ptr(gfn), *_tail(ws, dev)))
         return (gv if ctx.needs_input_grad[0] else None), None, (gfn if ctx.needs_input_grad[2] else None), None, None
 
 

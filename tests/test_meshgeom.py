@@ -171,6 +171,60 @@ def test_hip_1m_vertices_vs_statement(dev):
     assert (np.abs(g_avg - ga64) <= 1e-6 * mag).all()
 
 
+def index_width_meshes(name):
+    """the meshes of the same test of csrc/normals.hip (tests/test_normals.py). spike: a fan of 40 triangles around vertex 0 (valence 40
+    exceeds the 4-corner request group) + an unreferenced vertex; cfg1_icosphere2k: 5120 faces; its cut: the last 7 faces dropped"""
+    from largesteps import synthetic
+    if name == "spike":
+        k = 40
+        ang = np.linspace(0, 2 * np.pi, k, endpoint=False)
+        v = np.concatenate([[[0, 0, 0.3]], np.stack([np.cos(ang), np.sin(ang), 0.05 * np.cos(3 * ang)], 1), [[5, 5, 5]]]).astype(np.float32)
+        return v, np.stack([np.zeros(k, np.int64), 1 + np.arange(k), 1 + (np.arange(k) + 1) % k], 1)
+    v, f, _ = synthetic.config_mesh("cfg1_icosphere2k")
+    return v, (f[:-7] if name.endswith("_cut") else f)
+
+
+def assert_same_bits(a, b):
+    assert a.keys() == b.keys()
+    for k in a:
+        assert torch.equal(a[k].view(torch.int32), b[k].view(torch.int32)), k
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["spike", "cfg1_icosphere2k", "cfg1_icosphere2k_cut"])
+def test_int64_index_kernels_give_the_bits_of_the_int32_ones(dev, name):
+    """The package narrows int64 faces to int32 (normals._prep), so nothing else runs the IDX = int64_t instantiations: every entry
+    point of csrc/meshgeom.hip through the C ABI with idx_bytes = 4 and 8 on the same mesh and the same corner ranking -- every output
+    bit-equal."""
+    from largesteps import _native, meshops, normals
+    v, f = index_width_meshes(name)
+    tv, f32 = _t(v.astype(np.float32), dev), _t(f.astype(np.int32), dev)
+    vv, ff, vptr, cpos, order = normals._prep(tv, f32)
+    assert ff.dtype == torch.int32
+    F, V = ff.shape[0], vv.shape[0]
+    lib, p = _native.lib(), _native.ptr
+    gen = torch.Generator(device=dev).manual_seed(0)
+    g_mass, g_avg = torch.randn(V, device=dev, generator=gen), torch.randn((), device=dev, generator=gen)
+
+    def run(faces):
+        mesh = (p(vv), p(faces), faces.element_size(), F, V)
+        ws = meshops._workspace(F, V, dev)
+        tail = (p(ws), ws.numel(), dev.index, _native.stream_of(dev))
+        o = {"mass": torch.zeros(V, device=dev), "avg": torch.zeros((), device=dev), "g_mass": torch.zeros((V, 3), device=dev),
+             "g_avg": torch.zeros((V, 3), device=dev)}
+        _native.check(lib.ls_massmatrix_voronoi(*mesh, p(vptr), p(order), p(o["mass"]), *tail[2:]))
+        _native.check(lib.ls_massmatrix_voronoi_backward(*mesh, p(vptr), p(cpos), p(g_mass), p(o["g_mass"]), *tail))
+        _native.check(lib.ls_average_edge_length(*mesh, p(o["avg"]), *tail))
+        _native.check(lib.ls_average_edge_length_backward(*mesh, p(vptr), p(cpos), p(g_avg), p(o["g_avg"]), *tail))
+        torch.cuda.synchronize()
+        return o
+
+    narrow, wide = run(ff), run(ff.to(torch.int64))
+    assert_same_bits({k: x.reshape(-1) for k, x in narrow.items()}, {k: x.reshape(-1) for k, x in wide.items()})
+    assert bool((narrow["mass"] > 0).any()) and float(narrow["avg"]) > 0 and bool(narrow["g_mass"].abs().max() > 0)      # the kernels ran
+    assert bool(narrow["mass"][-1] == 0) == (name == "spike")                                    # the unreferenced vertex
+
+
 @pytest.mark.gpu
 def test_hip_graph_capture_matches_eager(dev):
     from largesteps import synthetic

@@ -152,6 +152,14 @@ def test_hip_pair_paths_vs_reference(ref, dev, name, monkeypatch):
     close(g_f.cpu().numpy(), ref[f"{name}/grad_vn_fn"], 1e-5 * max(np.abs(ref[f"{name}/grad_vn_fn"]).max(), 1.0))
 
 
+def _spike(k=40):
+    """a fan of k triangles around vertex 0 + an unreferenced vertex"""
+    ang = np.linspace(0, 2 * np.pi, k, endpoint=False)
+    v = np.concatenate([[[0, 0, 0.3]], np.stack([np.cos(ang), np.sin(ang), 0.05 * np.cos(3 * ang)], 1), [[5, 5, 5]]]).astype(np.float32)
+    f = np.stack([np.zeros(k, np.int64), 1 + np.arange(k), 1 + (np.arange(k) + 1) % k], 1)
+    return v, f
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("idx", [np.int64, np.int32])
 @pytest.mark.parametrize("name", MESHES + ["cfg2_bunny70k", "spike"])
@@ -162,11 +170,8 @@ def test_vertex_major_forward_equals_the_corner_buffer_forward(ref, dev, name, i
     several trips."""
     import ctypes
     from largesteps import _native, normals, synthetic
-    if name == "spike":                                   # a fan of 40 triangles around vertex 0 + an unreferenced vertex
-        k = 40
-        ang = np.linspace(0, 2 * np.pi, k, endpoint=False)
-        v = np.concatenate([[[0, 0, 0.3]], np.stack([np.cos(ang), np.sin(ang), 0.05 * np.cos(3 * ang)], 1), [[5, 5, 5]]]).astype(np.float32)
-        f = np.stack([np.zeros(k, np.int64), 1 + np.arange(k), 1 + (np.arange(k) + 1) % k], 1)
+    if name == "spike":
+        v, f = _spike()
     elif name.startswith("cfg"):
         v, f, _ = synthetic.config_mesh(name)
     else:
@@ -192,6 +197,67 @@ def test_vertex_major_forward_equals_the_corner_buffer_forward(ref, dev, name, i
         assert torch.equal(a.view(torch.int32), b.view(torch.int32))
     assert lib.ls_vertex_normals_gathered(_native.ptr(vv), _native.ptr(ff), ff.element_size(), F, V, _native.ptr(vptr), None, _native.ptr(norms),
                                           _native.ptr(out_b), _native.ptr(raw_b), dev.index, _native.stream_of(dev)) == _native.LS_E_INVALID
+
+
+def index_width_meshes(name):
+    """spike: valence 40 exceeds the 8- and 4-corner request groups, 40 faces leave the 4-faces-per-thread kernels a clamped tail;
+    cfg1_icosphere2k: 5120 faces, several workgroups feed the fixed-order reductions (5120 = 5 x 1024: no tail there); its cut (the
+    last 7 faces dropped) has both at once"""
+    from largesteps import synthetic
+    if name == "spike":
+        return _spike()
+    v, f, _ = synthetic.config_mesh("cfg1_icosphere2k")
+    return v, (f[:-7] if name.endswith("_cut") else f)
+
+
+def assert_same_bits(a, b):
+    assert a.keys() == b.keys()
+    for k in a:
+        assert torch.equal(a[k].view(torch.int32), b[k].view(torch.int32)), k
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["spike", "cfg1_icosphere2k", "cfg1_icosphere2k_cut"])
+def test_int64_index_kernels_give_the_bits_of_the_int32_ones(dev, name):
+    """The package narrows int64 faces to int32 (normals._prep), so nothing else runs the IDX = int64_t instantiations: every entry
+    point of csrc/normals.hip through the C ABI with idx_bytes = 4 and 8 on the same mesh and the same corner ranking -- every output
+    bit-equal, the NaN rows of the unreferenced vertex included."""
+    from largesteps import _native, normals
+    v, f = index_width_meshes(name)
+    tv, f32 = _t(v.astype(np.float32), dev), _t(f.astype(np.int32), dev)
+    vv, ff, vptr, cpos, order = normals._prep(tv, f32)
+    assert ff.dtype == torch.int32
+    F, V = ff.shape[0], vv.shape[0]
+    lib, p = _native.lib(), _native.ptr
+    gen = torch.Generator(device=dev).manual_seed(0)
+    g_fn, g_out = torch.randn((3, F), device=dev, generator=gen), torch.randn((V, 3), device=dev, generator=gen)
+
+    def run(faces):
+        mesh = (p(vv), p(faces), faces.element_size(), F, V)
+        ws = normals._workspace(F, V, dev)
+        tail = (p(ws), ws.numel(), dev.index, _native.stream_of(dev))
+        o = {k: torch.zeros((3, F), device=dev) for k in ("fn", "fn_w", "gfn", "pair_gfn")}
+        o.update({k: torch.zeros((V, 3), device=dev) for k in ("fn_gv", "out", "raw", "gv", "out_n", "raw_n", "out_g", "raw_g", "g_raw", "pair_gv")})
+        o.update({k: torch.zeros(4, device=dev) for k in ("norms", "norms_w", "gN")})
+        _native.check(lib.ls_face_normals(*mesh, p(o["fn"]), *tail[2:]))
+        _native.check(lib.ls_face_normals_backward(*mesh, p(vptr), p(cpos), p(g_fn), p(o["fn_gv"]), *tail))
+        _native.check(lib.ls_vertex_normals(*mesh, p(vptr), p(cpos), p(o["fn"]), p(o["out"]), p(o["raw"]), p(o["norms"]), *tail))
+        _native.check(lib.ls_vertex_normals_backward(*mesh, p(vptr), p(cpos), p(o["fn"]), p(o["raw"]), p(o["norms"]), p(g_out), p(o["gv"]),
+                                                     p(o["gfn"]), *tail))
+        _native.check(lib.ls_face_normals_with_norms(*mesh, p(o["fn_w"]), p(o["norms_w"]), *tail))
+        _native.check(lib.ls_vertex_normals_from_norms(*mesh, p(vptr), p(cpos), p(o["norms_w"]), p(o["out_n"]), p(o["raw_n"]), *tail))
+        _native.check(lib.ls_vertex_normals_gathered(*mesh, p(vptr), p(order), p(o["norms_w"]), p(o["out_g"]), p(o["raw_g"]), *tail[2:]))
+        _native.check(lib.ls_normals_pair_backward_faces(*mesh, p(o["raw_n"]), p(o["norms_w"]), p(g_out), p(o["g_raw"]), p(o["gN"]),
+                                                         p(o["pair_gfn"]), *tail))
+        _native.check(lib.ls_normals_pair_backward_verts(*mesh, p(vptr), p(cpos), p(o["norms_w"]), p(o["g_raw"]), p(o["gN"]), p(g_fn),
+                                                         p(o["pair_gv"]), *tail))
+        torch.cuda.synchronize()
+        return o
+
+    narrow, wide = run(ff), run(ff.to(torch.int64))
+    assert_same_bits(narrow, wide)
+    assert torch.isfinite(narrow["fn"]).all() and bool(narrow["pair_gv"].abs().max() > 0)      # the kernels ran
+    assert torch.isnan(narrow["out"]).any() == (name == "spike")
 
 
 @pytest.mark.gpu
