@@ -34,6 +34,7 @@
  *   ls_massmatrix_voronoi*    scripts/geometry.py:35-89 (massmatrix_voronoi: Voronoi area per vertex, obtuse-triangle rule)
  *                        and its autograd gradient
  *   ls_texture_*         nvdiffrast.torch.texture as scripts/render.py calls it (the backgrounds), with gradients to tex and uv
+ *   ls_mip_*             the mipmap filter modes of nvdiffrast.torch.texture and the pixel differentials that choose their level
  *   ls_mesh_distance_*   igl.point_mesh_squared_distance / igl.hausdorff (figures/comparison/generate_data.py: the error column)
  */
 #ifndef LARGESTEPS_HIP_H
@@ -735,6 +736,49 @@ int ls_texture_order(const float* uv, int64_t B, int H, int W, int64_t Bt, int H
 int ls_texture_backward(const float* tex, int64_t Bt, int Ht, int Wt, int C, const float* uv, int64_t B, int H, int W, int filter,
                         int boundary, const float* grad_out, const int32_t* order, const int32_t* seg, float* grad_tex, float* grad_uv,
                         int device, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Mipmapped texture lookup and pixel differentials (largesteps/render.py: texture with the mipmap filter modes, texture_construct_mip,
+ * pixel_differentials, interpolate(diff_attrs=...); the rules are stated in csrc/mip.hip and DESIGN.md section 2.7, restated in numpy
+ * by tests/mip_statement.py). tex, uv, boundary as for ls_texture_*; Lmax in [0, 13] is the last level of the pyramid: every level
+ * before it has sides that are 1 or even and is not 1 x 1 (LS_E_INVALID otherwise). pyr holds levels 1 .. Lmax packed one after the
+ * other, level l as (Bt, H_l, W_l, C) with W_l = max(Wt >> l, 1); it may be NULL when Lmax = 0. uv_da (B, H, W, 4) fp32, 16-byte
+ * aligned, and bias (B, H, W) fp32: either may be NULL, not both. mode: LS_MIP_NEAREST (linear-mipmap-nearest) / LS_MIP_LINEAR
+ * (linear-mipmap-linear). LS_E_OVERFLOW when 2 B H W or the number of base positions of all levels does not fit int32. No entry point
+ * allocates or synchronises, none uses float atomics: outputs and gradients are bitwise reproducible. ASYNC.
+ *   ls_mip_workspace_bytes       workspace of ls_mip_order for B H W pixels.
+ *   ls_mip_build                 pyr from tex: a texel is ((c00 + c10) + (c01 + c11)) * 0.25f of its children ((a + b) * 0.5f of two).
+ *   ls_mip_fold                  the transpose of ls_mip_build, top down: every texel of level l (grad_tex for level 0) gains 0.25f
+ *                                (0.5f) of its parent's gradient in grad_pyr. Call it after ls_mip_backward.
+ *   ls_mip_pixel_differentials   out (B, H, W, 4) = (du/dX, du/dY, dv/dX, dv/dY) of the barycentrics in rast per pixel step, from the
+ *                                clip-space pos (B, V, 4) and the int32 faces; 0 for background and degenerate faces.
+ *   ls_mip_interpolate_da        out (B, H, W, 2 C) = [da_c/dX, da_c/dY] per channel from rast_db (the differentials above).
+ *   ls_mip_forward               out (B, H, W, C).
+ *   ls_mip_order                 order (2 B H W for LS_MIP_LINEAR, B H W for LS_MIP_NEAREST) = the items (pixel p at its lower level:
+ *                                p; at its upper level: B H W + p) sorted stably by (level, base tap), items without a gradient last;
+ *                                seg (K + 1), K = sum over the levels of Bt (H_l + 1) (W_l + 1). Depends on uv, uv_da, bias, the
+ *                                SHAPES and the two modes only.
+ *   ls_mip_backward              grad_tex (Bt, Ht, Wt, C) and grad_pyr (the layout of pyr): the gradient of every level BEFORE the fold;
+ *                                grad_uv (B, H, W, 2); grad_lod (B, H, W) = d loss / d lod, which is the gradient of bias;
+ *                                grad_uv_da (B, H, W, 4), which needs grad_lod. Any may be NULL; all given are overwritten.
+ * --------------------------------------------------------------------------------------------- */
+#define LS_MIP_NEAREST 0
+#define LS_MIP_LINEAR 1
+int ls_mip_workspace_bytes(int64_t B, int H, int W, size_t* bytes);
+int ls_mip_build(const float* tex, int64_t Bt, int Ht, int Wt, int C, int Lmax, float* pyr, int device, void* stream);
+int ls_mip_fold(float* grad_tex, int64_t Bt, int Ht, int Wt, int C, int Lmax, float* grad_pyr, int device, void* stream);
+int ls_mip_pixel_differentials(const float* rast, const float* pos, int64_t B, int64_t V, const int32_t* tri, int64_t F, int H, int W,
+                               float* out, int device, void* stream);
+int ls_mip_interpolate_da(const float* attr, int64_t attr_batch, int64_t V, int C, const float* rast, const float* rast_db, int64_t B,
+                          int H, int W, const int32_t* tri, int64_t F, float* out, int device, void* stream);
+int ls_mip_forward(const float* tex, const float* pyr, int64_t Bt, int Ht, int Wt, int C, int Lmax, const float* uv, const float* uv_da,
+                   const float* bias, int64_t B, int H, int W, int mode, int boundary, float* out, int device, void* stream);
+int ls_mip_order(const float* uv, const float* uv_da, const float* bias, int64_t B, int H, int W, int64_t Bt, int Ht, int Wt, int Lmax,
+                 int mode, int boundary, int32_t* order, int32_t* seg, void* ws, size_t ws_bytes, int device, void* stream);
+int ls_mip_backward(const float* tex, const float* pyr, int64_t Bt, int Ht, int Wt, int C, int Lmax, const float* uv, const float* uv_da,
+                    const float* bias, int64_t B, int H, int W, int mode, int boundary, const float* grad_out, const int32_t* order,
+                    const int32_t* seg, float* grad_tex, float* grad_pyr, float* grad_uv, float* grad_lod, float* grad_uv_da, int device,
+                    void* stream);
 
 #ifdef __cplusplus
 }

@@ -195,6 +195,18 @@ _SIGNATURES = {
                                  c_void_p]),
     "ls_texture_backward": (c_int, [c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_int, c_void_p]),
+    "ls_mip_workspace_bytes": (c_int, [c_i64, c_int, c_int, ctypes.POINTER(c_size_t)]),
+    "ls_mip_build": (c_int, [c_void_p, c_i64, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "ls_mip_fold": (c_int, [c_void_p, c_i64, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "ls_mip_pixel_differentials": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "ls_mip_interpolate_da": (c_int, [c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p, c_i64, c_int, c_int, c_void_p, c_i64, c_void_p, c_int,
+                                      c_void_p]),
+    "ls_mip_forward": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int,
+                               c_int, c_void_p, c_int, c_void_p]),
+    "ls_mip_order": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_i64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                             c_void_p, c_size_t, c_int, c_void_p]),
+    "ls_mip_backward": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int,
+                                c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

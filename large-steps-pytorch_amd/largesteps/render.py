@@ -10,6 +10,10 @@ tests/render_statement.py):
     color_aa = antialias(color, rast, pos, tri, pos_gradient_boost=1.0)
     texture(tex, uv, filter_mode='linear', boundary_mode='wrap')    tex (1 or B, Ht, Wt, C), uv (B, H, W, 2); nearest / linear, wrap / clamp /
                                                                zero (csrc/texture.hip, restated by tests/texture_statement.py)
+    out, uv_da = interpolate(attr, rast, tri, rast_db=rast_db, diff_attrs='all')       the attribute's change per pixel step
+    texture(tex, uv, uv_da, filter_mode='linear-mipmap-linear')     the mipmapped lookup (csrc/mip.hip, restated by tests/mip_statement.py);
+                                                               texture_construct_mip(tex) builds a reusable pyramid, pixel_differentials(rast,
+                                                               pos, tri) the differentials of the barycentrics themselves
 
 plus the renderer built on them: `persp_proj`, `SphericalHarmonics`, `NVDRenderer` (same constructor keys, same values as the
 reference's). Conventions: rast = (u, v, z/w, id + 1), 0 for background; an attribute interpolates as u a0 + v a1 + (1 - u - v) a2;
@@ -31,7 +35,7 @@ from . import _native
 from .normals import _plan as _corner_plan
 
 __all__ = ["RasterizeContext", "RasterizeGLContext", "RasterizeCudaContext", "rasterize", "interpolate", "antialias", "texture",
-           "persp_proj", "SphericalHarmonics", "NVDRenderer"]
+           "texture_construct_mip", "pixel_differentials", "persp_proj", "SphericalHarmonics", "NVDRenderer"]
 
 
 class RasterizeContext:
@@ -191,8 +195,9 @@ def rasterize(glctx, pos, tri, resolution, ranges=None, grad_db=True):
     tri : (F, 3) int32 or int64
     resolution : (H, W), each in [1, 4096]
     ranges : must be None (range mode is not supported)
-    grad_db : ignored; rast_db is returned only so that `rasterize(...)[0]` keeps working. It holds zeros (no image-space derivatives
-              are computed) and asking for its gradient raises.
+    grad_db : ignored. rast_db holds zeros (rasterize computes no image-space derivatives) and asking for its gradient raises; it carries
+              the detached pos and tri, from which `interpolate(..., rast_db=rast_db, diff_attrs=...)` computes the differentials when
+              they are wanted (`pixel_differentials`).
 
     rast (B, H, W, 4) = (u, v, z/w, triangle id + 1), 0 for background pixels. Coverage: a pixel is covered iff its centre lies in the
     projected triangle (top-left rule, watertight along shared edges) and z/w is in [-1, 1] (near and far clipping); the nearest
@@ -208,11 +213,96 @@ def rasterize(glctx, pos, tri, resolution, ranges=None, grad_db=True):
     rast, rast_db = _Rasterize.apply(pos, tri, H, W, slot)
     slot.version = rast._version
     _attach_order(rast, slot)
+    rast_db._largesteps_db = _DbSource(pos, tri, rast_db._version)
     return rast, rast_db
 
 
 def _attach_order(rast, slot):
     rast._largesteps_order = slot
+
+
+class _DbSource:
+    """What the zero placeholder `rast_db` of `rasterize` carries: the detached clip-space positions and the faces of its frame, and the
+    differentials once an `interpolate` has asked for them (computed at most once per frame, never kept across a stream capture)."""
+    __slots__ = ("pos", "tri", "pos_version", "version", "db")
+
+    def __init__(self, pos, tri, version):
+        self.pos, self.tri, self.pos_version, self.version, self.db = pos.detach(), tri, pos._version, version, None
+
+
+@_native.retry_on_oom
+def pixel_differentials(rast, pos, tri):
+    """
+    The change of the barycentrics per pixel step: (B, H, W, 4) fp32 = (du/dX, du/dY, dv/dX, dv/dY), X and Y in pixels (one pixel is
+    2 / W in NDC x, 2 / H in NDC y), u and v the perspective-correct weights of corners 0 and 1 as `rasterize` writes them.
+
+    rast : the first output of `rasterize`;  pos, tri : what `rasterize` was given.
+
+    For a covered pixel whose face has clip-space corners p_k = (x_k, y_k, w_k): a_k(Xn, Yn) = A_k Xn + B_k Yn + C_k are the rows of the
+    adjugate of [p_0; p_1; p_2], u = a_0 / s, v = a_1 / s, s = a_0 + a_1 + a_2, and du/dXn = (A_0 - u (A_0 + A_1 + A_2)) / s (likewise v
+    and Yn), times 2 / W (2 / H). Background pixels and degenerate faces (s or the determinant zero or not finite) get 0.
+
+    The result is not differentiable. nvdiffrast propagates a second-order term through its rast_db to pos; this package does not: the
+    level of detail chosen from these differentials is treated as a constant of the geometry.
+    """
+    r, p = _rast(rast), _pos(pos)
+    B, H, W, _ = r.shape
+    if p.shape[0] != B:
+        raise ValueError(f"pos has {p.shape[0]} batches for {B} images")
+    V = p.shape[1]
+    f, narrow, _, _ = _faces(tri, V)
+    F, dev = narrow.shape[0], r.device
+    out = torch.empty((B, H, W, 4), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _native.check(_native.lib().ls_mip_pixel_differentials(_native.ptr(r), _native.ptr(_aligned(p)), B, V, _native.ptr(narrow), F, H, W,
+                                                               _native.ptr(out), dev.index, _native.stream_of(dev)))
+    return out
+
+
+def _resolve_db(rast_db, rast):
+    """the differentials behind a rast_db: an ordinary tensor as it is, the placeholder of `rasterize` through `pixel_differentials`"""
+    if not isinstance(rast_db, torch.Tensor):
+        raise TypeError(f"rast_db must be a torch.Tensor, got {type(rast_db).__name__}")
+    src = getattr(rast_db, "_largesteps_db", None)
+    if src is None or src.version != rast_db._version:
+        if tuple(rast_db.shape) != tuple(rast.shape):
+            raise ValueError(f"rast_db must have the shape of rast {tuple(rast.shape)}, got {tuple(rast_db.shape)}")
+        d = rast_db.detach()
+        return _aligned(d if (d.dtype == torch.float32 and d.is_contiguous()) else d.to(torch.float32).contiguous())
+    if src.pos._version != src.pos_version:
+        raise ValueError("pos was changed in place after rasterize: its rast_db can no longer give the pixel differentials")
+    if torch.cuda.is_current_stream_capturing():
+        return pixel_differentials(rast, src.pos, src.tri)
+    if src.db is None:
+        src.db = pixel_differentials(rast, src.pos, src.tri)
+    return src.db
+
+
+def _attr_da(attr, rast, tri, db, diff_attrs):
+    r = _rast(rast)
+    B, H, W, _ = r.shape
+    a = (attr.unsqueeze(0) if attr.dim() == 2 else attr).detach()
+    if a.dtype != torch.float32 or not a.is_contiguous():
+        a = a.to(torch.float32).contiguous()
+    Ba, V, C = a.shape
+    if isinstance(diff_attrs, str):
+        if diff_attrs != 'all':
+            raise ValueError(f"diff_attrs must be 'all' or a list of channel indices, got {diff_attrs!r}")
+        sel = None
+    else:
+        sel = [int(c) for c in diff_attrs]
+        for c in sel:
+            if not 0 <= c < C:
+                raise IndexError(f"diff_attrs: channel {c} is outside [0, {C})")
+    f, narrow, _, _ = _faces(tri, V)
+    F, dev = narrow.shape[0], r.device
+    out = torch.empty((B, H, W, 2 * C), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _native.check(_native.lib().ls_mip_interpolate_da(_native.ptr(a), Ba, V, C, _native.ptr(r), _native.ptr(db), B, H, W, _native.ptr(narrow), F,
+                                                          _native.ptr(out), dev.index, _native.stream_of(dev)))
+    if sel is None or sel == list(range(C)):
+        return out
+    return torch.cat([out[..., 2 * c:2 * c + 2] for c in sel], dim=-1)
 
 
 class _Interpolate(Function):
@@ -271,22 +361,30 @@ class _Interpolate(Function):
 @_native.retry_on_oom
 def interpolate(attr, rast, tri, rast_db=None, diff_attrs=None):
     """
-    Interpolate vertex attributes over the rasterized images (nvdiffrast.torch.interpolate). Returns (out, None).
+    Interpolate vertex attributes over the rasterized images (nvdiffrast.torch.interpolate). Returns (out, attr_da); attr_da is None
+    unless diff_attrs is given.
 
     attr : (V, C), (1, V, C) (shared by every image, as the reference passes it) or (B, V, C) fp32
     rast : the first output of `rasterize`
     tri : the faces given to `rasterize`
-    rast_db, diff_attrs : must be None (attribute pixel differentials are not computed)
+    rast_db : the second output of `rasterize` (the differentials are then computed from its frame, once, by `pixel_differentials`) or
+              an ordinary (B, H, W, 4) tensor of (du/dX, du/dY, dv/dX, dv/dY), used as given. Needed only with diff_attrs.
+    diff_attrs : None, 'all' or a list of K channel indices in [0, C)
 
     out (B, H, W, C) = u a0 + v a1 + (1 - u - v) a2 per covered pixel, 0 for background. Gradients flow to attr and to rast[..., :2].
+    attr_da (B, H, W, 2 K) = [da_c/dX, da_c/dY] per selected channel, in order: da/dX = du/dX (a0 - a2) + dv/dX (a1 - a2), 0 for
+    background. For a two-channel uv attribute it is the uv_da of `texture`. It is not differentiable (see `pixel_differentials`).
     """
-    if diff_attrs is not None:
-        raise NotImplementedError("largesteps.render.interpolate: diff_attrs (attribute pixel differentials) is not supported")
+    if diff_attrs is not None and rast_db is None:
+        raise ValueError("largesteps.render.interpolate: diff_attrs needs rast_db (the second output of rasterize)")
     F = tri.shape[0] if isinstance(tri, torch.Tensor) and tri.dim() == 2 else 0
     slot = _order_slot(rast, F)
     out = _Interpolate.apply(attr, rast, tri, slot)
     _attach_order(rast, slot)
-    return out, None
+    if diff_attrs is None:
+        return out, None
+    with torch.no_grad():
+        return out, _attr_da(attr, rast, tri, _resolve_db(rast_db, rast), diff_attrs)
 
 
 class _Antialias(Function):
@@ -361,7 +459,7 @@ def antialias(color, rast, pos, tri, topology_hash=None, pos_gradient_boost=1.0)
 
 _FILTER_MODES = {'nearest': 0, 'linear': 1, 'auto': 1}                  # LS_TEXTURE_* of the header
 _BOUNDARY_MODES = {'wrap': 0, 'clamp': 1, 'zero': 2}
-_MIP_FILTER_MODES = ('linear-mipmap-nearest', 'linear-mipmap-linear')
+_MIP_FILTER_MODES = {'linear-mipmap-nearest': 0, 'linear-mipmap-linear': 1}     # LS_MIP_* of the header
 TEXTURE_MAX_SIZE = 8192                                                 # texels per side
 TEXTURE_MAX_CHANNELS = 32
 
@@ -450,6 +548,227 @@ class _Texture(Function):
         return (gt.view(ctx.shapes[0]) if need_tex else None), (gu.view(ctx.shapes[1]) if need_uv else None), None, None, None
 
 
+def _mip_last_level(Ht, Wt, max_mip_level=None):
+    """the last level of the pyramid of an Ht x Wt texture: 1 x 1, or max_mip_level if that comes first. Every level that is halved
+    must have sides that are 1 or even."""
+    if max_mip_level is not None and int(max_mip_level) < 0:
+        raise ValueError(f"max_mip_level must not be negative, got {max_mip_level}")
+    h, w, level = int(Ht), int(Wt), 0
+    while (h > 1 or w > 1) and (max_mip_level is None or level < int(max_mip_level)):
+        if (h > 1 and h % 2) or (w > 1 and w % 2):
+            raise ValueError(f"mip level {level} is {h} x {w} texels: each side must be 1 or even to build level {level + 1} "
+                             f"(pass max_mip_level={level} to stop here)")
+        h, w, level = max(h // 2, 1), max(w // 2, 1), level + 1
+    return level
+
+
+def _mip_texels(Ht, Wt, first, last):
+    """texels per batch entry of levels first .. last"""
+    return sum(max(Ht >> l, 1) * max(Wt >> l, 1) for l in range(first, last + 1))
+
+
+class _Mip:
+    """The opaque result of `texture_construct_mip`: levels 1 .. Lmax of one texture in one packed device buffer, and the identity of the
+    texture they were built from."""
+    __slots__ = ("shape", "Lmax", "pyr", "version", "ptr")
+
+    def __init__(self, tex, Lmax, pyr):
+        self.shape, self.Lmax, self.pyr, self.version, self.ptr = tuple(tex.shape), Lmax, pyr, tex._version, tex.data_ptr()
+
+    def check(self, tex):
+        if tuple(tex.shape) != self.shape or tex.data_ptr() != self.ptr or tex._version != self.version:
+            raise ValueError("the mip object is stale: it was built from another texture, or the texture was changed in place since; "
+                             "call texture_construct_mip again (or pass mip=None)")
+
+
+def _check_tex(tex):
+    if not isinstance(tex, torch.Tensor):
+        raise TypeError(f"tex must be a torch.Tensor, got {type(tex).__name__}")
+    if tex.dtype != torch.float32:
+        raise TypeError(f"tex must be float32, got {tex.dtype}")
+    if tex.dim() != 4:
+        raise ValueError(f"tex must be (1 or B, Ht, Wt, C), got {tuple(tex.shape)}")
+    Bt, Ht, Wt, C = tex.shape
+    if Bt < 1:
+        raise ValueError(f"tex must not be empty, got {tuple(tex.shape)}")
+    if not (1 <= Ht <= TEXTURE_MAX_SIZE and 1 <= Wt <= TEXTURE_MAX_SIZE):
+        raise ValueError(f"the texture must be between 1 and {TEXTURE_MAX_SIZE} texels a side, got {Ht} x {Wt}")
+    if not 1 <= C <= TEXTURE_MAX_CHANNELS:
+        raise ValueError(f"the texture must have between 1 and {TEXTURE_MAX_CHANNELS} channels, got {C}")
+
+
+def _build_pyramid(t, Lmax):
+    """levels 1 .. Lmax of the contiguous texture t, packed"""
+    Bt, Ht, Wt, C = t.shape
+    dev = t.device
+    pyr = torch.empty(max(Bt * _mip_texels(Ht, Wt, 1, Lmax) * C, 4), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _native.check(_native.lib().ls_mip_build(_native.ptr(t), Bt, Ht, Wt, C, Lmax, _native.ptr(pyr), dev.index, _native.stream_of(dev)))
+    return pyr
+
+
+@_native.retry_on_oom
+def texture_construct_mip(tex, max_mip_level=None, cube_mode=False):
+    """
+    The mipmap pyramid of a texture (nvdiffrast.torch.texture_construct_mip): an opaque object for `texture(..., mip=...)`, worth
+    building when one texture is looked up several times unchanged.
+
+    Level 0 is tex; level l + 1 has max(W_l / 2, 1) x max(H_l / 2, 1) texels, each the mean of its 2 x 2 children (2 x 1 or 1 x 2 when
+    one side is already 1), fp32 as ((c00 + c10) + (c01 + c11)) * 0.25 and (a + b) * 0.5. The last level is 1 x 1, or max_mip_level if
+    that comes first; a level that is halved must have sides that are 1 or even (ValueError). The object remembers the texture's
+    version: after an in-place change of tex it is stale and `texture` raises ValueError. Gradients do not flow through the object
+    itself -- `texture` sends the gradient of every level back to tex on its own.
+    """
+    if cube_mode:
+        raise NotImplementedError("largesteps.render.texture_construct_mip: cube_mode=True (cube maps) is not supported")
+    _check_tex(tex)
+    Lmax = _mip_last_level(tex.shape[1], tex.shape[2], max_mip_level)
+    if not tex.is_cuda:
+        raise NotImplementedError("largesteps.render.texture_construct_mip: the mipmap pyramid needs a HIP device")
+    t = tex.detach()
+    t = _aligned(t if t.is_contiguous() else t.contiguous())
+    return _Mip(tex, Lmax, _build_pyramid(t, Lmax))
+
+
+def _version_key(t):
+    return None if t is None else (t._version, t.data_ptr(), tuple(t.shape), tuple(t.stride()))
+
+
+class _MipOrder:
+    """The (pixel, level) items of one mipmapped lookup sorted by (level, base tap) -- the order the gradient of the pyramid sums in. It
+    depends on uv, uv_da, the bias, the texture's shape and the modes, not on the texture's values: cached on the uv tensor like
+    `_TexelOrder`, keyed by the versions of all three tensors."""
+    __slots__ = ("key", "order", "seg")
+
+    def __init__(self, key):
+        self.key, self.order, self.seg = key, None, None
+
+    def get(self, u, da, b, Bt, Ht, Wt, Lmax, mode, bnd):
+        if self.order is None:
+            B, H, W, _ = u.shape
+            dev = u.device
+            n = ctypes.c_size_t(0)
+            _native.check(_native.lib().ls_mip_workspace_bytes(B, H, W, ctypes.byref(n)))
+            ws = torch.empty(n.value, dtype=torch.uint8, device=dev)
+            order = torch.empty((2 if mode == 1 else 1) * B * H * W, dtype=torch.int32, device=dev)
+            nk = Bt * sum((max(Ht >> l, 1) + 1) * (max(Wt >> l, 1) + 1) for l in range(Lmax + 1))
+            seg = torch.empty(nk + 1, dtype=torch.int32, device=dev)
+            with torch.cuda.device(dev):
+                _native.check(_native.lib().ls_mip_order(_native.ptr(u), _native.ptr(da), _native.ptr(b), B, H, W, Bt, Ht, Wt, Lmax, mode, bnd,
+                                                         _native.ptr(order), _native.ptr(seg), _native.ptr(ws), ws.numel(), dev.index,
+                                                         _native.stream_of(dev)))
+            self.order, self.seg = order, seg
+        return self.order, self.seg
+
+
+def _mip_order_slot(uv, uv_da, bias, Bt, Ht, Wt, Lmax, mode, bnd):
+    if torch.cuda.is_current_stream_capturing():            # as for _TexelOrder: a replay sorts what it finds
+        return _MipOrder(None)
+    key = (_version_key(uv), _version_key(uv_da), _version_key(bias), Bt, Ht, Wt, Lmax, mode, bnd)
+    slot = getattr(uv, "_largesteps_mip_order", None)
+    if slot is not None and slot.key == key:
+        return slot
+    return _MipOrder(key)
+
+
+def _plain(t, align):
+    """detached, fp32-contiguous and aligned for the kernels' vector loads (None stays None)"""
+    if t is None:
+        return None
+    d = t.detach()
+    d = d if d.is_contiguous() else d.contiguous()
+    return d if d.data_ptr() % align == 0 else d.clone()
+
+
+class _TextureMip(Function):
+    @staticmethod
+    def forward(ctx, tex, uv, uv_da, bias, pyr, Lmax, mode, bnd, slot):
+        t, u, da, b = _plain(tex, 16), _plain(uv, 16), _plain(uv_da, 16), _plain(bias, 4)
+        Bt, Ht, Wt, C = t.shape
+        B, H, W, _ = u.shape
+        dev = u.device
+        if pyr is None:
+            pyr = _build_pyramid(t, Lmax)
+        out = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().ls_mip_forward(_native.ptr(t), _native.ptr(pyr), Bt, Ht, Wt, C, Lmax, _native.ptr(u), _native.ptr(da),
+                                                       _native.ptr(b), B, H, W, mode, bnd, _native.ptr(out), dev.index, _native.stream_of(dev)))
+        ctx.save_for_backward(t, pyr, u, da, b)
+        ctx.conf = (Lmax, mode, bnd)
+        ctx.slot = slot
+        ctx.shapes = (tuple(tex.shape), tuple(uv.shape), None if uv_da is None else tuple(uv_da.shape), None if bias is None else tuple(bias.shape))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        need_tex, need_uv, need_da, need_bias = ctx.needs_input_grad[:4]
+        if not (need_tex or need_uv or need_da or need_bias):
+            return (None,) * 9
+        t, pyr, u, da, b = ctx.saved_tensors
+        Lmax, mode, bnd = ctx.conf
+        Bt, Ht, Wt, C = t.shape
+        B, H, W, _ = u.shape
+        dev = u.device
+        g = _aligned(g.to(torch.float32).contiguous())
+        gt = torch.empty_like(t) if need_tex else None
+        gpyr = torch.empty_like(pyr) if need_tex else None
+        gu = torch.empty_like(u) if need_uv else None
+        glod = torch.empty((B, H, W), dtype=torch.float32, device=dev) if (need_da or need_bias) else None
+        gda = torch.empty_like(da) if need_da else None
+        order = seg = None
+        if need_tex:
+            order, seg = ctx.slot.get(u, da, b, Bt, Ht, Wt, Lmax, mode, bnd)
+        lib = _native.lib()
+        with torch.cuda.device(dev):
+            st = _native.stream_of(dev)
+            _native.check(lib.ls_mip_backward(_native.ptr(t), _native.ptr(pyr), Bt, Ht, Wt, C, Lmax, _native.ptr(u), _native.ptr(da), _native.ptr(b),
+                                              B, H, W, mode, bnd, _native.ptr(g), _native.ptr(order), _native.ptr(seg), _native.ptr(gt),
+                                              _native.ptr(gpyr), _native.ptr(gu), _native.ptr(glod), _native.ptr(gda), dev.index, st))
+            if need_tex and Lmax > 0:
+                _native.check(lib.ls_mip_fold(_native.ptr(gt), Bt, Ht, Wt, C, Lmax, _native.ptr(gpyr), dev.index, st))
+        s_tex, s_uv, s_da, s_b = ctx.shapes
+        return ((gt.view(s_tex) if need_tex else None), (gu.view(s_uv) if need_uv else None), (gda.view(s_da) if need_da else None),
+                (glod.view(s_b) if need_bias else None), None, None, None, None, None)
+
+
+def _check_mip_inputs(uv, uv_da, mip_level_bias):
+    """the level-of-detail inputs of a mipmapped lookup against uv (B, H, W, 2)"""
+    if uv_da is None and mip_level_bias is None:
+        raise ValueError("largesteps.render.texture: the mipmap filter modes need uv_da or mip_level_bias (or both) to choose a level")
+    B, H, W, _ = uv.shape
+    for t, what, shape in ((uv_da, "uv_da", (B, H, W, 4)), (mip_level_bias, "mip_level_bias", (B, H, W))):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what} must be a torch.Tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{what} must be float32, got {t.dtype}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{what} must be {shape}, got {tuple(t.shape)}")
+        if t.device != uv.device:
+            raise ValueError(f"{what} is on {t.device}, uv on {uv.device}")
+
+
+def _texture_mip(tex, uv, uv_da, mip_level_bias, mip, mode, bnd, max_mip_level):
+    _check_mip_inputs(uv, uv_da, mip_level_bias)
+    Bt, Ht, Wt, C = tex.shape
+    if 2 * uv.shape[0] * uv.shape[1] * uv.shape[2] >= 2 ** 31 - 1:
+        raise OverflowError(f"uv has {uv.numel() // 2} pixels: the mipmapped lookup indexes two items per pixel with int32")
+    if mip is not None:
+        if not isinstance(mip, _Mip):
+            raise TypeError(f"mip must come from texture_construct_mip, got {type(mip).__name__}")
+        mip.check(tex)
+        Lmax = mip.Lmax if max_mip_level is None else min(mip.Lmax, _mip_last_level(Ht, Wt, max_mip_level))
+        pyr = mip.pyr
+    else:
+        Lmax, pyr = _mip_last_level(Ht, Wt, max_mip_level), None
+    slot = _mip_order_slot(uv, uv_da, mip_level_bias, Bt, Ht, Wt, Lmax, mode, bnd)
+    out = _TextureMip.apply(tex, uv, uv_da, mip_level_bias, pyr, Lmax, mode, bnd, slot)
+    if slot.key is not None:
+        uv._largesteps_mip_order = slot
+    return out
+
+
 def _texture_cpu(tex, uv):
     """the lookup in plain torch, linear + wrap, forward only: what a CPU tensor gets (the device kernel keeps this operation order)"""
     with torch.no_grad():
@@ -474,12 +793,23 @@ def _texture_cpu(tex, uv):
 @_native.retry_on_oom
 def texture(tex, uv, uv_da=None, mip_level_bias=None, mip=None, filter_mode='linear', boundary_mode='wrap', max_mip_level=None):
     """
-    2D texture lookup (nvdiffrast.torch.texture without mipmaps): tex (1 or B, Ht, Wt, C), uv (B, H, W, 2) -> (B, H, W, C), all fp32.
+    2D texture lookup (nvdiffrast.torch.texture): tex (1 or B, Ht, Wt, C), uv (B, H, W, 2) -> (B, H, W, C), all fp32.
 
-    filter_mode : 'linear' (bilinear), 'nearest', 'auto' (= 'linear': no mipmaps). The mipmap modes raise NotImplementedError.
+    filter_mode : 'linear' (bilinear), 'nearest', 'auto' (= 'linear'), 'linear-mipmap-linear' (trilinear), 'linear-mipmap-nearest'.
     boundary_mode : 'wrap', 'clamp' or 'zero', applied to each tap index: modulo the size; clamped to [0, size - 1]; a tap outside
                     reads 0 and receives no gradient. 'cube' raises NotImplementedError.
-    uv_da, mip_level_bias, mip, max_mip_level : accepted and ignored.
+    uv_da, mip_level_bias, mip, max_mip_level : the mipmap modes' inputs (below); accepted and ignored by the other modes.
+
+    Mipmap modes (HIP device only). uv_da (B, H, W, 4) = (du/dX, du/dY, dv/dX, dv/dY) in texture units per pixel (the second output of
+    `interpolate(uv_attr, rast, tri, rast_db, diff_attrs='all')`), mip_level_bias (B, H, W); one may be None, not both. mip: a pyramid
+    from `texture_construct_mip` (built here otherwise; see there for its rules), max_mip_level: the last level Lmax to use.
+    With sx = du/dX Wt, sy = du/dY Wt, tx = dv/dX Ht, ty = dv/dY Ht, A = sx^2 + tx^2, B = sy^2 + ty^2, Cc = sx sy + tx ty:
+    m = (A + B) / 2 + sqrt((A - B)^2 / 4 + Cc^2) is the squared major axis of the pixel's footprint in level-0 texels and
+    lod = log2(m) / 2 + bias (the bias alone without uv_da), clamped to [0, Lmax]. 'linear-mipmap-linear': l0 = floor(lod),
+    f = lod - l0, out = c0 + (c1 - c0) f with c_l the bilinear lookup of level l (when f = 0 or l0 = Lmax only l0 is read);
+    'linear-mipmap-nearest': the level min(floor(lod + 1/2), Lmax). A non-finite uv, uv_da or bias gives 0 and no gradient. Gradients
+    flow to tex through every level, to uv from both levels, and to mip_level_bias and uv_da through d out / d lod = c1 - c0 (zero where
+    lod was clamped and in 'linear-mipmap-nearest').
 
     Texel (i, j) has its centre at ((i + 0.5) / Wt, (j + 0.5) / Ht). Linear: x = u Wt - 0.5, i0 = floor(x), fx = x - i0 (likewise y),
     out = top + (bot - top) fy with top = t00 + (t10 - t00) fx, bot = t01 + (t11 - t01) fx. Nearest: the texel (floor(u Wt), floor(v Ht)).
@@ -490,11 +820,12 @@ def texture(tex, uv, uv_da=None, mip_level_bias=None, mip=None, filter_mode='lin
     and version. Tensors on a HIP device take the native path whether or not a gradient is wanted; CPU tensors get a plain-torch
     forward without gradient, for 'linear' + 'wrap' only.
     """
-    if filter_mode in _MIP_FILTER_MODES:
-        raise NotImplementedError(f"largesteps.render.texture: filter_mode={filter_mode!r} (mipmaps) is not supported")
+    mipmapped = filter_mode in _MIP_FILTER_MODES
+    if mipmapped and not (isinstance(uv, torch.Tensor) and uv.is_cuda and isinstance(tex, torch.Tensor) and tex.is_cuda):
+        raise NotImplementedError(f"largesteps.render.texture: filter_mode={filter_mode!r} (mipmaps) needs a HIP device")
     if boundary_mode == 'cube':
         raise NotImplementedError("largesteps.render.texture: boundary_mode='cube' (cube maps) is not supported")
-    if filter_mode not in _FILTER_MODES:
+    if filter_mode not in _FILTER_MODES and not mipmapped:
         raise ValueError(f"filter_mode must be one of {sorted(_FILTER_MODES)}, got {filter_mode!r}")
     if boundary_mode not in _BOUNDARY_MODES:
         raise ValueError(f"boundary_mode must be one of {sorted(_BOUNDARY_MODES)}, got {boundary_mode!r}")
@@ -521,6 +852,8 @@ def texture(tex, uv, uv_da=None, mip_level_bias=None, mip=None, filter_mode='lin
         raise OverflowError(f"uv has {B * H * W} pixels: the kernels index them with int32")
     if tex.device != uv.device:
         raise ValueError(f"tex is on {tex.device}, uv on {uv.device}")
+    if mipmapped:
+        return _texture_mip(tex, uv, uv_da, mip_level_bias, mip, _MIP_FILTER_MODES[filter_mode], _BOUNDARY_MODES[boundary_mode], max_mip_level)
     filt, bnd = _FILTER_MODES[filter_mode], _BOUNDARY_MODES[boundary_mode]
     if not uv.is_cuda:
         if (filt, bnd) != (1, 0):
