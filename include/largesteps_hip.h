@@ -641,12 +641,37 @@ int ls_remesh_destroy(void* handle);
  *   ls_mesh_distance_max      out_sqd[0] (fp64, device) = max over the n points of their squared distance (0 for n = 0). ASYNC.
  *   ls_mesh_distance_destroy  synchronises the device (queries may run on any stream), then gives the handle's buffer back to the
  *                             scratch pool (ls_release_scratch empties it). NULL is accepted.
+ * The gradient of sqrD (no second derivatives). The closest point is C = sum_k w_k V[F[I, k]]; the weights w follow from the same
+ * region / segment tests as C. With d = p - C and g the incoming gradient of sqrD: d/dp = 2 g d, d/dV[F[I, k]] = -2 g w_k d (C minimises
+ * over the face, so no derivative of w enters; on a tie this is the subgradient of the face the tie rule chose). Every term is formed in
+ * fp64 and rounded to fp32 once; the vertex gradient is summed without float atomics in one fixed order (points of a face in ascending
+ * id, a vertex's corners in the rank order of ls_corner_ranks): bitwise reproducible, no host synchronisation, capturable.
+ *   ls_mesh_distance_weights  W (n, 3) fp64 = the weights of point P[i] on face I[i] of the handle's mesh. I must come from
+ *                             ls_mesh_distance_query on the same handle and positions; it is not range-checked on the host (that would
+ *                             synchronise): an I outside [0, F) reads nothing and gives NaN weights. ASYNC.
+ *   ls_mesh_distance_backward_workspace_bytes  the workspace of ls_mesh_distance_backward for n points and F faces.
+ *   ls_mesh_distance_backward P, I, C as the query took and returned them, g (n) fp64 the gradient of sqrD; vptr (V + 1) and
+ *                             corner_order (3 F) the ranking of ls_corner_ranks over the handle's faces (corner_order: rank -> corner,
+ *                             the inverse of its cpos). gP (n, 3) fp32 and gV (V, 3) fp32 may each be NULL; I, vptr, corner_order and
+ *                             the workspace are needed for gV only. A point whose I is outside [0, F) adds nothing to gV (I must come
+ *                             from the query, as above). LS_E_INVALID for a null required pointer, LS_E_WORKSPACE for a workspace
+ *                             below ls_mesh_distance_backward_workspace_bytes(n, F). ASYNC.
+ *   ls_mesh_distance_update   new positions verts (V, 3) fp32 for the handle's faces: the bounds, the slack and the LBVH are rebuilt in
+ *                             the handle's buffer (no allocation, no device synchronisation); afterwards the handle answers exactly as
+ *                             a fresh one built from verts. Queries of the handle in flight on other streams must have finished. SYNC
+ *                             (the stream is synchronised: the bounds come to the host).
  * --------------------------------------------------------------------------------------------- */
 int ls_mesh_distance_create(const float* verts, int64_t V, const void* faces, int idx_bytes, int64_t F, int device, void* stream,
                             void** handle);
 int ls_mesh_distance_query(void* handle, const float* P, int64_t n, double* sqrD, int64_t* I, double* C, void* stream);
 int ls_mesh_distance_max(void* handle, const float* P, int64_t n, double* out_sqd, void* stream);
 int ls_mesh_distance_destroy(void* handle);
+int ls_mesh_distance_weights(void* handle, const float* P, int64_t n, const int64_t* I, double* W, void* stream);
+int ls_mesh_distance_backward_workspace_bytes(int64_t n, int64_t F, size_t* bytes);
+int ls_mesh_distance_backward(void* handle, const float* P, int64_t n, const int64_t* I, const double* C, const double* g,
+                              const int32_t* vptr, const int32_t* corner_order, float* gP, float* gV, void* ws, size_t ws_bytes,
+                              void* stream);
+int ls_mesh_distance_update(void* handle, const float* verts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * AdamUniform step (optimize.py:18-41) on n contiguous fp32 elements, two kernels, no host sync:

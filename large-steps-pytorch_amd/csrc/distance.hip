@@ -13,7 +13,16 @@
 //     remesher's walk does not, beyond about 170 diagonals).
 // The directed maximum reduces max_p d2(p) per wave and adds it with an integer atomicMax on the bits: for non-negative doubles the
 // bit order is the value order, so the result does not depend on the schedule.
+//
+// The gradient of sqrD ("Gradient"). With C the closest point on face I = (a, b, c), C = w_a a + w_b b + w_c c: the
+// weights w come from the same fp64 region / segment tests that produce C (md_weights below mirrors md_point_tri branch by branch), one
+// face per point, after the walk. C minimises over the face, so no derivative of w enters (envelope theorem): with d = p - C and g the
+// incoming gradient, d sqrD / dp = 2 g d and d sqrD / d V[F[I, k]] = -2 g w_k d, each term formed in fp64 and rounded to fp32 once.
+// The vertex gradient has no float atomics: the points are grouped by their face (groupby.h: stable, so ascending point id within a face),
+// seg_sum adds the 9 terms of a face's points in that order (a thread up to 64 points, else the wave lane-strided and the xor butterfly),
+// and a thread per vertex adds its corners' face rows in the rank order of meshface.h. Bitwise reproducible, no host synchronisation.
 #include "common.h"
+#include "groupby.h"
 #include "lbvh.h"
 #include "meshface.h"
 #include <algorithm>
@@ -106,6 +115,142 @@ __global__ __launch_bounds__(BLOCK) void k_md_query(const float* __restrict__ Q,
     if ((threadIdx.x & (WAVE - 1)) == 0) atomicMax(dmax, (u64)__double_as_longlong(d2));
 }
 
+// ---- the barycentric weights of the closest point ------------------------------------------------------------------------------
+// the weights of lbvh_point_tri's point on (a, b, c): its tests, in its order, with its quotients
+__device__ inline void md_tri_weights(const double p[3], const double a[3], const double b[3], const double c[3], double w[3]) {
+    const double ab[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, ac[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+    const double ap[3] = {p[0] - a[0], p[1] - a[1], p[2] - a[2]};
+    const double d1 = lbvh_dd(ab[0], ab[1], ab[2], ap[0], ap[1], ap[2]), d2 = lbvh_dd(ac[0], ac[1], ac[2], ap[0], ap[1], ap[2]);
+    if (d1 <= 0.0 && d2 <= 0.0) { w[0] = 1.0; w[1] = 0.0; w[2] = 0.0; return; }
+    const double bp[3] = {p[0] - b[0], p[1] - b[1], p[2] - b[2]};
+    const double d3 = lbvh_dd(ab[0], ab[1], ab[2], bp[0], bp[1], bp[2]), d4 = lbvh_dd(ac[0], ac[1], ac[2], bp[0], bp[1], bp[2]);
+    if (d3 >= 0.0 && d4 <= d3) { w[0] = 0.0; w[1] = 1.0; w[2] = 0.0; return; }
+    const double vc = d1 * d4 - d3 * d2;
+    if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {
+        const double v = d1 / (d1 - d3);
+        w[0] = 1.0 - v; w[1] = v; w[2] = 0.0;
+        return;
+    }
+    const double cp[3] = {p[0] - c[0], p[1] - c[1], p[2] - c[2]};
+    const double d5 = lbvh_dd(ab[0], ab[1], ab[2], cp[0], cp[1], cp[2]), d6 = lbvh_dd(ac[0], ac[1], ac[2], cp[0], cp[1], cp[2]);
+    if (d6 >= 0.0 && d5 <= d6) { w[0] = 0.0; w[1] = 0.0; w[2] = 1.0; return; }
+    const double vb = d5 * d2 - d1 * d6;
+    if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {
+        const double u = d2 / (d2 - d6);
+        w[0] = 1.0 - u; w[1] = 0.0; w[2] = u;
+        return;
+    }
+    const double va = d3 * d6 - d5 * d4;
+    if (va <= 0.0 && d4 - d3 >= 0.0 && d5 - d6 >= 0.0) {
+        const double u = (d4 - d3) / ((d4 - d3) + (d5 - d6));
+        w[0] = 0.0; w[1] = 1.0 - u; w[2] = u;
+        return;
+    }
+    const double den = 1.0 / ((va + vb) + vc), v = vb * den, u = vc * den;
+    w[0] = (1.0 - v) - u; w[1] = v; w[2] = u;
+}
+// the weights of md_point_seg's point on the two ends of the segment a b
+__device__ __forceinline__ void md_seg_weights(const double p[3], const double a[3], const double b[3], double& wa, double& wb) {
+    const double ab[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
+    const double t = lbvh_dd(p[0] - a[0], p[1] - a[1], p[2] - a[2], ab[0], ab[1], ab[2]), l = lbvh_dd(ab[0], ab[1], ab[2], ab[0], ab[1], ab[2]);
+    if (t <= 0.0) { wa = 1.0; wb = 0.0; }
+    else if (t >= l) { wa = 0.0; wb = 1.0; }
+    else { const double s = t / l; wa = 1.0 - s; wb = s; }
+}
+// the weights of md_point_tri's point: the guard, and on a degenerate face the segment md_point_tri picks (ab, bc, ca; a later one only
+// when strictly closer), the corner off that segment getting 0
+__device__ inline void md_weights(const double p[3], const double a[3], const double b[3], const double c[3], double w[3]) {
+    const double ab[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, ac[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+    const double cx = ab[1] * ac[2] - ab[2] * ac[1], cy = ab[2] * ac[0] - ab[0] * ac[2], cz = ab[0] * ac[1] - ab[1] * ac[0];
+    double r[3], s[3], u0, u1;
+    if ((cx * cx + cy * cy) + cz * cz > 0.0) {
+        lbvh_point_tri(p, a, b, c, r);
+        if (isfinite(r[0]) && isfinite(r[1]) && isfinite(r[2])) { md_tri_weights(p, a, b, c, w); return; }
+    }
+    md_point_seg(p, a, b, r);
+    double d = md_d2(p, r);
+    md_seg_weights(p, a, b, u0, u1);
+    w[0] = u0; w[1] = u1; w[2] = 0.0;
+    md_point_seg(p, b, c, s);
+    double e = md_d2(p, s);
+    if (e < d) { d = e; md_seg_weights(p, b, c, u0, u1); w[0] = 0.0; w[1] = u0; w[2] = u1; }
+    md_point_seg(p, c, a, s);
+    e = md_d2(p, s);
+    if (e < d) { md_seg_weights(p, c, a, u0, u1); w[0] = u1; w[1] = 0.0; w[2] = u0; }
+}
+
+// one thread per point: W[i] = the weights of point i on face I[i]; an I outside [0, T) gives NaN weights (and reads nothing)
+__global__ __launch_bounds__(BLOCK) void k_md_weights(const float* __restrict__ Q, int n, const float* __restrict__ P, const int* __restrict__ faces, int T,
+                                                      const int64_t* __restrict__ I, double* __restrict__ W) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int64_t f = I[i];
+    double w[3];
+    if (f < 0 || f >= T) w[0] = w[1] = w[2] = __longlong_as_double(0x7ff8000000000000ll);
+    else {
+        const double p[3] = {Q[3 * (size_t)i], Q[3 * (size_t)i + 1], Q[3 * (size_t)i + 2]};
+        double a[3], b[3], c[3];
+        for (int k = 0; k < 3; ++k) { a[k] = P[3 * (size_t)faces[3 * f] + k]; b[k] = P[3 * (size_t)faces[3 * f + 1] + k]; c[k] = P[3 * (size_t)faces[3 * f + 2] + k]; }
+        md_weights(p, a, b, c, w);
+    }
+    W[3 * (size_t)i] = w[0]; W[3 * (size_t)i + 1] = w[1]; W[3 * (size_t)i + 2] = w[2];
+}
+
+// ---- the gradient ----------------------------------------------------------------------------------------------------------------
+// gP[i] = fl32(2 g_i (p_i - C_i)), fp64 until the one rounding
+__global__ __launch_bounds__(BLOCK) void k_md_grad_points(const float* __restrict__ Q, const double* __restrict__ C, const double* __restrict__ g, int n,
+                                                          float* __restrict__ gP) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const double s = 2.0 * g[i];
+    for (int q = 0; q < 3; ++q) gP[3 * (size_t)i + q] = (float)(s * ((double)Q[3 * (size_t)i + q] - C[3 * (size_t)i + q]));
+}
+// the group-by key of a point: its face, or T ("no group") for an I outside [0, T)
+__global__ __launch_bounds__(BLOCK) void k_md_keys(const int64_t* __restrict__ I, int n, int T, int* __restrict__ keys) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int64_t f = I[i];
+    keys[i] = (f < 0 || f >= T) ? T : (int)f;
+}
+// rows[f][3 k + q] = sum over the points of face f, in sorted order, of fl32(-(2 g w_k) d_q): the G of seg_sum
+struct MdRows {
+    const float* __restrict__ Q; const double* __restrict__ C; const double* __restrict__ g; const double* __restrict__ W;
+    const int* __restrict__ order; const int* __restrict__ seg; float* __restrict__ rows;
+    __device__ __forceinline__ int count(int64_t key) const { return seg[key + 1] - seg[key]; }
+    __device__ __forceinline__ void walk(int64_t key, int start, int step, float (&acc)[9]) const {
+        const int e = seg[key + 1];
+        for (int j = seg[key] + start; j < e; j += step) {
+            const size_t i = (size_t)order[j];
+            const double s = 2.0 * g[i];
+            const double d[3] = {(double)Q[3 * i] - C[3 * i], (double)Q[3 * i + 1] - C[3 * i + 1], (double)Q[3 * i + 2] - C[3 * i + 2]};
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double sw = s * W[3 * i + k];
+#pragma unroll
+                for (int q = 0; q < 3; ++q) acc[3 * k + q] += (float)(-(sw * d[q]));
+            }
+        }
+    }
+    __device__ __forceinline__ void store(int64_t key, const float (&acc)[9]) const {
+#pragma unroll
+        for (int q = 0; q < 9; ++q) rows[key * 9 + q] = acc[q];
+    }
+};
+__global__ __launch_bounds__(256) void k_md_face_rows(MdRows r, int64_t T) { seg_sum<9>(T, r); }
+// gV[v] = the (x, y, z) of the vertex's corners in its faces' rows, added in rank order (0 for a vertex without faces)
+__global__ __launch_bounds__(256) void k_md_gather_verts(const float* __restrict__ rows, const int* __restrict__ vptr, const int* __restrict__ order, int64_t V,
+                                                         float* __restrict__ gV) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= V) return;
+    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+    for (int r = vptr[v]; r < vptr[v + 1]; ++r) {
+        const int c = order[r];
+        const float* row = rows + (size_t)(c / 3) * 9 + 3 * (c % 3);
+        s0 += row[0]; s1 += row[1]; s2 += row[2];
+    }
+    gV[3 * v] = s0; gV[3 * v + 1] = s1; gV[3 * v + 2] = s2;
+}
+
 // ---- the handle ----------------------------------------------------------------------------------------------------------------
 struct MeshDistanceHandle {
     int device = 0, V = 0, T = 0;
@@ -145,6 +290,18 @@ static int md_alloc(MeshDistanceHandle* H) {
     H->bvh.bb = (unsigned*)(H->small + 8);
     return LS_OK;
 }
+// the bounds, the slack and the LBVH of the positions in H->pos, in the handle's buffer; the stream is synchronised
+static int md_build(MeshDistanceHandle* H, hipStream_t st) {
+    float lo[3], hi[3];
+    int rc = lbvh_bounds(H->pos, H->V, H->bvh, st, lo, hi);
+    if (rc) return rc;
+    double M = 0.0;
+    for (int q = 0; q < 3; ++q) M = std::max(M, std::max(std::fabs((double)lo[q]), std::fabs((double)hi[q])));
+    H->slack = MD_SLACK * M;
+    if ((rc = lbvh_build(H->pos, H->faces, H->T, 0.0f, H->bvh, st))) return rc;
+    LS_HIP(hipStreamSynchronize(st));
+    return LS_OK;
+}
 extern "C" int ls_mesh_distance_create(const float* verts, int64_t V, const void* faces, int idx_bytes, int64_t F, int device, void* stream,
                                        void** handle) {
     LS_REQUIRE(handle, LS_E_INVALID, "ls_mesh_distance_create: null handle pointer");
@@ -172,15 +329,19 @@ extern "C" int ls_mesh_distance_create(const float* verts, int64_t V, const void
     if (!faces_in(faces, idx_bytes, n, V, H->faces, H->small, st, &bad))
         return fail(hip_fail(hipGetLastError(), "ls_mesh_distance_create", __FILE__, __LINE__));
     if (bad) { set_error("mesh distance: a face index is outside [0, %lld)", (long long)V); return fail(LS_E_INDEX); }
-    float lo[3], hi[3];
-    if ((rc = lbvh_bounds(H->pos, H->V, H->bvh, st, lo, hi))) return fail(rc);
-    double M = 0.0;
-    for (int q = 0; q < 3; ++q) M = std::max(M, std::max(std::fabs((double)lo[q]), std::fabs((double)hi[q])));
-    H->slack = MD_SLACK * M;
-    if ((rc = lbvh_build(H->pos, H->faces, H->T, 0.0f, H->bvh, st))) return fail(rc);
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(hip_fail(hipGetLastError(), "ls_mesh_distance_create", __FILE__, __LINE__));
+    if ((rc = md_build(H, st))) return fail(rc);
     *handle = H;
     return LS_OK;
+}
+
+extern "C" int ls_mesh_distance_update(void* handle, const float* verts, void* stream) {
+    LS_REQUIRE(handle && verts, LS_E_INVALID, "ls_mesh_distance_update: null argument");
+    MeshDistanceHandle* H = (MeshDistanceHandle*)handle;
+    DeviceGuard g(H->device);
+    LS_HIP(g.err);
+    const hipStream_t st = (hipStream_t)stream;
+    LS_HIP(hipMemcpyAsync(H->pos, verts, sizeof(float) * 3 * (size_t)H->V, hipMemcpyDeviceToDevice, st));
+    return md_build(H, st);
 }
 
 static int md_launch(MeshDistanceHandle* H, const float* P, int64_t n, double* sqrD, int64_t* I, double* C, u64* dmax, hipStream_t st) {
@@ -210,6 +371,79 @@ extern "C" int ls_mesh_distance_max(void* handle, const float* P, int64_t n, dou
     LS_HIP(hipMemsetAsync(out_sqd, 0, sizeof(double), (hipStream_t)stream));
     if (n == 0) return LS_OK;
     return md_launch(H, P, n, nullptr, nullptr, nullptr, (u64*)out_sqd, (hipStream_t)stream);
+}
+
+extern "C" int ls_mesh_distance_weights(void* handle, const float* P, int64_t n, const int64_t* I, double* W, void* stream) {
+    LS_REQUIRE(handle && n >= 0 && (n == 0 || (P && I && W)), LS_E_INVALID, "ls_mesh_distance_weights: bad argument");
+    LS_REQUIRE(n < INT32_MAX - BLOCK, LS_E_OVERFLOW, "ls_mesh_distance_weights: more than 2^31 query points");
+    MeshDistanceHandle* H = (MeshDistanceHandle*)handle;
+    if (n == 0) return LS_OK;
+    DeviceGuard g(H->device);
+    LS_HIP(g.err);
+    hipLaunchKernelGGL(k_md_weights, dim3(div_up(n, BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, P, (int)n, (const float*)H->pos, (const int*)H->faces, H->T,
+                       I, W);
+    LS_HIP(hipGetLastError());
+    return LS_OK;
+}
+
+namespace {
+struct MdWs {          // the regions of the backward's workspace (sized from n and F alone)
+    size_t keys, order, seg, sort, W, rows, total;
+};
+MdWs md_layout(int64_t n, int64_t F) {
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const int64_t m = std::max<int64_t>(n, 1);
+    MdWs w;
+    size_t o = 0;
+    w.keys = o; o += al(4 * (size_t)m);
+    w.order = o; o += al(4 * (size_t)m);
+    w.seg = o; o += al(4 * (size_t)(F + 2));
+    w.sort = o; o += al(sort_scratch_bytes(m, true));
+    w.W = o; o += al(24 * (size_t)m);
+    w.rows = o; o += al(36 * (size_t)F);
+    w.total = o;
+    return w;
+}
+}  // namespace
+
+extern "C" int ls_mesh_distance_backward_workspace_bytes(int64_t n, int64_t F, size_t* bytes) {
+    LS_REQUIRE(bytes && n >= 0 && F > 0, LS_E_INVALID, "ls_mesh_distance_backward_workspace_bytes: bad argument");
+    LS_REQUIRE(n < INT32_MAX - BLOCK && 3 * F < INT32_MAX, LS_E_OVERFLOW, "ls_mesh_distance_backward_workspace_bytes: more than 2^31 points or corners");
+    *bytes = md_layout(n, F).total;
+    return LS_OK;
+}
+
+extern "C" int ls_mesh_distance_backward(void* handle, const float* P, int64_t n, const int64_t* I, const double* C, const double* g,
+                                         const int32_t* vptr, const int32_t* corner_order, float* gP, float* gV, void* ws, size_t ws_bytes,
+                                         void* stream) {
+    LS_REQUIRE(handle && n >= 0 && (n == 0 || (P && C && g)), LS_E_INVALID, "ls_mesh_distance_backward: bad argument");
+    LS_REQUIRE(!gV || (vptr && corner_order && ws && (n == 0 || I)), LS_E_INVALID,
+               "ls_mesh_distance_backward: the vertex gradient needs I, the corner ranking and a workspace");
+    LS_REQUIRE(n < INT32_MAX - BLOCK, LS_E_OVERFLOW, "ls_mesh_distance_backward: more than 2^31 query points");
+    MeshDistanceHandle* H = (MeshDistanceHandle*)handle;
+    const MdWs L = md_layout(n, H->T);
+    LS_REQUIRE(!gV || ws_bytes >= L.total, LS_E_WORKSPACE, "ls_mesh_distance_backward: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
+    DeviceGuard guard(H->device);
+    LS_HIP(guard.err);
+    const hipStream_t st = (hipStream_t)stream;
+    if (gP && n > 0) hipLaunchKernelGGL(k_md_grad_points, dim3(div_up(n, BLOCK)), dim3(BLOCK), 0, st, P, C, g, (int)n, gP);
+    if (gV && n == 0) LS_HIP(hipMemsetAsync(gV, 0, sizeof(float) * 3 * (size_t)H->V, st));
+    if (gV && n > 0) {
+        char* w = (char*)ws;
+        int* keys = (int*)(w + L.keys);
+        int* order = (int*)(w + L.order);
+        int* seg = (int*)(w + L.seg);
+        double* W = (double*)(w + L.W);
+        float* rows = (float*)(w + L.rows);
+        hipLaunchKernelGGL(k_md_weights, dim3(div_up(n, BLOCK)), dim3(BLOCK), 0, st, P, (int)n, (const float*)H->pos, (const int*)H->faces, H->T, I, W);
+        hipLaunchKernelGGL(k_md_keys, dim3(div_up(n, BLOCK)), dim3(BLOCK), 0, st, I, (int)n, H->T, keys);
+        int rc = group_by_key<true>(keys, n, H->T, order, seg, sort_scratch_carve(w + L.sort, n, true), st);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_md_face_rows, dim3(div_up(H->T, 256)), dim3(256), 0, st, MdRows{P, C, g, W, order, seg, rows}, (int64_t)H->T);
+        hipLaunchKernelGGL(k_md_gather_verts, dim3(div_up(H->V, 256)), dim3(256), 0, st, (const float*)rows, vptr, corner_order, (int64_t)H->V, gV);
+    }
+    LS_HIP(hipGetLastError());
+    return LS_OK;
 }
 
 extern "C" int ls_mesh_distance_destroy(void* handle) {

@@ -10,7 +10,27 @@ fa)`` with libigl's CPU implementation; the `influence` and `viewpoints` noteboo
 
 The arithmetic is fp64 from fp32 coordinates; ties of the squared distance go to the lowest face id; a degenerate face (its area term
 |ab x ac|^2 is not positive) is measured as its closest edge segment. DESIGN.md section 2.8 states the rules, tests/distance_statement.py
-restates them as a brute force, and the device answers with the same bits. Results are bitwise reproducible. No autograd.
+restates them as a brute force, and the device answers with the same bits. Results are bitwise reproducible.
+
+Autograd. With tensor input, `MeshDistance.squared_distance(P)` and `point_mesh_squared_distance(P, V, F)` return a differentiable
+sqrD (float64) when grad mode is on and P, or the tensor V the handle was built from (or last updated with), requires grad; I and C
+are marked non-differentiable. The closest point is C = sum_k w_k V[F[I, k]] with the weights w of the same region tests; C minimises
+over the face, so with d = p - C the gradient of sqrD is 2 d to p and -2 w_k d to corner k (first derivatives only). Where the
+distance is not differentiable -- a point equidistant from several faces, a point on a vertex or an edge -- this is the gradient of
+the face the tie rule chose: the chosen subgradient. Gradients are float32 like their inputs, every term formed in float64 and rounded
+once, summed per vertex without float atomics in a fixed order (csrc/distance.hip): bitwise reproducible. `max_squared_distance` and
+`hausdorff` stay non-differentiable; numpy input, or input that requires no grad, takes exactly the non-differentiable path.
+
+A handle holds a copy of the positions. `MeshDistance.update(V)` moves the mesh (same faces, same vertex count) in place of destroying
+and rebuilding the handle; a backward whose forward ran before an `update`, or after an in-place change of the source V that no
+`update` followed, raises RuntimeError, because the handle no longer holds the positions of that forward.
+
+Stream capture (torch.cuda.graph): queries and both gradients against a handle that is not updated inside the captured body are
+capturable, after one eager warm-up pass (the first gradient to V builds the corner ranking of the faces, which synchronises).
+Construction, `update` and `point_mesh_squared_distance` itself (it builds and destroys a handle) synchronise and are not. A
+differentiable result of `point_mesh_squared_distance` keeps its handle until its graph is freed, and releasing a handle synchronises
+the device: let that graph go (drop the result and the tensors computed from it) outside any capture. A `MeshDistance` of your
+own is released by `close()` or its `with` block, when you choose.
 
 Input conventions follow remesh_botsch: numpy input (V float64 or float32, converted to fp32; F integer) runs on the current HIP device
 and returns numpy; tensor input (V and query points fp32, F int32 / int64, all on one HIP device) returns tensors on that device. CPU
@@ -21,8 +41,11 @@ import math
 
 import numpy as np
 import torch
+from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from . import _native
+from .normals import _plan
 
 
 def _as_points(P, what):
@@ -73,9 +96,64 @@ def _on(x, device):
     return torch.from_numpy(x).to(device)
 
 
+def _backward_workspace(n, F, dev):
+    c = ctypes.c_size_t(0)
+    _native.check(_native.lib().ls_mesh_distance_backward_workspace_bytes(n, F, ctypes.byref(c)))
+    return torch.empty(c.value, dtype=torch.uint8, device=dev)
+
+
+@_native.retry_on_oom
+def _gradients(m, p, I, C, g, need_p, need_v):
+    """(gP or None, gV or None) of one backward pass: its allocations and the native call"""
+    n, dev = p.shape[0], m.device
+    g = g.to(torch.float64).contiguous()
+    gP = torch.empty_like(p) if need_p else None
+    gV = vptr = order = ws = None
+    if need_v:
+        gV = torch.empty_like(m.V)
+        vptr, order = m._corner_ranks()
+        ws = _backward_workspace(n, m._f.shape[0], dev)
+    with torch.cuda.device(dev):
+        _native.check(_native.lib().ls_mesh_distance_backward(m._h, _native.ptr(p), n, _native.ptr(I), _native.ptr(C), _native.ptr(g),
+                                                              _native.ptr(vptr), _native.ptr(order), _native.ptr(gP), _native.ptr(gV),
+                                                              _native.ptr(ws), ws.numel() if ws is not None else 0, _native.stream_of(dev)))
+    return gP, gV
+
+
+class _SquaredDistance(Function):
+    """sqrD, I, C of the points P against the handle m; V is m's source tensor (or None): the positions the handle holds"""
+
+    @staticmethod
+    def forward(ctx, P, V, m):
+        p = P.detach().contiguous()
+        sqrD, I, C = m._query(p)
+        ctx.m, ctx.version = m, m._version
+        if ctx.needs_input_grad[1]:
+            m._corner_ranks()              # once per handle (synchronises): every later forward and backward finds it
+        ctx.save_for_backward(p, I, C)
+        ctx.mark_non_differentiable(I, C)
+        return sqrD, I, C
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _gI, _gC):
+        p, I, C = ctx.saved_tensors
+        m = ctx.m
+        if not m._h:
+            raise RuntimeError("mesh distance: the handle of this forward pass was closed before its backward pass")
+        if m._version != ctx.version:
+            raise RuntimeError("mesh distance: the handle was updated after this forward pass; it no longer holds the positions the "
+                               "distances were computed from. Run the backward pass before MeshDistance.update")
+        m._check_source()
+        gP, gV = _gradients(m, p, I, C, g, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return gP, gV, None
+
+
 class MeshDistance:
-    """The LBVH of one fixed mesh (V, F) on a HIP device, for distance queries from any number of point sets: the figure's target mesh,
-    built once and queried at every recorded step. numpy (V, F) go to the current HIP device; tensors stay on theirs."""
+    """The LBVH of one mesh (V, F) on a HIP device, for distance queries from any number of point sets: the figure's target mesh,
+    built once and queried at every recorded step, or a moving mesh whose positions `update` replaces at every step. numpy (V, F) go
+    to the current HIP device; tensors stay on theirs. Built from a tensor V, the handle remembers it: a query is differentiable in
+    it (module docstring)."""
 
     def __init__(self, V, F):
         v, v_np = _as_points(V, "V")
@@ -87,19 +165,68 @@ class MeshDistance:
         self.device = _current_device() if v_np else v.device
         self.V = _on(v, self.device)
         f = _on(f, self.device)
+        self._f = f
+        self._ranks = None
+        self._version = 0                  # bumped by update: a backward pass belongs to the positions of its forward pass
+        self._remember(V)
         self._h = ctypes.c_void_p(0)
         with torch.cuda.device(self.device):
             _native.check(_native.lib().ls_mesh_distance_create(_native.ptr(self.V), self.V.shape[0], _native.ptr(f), f.element_size(), f.shape[0],
                                                                 self.device.index, _native.stream_of(self.device), ctypes.byref(self._h)))
 
+    def _remember(self, V):
+        """the tensor the positions came from, and its version: what a gradient to V flows into"""
+        self._src = V if isinstance(V, torch.Tensor) else None
+        self._src_version = V._version if self._src is not None else 0
+
+    def _check_source(self):
+        if self._src is not None and self._src._version != self._src_version:
+            raise RuntimeError("mesh distance: the tensor V this handle was built from was changed in place; the handle still holds the "
+                               "old positions. Call MeshDistance.update(V) after changing V")
+
+    def _corner_ranks(self):
+        """(vptr, rank -> corner) of the faces, the summation order of the gradient to V (largesteps.normals._plan)"""
+        if self._ranks is None:
+            vptr, _, _, order = _plan(self._f, self.V.shape[0])
+            self._ranks = (vptr, order)
+        return self._ranks
+
+    @_native.retry_on_oom
+    def update(self, V):
+        """New positions V (the same vertex count; the faces stay) in place of destroying and rebuilding the handle: afterwards it
+        answers exactly as MeshDistance(V, F) would, and V is the tensor its gradient flows into. Synchronises the stream."""
+        v, v_np = _as_points(V, "V")
+        if v.shape[0] != self.V.shape[0]:
+            raise ValueError(f"mesh distance: update needs the handle's {self.V.shape[0]} vertices, got {v.shape[0]}")
+        if not self._h:
+            raise RuntimeError("mesh distance: update of a closed handle")
+        v = _on(v, self.device)
+        with torch.cuda.device(self.device):
+            _native.check(_native.lib().ls_mesh_distance_update(self._h, _native.ptr(v), _native.stream_of(self.device)))
+        self.V = v
+        self._version += 1
+        self._remember(V)
+
     def _points(self, P):
         p, p_np = _as_points(P, "P")
         return _on(p, self.device), p_np
 
+    @_native.retry_on_oom
     def squared_distance(self, P):
         """(sqrD (n,) float64, I (n,) int64, C (n, 3) float64): for every row of P its squared distance to the mesh, the id of the
-        nearest face (the lowest on a tie) and the closest point on it. numpy P gives numpy results, a tensor gives tensors."""
+        nearest face (the lowest on a tie) and the closest point on it. numpy P gives numpy results, a tensor gives tensors. With a
+        tensor P, grad mode on and P or the handle's source V requiring grad, sqrD is differentiable (module docstring)."""
+        if isinstance(P, torch.Tensor) and torch.is_grad_enabled() and (P.requires_grad or (self._src is not None and self._src.requires_grad)):
+            _on(_as_points(P, "P")[0], self.device)            # the argument checks of the plain path
+            self._check_source()
+            return _SquaredDistance.apply(P, self._src, self)
         p, p_np = self._points(P)
+        sqrD, I, C = self._query(p)
+        if p_np:
+            return sqrD.cpu().numpy(), I.cpu().numpy(), C.cpu().numpy()
+        return sqrD, I, C
+
+    def _query(self, p):
         n = p.shape[0]
         sqrD = torch.empty(n, dtype=torch.float64, device=self.device)
         I = torch.empty(n, dtype=torch.int64, device=self.device)
@@ -107,8 +234,6 @@ class MeshDistance:
         with torch.cuda.device(self.device):
             _native.check(_native.lib().ls_mesh_distance_query(self._h, _native.ptr(p), n, _native.ptr(sqrD), _native.ptr(I), _native.ptr(C),
                                                                _native.stream_of(self.device)))
-        if p_np:
-            return sqrD.cpu().numpy(), I.cpu().numpy(), C.cpu().numpy()
         return sqrD, I, C
 
     def max_squared_distance(self, P):
@@ -153,9 +278,17 @@ class MeshDistance:
 def point_mesh_squared_distance(P, V, F):
     """libigl's point_mesh_squared_distance(P, V, F) -> (sqrD, I, C): for every row of P the squared distance to the mesh (V, F), the id
     of the nearest face (the lowest on a tie) and the closest point. sqrD and C are float64, I int64; numpy input gives numpy, tensors
-    give tensors on their device."""
-    with MeshDistance(V, F) as m:
-        return m.squared_distance(P)
+    give tensors on their device. sqrD is differentiable in tensors P and V that require grad (module docstring); its graph then keeps
+    the handle, which is released with the graph instead of on return. The release synchronises the device, so let the graph go (drop sqrD
+    and the tensors computed from it) outside any stream capture; with a MeshDistance of your own, `close()` decides the moment."""
+    m = MeshDistance(V, F)
+    out = None
+    try:
+        out = m.squared_distance(P)
+        return out
+    finally:
+        if not (out is not None and isinstance(out[0], torch.Tensor) and out[0].requires_grad):
+            m.close()
 
 
 @_native.retry_on_oom
