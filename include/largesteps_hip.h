@@ -125,7 +125,8 @@ int ls_solver_solve(ls_solver* s, const float* b, const float* x0, float* x, int
  * the upper end of spec(D^-1 M) is the handle's own Gershgorin bound. The iteration count is fixed a priori:
  * ceil(log(2/t) / log((sqrt(kappa)+1)/(sqrt(kappa)-1))) for the requested residual reduction t (rtol, or
  * max(rtol||b||, atol)/||r0|| after one residual evaluation when x0 or atol is given). h_info->rnorm is the TRUE
- * fp32 residual of the returned x. SYNC once at the end. LS_E_STATE without a spectrum, LS_E_NOT_CONVERGED if the
+ * fp32 residual of the returned x. SYNC once at the end. LS_E_STATE without a spectrum or with an empty one (a_min /
+ * max diag above the Gershgorin bound: no lower bound of the spectrum), LS_E_NOT_CONVERGED if the
  * count exceeds max_iter or the final check fails: ||b - M x|| must be <= max(request, 8 eps32 ||M|| ||x||), the
  * backward-stable fp32 level (callers fall back to ls_solver_solve). */
 int ls_solver_set_spectrum(ls_solver* s, double a_min);

@@ -1081,6 +1081,9 @@ int solve_cheb(ls_solver* s, const float* b, const float* x0, float* x, int k, d
                "Chebyshev: no certified spectral enclosure for this matrix (ls_solver_set_spectrum)");
     const Geometry g = geometry(s);
     const double lmin = 0.98 * s->a_min / s->dmax, lmax = s->gersh * (1.0 + 1e-5);
+    // a_min above Gershgorin's bound of the largest eigenvalue is no lower bound of the spectrum: rate < 0, log(rate) is not a number
+    LS_REQUIRE(lmin < lmax, LS_E_STATE, "Chebyshev: the spectral enclosure is empty (a_min / max diag = %g is above the Gershgorin bound %g)",
+               s->a_min / s->dmax, s->gersh);
     const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sigma1 = theta / delta;
     const double sk = sqrt(lmax / lmin), rate = (sk - 1.0) / (sk + 1.0);
     int rc;
@@ -1342,6 +1345,8 @@ extern "C" int ls_solver_chebyshev_iterations(const ls_solver* s, double reducti
     LS_REQUIRE(s && h_n && reduction > 0.0, LS_E_INVALID, "ls_solver_chebyshev_iterations: bad argument");
     LS_REQUIRE(s->a_min > 0.0 && s->gersh > 0.0 && s->dmax > 0.0, LS_E_STATE, "Chebyshev: no certified spectral enclosure for this matrix");
     const double lmin = 0.98 * s->a_min / s->dmax, lmax = s->gersh * (1.0 + 1e-5);
+    LS_REQUIRE(lmin < lmax, LS_E_STATE, "Chebyshev: the spectral enclosure is empty (a_min / max diag = %g is above the Gershgorin bound %g)",
+               s->a_min / s->dmax, s->gersh);
     const double sk = sqrt(lmax / lmin), rate = (sk - 1.0) / (sk + 1.0);
     *h_n = reduction >= 1.0 ? 0 : (int)std::min(2.0e9, ceil(log(2.0 / reduction) / -log(rate)));
     return LS_OK;
