@@ -731,6 +731,50 @@ int ls_raster_antialias_backward(const float* color, int C, const float* rast, c
                                  float* grad_color, float* grad_pos, void* ws, size_t ws_bytes, int device, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Range mode of the rasterizer (largesteps/render.py: rasterize(..., ranges=...); csrc/raster.hip). One pos
+ * (V, 4) is shared; image b of B draws the faces tri[start_b : start_b + count_b]. ranges: a DEVICE int32 table (B, 3) = (start, count,
+ * item_ptr), item_ptr the exclusive prefix sum of the counts, 0 <= start, 0 <= count, start + count <= F (the caller checks: the kernels
+ * trust the table); ranges may overlap, be unsorted or empty. An item is a pair (b, f) with f in range b, numbered item_ptr[b] + f - start_b;
+ * N = the sum of the counts. rast (B, H, W, 4) carries GLOBAL ids (face + 1). The slice law:
+ *   image b is, bit for bit, what the instanced entry points give for pos as one batch and the faces tri[start_b : start_b + count_b],
+ *   with start_b added to the id channel of covered pixels -- for the frame, the interpolation and the antialiasing -- and every gradient
+ *   (grad_pos of ls_range_backward and of ls_range_antialias_backward, grad_attr, grad_color) is bit for bit the sum of the B slice calls'
+ *   gradients, accumulated in ascending b starting from image 0's.
+ * A pixel whose id is outside [start_b + 1, start_b + count_b] counts as background. Interpolation itself and its rast gradient are
+ * ls_raster_interpolate / ls_raster_interpolate_backward with attr_batch 1 (ids are global, attr is shared). Limits: B >= 1; N, 3 N and
+ * B H W fit int32; F < 2^24 (LS_E_INVALID / LS_E_OVERFLOW as above). No entry point allocates or synchronises, none uses float atomics. ASYNC.
+ *   ls_range_workspace_bytes            workspace of the entry points below for B images, N items and C channels.
+ *   ls_range_forward                    rast.
+ *   ls_range_pixel_order                order (B H W) = the pixels sorted stably by item (background and foreign ids last), seg (N + 1).
+ *   ls_range_backward                   grad_pos (V, 4) from grad_rast[..., 0:2]; grad_pos[..., 2] = 0. Overwritten.
+ *   ls_range_interpolate_backward       grad_attr (V, C) from grad_out (B, H, W, C).
+ *   ls_range_adjacency                  adj (3 N): the ITEM across edge e of item n at adj[3 n + e], -1 when the edge has one face or
+ *                                       more than two WITHIN the image. Radix sort of the items' half-edges by (image, edge).
+ *   ls_range_antialias                  out (B, H, W, C); silhouettes are those of each image's own faces.
+ *   ls_range_antialias_backward         grad_color (B, H, W, C) and grad_pos (V, 4) (scaled by boost, [..., 2] = 0); either may be NULL.
+ * --------------------------------------------------------------------------------------------- */
+int ls_range_workspace_bytes(int64_t B, int64_t N, int H, int W, int C, size_t* bytes);
+int ls_range_forward(const float* pos, int64_t V, const int32_t* tri, int64_t F, const int32_t* ranges, int64_t B, int64_t N, int H, int W,
+                     float* rast, void* ws, size_t ws_bytes, int device, void* stream);
+int ls_range_pixel_order(const float* rast, const int32_t* ranges, int64_t B, int64_t N, int64_t F, int H, int W, int32_t* order,
+                         int32_t* seg, void* ws, size_t ws_bytes, int device, void* stream);
+int ls_range_backward(const float* pos, int64_t V, const int32_t* tri, int64_t F, const int32_t* ranges, int64_t B, int64_t N, int H, int W,
+                      const float* grad_rast, const int32_t* order, const int32_t* seg, const int32_t* vptr, const int32_t* corner_order,
+                      float* grad_pos, void* ws, size_t ws_bytes, int device, void* stream);
+int ls_range_interpolate_backward(const float* rast, const int32_t* ranges, int64_t B, int64_t N, int H, int W, int64_t V, int C,
+                                  const float* grad_out, const int32_t* order, const int32_t* seg, const int32_t* vptr,
+                                  const int32_t* corner_order, float* grad_attr, void* ws, size_t ws_bytes, int device, void* stream);
+int ls_range_adjacency_workspace_bytes(int64_t N, size_t* bytes);
+int ls_range_adjacency(const int32_t* tri, int64_t F, const int32_t* ranges, int64_t B, int64_t N, int32_t* adj, void* ws, size_t ws_bytes,
+                       int device, void* stream);
+int ls_range_antialias(const float* color, int C, const float* rast, const float* pos, int64_t V, const int32_t* tri, int64_t F,
+                       const int32_t* ranges, int64_t B, int64_t N, int H, int W, const int32_t* adj, float* out, int device, void* stream);
+int ls_range_antialias_backward(const float* color, int C, const float* rast, const float* pos, int64_t V, const int32_t* tri, int64_t F,
+                                const int32_t* ranges, int64_t B, int64_t N, int H, int W, const int32_t* adj, const float* grad_out,
+                                float boost, const int32_t* order, const int32_t* seg, const int32_t* vptr, const int32_t* corner_order,
+                                float* grad_color, float* grad_pos, void* ws, size_t ws_bytes, int device, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Differentiable 2D texture lookup (largesteps/render.py: texture; the rules are stated in csrc/texture.hip and DESIGN.md section 2.7,
  * restated in numpy by tests/texture_statement.py). tex (Bt, Ht, Wt, C) fp32 with Bt 1 (shared by every image) or B, 1 <= Ht, Wt <= 8192,
  * 1 <= C <= 32; uv (B, H, W, 2) fp32, 8-byte aligned; out (B, H, W, C). filter: LS_TEXTURE_NEAREST / _LINEAR; boundary: LS_TEXTURE_WRAP /

@@ -24,6 +24,13 @@
 // fixed order (a thread per face; a face with more than 64 pixels is summed by the whole wave, lane-strided, then a butterfly): face rows
 // [B F][9] (the x, y, w gradient of each corner) or [B F][C][3] (attribute gradients). A per-vertex pass adds a vertex's face rows in the
 // corner ranking of the normals (ls_corner_ranks): every output and gradient is bitwise reproducible.
+//
+// Range mode (ls_range_*): pos (V, 4) is shared and image b draws the faces tri[start_b : start_b + count_b] of a range table
+// (B, 3) = (start, count, item_ptr). The slice law: image b is, bit for bit, the instanced frame of pos[None] and that slice with start_b
+// added to the ids of covered pixels, and every gradient is the sum of the B slice calls' gradients added in ascending b. An ITEM is a
+// pair (b, f), f in range b, numbered item_ptr[b] + f - start_b, N = sum count_b of them: the depth pass, the tile scan, the pixel-order
+// keys, seg, the face rows and the edge adjacency (per image: the neighbour across an edge WITHIN the slice) are all indexed by item.
+// Both modes run the same device functions and kernels, through a mapping (MapInst, MapRange) from keys to (image, face, pos batch).
 #include "common.h"
 #include "groupby.h"
 #include <algorithm>
@@ -130,13 +137,57 @@ __device__ __forceinline__ bool rs_bbox(const RTri& t, int H, int W, int& x0, in
 
 __device__ __forceinline__ u64 rs_key(float zf, int f) { return ((u64)key_of(zf) << 32) | (unsigned)f; }
 
-// one thread per (b, f): small triangles rasterized here, large ones only counted in tiles
-__global__ __launch_bounds__(256) void k_rs_small(const float* __restrict__ pos, const int* __restrict__ tri, int B, int64_t V, int64_t F, int H,
-                                                  int W, u64* __restrict__ depth, int* __restrict__ tiles) {
+// face id of a pixel from the fourth rast channel: 0 for background and for anything that is not an id in [1, F]
+__device__ __forceinline__ int rs_id(const float* __restrict__ rast, int64_t pix, int64_t F) {
+    const float r = rast[pix * 4 + 3];
+    return (r >= 1.0f && r <= (float)F) ? (int)r : 0;
+}
+
+// ---- the two modes ------------------------------------------------------------------------------------------------------------------
+// What a kernel asks of its mode: the image and the face of a key, the key of (image, face), the pos batch an image reads, the id of a
+// pixel (0: background for this image), and where the adjacency keeps a face's row and what its entries mean.
+struct MapInst {       // instanced: every image draws all F faces from its own pos batch; key = b F + f
+    __device__ __forceinline__ int64_t image(int64_t key, int64_t F) const { return key / F; }
+    __device__ __forceinline__ int64_t face(int64_t key, int64_t b, int64_t F) const { return key - b * F; }
+    __device__ __forceinline__ int64_t key(int64_t b, int64_t f, int64_t F) const { return b * F + f; }
+    __device__ __forceinline__ int64_t pos_batch(int64_t b) const { return b; }
+    __device__ __forceinline__ int id(const float* __restrict__ rast, int64_t pix, int64_t, int64_t F) const { return rs_id(rast, pix, F); }
+    __device__ __forceinline__ size_t adj_row(int64_t, int t) const { return (size_t)t; }
+    __device__ __forceinline__ int adj_face(int64_t, int opp) const { return opp; }
+};
+
+struct MapRange {      // range mode: image b draws faces [start_b, start_b + count_b) from the one pos; key = the item
+    const int* __restrict__ rt;               // (B, 3): start, count, item_ptr
+    int B;
+    __device__ __forceinline__ int64_t image(int64_t key, int64_t) const {        // the last image whose item_ptr is <= key (empty ranges are passed over)
+        int lo = 0, hi = B;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (rt[3 * mid + 2] <= key) lo = mid; else hi = mid;
+        }
+        return lo;
+    }
+    __device__ __forceinline__ int64_t face(int64_t key, int64_t b, int64_t) const { return rt[3 * b] + (key - rt[3 * b + 2]); }
+    __device__ __forceinline__ int64_t key(int64_t b, int64_t f, int64_t) const { return rt[3 * b + 2] + (f - rt[3 * b]); }
+    __device__ __forceinline__ int64_t pos_batch(int64_t) const { return 0; }
+    // an id outside [start_b + 1, start_b + count_b] (a rast edited by the caller, or of another call) is background
+    __device__ __forceinline__ int id(const float* __restrict__ rast, int64_t pix, int64_t b, int64_t) const {
+        const float r = rast[pix * 4 + 3];
+        const int s = rt[3 * b], c = rt[3 * b + 1];
+        return (r >= (float)(s + 1) && r <= (float)(s + c)) ? (int)r : 0;
+    }
+    __device__ __forceinline__ size_t adj_row(int64_t b, int t) const { return (size_t)(rt[3 * b + 2] + (t - rt[3 * b])); }
+    __device__ __forceinline__ int adj_face(int64_t b, int opp) const { return rt[3 * b] + (opp - rt[3 * b + 2]); }      // entries are items
+};
+
+// one thread per key (b, f): small triangles rasterized here, large ones only counted in tiles
+template <class Map>
+__global__ __launch_bounds__(256) void k_rs_small(Map map, const float* __restrict__ pos, const int* __restrict__ tri, int64_t nk, int64_t V,
+                                                  int64_t F, int H, int W, u64* __restrict__ depth, int* __restrict__ tiles) {
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= (int64_t)B * F) return;
-    const int64_t b = k / F, f = k - b * F;
-    const RTri t = rs_setup(pos, tri, b, V, f);
+    if (k >= nk) return;
+    const int64_t b = map.image(k, F), f = map.face(k, b, F);
+    const RTri t = rs_setup(pos, tri, map.pos_batch(b), V, f);
     int x0, x1, y0, y1, nt = 0;
     if (rs_visible(t) && rs_bbox(t, H, W, x0, x1, y0, y1)) {
         const int bw = x1 - x0 + 1, bh = y1 - y0 + 1;
@@ -157,10 +208,10 @@ __global__ __launch_bounds__(256) void k_rs_small(const float* __restrict__ pos,
     tiles[k] = nt;
 }
 
-// the cooperative path: tile number t -> triangle k (toff[k] <= t < toff[k + 1]) and tile t - toff[k] of its box, a pixel per thread
-__global__ __launch_bounds__(256) void k_rs_large(const float* __restrict__ pos, const int* __restrict__ tri, int B, int64_t V, int64_t F, int H,
-                                                  int W, const int* __restrict__ toff, u64* __restrict__ depth) {
-    const int64_t nk = (int64_t)B * F;
+// the cooperative path: tile number t -> key k (toff[k] <= t < toff[k + 1]) and tile t - toff[k] of its box, a pixel per thread
+template <class Map>
+__global__ __launch_bounds__(256) void k_rs_large(Map map, const float* __restrict__ pos, const int* __restrict__ tri, int64_t nk, int64_t V,
+                                                  int64_t F, int H, int W, const int* __restrict__ toff, u64* __restrict__ depth) {
     const int total = toff[nk];
     for (int tile = blockIdx.x; tile < total; tile += gridDim.x) {
         int64_t lo = 0, hi = nk;
@@ -168,8 +219,8 @@ __global__ __launch_bounds__(256) void k_rs_large(const float* __restrict__ pos,
             const int64_t mid = (lo + hi) >> 1;
             if (toff[mid] <= tile) lo = mid; else hi = mid;
         }
-        const int64_t b = lo / F, f = lo - b * F;
-        const RTri t = rs_setup(pos, tri, b, V, f);
+        const int64_t b = map.image(lo, F), f = map.face(lo, b, F);
+        const RTri t = rs_setup(pos, tri, map.pos_batch(b), V, f);
         int x0, x1, y0, y1;
         if (!rs_bbox(t, H, W, x0, x1, y0, y1)) continue;
         const int per_row = (x1 - x0 + RS_TILE) / RS_TILE;
@@ -184,8 +235,9 @@ __global__ __launch_bounds__(256) void k_rs_large(const float* __restrict__ pos,
     }
 }
 
-__global__ __launch_bounds__(256) void k_rs_resolve(const float* __restrict__ pos, const int* __restrict__ tri, int B, int64_t V, int64_t F, int H,
-                                                    int W, const u64* __restrict__ depth, float* __restrict__ rast) {
+template <class Map>
+__global__ __launch_bounds__(256) void k_rs_resolve(Map map, const float* __restrict__ pos, const int* __restrict__ tri, int B, int64_t V, int64_t F,
+                                                    int H, int W, const u64* __restrict__ depth, float* __restrict__ rast) {
     const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t HW = (int64_t)H * W;
     if (pix >= B * HW) return;
@@ -194,7 +246,7 @@ __global__ __launch_bounds__(256) void k_rs_resolve(const float* __restrict__ po
     if (key != ~0ull) {
         const int64_t b = pix / HW, r = pix - b * HW, y = r / W, x = r - y * W;
         const int f = (int)(unsigned)(key & 0xffffffffull);
-        const RTri t = rs_setup(pos, tri, b, V, f);
+        const RTri t = rs_setup(pos, tri, map.pos_batch(b), V, f);
         double E[3];
         float zf = 0.0f;
         rs_cover(t, rs_centre((int)x, W), rs_centre((int)y, H), E, zf);
@@ -204,17 +256,14 @@ __global__ __launch_bounds__(256) void k_rs_resolve(const float* __restrict__ po
     *reinterpret_cast<float4*>(rast + pix * 4) = out;
 }
 
-// face id of a pixel from the fourth rast channel: 0 for background and for anything that is not an id in [1, F]
-__device__ __forceinline__ int rs_id(const float* __restrict__ rast, int64_t pix, int64_t F) {
-    const float r = rast[pix * 4 + 3];
-    return (r >= 1.0f && r <= (float)F) ? (int)r : 0;
-}
-
-__global__ __launch_bounds__(256) void k_rs_keys(const float* __restrict__ rast, int64_t N, int64_t HW, int64_t F, int B, int* __restrict__ keys) {
+template <class Map>
+__global__ __launch_bounds__(256) void k_rs_keys(Map map, const float* __restrict__ rast, int64_t N, int64_t HW, int64_t F, int64_t nk,
+                                                 int* __restrict__ keys) {
     const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (pix >= N) return;
-    const int id = rs_id(rast, pix, F);
-    keys[pix] = id ? (int)((pix / HW) * F + id - 1) : (int)((int64_t)B * F);
+    const int64_t b = pix / HW;
+    const int id = map.id(rast, pix, b, F);
+    keys[pix] = id ? (int)map.key(b, id - 1, F) : (int)nk;
 }
 
 // ---- sums in pixel order ---------------------------------------------------------------------------------------------------------
@@ -242,12 +291,13 @@ __global__ __launch_bounds__(256) void k_rs_seg_sum(R r, const int* __restrict__
 }
 
 // rasterize backward: d (gu u + gv v) / d (x, y, w) of the three corners, u = E_0 / S, v = E_1 / S
+template <class Map>
 struct RowRaster {
     static constexpr int K = 9;
-    const float* pos; const int* tri; const float* grad; int64_t V, F; int H, W;
+    Map map; const float* pos; const int* tri; const float* grad; int64_t V, F; int H, W;
     __device__ __forceinline__ void add(int pix, int64_t key, float (&acc)[K]) const {
-        const int64_t b = key / F, f = key - b * F, HW = (int64_t)H * W, rr = pix - b * HW, y = rr / W, x = rr - y * W;
-        const RTri t = rs_setup(pos, tri, b, V, f);
+        const int64_t b = map.image(key, F), f = map.face(key, b, F), HW = (int64_t)H * W, rr = pix - b * HW, y = rr / W, x = rr - y * W;
+        const RTri t = rs_setup(pos, tri, map.pos_batch(b), V, f);
         const double px = rs_centre((int)x, W), py = rs_centre((int)y, H);
         double E[3];
 #pragma unroll
@@ -304,14 +354,17 @@ struct AAHit {
     float dA[3], dB[3];   // d alpha / d (x, y, w) of corners e and e + 1
 };
 
+template <class Map>
 struct AAMesh {
-    const float* pos; const int* tri; const int* adj; const float* rast; int64_t V, F; int H, W;
+    Map map; const float* pos; const int* tri; const int* adj; const float* rast; int64_t V, F; int H, W;
 };
 
-__device__ __forceinline__ AAHit aa_pair(const AAMesh& m, int64_t b, int64_t pixP, int64_t pixQ, int xP, int yP, int axis) {
+template <class Map>
+__device__ __forceinline__ AAHit aa_pair(const AAMesh<Map>& m, int64_t b, int64_t pixP, int64_t pixQ, int xP, int yP, int axis) {
     AAHit h;
     h.found = false;
-    const int idP = rs_id(m.rast, pixP, m.F), idQ = rs_id(m.rast, pixQ, m.F);
+    const int idP = m.map.id(m.rast, pixP, b, m.F), idQ = m.map.id(m.rast, pixQ, b, m.F);
+    const size_t pb = (size_t)m.map.pos_batch(b) * m.V;
     h.near = 0; h.e = 0; h.t = 0; h.alpha = 0.0f;
     if (idP == idQ) return h;
     const float zP = idP ? m.rast[pixP * 4 + 2] : __int_as_float(0x7f800000), zQ = idQ ? m.rast[pixQ * 4 + 2] : __int_as_float(0x7f800000);
@@ -322,7 +375,7 @@ __device__ __forceinline__ AAHit aa_pair(const AAMesh& m, int64_t b, int64_t pix
     const float dir = h.near ? -1.0f : 1.0f;
     float4 q[3];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) q[i] = *reinterpret_cast<const float4*>(m.pos + ((size_t)b * m.V + m.tri[3 * (size_t)t + i]) * 4);
+    for (int i = 0; i < 3; ++i) q[i] = *reinterpret_cast<const float4*>(m.pos + (pb + m.tri[3 * (size_t)t + i]) * 4);
     const bool st = rs_det(q[0], q[1], q[2]) > 0.0;
     const float hw = 0.5f * (float)m.W, hh = 0.5f * (float)m.H;
 #pragma unroll
@@ -330,11 +383,12 @@ __device__ __forceinline__ AAHit aa_pair(const AAMesh& m, int64_t b, int64_t pix
         if (h.found) continue;
         const float4 A = q[e], Bv = q[(e + 1) % 3];
         if (!(A.w > 0.0f && Bv.w > 0.0f)) continue;
-        const int opp = m.adj[3 * (size_t)t + e];
-        if (opp >= 0) {
+        const int across = m.adj[3 * m.map.adj_row(b, t) + e];
+        if (across >= 0) {
+            const int opp = m.map.adj_face(b, across);
             float4 o[3];
 #pragma unroll
-            for (int i = 0; i < 3; ++i) o[i] = *reinterpret_cast<const float4*>(m.pos + ((size_t)b * m.V + m.tri[3 * (size_t)opp + i]) * 4);
+            for (int i = 0; i < 3; ++i) o[i] = *reinterpret_cast<const float4*>(m.pos + (pb + m.tri[3 * (size_t)opp + i]) * 4);
             if ((rs_det(o[0], o[1], o[2]) > 0.0) == st) continue;
         }
         const float XA = (A.x / A.w + 1.0f) * hw, YA = (A.y / A.w + 1.0f) * hh;
@@ -362,7 +416,8 @@ __device__ __forceinline__ AAHit aa_pair(const AAMesh& m, int64_t b, int64_t pix
 }
 
 // pair d of a pixel, in the fixed order left, right, below, above (false: outside the image); selfP: the pixel is P of the pair
-__device__ __forceinline__ bool aa_neighbour(const AAMesh& m, int64_t b, int x, int y, int d, AAHit& h, bool& selfP, int64_t& other) {
+template <class Map>
+__device__ __forceinline__ bool aa_neighbour(const AAMesh<Map>& m, int64_t b, int x, int y, int d, AAHit& h, bool& selfP, int64_t& other) {
     const int64_t pix = ((int64_t)b * m.H + y) * m.W + x;
     if (d == 0) { if (x == 0) return false; other = pix - 1; selfP = false; h = aa_pair(m, b, other, pix, x - 1, y, 0); }
     else if (d == 1) { if (x + 1 >= m.W) return false; other = pix + 1; selfP = true; h = aa_pair(m, b, pix, other, x, y, 0); }
@@ -376,7 +431,8 @@ __device__ __forceinline__ bool aa_receiver(const AAHit& h, bool selfP) {
     return h.alpha > 0.5f ? !self_near : self_near;
 }
 
-__global__ __launch_bounds__(256) void k_aa_forward(AAMesh m, int B, const float* __restrict__ color, int C, float* __restrict__ out) {
+template <class Map>
+__global__ __launch_bounds__(256) void k_aa_forward(AAMesh<Map> m, int B, const float* __restrict__ color, int C, float* __restrict__ out) {
     const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t HW = (int64_t)m.H * m.W;
     if (pix >= B * HW) return;
@@ -395,7 +451,8 @@ __global__ __launch_bounds__(256) void k_aa_forward(AAMesh m, int B, const float
 }
 
 // gradient of the colour: g_col[p] = g[p] + per pair (p receives: -fac g[p]; the other receives: +fac g[other])
-__global__ __launch_bounds__(256) void k_aa_grad_color(AAMesh m, int B, const float* __restrict__ g, int C, float* __restrict__ gcol) {
+template <class Map>
+__global__ __launch_bounds__(256) void k_aa_grad_color(AAMesh<Map> m, int B, const float* __restrict__ g, int C, float* __restrict__ gcol) {
     const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t HW = (int64_t)m.H * m.W;
     if (pix >= B * HW) return;
@@ -418,11 +475,12 @@ __global__ __launch_bounds__(256) void k_aa_grad_color(AAMesh m, int B, const fl
 }
 
 // antialias backward, position rows: the pairs in which this pixel is the nearer one (its own triangle t = key's face)
+template <class Map>
 struct RowAA {
     static constexpr int K = 9;
-    AAMesh m; const float* color; const float* g; int C; float boost;
+    AAMesh<Map> m; const float* color; const float* g; int C; float boost;
     __device__ __forceinline__ void add(int pix, int64_t key, float (&acc)[K]) const {
-        const int64_t HW = (int64_t)m.H * m.W, b = key / m.F, r = pix - b * HW;
+        const int64_t HW = (int64_t)m.H * m.W, b = m.map.image(key, m.F), r = pix - b * HW;
         const int y = (int)(r / m.W), x = (int)(r - (int64_t)y * m.W);
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
@@ -481,6 +539,50 @@ __global__ __launch_bounds__(256) void k_rs_gather_attr(const float* __restrict_
     out[k] = s;
 }
 
+// Range mode: grad_pos (V, 4) and grad_attr (V, C). Per image b a partial sum from zero over the vertex's corners whose face lies in range
+// b, in rank order (they are in the relative order of the slice's own ranking: ls_corner_ranks ranks by ascending corner id) -- bit for
+// bit the gradient of the slice call -- and the partial sums added in ascending b, starting from image 0's.
+__global__ __launch_bounds__(256) void k_rg_gather_pos(const float* __restrict__ rows, const int* __restrict__ vptr, const int* __restrict__ order,
+                                                       const int* __restrict__ rt, int B, int64_t V, float* __restrict__ out) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= V) return;
+    const int r0 = vptr[v], r1 = vptr[v + 1];
+    float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f;
+    for (int b = 0; b < B; ++b) {
+        const int start = rt[3 * b], count = rt[3 * b + 1], ptr = rt[3 * b + 2];
+        float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+        for (int r = r0; r < r1; ++r) {
+            const int c = order[r], f = c / 3;
+            if (f < start || f - start >= count) continue;
+            const float* row = rows + (size_t)(ptr + (f - start)) * 9 + 3 * (c % 3);
+            s0 += row[0]; s1 += row[1]; s2 += row[2];
+        }
+        if (b == 0) { t0 = s0; t1 = s1; t2 = s2; }
+        else { t0 = t0 + s0; t1 = t1 + s1; t2 = t2 + s2; }
+    }
+    *reinterpret_cast<float4*>(out + v * 4) = make_float4(t0, t1, 0.0f, t2);
+}
+
+__global__ __launch_bounds__(256) void k_rg_gather_attr(const float* __restrict__ rows, const int* __restrict__ vptr, const int* __restrict__ order,
+                                                        const int* __restrict__ rt, int B, int64_t V, int C, float* __restrict__ out) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= V * C) return;
+    const int64_t c = k % C, v = k / C;
+    const int r0 = vptr[v], r1 = vptr[v + 1];
+    float t = 0.0f;
+    for (int b = 0; b < B; ++b) {
+        const int start = rt[3 * b], count = rt[3 * b + 1], ptr = rt[3 * b + 2];
+        float s = 0.0f;
+        for (int r = r0; r < r1; ++r) {
+            const int cr = order[r], f = cr / 3;
+            if (f < start || f - start >= count) continue;
+            s += rows[(size_t)(ptr + (f - start)) * (3 * (size_t)C) + 3 * c + (cr % 3)];
+        }
+        t = b == 0 ? s : t + s;
+    }
+    out[k] = t;
+}
+
 // ---- interpolate forward and the rast gradient -------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_rs_interp(const float* __restrict__ attr, int Ba, int64_t V, int C, const float* __restrict__ rast,
                                                    int B, int64_t HW, const int* __restrict__ tri, int64_t F, float* __restrict__ out) {
@@ -531,13 +633,37 @@ struct KeyEdge {       // half-edge h = 3 f + e, edge (tri[h], tri[3 f + (e + 1)
     __device__ __forceinline__ unsigned digit(int h, int pass) const { return (word(h, pass / 4) >> (8 * (pass & 3))) & 255u; }
 };
 
-// sorted half-edges: an edge with exactly two half-edges pairs them; any other count leaves -1 (boundary or non-manifold)
-__global__ __launch_bounds__(256) void k_rs_adjacency(KeyEdge key, const int* __restrict__ sorted, int64_t n, int* __restrict__ adj) {
+// range mode: half-edge h = 3 n + e of item n = (b, f): KeyEdge's two words over face f, and the image as word 2 -- an edge pairs its
+// half-edges within one image only
+struct KeyItemEdge {
+    const int* tri; MapRange map;
+    __device__ __forceinline__ unsigned word(int h, int w) const {
+        const int n = h / 3, e = h - 3 * n;
+        const int64_t b = map.image(n, 0);
+        if (w == 2) return (unsigned)b;
+        const int64_t f = map.face(n, b, 0);
+        const unsigned a = (unsigned)tri[3 * f + e], c = (unsigned)tri[3 * f + (e + 1) % 3];
+        return w == 0 ? min(a, c) : max(a, c);
+    }
+};
+
+// sorted half-edges: an edge with exactly two half-edges pairs them; any other count leaves -1 (boundary or non-manifold). adj holds the
+// face (instanced) or the item (range mode) of the other half-edge.
+template <class Key, int WORDS>
+__global__ __launch_bounds__(256) void k_rs_adjacency(Key key, const int* __restrict__ sorted, int64_t n, int* __restrict__ adj) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int h = sorted[i];
-    const unsigned a0 = key.word(h, 0), a1 = key.word(h, 1);
-    auto same = [&](int64_t j) { return j >= 0 && j < n && key.word(sorted[j], 0) == a0 && key.word(sorted[j], 1) == a1; };
+    unsigned a[WORDS];
+#pragma unroll
+    for (int w = 0; w < WORDS; ++w) a[w] = key.word(h, w);
+    auto same = [&](int64_t j) {
+        if (j < 0 || j >= n) return false;
+        bool eq = true;
+#pragma unroll
+        for (int w = 0; w < WORDS; ++w) eq = eq && key.word(sorted[j], w) == a[w];
+        return eq;
+    };
     int other = -1;
     if (same(i + 1) && !same(i - 1) && !same(i + 2)) other = sorted[i + 1];
     if (same(i - 1) && !same(i - 2) && !same(i + 1)) other = sorted[i - 1];
@@ -554,9 +680,9 @@ struct RsWs {          // the workspace's regions (sized from the shapes alone)
     size_t depth, tiles, toff, bsum, keys, sort, rows, total;
 };
 
-RsWs rs_layout(int64_t B, int64_t F, int64_t H, int64_t W, int64_t C) {
+// N pixels, nk keys (B F faces of an instanced frame, the items of a range-mode one)
+RsWs rs_layout_keys(int64_t N, int64_t nk, int64_t C) {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const int64_t N = B * H * W, nk = B * F;
     RsWs w;
     size_t o = 0;
     w.depth = o; o += al(8 * (size_t)N);
@@ -570,6 +696,8 @@ RsWs rs_layout(int64_t B, int64_t F, int64_t H, int64_t W, int64_t C) {
     return w;
 }
 
+RsWs rs_layout(int64_t B, int64_t F, int64_t H, int64_t W, int64_t C) { return rs_layout_keys(B * H * W, B * F, C); }
+
 int rs_check(int64_t B, int64_t V, int64_t F, int H, int W, const char* who) {
     LS_REQUIRE(B >= 1 && V >= 0 && F >= 0 && H >= 1 && W >= 1 && H <= 4096 && W <= 4096, LS_E_INVALID, "%s: bad sizes (B %lld V %lld F %lld H %d W %d)",
                who, (long long)B, (long long)V, (long long)F, H, W);
@@ -577,6 +705,45 @@ int rs_check(int64_t B, int64_t V, int64_t F, int H, int W, const char* who) {
                LS_E_OVERFLOW, "%s: the problem does not fit the int32 index space (B %lld V %lld F %lld H %d W %d)", who, (long long)B,
                (long long)V, (long long)F, H, W);
     return LS_OK;
+}
+
+// range mode: B images, N items over F faces and V shared vertices
+int rg_check(int64_t B, int64_t N, int64_t V, int64_t F, int H, int W, const char* who) {
+    LS_REQUIRE(B >= 1 && N >= 0 && V >= 0 && F >= 0 && H >= 1 && W >= 1 && H <= 4096 && W <= 4096, LS_E_INVALID,
+               "%s: bad sizes (B %lld N %lld V %lld F %lld H %d W %d)", who, (long long)B, (long long)N, (long long)V, (long long)F, H, W);
+    LS_REQUIRE(B * H * W < ((int64_t)1 << 31) - 1 && 3 * N < ((int64_t)1 << 31) - 1 && F < ((int64_t)1 << 24) && V < ((int64_t)1 << 31),
+               LS_E_OVERFLOW, "%s: the problem does not fit the int32 index space (B %lld N %lld V %lld F %lld H %d W %d)", who, (long long)B,
+               (long long)N, (long long)V, (long long)F, H, W);
+    return LS_OK;
+}
+
+// ---- the launches both modes share: `map` takes a key to its image and face, nk keys --------------------------------------------------
+template <class Map>
+int rs_forward(Map map, const float* pos, const int32_t* tri, int64_t B, int64_t nk, int64_t V, int64_t F, int H, int W, float* rast, char* w,
+               const RsWs& L, hipStream_t st) {
+    u64* depth = (u64*)(w + L.depth);
+    int* tiles = (int*)(w + L.tiles);
+    int* toff = (int*)(w + L.toff);
+    const int64_t N = B * H * W;
+    LS_HIP(hipMemsetAsync(depth, 0xff, 8 * (size_t)N, st));
+    if (nk > 0) {
+        hipLaunchKernelGGL(k_rs_small<Map>, dim3(div_up(nk, 256)), dim3(256), 0, st, map, pos, tri, nk, V, F, H, W, depth, tiles);
+        int rc = exclusive_scan(tiles, nk, toff, (int*)(w + L.bsum), st);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_rs_large<Map>, dim3(RS_LARGE_GRID), dim3(256), 0, st, map, pos, tri, nk, V, F, H, W, (const int*)toff, depth);
+    }
+    hipLaunchKernelGGL(k_rs_resolve<Map>, dim3(div_up(N, 256)), dim3(256), 0, st, map, pos, tri, (int)B, V, F, H, W, (const u64*)depth, rast);
+    LS_HIP(hipGetLastError());
+    return LS_OK;
+}
+
+template <class Map>
+int rs_pixel_order(Map map, const float* rast, int64_t B, int64_t nk, int64_t F, int H, int W, int32_t* order, int32_t* seg, char* w,
+                   const RsWs& L, hipStream_t st) {
+    const int64_t N = B * H * W;
+    int* keys = (int*)(w + L.keys);
+    hipLaunchKernelGGL(k_rs_keys<Map>, dim3(div_up(N, 256)), dim3(256), 0, st, map, rast, N, (int64_t)H * W, F, nk, keys);
+    return group_by_key<false>(keys, N, nk, order, seg, sort_scratch_carve(w + L.sort, N, false), st);
 }
 
 }  // namespace
@@ -598,22 +765,7 @@ extern "C" int ls_raster_forward(const float* pos, int64_t B, int64_t V, const i
     LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_raster_forward: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
     DeviceGuard g(device);
     LS_HIP(g.err);
-    hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)ws;
-    u64* depth = (u64*)(w + L.depth);
-    int* tiles = (int*)(w + L.tiles);
-    int* toff = (int*)(w + L.toff);
-    const int64_t N = B * H * W, nk = B * F;
-    LS_HIP(hipMemsetAsync(depth, 0xff, 8 * (size_t)N, st));
-    if (nk > 0) {
-        hipLaunchKernelGGL(k_rs_small, dim3(div_up(nk, 256)), dim3(256), 0, st, pos, tri, (int)B, V, F, H, W, depth, tiles);
-        rc = exclusive_scan(tiles, nk, toff, (int*)(w + L.bsum), st);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_rs_large, dim3(RS_LARGE_GRID), dim3(256), 0, st, pos, tri, (int)B, V, F, H, W, (const int*)toff, depth);
-    }
-    hipLaunchKernelGGL(k_rs_resolve, dim3(div_up(N, 256)), dim3(256), 0, st, pos, tri, (int)B, V, F, H, W, (const u64*)depth, rast);
-    LS_HIP(hipGetLastError());
-    return LS_OK;
+    return rs_forward(MapInst{}, pos, tri, B, B * F, V, F, H, W, rast, (char*)ws, L, (hipStream_t)stream);
 }
 
 extern "C" int ls_raster_pixel_order(const float* rast, int64_t B, int64_t F, int H, int W, int32_t* order, int32_t* seg, void* ws,
@@ -625,12 +777,7 @@ extern "C" int ls_raster_pixel_order(const float* rast, int64_t B, int64_t F, in
     LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_raster_pixel_order: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
     DeviceGuard g(device);
     LS_HIP(g.err);
-    hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)ws;
-    const int64_t N = B * H * W, nk = B * F;
-    int* keys = (int*)(w + L.keys);
-    hipLaunchKernelGGL(k_rs_keys, dim3(div_up(N, 256)), dim3(256), 0, st, rast, N, (int64_t)H * W, F, (int)B, keys);
-    return group_by_key<false>(keys, N, nk, order, seg, sort_scratch_carve(w + L.sort, N, false), st);
+    return rs_pixel_order(MapInst{}, rast, B, B * F, F, H, W, order, seg, (char*)ws, L, (hipStream_t)stream);
 }
 
 extern "C" int ls_raster_backward(const float* pos, int64_t B, int64_t V, const int32_t* tri, int64_t F, int H, int W, const float* grad_rast,
@@ -648,8 +795,8 @@ extern "C" int ls_raster_backward(const float* pos, int64_t B, int64_t V, const 
     float* rows = (float*)((char*)ws + L.rows);
     const int64_t nk = B * F;
     if (nk > 0) {
-        RowRaster r{pos, tri, grad_rast, V, F, H, W};
-        hipLaunchKernelGGL(k_rs_seg_sum<RowRaster>, dim3(div_up(nk, 256)), dim3(256), 0, st, r, order, seg, nk, 9, 0, rows);
+        RowRaster<MapInst> r{MapInst{}, pos, tri, grad_rast, V, F, H, W};
+        hipLaunchKernelGGL(k_rs_seg_sum<RowRaster<MapInst>>, dim3(div_up(nk, 256)), dim3(256), 0, st, r, order, seg, nk, 9, 0, rows);
     }
     if (B * V > 0)
         hipLaunchKernelGGL(k_rs_gather_pos, dim3(div_up(B * V, 256)), dim3(256), 0, st, (const float*)rows, vptr, corner_order, (int)B, V, F, grad_pos);
@@ -731,7 +878,7 @@ extern "C" int ls_raster_adjacency(const int32_t* tri, int64_t F, int32_t* adj, 
     KeyEdge key{tri};
     rc = radix_argsort_words(key, n, 2, ord_a, sort_scratch_carve(ord_a + n, n, true), st, &sorted);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_rs_adjacency, dim3(div_up(n, 256)), dim3(256), 0, st, key, sorted, n, adj);
+    hipLaunchKernelGGL((k_rs_adjacency<KeyEdge, 2>), dim3(div_up(n, 256)), dim3(256), 0, st, key, sorted, n, adj);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
@@ -745,8 +892,8 @@ extern "C" int ls_raster_antialias(const float* color, int C, const float* rast,
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
     const int64_t N = B * H * W;
-    AAMesh m{pos, tri, adj, rast, V, F, H, W};
-    hipLaunchKernelGGL(k_aa_forward, dim3(div_up(N, 256)), dim3(256), 0, st, m, (int)B, color, C, out);
+    AAMesh<MapInst> m{MapInst{}, pos, tri, adj, rast, V, F, H, W};
+    hipLaunchKernelGGL(k_aa_forward<MapInst>, dim3(div_up(N, 256)), dim3(256), 0, st, m, (int)B, color, C, out);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
@@ -768,16 +915,175 @@ extern "C" int ls_raster_antialias_backward(const float* color, int C, const flo
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
     const int64_t N = B * H * W, nk = B * F;
-    AAMesh m{pos, tri, adj, rast, V, F, H, W};
-    if (grad_color) hipLaunchKernelGGL(k_aa_grad_color, dim3(div_up(N, 256)), dim3(256), 0, st, m, (int)B, grad_out, C, grad_color);
+    AAMesh<MapInst> m{MapInst{}, pos, tri, adj, rast, V, F, H, W};
+    if (grad_color) hipLaunchKernelGGL(k_aa_grad_color<MapInst>, dim3(div_up(N, 256)), dim3(256), 0, st, m, (int)B, grad_out, C, grad_color);
     if (grad_pos) {
         float* rows = (float*)((char*)ws + L.rows);
         if (nk > 0) {
-            RowAA r{m, color, grad_out, C, boost};
-            hipLaunchKernelGGL(k_rs_seg_sum<RowAA>, dim3(div_up(nk, 256)), dim3(256), 0, st, r, order, seg, nk, 9, 0, rows);
+            RowAA<MapInst> r{m, color, grad_out, C, boost};
+            hipLaunchKernelGGL(k_rs_seg_sum<RowAA<MapInst>>, dim3(div_up(nk, 256)), dim3(256), 0, st, r, order, seg, nk, 9, 0, rows);
         }
         if (B * V > 0)
             hipLaunchKernelGGL(k_rs_gather_pos, dim3(div_up(B * V, 256)), dim3(256), 0, st, (const float*)rows, vptr, corner_order, (int)B, V, F,
+                               grad_pos);
+    }
+    LS_HIP(hipGetLastError());
+    return LS_OK;
+}
+
+// ---- range mode ---------------------------------------------------------------------------------------------------------------------------
+extern "C" int ls_range_workspace_bytes(int64_t B, int64_t N, int H, int W, int C, size_t* bytes) {
+    int rc = rg_check(B, N, 0, 0, H, W, "ls_range_workspace_bytes");
+    if (rc) return rc;
+    LS_REQUIRE(bytes && C >= 0, LS_E_INVALID, "ls_range_workspace_bytes: bad argument");
+    *bytes = rs_layout_keys(B * H * W, N, C).total;
+    return LS_OK;
+}
+
+extern "C" int ls_range_forward(const float* pos, int64_t V, const int32_t* tri, int64_t F, const int32_t* ranges, int64_t B, int64_t N, int H,
+                                int W, float* rast, void* ws, size_t ws_bytes, int device, void* stream) {
+    int rc = rg_check(B, N, V, F, H, W, "ls_range_forward");
+    if (rc) return rc;
+    const RsWs L = rs_layout_keys(B * H * W, N, 0);
+    LS_REQUIRE(rast && ws && ranges && ((pos && tri) || N == 0), LS_E_INVALID, "ls_range_forward: null argument");
+    LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_range_forward: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
+    DeviceGuard g(device);
+    LS_HIP(g.err);
+    return rs_forward(MapRange{ranges, (int)B}, pos, tri, B, N, V, F, H, W, rast, (char*)ws, L, (hipStream_t)stream);
+}
+
+extern "C" int ls_range_pixel_order(const float* rast, const int32_t* ranges, int64_t B, int64_t N, int64_t F, int H, int W, int32_t* order,
+                                    int32_t* seg, void* ws, size_t ws_bytes, int device, void* stream) {
+    int rc = rg_check(B, N, 0, F, H, W, "ls_range_pixel_order");
+    if (rc) return rc;
+    const RsWs L = rs_layout_keys(B * H * W, N, 0);
+    LS_REQUIRE(rast && ranges && order && seg && ws, LS_E_INVALID, "ls_range_pixel_order: null argument");
+    LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_range_pixel_order: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
+    DeviceGuard g(device);
+    LS_HIP(g.err);
+    return rs_pixel_order(MapRange{ranges, (int)B}, rast, B, N, F, H, W, order, seg, (char*)ws, L, (hipStream_t)stream);
+}
+
+extern "C" int ls_range_backward(const float* pos, int64_t V, const int32_t* tri, int64_t F, const int32_t* ranges, int64_t B, int64_t N, int H,
+                                 int W, const float* grad_rast, const int32_t* order, const int32_t* seg, const int32_t* vptr,
+                                 const int32_t* corner_order, float* grad_pos, void* ws, size_t ws_bytes, int device, void* stream) {
+    int rc = rg_check(B, N, V, F, H, W, "ls_range_backward");
+    if (rc) return rc;
+    const RsWs L = rs_layout_keys(B * H * W, N, 0);
+    LS_REQUIRE(grad_rast && ranges && order && seg && vptr && grad_pos && ws && (pos || V == 0) && ((tri && corner_order) || F == 0), LS_E_INVALID,
+               "ls_range_backward: null argument");
+    LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_range_backward: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
+    DeviceGuard g(device);
+    LS_HIP(g.err);
+    hipStream_t st = (hipStream_t)stream;
+    float* rows = (float*)((char*)ws + L.rows);
+    const MapRange map{ranges, (int)B};
+    if (N > 0) {
+        RowRaster<MapRange> r{map, pos, tri, grad_rast, V, F, H, W};
+        hipLaunchKernelGGL(k_rs_seg_sum<RowRaster<MapRange>>, dim3(div_up(N, 256)), dim3(256), 0, st, r, order, seg, N, 9, 0, rows);
+    }
+    if (V > 0)
+        hipLaunchKernelGGL(k_rg_gather_pos, dim3(div_up(V, 256)), dim3(256), 0, st, (const float*)rows, vptr, corner_order, ranges, (int)B, V, grad_pos);
+    LS_HIP(hipGetLastError());
+    return LS_OK;
+}
+
+extern "C" int ls_range_interpolate_backward(const float* rast, const int32_t* ranges, int64_t B, int64_t N, int H, int W, int64_t V, int C,
+                                             const float* grad_out, const int32_t* order, const int32_t* seg, const int32_t* vptr,
+                                             const int32_t* corner_order, float* grad_attr, void* ws, size_t ws_bytes, int device, void* stream) {
+    int rc = rg_check(B, N, V, 0, H, W, "ls_range_interpolate_backward");
+    if (rc) return rc;
+    LS_REQUIRE(C >= 1, LS_E_INVALID, "ls_range_interpolate_backward: C %d", C);
+    const RsWs L = rs_layout_keys(B * H * W, N, C);
+    LS_REQUIRE(rast && ranges && grad_out && order && seg && vptr && grad_attr && ws && (corner_order || N == 0), LS_E_INVALID,
+               "ls_range_interpolate_backward: null argument");
+    LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_range_interpolate_backward: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
+    DeviceGuard g(device);
+    LS_HIP(g.err);
+    hipStream_t st = (hipStream_t)stream;
+    float* rows = (float*)((char*)ws + L.rows);
+    if (N > 0)
+        for (int c = 0; c < C; ++c) {
+            RowInterp r{rast, grad_out, C, c};
+            hipLaunchKernelGGL(k_rs_seg_sum<RowInterp>, dim3(div_up(N, 256)), dim3(256), 0, st, r, order, seg, N, 3 * C, 3 * c, rows);
+        }
+    if (V * C > 0)
+        hipLaunchKernelGGL(k_rg_gather_attr, dim3(div_up(V * C, 256)), dim3(256), 0, st, (const float*)rows, vptr, corner_order, ranges, (int)B, V, C,
+                           grad_attr);
+    LS_HIP(hipGetLastError());
+    return LS_OK;
+}
+
+extern "C" int ls_range_adjacency_workspace_bytes(int64_t N, size_t* bytes) {
+    LS_REQUIRE(bytes && N >= 0 && 3 * N < ((int64_t)1 << 31) - 1, LS_E_INVALID, "ls_range_adjacency_workspace_bytes: bad argument");
+    *bytes = 4 * (size_t)(3 * N) + sort_scratch_bytes(3 * N, true);       // the half-edge ids, the sort's scratch behind them
+    return LS_OK;
+}
+
+extern "C" int ls_range_adjacency(const int32_t* tri, int64_t F, const int32_t* ranges, int64_t B, int64_t N, int32_t* adj, void* ws,
+                                  size_t ws_bytes, int device, void* stream) {
+    size_t need = 0;
+    int rc = ls_range_adjacency_workspace_bytes(N, &need);
+    if (rc) return rc;
+    LS_REQUIRE(B >= 1 && F >= 0 && adj && ws && ranges && (tri || N == 0), LS_E_INVALID, "ls_range_adjacency: bad argument");
+    LS_REQUIRE(ws_bytes >= need, LS_E_WORKSPACE, "ls_range_adjacency: workspace too small (%zu < %zu bytes)", ws_bytes, need);
+    if (N == 0) return LS_OK;
+    DeviceGuard g(device);
+    LS_HIP(g.err);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n = 3 * N;
+    int* ord_a = (int*)ws;
+    const int* sorted = nullptr;
+    KeyItemEdge key{tri, MapRange{ranges, (int)B}};
+    rc = radix_argsort_words(key, n, 3, ord_a, sort_scratch_carve(ord_a + n, n, true), st, &sorted, radix_passes(B - 1));
+    if (rc) return rc;
+    hipLaunchKernelGGL((k_rs_adjacency<KeyItemEdge, 3>), dim3(div_up(n, 256)), dim3(256), 0, st, key, sorted, n, adj);
+    LS_HIP(hipGetLastError());
+    return LS_OK;
+}
+
+extern "C" int ls_range_antialias(const float* color, int C, const float* rast, const float* pos, int64_t V, const int32_t* tri, int64_t F,
+                                  const int32_t* ranges, int64_t B, int64_t N, int H, int W, const int32_t* adj, float* out, int device,
+                                  void* stream) {
+    int rc = rg_check(B, N, V, F, H, W, "ls_range_antialias");
+    if (rc) return rc;
+    LS_REQUIRE(C >= 1 && color && rast && out && ranges && ((pos && tri && adj) || N == 0), LS_E_INVALID, "ls_range_antialias: bad argument");
+    DeviceGuard g(device);
+    LS_HIP(g.err);
+    hipStream_t st = (hipStream_t)stream;
+    AAMesh<MapRange> m{MapRange{ranges, (int)B}, pos, tri, adj, rast, V, F, H, W};
+    hipLaunchKernelGGL(k_aa_forward<MapRange>, dim3(div_up(B * H * W, 256)), dim3(256), 0, st, m, (int)B, color, C, out);
+    LS_HIP(hipGetLastError());
+    return LS_OK;
+}
+
+extern "C" int ls_range_antialias_backward(const float* color, int C, const float* rast, const float* pos, int64_t V, const int32_t* tri, int64_t F,
+                                           const int32_t* ranges, int64_t B, int64_t N, int H, int W, const int32_t* adj, const float* grad_out,
+                                           float boost, const int32_t* order, const int32_t* seg, const int32_t* vptr,
+                                           const int32_t* corner_order, float* grad_color, float* grad_pos, void* ws, size_t ws_bytes, int device,
+                                           void* stream) {
+    int rc = rg_check(B, N, V, F, H, W, "ls_range_antialias_backward");
+    if (rc) return rc;
+    const RsWs L = rs_layout_keys(B * H * W, N, 0);
+    LS_REQUIRE(C >= 1 && color && rast && grad_out && ranges && ((pos && tri && adj) || N == 0), LS_E_INVALID,
+               "ls_range_antialias_backward: bad argument");
+    LS_REQUIRE(!grad_pos || (order && seg && vptr && ws && (corner_order || F == 0)), LS_E_INVALID,
+               "ls_range_antialias_backward: grad_pos needs the pixel order, the corner ranking and a workspace");
+    LS_REQUIRE(!grad_pos || ws_bytes >= L.total, LS_E_WORKSPACE, "ls_range_antialias_backward: workspace too small (%zu < %zu bytes)", ws_bytes,
+               L.total);
+    DeviceGuard g(device);
+    LS_HIP(g.err);
+    hipStream_t st = (hipStream_t)stream;
+    AAMesh<MapRange> m{MapRange{ranges, (int)B}, pos, tri, adj, rast, V, F, H, W};
+    if (grad_color) hipLaunchKernelGGL(k_aa_grad_color<MapRange>, dim3(div_up(B * H * W, 256)), dim3(256), 0, st, m, (int)B, grad_out, C, grad_color);
+    if (grad_pos) {
+        float* rows = (float*)((char*)ws + L.rows);
+        if (N > 0) {
+            RowAA<MapRange> r{m, color, grad_out, C, boost};
+            hipLaunchKernelGGL(k_rs_seg_sum<RowAA<MapRange>>, dim3(div_up(N, 256)), dim3(256), 0, st, r, order, seg, N, 9, 0, rows);
+        }
+        if (V > 0)
+            hipLaunchKernelGGL(k_rg_gather_pos, dim3(div_up(V, 256)), dim3(256), 0, st, (const float*)rows, vptr, corner_order, ranges, (int)B, V,
                                grad_pos);
     }
     LS_HIP(hipGetLastError());

@@ -194,6 +194,22 @@ _SIGNATURES = {
     "ls_raster_antialias_backward": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_void_p, c_i64, c_void_p, c_void_p,
                                              c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int,
                                              c_void_p]),
+    "ls_range_workspace_bytes": (c_int, [c_i64, c_i64, c_int, c_int, c_int, ctypes.POINTER(c_size_t)]),
+    "ls_range_forward": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_int, c_int, c_void_p, c_void_p, c_size_t, c_int,
+                                 c_void_p]),
+    "ls_range_pixel_order": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_int,
+                                     c_void_p]),
+    "ls_range_backward": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "ls_range_interpolate_backward": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_int, c_int, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "ls_range_adjacency_workspace_bytes": (c_int, [c_i64, ctypes.POINTER(c_size_t)]),
+    "ls_range_adjacency": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "ls_range_antialias": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_int, c_int, c_void_p,
+                                   c_void_p, c_int, c_void_p]),
+    "ls_range_antialias_backward": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_int, c_int,
+                                            c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_size_t, c_int, c_void_p]),
     "ls_texture_workspace_bytes": (c_int, [c_i64, c_int, c_int, ctypes.POINTER(c_size_t)]),
     "ls_texture_forward": (c_int, [c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "ls_texture_order": (c_int, [c_void_p, c_i64, c_int, c_int, c_i64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_int,

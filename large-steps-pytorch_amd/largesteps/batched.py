@@ -33,6 +33,7 @@ class MeshBatch:
             vp.append(vp[-1] + v.shape[0])
             fp.append(fp[-1] + f.shape[0])
         self.vertex_ptr, self.face_ptr = vp, fp
+        self._ranges = None
         self.verts = torch.cat([v.detach().to(torch.float32) for v in verts_list], 0).contiguous()
         self.faces = torch.cat([f.long() + o for f, o in zip(faces_list, vp[:-1])], 0).contiguous()
         # layout for the dissection: mesh i shifted along x by the sum of the extents before it (+ 25 % gaps)
@@ -47,6 +48,13 @@ class MeshBatch:
 
     def __len__(self):
         return len(self.vertex_ptr) - 1
+
+    def ranges(self):
+        """(B, 2) int32 CPU rows (first face, number of faces) of the meshes in `faces`: `render.rasterize(ctx, pos, batch.faces, res,
+        ranges=batch.ranges())` renders mesh b into image b. One tensor per batch, so the renderer's per-tensor caches hold across steps."""
+        if self._ranges is None:
+            self._ranges = torch.tensor([[a, b - a] for a, b in zip(self.face_ptr[:-1], self.face_ptr[1:])], dtype=torch.int32)
+        return self._ranges
 
     def split(self, x):
         """per-mesh views of a per-vertex tensor of the batch"""

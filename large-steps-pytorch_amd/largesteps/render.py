@@ -6,6 +6,8 @@ Primitives (autograd Functions over hand-written HIP, csrc/raster.hip; the rules
 tests/render_statement.py):
 
     rast, rast_db = rasterize(ctx, pos, tri, resolution)       pos (B, V, 4) clip space, tri (F, 3) int32 / int64, resolution (H, W)
+    rast, rast_db = rasterize(ctx, pos, tri, resolution, ranges=R)     range mode: pos (V, 4), R (B, 2) int32 CPU rows (start, count);
+                                                               image b draws tri[start_b : start_b + count_b] (the slice law, below)
     out, _ = interpolate(attr, rast, tri)                      attr (V, C), (1, V, C) or (B, V, C)
     color_aa = antialias(color, rast, pos, tri, pos_gradient_boost=1.0)
     texture(tex, uv, filter_mode='linear', boundary_mode='wrap')    tex (1 or B, Ht, Wt, C), uv (B, H, W, 2); nearest / linear, wrap / clamp /
@@ -23,6 +25,14 @@ and (scaled by pos_gradient_boost) to pos, texture to tex and (linear filtering)
 antialias learns a texture and moves the geometry under it. No float atomics anywhere: images and gradients are bitwise reproducible, and no call
 synchronises with the host once a face tensor has been seen (its edge adjacency and corner ranking are cached per tensor object), so
 the whole render can sit inside `CapturedStep`. There is no CPU path (but a plain-torch `texture` forward, linear + wrap, for CPU tensors).
+
+Range mode renders B different meshes (`MeshBatch.faces` with `MeshBatch.ranges()`) in one call. The slice law: image b of a range-mode
+call is, bit for bit, what the instanced call on pos[None] and the slice tri[start_b : start_b + count_b] produces, with start_b added
+to the id channel of covered pixels -- for `rasterize`, `interpolate` and `antialias` -- and every gradient (pos from rasterize and from
+antialias, attr, color, rast[..., :2]) equals bit for bit the sum of the B slice calls' gradients, accumulated in ascending b starting
+from image 0's. Ranges may overlap, be unsorted, be empty (an all-zero image) or leave faces out; silhouettes are those of each image's
+own faces (a closed surface cut by a range has a boundary along the cut). The rast of a range-mode call carries its range table:
+`interpolate` and `antialias` must be given that very tensor.
 """
 import ctypes
 import weakref
@@ -188,13 +198,19 @@ class _Rasterize(Function):
 @_native.retry_on_oom
 def rasterize(glctx, pos, tri, resolution, ranges=None, grad_db=True):
     """
-    Rasterize triangles (nvdiffrast.torch.rasterize, instanced mode). Returns (rast, rast_db).
+    Rasterize triangles (nvdiffrast.torch.rasterize, instanced and range mode). Returns (rast, rast_db).
 
     glctx : RasterizeContext (ignored)
-    pos : (B, V, 4) fp32 clip-space positions on a HIP device
+    pos : (B, V, 4) fp32 clip-space positions on a HIP device; (V, 4) in range mode
     tri : (F, 3) int32 or int64
     resolution : (H, W), each in [1, 4096]
-    ranges : must be None (range mode is not supported)
+    ranges : None (instanced mode), or range mode: a (B, 2) int32 CPU tensor of (start, count) rows with 0 <= start, 0 <= count and
+             start + count <= F. pos is then (V, 4), shared by the B images, and image b holds the faces tri[start_b : start_b + count_b]
+             with GLOBAL ids (face index in tri, plus one): bit for bit the instanced frame of pos[None] and that slice, start_b added to
+             the ids (the slice law of the module's docstring). Ranges may overlap, be unsorted or empty. The device copy of the table is
+             cached per ranges tensor (identity, version, data pointer): keep one tensor (`MeshBatch.ranges()`) and nothing is copied
+             from the host after the first call. The returned rast carries the table for `interpolate` and `antialias`; rast_db is
+             then a plain zero tensor (pixel differentials are not supported in range mode).
     grad_db : ignored. rast_db holds zeros (rasterize computes no image-space derivatives) and asking for its gradient raises; it carries
               the detached pos and tri, from which `interpolate(..., rast_db=rast_db, diff_attrs=...)` computes the differentials when
               they are wanted (`pixel_differentials`).
@@ -203,9 +219,9 @@ def rasterize(glctx, pos, tri, resolution, ranges=None, grad_db=True):
     projected triangle (top-left rule, watertight along shared edges) and z/w is in [-1, 1] (near and far clipping); the nearest
     covering triangle wins (ties: the lower id). The gradient of rast[..., 0:2] flows to pos; the gradient of the z/w channel is dropped.
     """
-    if ranges is not None:
-        raise NotImplementedError("largesteps.render.rasterize: range mode (ranges=...) is not supported; pass pos as (B, V, 4)")
     H, W = (int(resolution[0]), int(resolution[1]))
+    if ranges is not None:
+        return _rasterize_range(pos, tri, H, W, resolution, ranges)
     if not (1 <= H <= 4096 and 1 <= W <= 4096):
         raise ValueError(f"resolution must be (H, W) with each in [1, 4096], got {tuple(resolution)}")
     F = tri.shape[0] if isinstance(tri, torch.Tensor) and tri.dim() == 2 else 0
@@ -219,6 +235,321 @@ def rasterize(glctx, pos, tri, resolution, ranges=None, grad_db=True):
 
 def _attach_order(rast, slot):
     rast._largesteps_order = slot
+
+
+# ---- range mode ------------------------------------------------------------------------------------------------------------------------
+_range_tables = {}
+
+
+class _RangeTable:
+    """The device table (B, 3) = (start, count, item_ptr) of one ranges tensor, and the item adjacency of every face tensor it was used with
+    (cached per (face tensor, ranges tensor) in the style of `_adjacent`)."""
+    __slots__ = ("B", "N", "F", "dev", "adj", "__weakref__")
+
+    def __init__(self, B, N, F, dev):
+        self.B, self.N, self.F, self.dev, self.adj = B, N, F, dev, {}
+
+    def adjacency(self, f, narrow):
+        """(3 N) int32: the item across each edge of each item within its image, -1 for none"""
+        key = id(f)
+        hit = self.adj.get(key)
+        if hit is not None:
+            ref, version, ptr, adj = hit
+            if ref() is f and version == f._version and ptr == f.data_ptr():
+                return adj
+            del self.adj[key]
+        dev = self.dev.device
+        n = ctypes.c_size_t(0)
+        _native.check(_native.lib().ls_range_adjacency_workspace_bytes(self.N, ctypes.byref(n)))
+        ws = torch.empty(n.value, dtype=torch.uint8, device=dev)
+        adj = torch.empty(max(3 * self.N, 1), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().ls_range_adjacency(_native.ptr(narrow), narrow.shape[0], _native.ptr(self.dev), self.B, self.N,
+                                                           _native.ptr(adj), _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
+        for k in [k for k, h in self.adj.items() if h[0]() is None]:
+            del self.adj[k]
+        if len(self.adj) >= 8:
+            self.adj.clear()
+        try:
+            self.adj[key] = (weakref.ref(f), f._version, f.data_ptr(), adj)
+        except TypeError:
+            pass
+        return adj
+
+
+def _check_ranges(ranges, F):
+    """Host validation of a range-mode `ranges` against F faces (a CPU tensor: no synchronisation). Returns (B, N = the number of items)."""
+    if not isinstance(ranges, torch.Tensor):
+        raise TypeError(f"ranges must be a torch.Tensor, got {type(ranges).__name__}")
+    if ranges.device.type != "cpu":
+        raise ValueError(f"ranges must be a CPU tensor (its rows are read on the host), got device '{ranges.device}'")
+    if ranges.dtype != torch.int32:
+        raise TypeError(f"ranges must be int32, got {ranges.dtype}")
+    if ranges.dim() != 2 or ranges.shape[1] != 2 or ranges.shape[0] < 1:
+        raise ValueError(f"ranges must be (B, 2) rows of (start, count) with B >= 1, got {tuple(ranges.shape)}")
+    r = ranges.to(torch.int64)
+    start, count = r[:, 0], r[:, 1]
+    bad = (start < 0) | (count < 0) | (start + count > F)
+    if bool(bad.any()):
+        b = int(torch.nonzero(bad)[0])
+        raise ValueError(f"ranges[{b}] = (start {int(start[b])}, count {int(count[b])}) is outside the {F} faces of tri: "
+                         "0 <= start, 0 <= count and start + count <= F are required")
+    N = int(count.sum())
+    if 3 * N >= 2 ** 31 - 1:
+        raise OverflowError(f"ranges hold {N} faces in all: the kernels index their corners with int32")
+    return ranges.shape[0], N
+
+
+def _range_table(ranges, F, dev):
+    """the device table of `ranges`, validated against F faces; cached per ranges tensor (identity, version, data pointer)"""
+    key = id(ranges)
+    hit = _range_tables.get(key)
+    if hit is not None:
+        ref, version, ptr, tab = hit
+        if ref() is ranges and version == ranges._version and ptr == ranges.data_ptr() and tab.F == F and tab.dev.device == dev:
+            return tab
+        del _range_tables[key]
+    B, N = _check_ranges(ranges, F)
+    host = torch.empty((B, 3), dtype=torch.int32)
+    host[:, :2] = ranges
+    count = ranges[:, 1].to(torch.int64)
+    host[:, 2] = (torch.cumsum(count, 0) - count).to(torch.int32)
+    tab = _RangeTable(B, N, F, host.to(dev))
+    for k in [k for k, h in _range_tables.items() if h[0]() is None]:
+        del _range_tables[k]
+    if len(_range_tables) >= 8:
+        _range_tables.clear()
+    _range_tables[key] = (weakref.ref(ranges), ranges._version, ranges.data_ptr(), tab)
+    return tab
+
+
+class _RangeFrame:
+    """What the rast of a range-mode `rasterize` carries: the range table and, made at most once per version of the rast by the first
+    backward that needs it, its pixels sorted by item -- the order every backward sums in."""
+    __slots__ = ("tab", "version", "order", "seg")
+
+    def __init__(self, tab):
+        self.tab, self.version, self.order, self.seg = tab, None, None, None
+
+    def pixel_order(self, r, version):
+        if self.order is None or self.version != version:
+            tab = self.tab
+            B, H, W, _ = r.shape
+            dev = r.device
+            order = torch.empty(B * H * W, dtype=torch.int32, device=dev)
+            seg = torch.empty(tab.N + 1, dtype=torch.int32, device=dev)
+            ws = _range_workspace(B, tab.N, H, W, 0, dev)
+            with torch.cuda.device(dev):
+                _native.check(_native.lib().ls_range_pixel_order(_native.ptr(r), _native.ptr(tab.dev), B, tab.N, tab.F, H, W, _native.ptr(order),
+                                                                 _native.ptr(seg), _native.ptr(ws), ws.numel(), dev.index,
+                                                                 _native.stream_of(dev)))
+            self.order, self.seg, self.version = order, seg, version
+        return self.order, self.seg
+
+
+def _range_frame(rast):
+    """the range frame of a rast that a range-mode `rasterize` returned, None for any other tensor"""
+    frame = getattr(rast, "_largesteps_range", None)
+    if frame is None or not isinstance(rast, torch.Tensor) or rast.dim() != 4 or rast.shape[0] != frame.tab.B:
+        return None
+    return frame
+
+
+def _range_workspace(B, N, H, W, C, dev):
+    n = ctypes.c_size_t(0)
+    _native.check(_native.lib().ls_range_workspace_bytes(B, N, H, W, C, ctypes.byref(n)))
+    return torch.empty(n.value, dtype=torch.uint8, device=dev)
+
+
+def _pos_shared(pos):
+    """the (V, 4) positions of range mode, detached, fp32 and contiguous"""
+    _native.require_device(pos, "pos")
+    if pos.dim() != 2 or pos.shape[1] != 4:
+        raise ValueError(f"pos must be (V, 4) clip-space positions in range mode, got {tuple(pos.shape)}")
+    p = pos.detach()
+    if p.dtype != torch.float32 or not p.is_contiguous():
+        p = p.to(torch.float32).contiguous()
+    return _aligned(p)
+
+
+def _range_faces(tri, V, tab):
+    f, narrow, vptr, order = _faces(tri, V)
+    if narrow.shape[0] != tab.F:
+        raise ValueError(f"tri has {narrow.shape[0]} faces, the range-mode rast was rasterized from {tab.F}")
+    return f, narrow, vptr, order
+
+
+class _RasterizeRange(Function):
+    @staticmethod
+    def forward(ctx, pos, tri, H, W, frame):
+        p = _pos_shared(pos)
+        V, tab = p.shape[0], frame.tab
+        f, narrow, vptr, order = _range_faces(tri, V, tab)
+        B, N, F, dev = tab.B, tab.N, tab.F, p.device
+        rast = torch.empty((B, H, W, 4), dtype=torch.float32, device=dev)
+        ws = _range_workspace(B, N, H, W, 0, dev)
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().ls_range_forward(_native.ptr(p), V, _native.ptr(narrow), F, _native.ptr(tab.dev), B, N, H, W,
+                                                         _native.ptr(rast), _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
+        rast_db = torch.zeros((B, H, W, 4), dtype=torch.float32, device=dev)
+        ctx.mark_non_differentiable(rast_db)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(p, narrow, vptr, order, rast)
+        ctx.frame = frame
+        ctx.HW = (H, W)
+        ctx.pos_shape = tuple(pos.shape)
+        return rast, rast_db
+
+    @staticmethod
+    def backward(ctx, g_rast, g_db):
+        if g_rast is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        p, narrow, vptr, corner_order, rast = ctx.saved_tensors
+        tab = ctx.frame.tab
+        V, B, N, F, dev = p.shape[0], tab.B, tab.N, tab.F, p.device
+        H, W = ctx.HW
+        g = g_rast.to(torch.float32).contiguous()
+        order, seg = ctx.frame.pixel_order(rast, rast._version)
+        ws = _range_workspace(B, N, H, W, 0, dev)
+        gp = torch.empty_like(p)
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().ls_range_backward(_native.ptr(p), V, _native.ptr(narrow), F, _native.ptr(tab.dev), B, N, H, W,
+                                                          _native.ptr(g), _native.ptr(order), _native.ptr(seg), _native.ptr(vptr),
+                                                          _native.ptr(corner_order), _native.ptr(gp), _native.ptr(ws), ws.numel(), dev.index,
+                                                          _native.stream_of(dev)))
+        return gp.view(ctx.pos_shape), None, None, None, None
+
+
+def _rasterize_range(pos, tri, H, W, resolution, ranges):
+    for t, what in ((pos, "pos"), (tri, "tri")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what} must be a torch.Tensor, got {type(t).__name__}")
+    if pos.dim() == 3:
+        raise ValueError(f"range mode (ranges=...) takes one shared pos (V, 4), got {tuple(pos.shape)}: a (B, V, 4) pos is instanced mode "
+                         "(ranges=None)")
+    if pos.dim() != 2 or pos.shape[1] != 4:
+        raise ValueError(f"pos must be (V, 4) clip-space positions in range mode, got {tuple(pos.shape)}")
+    if tri.dim() != 2 or tri.shape[1] != 3:
+        raise ValueError(f"tri must be (F, 3), got {tuple(tri.shape)}")
+    F = tri.shape[0]
+    on_device = pos.is_cuda and tri.is_cuda
+    tab = _range_table(ranges, F, pos.device) if on_device else None
+    if tab is None:
+        _check_ranges(ranges, F)
+    if not (1 <= H <= 4096 and 1 <= W <= 4096):
+        raise ValueError(f"resolution must be (H, W) with each in [1, 4096], got {tuple(resolution)}")
+    if not on_device:
+        raise NotImplementedError("largesteps.render.rasterize: range mode (ranges=...) needs a HIP device: pos and tri must live on 'cuda' "
+                                  "(there is no CPU path in this package)")
+    if tab.B * H * W >= 2 ** 31 - 1:
+        raise OverflowError(f"{tab.B} images of {H} x {W} pixels: the kernels index pixels with int32")
+    frame = _RangeFrame(tab)
+    rast, rast_db = _RasterizeRange.apply(pos, tri, H, W, frame)
+    rast._largesteps_range = frame
+    return rast, rast_db
+
+
+class _InterpolateRange(Function):
+    @staticmethod
+    def forward(ctx, attr, rast, tri, frame):
+        _native.require_device(attr, "attr")
+        r = _rast(rast)
+        B, H, W, _ = r.shape
+        a = (attr.unsqueeze(0) if attr.dim() == 2 else attr).detach()
+        if a.dtype != torch.float32 or not a.is_contiguous():
+            a = a.to(torch.float32).contiguous()
+        _, V, C = a.shape
+        f, narrow, vptr, order = _range_faces(tri, V, frame.tab)
+        F, dev = narrow.shape[0], r.device
+        out = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):          # ids are global and attr is shared: the instanced kernel as it is
+            _native.check(_native.lib().ls_raster_interpolate(_native.ptr(a), 1, V, C, _native.ptr(r), B, H, W, _native.ptr(narrow), F,
+                                                              _native.ptr(out), dev.index, _native.stream_of(dev)))
+        ctx.save_for_backward(a, r, narrow, vptr, order)
+        ctx.frame = frame
+        ctx.rast_version = rast._version
+        ctx.attr_shape = tuple(attr.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        need_attr, need_rast = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_attr or need_rast):
+            return None, None, None, None
+        a, r, narrow, vptr, corner_order = ctx.saved_tensors
+        tab = ctx.frame.tab
+        B, H, W, _ = r.shape
+        _, V, C = a.shape
+        F, dev = narrow.shape[0], r.device
+        g = g.to(torch.float32).contiguous()
+        ga = torch.empty_like(a) if need_attr else None
+        gr = torch.empty((B, H, W, 4), dtype=torch.float32, device=dev) if need_rast else None
+        lib = _native.lib()
+        with torch.cuda.device(dev):
+            st = _native.stream_of(dev)
+            if need_rast:
+                _native.check(lib.ls_raster_interpolate_backward(
+                    _native.ptr(a), 1, V, C, _native.ptr(r), B, H, W, _native.ptr(narrow), F, _native.ptr(g), None, None, None, None, None,
+                    _native.ptr(gr), None, 0, dev.index, st))
+            if need_attr:
+                order, seg = ctx.frame.pixel_order(r, ctx.rast_version)
+                ws = _range_workspace(B, tab.N, H, W, C, dev)
+                _native.check(lib.ls_range_interpolate_backward(
+                    _native.ptr(r), _native.ptr(tab.dev), B, tab.N, H, W, V, C, _native.ptr(g), _native.ptr(order), _native.ptr(seg),
+                    _native.ptr(vptr), _native.ptr(corner_order), _native.ptr(ga), _native.ptr(ws), ws.numel(), dev.index, st))
+        return (ga.view(ctx.attr_shape) if need_attr else None), gr, None, None
+
+
+class _AntialiasRange(Function):
+    @staticmethod
+    def forward(ctx, color, rast, pos, tri, boost, frame):
+        _native.require_device(color, "color")
+        r = _rast(rast)
+        p = _pos_shared(pos)
+        B, H, W, _ = r.shape
+        if color.dim() != 4 or tuple(color.shape[:3]) != (B, H, W):
+            raise ValueError(f"color must be ({B}, {H}, {W}, C), got {tuple(color.shape)}")
+        c = color.detach()
+        if c.dtype != torch.float32 or not c.is_contiguous():
+            c = c.to(torch.float32).contiguous()
+        C, V, tab = c.shape[3], p.shape[0], frame.tab
+        f, narrow, vptr, order = _range_faces(tri, V, tab)
+        adj = tab.adjacency(f, narrow)
+        F, dev = narrow.shape[0], r.device
+        out = torch.empty_like(c)
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().ls_range_antialias(_native.ptr(c), C, _native.ptr(r), _native.ptr(p), V, _native.ptr(narrow), F,
+                                                           _native.ptr(tab.dev), B, tab.N, H, W, _native.ptr(adj), _native.ptr(out), dev.index,
+                                                           _native.stream_of(dev)))
+        ctx.save_for_backward(c, r, p, narrow, adj, vptr, order)
+        ctx.boost = float(boost)
+        ctx.frame = frame
+        ctx.rast_version = rast._version
+        ctx.pos_shape = tuple(pos.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        need_color, need_pos = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
+        if not (need_color or need_pos):
+            return None, None, None, None, None, None
+        c, r, p, narrow, adj, vptr, corner_order = ctx.saved_tensors
+        tab = ctx.frame.tab
+        B, H, W, C = c.shape
+        V, F, dev = p.shape[0], narrow.shape[0], c.device
+        g = g.to(torch.float32).contiguous()
+        gc = torch.empty_like(c) if need_color else None
+        gp = torch.empty_like(p) if need_pos else None
+        order = seg = ws = None
+        if need_pos:
+            order, seg = ctx.frame.pixel_order(r, ctx.rast_version)
+            ws = _range_workspace(B, tab.N, H, W, 0, dev)
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().ls_range_antialias_backward(
+                _native.ptr(c), C, _native.ptr(r), _native.ptr(p), V, _native.ptr(narrow), F, _native.ptr(tab.dev), B, tab.N, H, W,
+                _native.ptr(adj), _native.ptr(g), ctx.boost, _native.ptr(order), _native.ptr(seg), _native.ptr(vptr), _native.ptr(corner_order),
+                _native.ptr(gc), _native.ptr(gp), _native.ptr(ws), 0 if ws is None else ws.numel(), dev.index, _native.stream_of(dev)))
+        return gc, None, (gp.view(ctx.pos_shape) if need_pos else None), None, None, None
 
 
 class _DbSource:
@@ -245,6 +576,9 @@ def pixel_differentials(rast, pos, tri):
     The result is not differentiable. nvdiffrast propagates a second-order term through its rast_db to pos; this package does not: the
     level of detail chosen from these differentials is treated as a constant of the geometry.
     """
+    if isinstance(pos, torch.Tensor) and pos.dim() == 2:
+        raise NotImplementedError("largesteps.render.pixel_differentials: a (V, 4) pos (range mode) is not supported; pixel differentials "
+                                  "need instanced mode, pos (B, V, 4)")
     r, p = _rast(rast), _pos(pos)
     B, H, W, _ = r.shape
     if p.shape[0] != B:
@@ -365,7 +699,9 @@ def interpolate(attr, rast, tri, rast_db=None, diff_attrs=None):
     unless diff_attrs is given.
 
     attr : (V, C), (1, V, C) (shared by every image, as the reference passes it) or (B, V, C) fp32
-    rast : the first output of `rasterize`
+    rast : the first output of `rasterize`. The rast of a range-mode call (it carries the range table; pass the very tensor `rasterize`
+           returned) takes attr (V, C) or (1, V, C) only, indexed by the global vertex ids of tri; the slice law of the module's docstring
+           holds for out and for both gradients. diff_attrs is not supported with it (NotImplementedError).
     tri : the faces given to `rasterize`
     rast_db : the second output of `rasterize` (the differentials are then computed from its frame, once, by `pixel_differentials`) or
               an ordinary (B, H, W, 4) tensor of (du/dX, du/dY, dv/dX, dv/dY), used as given. Needed only with diff_attrs.
@@ -377,6 +713,14 @@ def interpolate(attr, rast, tri, rast_db=None, diff_attrs=None):
     """
     if diff_attrs is not None and rast_db is None:
         raise ValueError("largesteps.render.interpolate: diff_attrs needs rast_db (the second output of rasterize)")
+    frame = _range_frame(rast)
+    if frame is not None:
+        if diff_attrs is not None:
+            raise NotImplementedError("largesteps.render.interpolate: diff_attrs is not supported for a rast of range mode (ranges=...)")
+        if not isinstance(attr, torch.Tensor) or attr.dim() not in (2, 3) or (attr.dim() == 3 and attr.shape[0] != 1):
+            raise ValueError("attr must be (V, C) or (1, V, C) for a rast of range mode (the images share one vertex array), got "
+                             f"{tuple(attr.shape) if isinstance(attr, torch.Tensor) else type(attr).__name__}")
+        return _InterpolateRange.apply(attr, rast, tri, frame), None
     F = tri.shape[0] if isinstance(tri, torch.Tensor) and tri.dim() == 2 else 0
     slot = _order_slot(rast, F)
     out = _Interpolate.apply(attr, rast, tri, slot)
@@ -449,7 +793,20 @@ def antialias(color, rast, pos, tri, topology_hash=None, pos_gradient_boost=1.0)
         alpha > 1/2: other += (alpha - 1/2) (c_n - c_o)        alpha < 1/2: nearer += (1/2 - alpha) (c_o - c_n)
     which makes the image continuous in the vertex positions. Gradients flow to color and to pos (the latter scaled by
     pos_gradient_boost). topology_hash is accepted and ignored (the edge adjacency is cached per face tensor).
+
+    Range mode: pos (V, 4) and the rast that the range-mode `rasterize` returned (the tensor itself: it carries the range table). The
+    silhouette test then uses each image's own faces -- the neighbour across an edge within tri[start_b : start_b + count_b], cached per
+    (face tensor, ranges tensor) -- and the slice law of the module's docstring holds for the image and for both gradients.
     """
+    frame = _range_frame(rast)
+    if isinstance(pos, torch.Tensor) and pos.dim() == 2:
+        if frame is None:
+            raise ValueError("largesteps.render.antialias: a (V, 4) pos is range mode and needs the range table that its rast carries: pass "
+                             "the tensor that rasterize(..., ranges=...) returned (not a copy of it)")
+        return _AntialiasRange.apply(color, rast, pos, tri, float(pos_gradient_boost), frame)
+    if frame is not None:
+        raise ValueError(f"rast comes from a range-mode rasterize: pos must be the (V, 4) positions given to it, got "
+                         f"{tuple(pos.shape) if isinstance(pos, torch.Tensor) else type(pos).__name__}")
     F = tri.shape[0] if isinstance(tri, torch.Tensor) and tri.dim() == 2 else 0
     slot = _order_slot(rast, F)
     out = _Antialias.apply(color, rast, pos, tri, float(pos_gradient_boost), slot)
