@@ -717,33 +717,187 @@ int rg_check(int64_t B, int64_t N, int64_t V, int64_t F, int H, int W, const cha
     return LS_OK;
 }
 
-// ---- the launches both modes share: `map` takes a key to its image and face, nk keys --------------------------------------------------
+// ---- a mode above the kernels: its key map, B images, nk keys (the workspace is rs_layout_keys(B H W, nk, C)), V vertices (per image when
+// instanced) and F faces -- and, by overload, its size check and the launches of its two gather kernels (whose summation orders differ: the
+// slice law). Each extern "C" function below hands its mode `m`, its name `who` and its pointer test `ok` to a body written once -------------
 template <class Map>
-int rs_forward(Map map, const float* pos, const int32_t* tri, int64_t B, int64_t nk, int64_t V, int64_t F, int H, int W, float* rast, char* w,
-               const RsWs& L, hipStream_t st) {
+struct Mode {
+    Map map;
+    int64_t B, nk, V, F;
+};
+using Inst = Mode<MapInst>;
+using Range = Mode<MapRange>;
+
+Inst inst(int64_t B, int64_t V, int64_t F) { return {MapInst{}, B, B * F, V, F}; }
+Range range(const int32_t* ranges, int64_t B, int64_t N, int64_t V, int64_t F) { return {MapRange{ranges, (int)B}, B, N, V, F}; }
+
+int rs_check(const Inst& m, int H, int W, const char* who) { return rs_check(m.B, m.V, m.F, H, W, who); }
+int rs_check(const Range& m, int H, int W, const char* who) { return rg_check(m.B, m.nk, m.V, m.F, H, W, who); }
+
+void rs_gather_pos(const Inst& m, const float* rows, const int32_t* vptr, const int32_t* corner_order, float* grad_pos, hipStream_t st) {
+    if (m.B * m.V > 0)
+        hipLaunchKernelGGL(k_rs_gather_pos, dim3(div_up(m.B * m.V, 256)), dim3(256), 0, st, rows, vptr, corner_order, (int)m.B, m.V, m.F, grad_pos);
+}
+void rs_gather_pos(const Range& m, const float* rows, const int32_t* vptr, const int32_t* corner_order, float* grad_pos, hipStream_t st) {
+    if (m.V > 0)
+        hipLaunchKernelGGL(k_rg_gather_pos, dim3(div_up(m.V, 256)), dim3(256), 0, st, rows, vptr, corner_order, m.map.rt, m.map.B, m.V, grad_pos);
+}
+
+void rs_gather_attr(const Inst& m, const float* rows, const int32_t* vptr, const int32_t* corner_order, int64_t attr_batch, int C, float* grad_attr,
+                    hipStream_t st) {
+    if (attr_batch * m.V * C > 0)
+        hipLaunchKernelGGL(k_rs_gather_attr, dim3(div_up(attr_batch * m.V * C, 256)), dim3(256), 0, st, rows, vptr, corner_order, (int)m.B,
+                           (int)attr_batch, m.V, m.F, C, grad_attr);
+}
+void rs_gather_attr(const Range& m, const float* rows, const int32_t* vptr, const int32_t* corner_order, int64_t, int C, float* grad_attr,
+                    hipStream_t st) {
+    if (m.V * C > 0)
+        hipLaunchKernelGGL(k_rg_gather_attr, dim3(div_up(m.V * C, 256)), dim3(256), 0, st, rows, vptr, corner_order, m.map.rt, m.map.B, m.V, C,
+                           grad_attr);
+}
+
+template <class Map>
+int rs_forward(const Mode<Map>& m, const char* who, bool ok, const float* pos, const int32_t* tri, int H, int W, float* rast, void* ws, size_t ws_bytes,
+               int device, void* stream) {
+    int rc = rs_check(m, H, W, who);
+    if (rc) return rc;
+    const RsWs L = rs_layout_keys(m.B * H * W, m.nk, 0);
+    LS_REQUIRE(ok, LS_E_INVALID, "%s: null argument", who);
+    LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, L.total);
+    DeviceGuard g(device);
+    LS_HIP(g.err);
+    hipStream_t st = (hipStream_t)stream;
+    char* w = (char*)ws;
     u64* depth = (u64*)(w + L.depth);
     int* tiles = (int*)(w + L.tiles);
     int* toff = (int*)(w + L.toff);
-    const int64_t N = B * H * W;
+    const int64_t N = m.B * H * W, nk = m.nk;
     LS_HIP(hipMemsetAsync(depth, 0xff, 8 * (size_t)N, st));
     if (nk > 0) {
-        hipLaunchKernelGGL(k_rs_small<Map>, dim3(div_up(nk, 256)), dim3(256), 0, st, map, pos, tri, nk, V, F, H, W, depth, tiles);
-        int rc = exclusive_scan(tiles, nk, toff, (int*)(w + L.bsum), st);
+        hipLaunchKernelGGL(k_rs_small<Map>, dim3(div_up(nk, 256)), dim3(256), 0, st, m.map, pos, tri, nk, m.V, m.F, H, W, depth, tiles);
+        rc = exclusive_scan(tiles, nk, toff, (int*)(w + L.bsum), st);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_rs_large<Map>, dim3(RS_LARGE_GRID), dim3(256), 0, st, map, pos, tri, nk, V, F, H, W, (const int*)toff, depth);
+        hipLaunchKernelGGL(k_rs_large<Map>, dim3(RS_LARGE_GRID), dim3(256), 0, st, m.map, pos, tri, nk, m.V, m.F, H, W, (const int*)toff, depth);
     }
-    hipLaunchKernelGGL(k_rs_resolve<Map>, dim3(div_up(N, 256)), dim3(256), 0, st, map, pos, tri, (int)B, V, F, H, W, (const u64*)depth, rast);
+    hipLaunchKernelGGL(k_rs_resolve<Map>, dim3(div_up(N, 256)), dim3(256), 0, st, m.map, pos, tri, (int)m.B, m.V, m.F, H, W, (const u64*)depth,
+                       rast);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
 
 template <class Map>
-int rs_pixel_order(Map map, const float* rast, int64_t B, int64_t nk, int64_t F, int H, int W, int32_t* order, int32_t* seg, char* w,
-                   const RsWs& L, hipStream_t st) {
-    const int64_t N = B * H * W;
-    int* keys = (int*)(w + L.keys);
-    hipLaunchKernelGGL(k_rs_keys<Map>, dim3(div_up(N, 256)), dim3(256), 0, st, map, rast, N, (int64_t)H * W, F, nk, keys);
-    return group_by_key<false>(keys, N, nk, order, seg, sort_scratch_carve(w + L.sort, N, false), st);
+int rs_pixel_order(const Mode<Map>& m, const char* who, bool ok, const float* rast, int H, int W, int32_t* order, int32_t* seg, void* ws,
+                   size_t ws_bytes, int device, void* stream) {
+    int rc = rs_check(m, H, W, who);
+    if (rc) return rc;
+    const RsWs L = rs_layout_keys(m.B * H * W, m.nk, 0);
+    LS_REQUIRE(ok, LS_E_INVALID, "%s: null argument", who);
+    LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, L.total);
+    DeviceGuard g(device);
+    LS_HIP(g.err);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t N = m.B * H * W, nk = m.nk;
+    int* keys = (int*)((char*)ws + L.keys);
+    hipLaunchKernelGGL(k_rs_keys<Map>, dim3(div_up(N, 256)), dim3(256), 0, st, m.map, rast, N, (int64_t)H * W, m.F, nk, keys);
+    return group_by_key<false>(keys, N, nk, order, seg, sort_scratch_carve((char*)ws + L.sort, N, false), st);
+}
+
+template <class Map>
+int rs_backward(const Mode<Map>& m, const char* who, bool ok, const float* pos, const int32_t* tri, int H, int W, const float* grad_rast,
+                const int32_t* order, const int32_t* seg, const int32_t* vptr, const int32_t* corner_order, float* grad_pos, void* ws,
+                size_t ws_bytes, int device, void* stream) {
+    int rc = rs_check(m, H, W, who);
+    if (rc) return rc;
+    const RsWs L = rs_layout_keys(m.B * H * W, m.nk, 0);
+    LS_REQUIRE(ok, LS_E_INVALID, "%s: null argument", who);
+    LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, L.total);
+    DeviceGuard g(device);
+    LS_HIP(g.err);
+    hipStream_t st = (hipStream_t)stream;
+    float* rows = (float*)((char*)ws + L.rows);
+    const int64_t nk = m.nk;
+    if (nk > 0) {
+        RowRaster<Map> r{m.map, pos, tri, grad_rast, m.V, m.F, H, W};
+        hipLaunchKernelGGL(k_rs_seg_sum<RowRaster<Map>>, dim3(div_up(nk, 256)), dim3(256), 0, st, r, order, seg, nk, 9, 0, rows);
+    }
+    rs_gather_pos(m, rows, vptr, corner_order, grad_pos, st);
+    LS_HIP(hipGetLastError());
+    return LS_OK;
+}
+
+// the grad_attr half of interpolate's backward, after its entry point's checks
+template <class Map>
+void rs_interp_grad_attr(const Mode<Map>& m, const float* rast, int64_t attr_batch, int C, const float* grad_out, const int32_t* order,
+                         const int32_t* seg, const int32_t* vptr, const int32_t* corner_order, float* grad_attr, float* rows, hipStream_t st) {
+    const int64_t nk = m.nk;
+    if (nk > 0)
+        for (int c = 0; c < C; ++c) {
+            RowInterp r{rast, grad_out, C, c};
+            hipLaunchKernelGGL(k_rs_seg_sum<RowInterp>, dim3(div_up(nk, 256)), dim3(256), 0, st, r, order, seg, nk, 3 * C, 3 * c, rows);
+        }
+    rs_gather_attr(m, rows, vptr, corner_order, attr_batch, C, grad_attr, st);
+}
+
+// the half-edge ids of nk faces or items, the sort's scratch behind them
+size_t rs_adjacency_bytes(int64_t nk) { return 4 * (size_t)(3 * nk) + sort_scratch_bytes(3 * nk, true); }
+
+// the n half-edges sorted by the WORDS words of `key` (the last one `last_bytes` wide), each paired with the other one of its edge
+template <class Key, int WORDS>
+int rs_adjacency(Key key, int64_t n, int last_bytes, int32_t* adj, void* ws, int device, void* stream) {
+    DeviceGuard g(device);
+    LS_HIP(g.err);
+    hipStream_t st = (hipStream_t)stream;
+    int* ord_a = (int*)ws;
+    const int* sorted = nullptr;
+    int rc = radix_argsort_words(key, n, WORDS, ord_a, sort_scratch_carve(ord_a + n, n, true), st, &sorted, last_bytes);
+    if (rc) return rc;
+    hipLaunchKernelGGL((k_rs_adjacency<Key, WORDS>), dim3(div_up(n, 256)), dim3(256), 0, st, key, sorted, n, adj);
+    LS_HIP(hipGetLastError());
+    return LS_OK;
+}
+
+template <class Map>
+int rs_antialias(const Mode<Map>& m, const char* who, bool ok, const float* color, int C, const float* rast, const float* pos, const int32_t* tri,
+                 const int32_t* adj, int H, int W, float* out, int device, void* stream) {
+    int rc = rs_check(m, H, W, who);
+    if (rc) return rc;
+    LS_REQUIRE(ok, LS_E_INVALID, "%s: bad argument", who);
+    DeviceGuard g(device);
+    LS_HIP(g.err);
+    AAMesh<Map> mesh{m.map, pos, tri, adj, rast, m.V, m.F, H, W};
+    hipLaunchKernelGGL(k_aa_forward<Map>, dim3(div_up(m.B * H * W, 256)), dim3(256), 0, (hipStream_t)stream, mesh, (int)m.B, color, C, out);
+    LS_HIP(hipGetLastError());
+    return LS_OK;
+}
+
+template <class Map>
+int rs_antialias_backward(const Mode<Map>& m, const char* who, bool ok, const float* color, int C, const float* rast, const float* pos,
+                          const int32_t* tri, const int32_t* adj, int H, int W, const float* grad_out, float boost, const int32_t* order,
+                          const int32_t* seg, const int32_t* vptr, const int32_t* corner_order, float* grad_color, float* grad_pos, void* ws,
+                          size_t ws_bytes, int device, void* stream) {
+    int rc = rs_check(m, H, W, who);
+    if (rc) return rc;
+    const int64_t N = m.B * H * W, nk = m.nk;
+    const RsWs L = rs_layout_keys(N, nk, 0);
+    LS_REQUIRE(ok, LS_E_INVALID, "%s: bad argument", who);
+    LS_REQUIRE(!grad_pos || (order && seg && vptr && ws && (corner_order || m.F == 0)), LS_E_INVALID,
+               "%s: grad_pos needs the pixel order, the corner ranking and a workspace", who);
+    LS_REQUIRE(!grad_pos || ws_bytes >= L.total, LS_E_WORKSPACE, "%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, L.total);
+    DeviceGuard g(device);
+    LS_HIP(g.err);
+    hipStream_t st = (hipStream_t)stream;
+    AAMesh<Map> mesh{m.map, pos, tri, adj, rast, m.V, m.F, H, W};
+    if (grad_color) hipLaunchKernelGGL(k_aa_grad_color<Map>, dim3(div_up(N, 256)), dim3(256), 0, st, mesh, (int)m.B, grad_out, C, grad_color);
+    if (grad_pos) {
+        float* rows = (float*)((char*)ws + L.rows);
+        if (nk > 0) {
+            RowAA<Map> r{mesh, color, grad_out, C, boost};
+            hipLaunchKernelGGL(k_rs_seg_sum<RowAA<Map>>, dim3(div_up(nk, 256)), dim3(256), 0, st, r, order, seg, nk, 9, 0, rows);
+        }
+        rs_gather_pos(m, rows, vptr, corner_order, grad_pos, st);
+    }
+    LS_HIP(hipGetLastError());
+    return LS_OK;
 }
 
 }  // namespace
@@ -758,50 +912,21 @@ extern "C" int ls_raster_workspace_bytes(int64_t B, int64_t F, int H, int W, int
 
 extern "C" int ls_raster_forward(const float* pos, int64_t B, int64_t V, const int32_t* tri, int64_t F, int H, int W, float* rast, void* ws,
                                  size_t ws_bytes, int device, void* stream) {
-    int rc = rs_check(B, V, F, H, W, "ls_raster_forward");
-    if (rc) return rc;
-    const RsWs L = rs_layout(B, F, H, W, 0);
-    LS_REQUIRE(rast && ws && (pos || V == 0) && (tri || F == 0), LS_E_INVALID, "ls_raster_forward: null argument");
-    LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_raster_forward: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
-    DeviceGuard g(device);
-    LS_HIP(g.err);
-    return rs_forward(MapInst{}, pos, tri, B, B * F, V, F, H, W, rast, (char*)ws, L, (hipStream_t)stream);
+    return rs_forward(inst(B, V, F), "ls_raster_forward", rast && ws && (pos || V == 0) && (tri || F == 0), pos, tri, H, W, rast, ws, ws_bytes,
+                      device, stream);
 }
 
 extern "C" int ls_raster_pixel_order(const float* rast, int64_t B, int64_t F, int H, int W, int32_t* order, int32_t* seg, void* ws,
                                      size_t ws_bytes, int device, void* stream) {
-    int rc = rs_check(B, 0, F, H, W, "ls_raster_pixel_order");
-    if (rc) return rc;
-    const RsWs L = rs_layout(B, F, H, W, 0);
-    LS_REQUIRE(rast && order && seg && ws, LS_E_INVALID, "ls_raster_pixel_order: null argument");
-    LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_raster_pixel_order: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
-    DeviceGuard g(device);
-    LS_HIP(g.err);
-    return rs_pixel_order(MapInst{}, rast, B, B * F, F, H, W, order, seg, (char*)ws, L, (hipStream_t)stream);
+    return rs_pixel_order(inst(B, 0, F), "ls_raster_pixel_order", rast && order && seg && ws, rast, H, W, order, seg, ws, ws_bytes, device, stream);
 }
 
 extern "C" int ls_raster_backward(const float* pos, int64_t B, int64_t V, const int32_t* tri, int64_t F, int H, int W, const float* grad_rast,
                                   const int32_t* order, const int32_t* seg, const int32_t* vptr, const int32_t* corner_order, float* grad_pos,
                                   void* ws, size_t ws_bytes, int device, void* stream) {
-    int rc = rs_check(B, V, F, H, W, "ls_raster_backward");
-    if (rc) return rc;
-    const RsWs L = rs_layout(B, F, H, W, 0);
-    LS_REQUIRE(grad_rast && order && seg && vptr && grad_pos && ws && (pos || V == 0) && (tri || F == 0) && (corner_order || F == 0),
-               LS_E_INVALID, "ls_raster_backward: null argument");
-    LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_raster_backward: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
-    DeviceGuard g(device);
-    LS_HIP(g.err);
-    hipStream_t st = (hipStream_t)stream;
-    float* rows = (float*)((char*)ws + L.rows);
-    const int64_t nk = B * F;
-    if (nk > 0) {
-        RowRaster<MapInst> r{MapInst{}, pos, tri, grad_rast, V, F, H, W};
-        hipLaunchKernelGGL(k_rs_seg_sum<RowRaster<MapInst>>, dim3(div_up(nk, 256)), dim3(256), 0, st, r, order, seg, nk, 9, 0, rows);
-    }
-    if (B * V > 0)
-        hipLaunchKernelGGL(k_rs_gather_pos, dim3(div_up(B * V, 256)), dim3(256), 0, st, (const float*)rows, vptr, corner_order, (int)B, V, F, grad_pos);
-    LS_HIP(hipGetLastError());
-    return LS_OK;
+    const bool ok = grad_rast && order && seg && vptr && grad_pos && ws && (pos || V == 0) && (tri || F == 0) && (corner_order || F == 0);
+    return rs_backward(inst(B, V, F), "ls_raster_backward", ok, pos, tri, H, W, grad_rast, order, seg, vptr, corner_order, grad_pos, ws, ws_bytes,
+                       device, stream);
 }
 
 extern "C" int ls_raster_interpolate(const float* attr, int64_t attr_batch, int64_t V, int C, const float* rast, int64_t B, int H, int W,
@@ -837,28 +962,19 @@ extern "C" int ls_raster_interpolate_backward(const float* attr, int64_t attr_ba
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
-    const int64_t N = B * H * W, nk = B * F;
     if (grad_rast)
-        hipLaunchKernelGGL(k_rs_interp_grad_rast, dim3(div_up(N, 256)), dim3(256), 0, st, attr, (int)attr_batch, V, C, rast, (int)B, (int64_t)H * W,
-                           tri, F, grad_out, grad_rast);
-    if (grad_attr) {
-        float* rows = (float*)((char*)ws + L.rows);
-        if (nk > 0)
-            for (int c = 0; c < C; ++c) {
-                RowInterp r{rast, grad_out, C, c};
-                hipLaunchKernelGGL(k_rs_seg_sum<RowInterp>, dim3(div_up(nk, 256)), dim3(256), 0, st, r, order, seg, nk, 3 * C, 3 * c, rows);
-            }
-        if (attr_batch * V * C > 0)
-            hipLaunchKernelGGL(k_rs_gather_attr, dim3(div_up(attr_batch * V * C, 256)), dim3(256), 0, st, (const float*)rows, vptr, corner_order,
-                               (int)B, (int)attr_batch, V, F, C, grad_attr);
-    }
+        hipLaunchKernelGGL(k_rs_interp_grad_rast, dim3(div_up(B * H * W, 256)), dim3(256), 0, st, attr, (int)attr_batch, V, C, rast, (int)B,
+                           (int64_t)H * W, tri, F, grad_out, grad_rast);
+    if (grad_attr)
+        rs_interp_grad_attr(inst(B, V, F), rast, attr_batch, C, grad_out, order, seg, vptr, corner_order, grad_attr,
+                            (float*)((char*)ws + L.rows), st);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
 
 extern "C" int ls_raster_adjacency_workspace_bytes(int64_t F, size_t* bytes) {
     LS_REQUIRE(bytes && F >= 0 && 3 * F < ((int64_t)1 << 31) - 1, LS_E_INVALID, "ls_raster_adjacency_workspace_bytes: bad argument");
-    *bytes = 4 * (size_t)(3 * F) + sort_scratch_bytes(3 * F, true);       // the half-edge ids, the sort's scratch behind them
+    *bytes = rs_adjacency_bytes(F);
     return LS_OK;
 }
 
@@ -869,66 +985,22 @@ extern "C" int ls_raster_adjacency(const int32_t* tri, int64_t F, int32_t* adj, 
     LS_REQUIRE(adj && ws && (tri || F == 0), LS_E_INVALID, "ls_raster_adjacency: null argument");
     LS_REQUIRE(ws_bytes >= need, LS_E_WORKSPACE, "ls_raster_adjacency: workspace too small (%zu < %zu bytes)", ws_bytes, need);
     if (F == 0) return LS_OK;
-    DeviceGuard g(device);
-    LS_HIP(g.err);
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t n = 3 * F;
-    int* ord_a = (int*)ws;
-    const int* sorted = nullptr;
-    KeyEdge key{tri};
-    rc = radix_argsort_words(key, n, 2, ord_a, sort_scratch_carve(ord_a + n, n, true), st, &sorted);
-    if (rc) return rc;
-    hipLaunchKernelGGL((k_rs_adjacency<KeyEdge, 2>), dim3(div_up(n, 256)), dim3(256), 0, st, key, sorted, n, adj);
-    LS_HIP(hipGetLastError());
-    return LS_OK;
+    return rs_adjacency<KeyEdge, 2>(KeyEdge{tri}, 3 * F, 4, adj, ws, device, stream);
 }
 
 extern "C" int ls_raster_antialias(const float* color, int C, const float* rast, const float* pos, int64_t B, int64_t V, int H, int W,
                                    const int32_t* tri, int64_t F, const int32_t* adj, float* out, int device, void* stream) {
-    int rc = rs_check(B, V, F, H, W, "ls_raster_antialias");
-    if (rc) return rc;
-    LS_REQUIRE(C >= 1 && color && rast && out && (pos || V == 0) && ((tri && adj) || F == 0), LS_E_INVALID, "ls_raster_antialias: bad argument");
-    DeviceGuard g(device);
-    LS_HIP(g.err);
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t N = B * H * W;
-    AAMesh<MapInst> m{MapInst{}, pos, tri, adj, rast, V, F, H, W};
-    hipLaunchKernelGGL(k_aa_forward<MapInst>, dim3(div_up(N, 256)), dim3(256), 0, st, m, (int)B, color, C, out);
-    LS_HIP(hipGetLastError());
-    return LS_OK;
+    const bool ok = C >= 1 && color && rast && out && (pos || V == 0) && ((tri && adj) || F == 0);
+    return rs_antialias(inst(B, V, F), "ls_raster_antialias", ok, color, C, rast, pos, tri, adj, H, W, out, device, stream);
 }
 
 extern "C" int ls_raster_antialias_backward(const float* color, int C, const float* rast, const float* pos, int64_t B, int64_t V, int H, int W,
                                             const int32_t* tri, int64_t F, const int32_t* adj, const float* grad_out, float boost,
                                             const int32_t* order, const int32_t* seg, const int32_t* vptr, const int32_t* corner_order,
                                             float* grad_color, float* grad_pos, void* ws, size_t ws_bytes, int device, void* stream) {
-    int rc = rs_check(B, V, F, H, W, "ls_raster_antialias_backward");
-    if (rc) return rc;
-    const RsWs L = rs_layout(B, F, H, W, 0);
-    LS_REQUIRE(C >= 1 && color && rast && grad_out && (pos || V == 0) && ((tri && adj) || F == 0), LS_E_INVALID,
-               "ls_raster_antialias_backward: bad argument");
-    LS_REQUIRE(!grad_pos || (order && seg && vptr && ws && (corner_order || F == 0)), LS_E_INVALID,
-               "ls_raster_antialias_backward: grad_pos needs the pixel order, the corner ranking and a workspace");
-    LS_REQUIRE(!grad_pos || ws_bytes >= L.total, LS_E_WORKSPACE, "ls_raster_antialias_backward: workspace too small (%zu < %zu bytes)", ws_bytes,
-               L.total);
-    DeviceGuard g(device);
-    LS_HIP(g.err);
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t N = B * H * W, nk = B * F;
-    AAMesh<MapInst> m{MapInst{}, pos, tri, adj, rast, V, F, H, W};
-    if (grad_color) hipLaunchKernelGGL(k_aa_grad_color<MapInst>, dim3(div_up(N, 256)), dim3(256), 0, st, m, (int)B, grad_out, C, grad_color);
-    if (grad_pos) {
-        float* rows = (float*)((char*)ws + L.rows);
-        if (nk > 0) {
-            RowAA<MapInst> r{m, color, grad_out, C, boost};
-            hipLaunchKernelGGL(k_rs_seg_sum<RowAA<MapInst>>, dim3(div_up(nk, 256)), dim3(256), 0, st, r, order, seg, nk, 9, 0, rows);
-        }
-        if (B * V > 0)
-            hipLaunchKernelGGL(k_rs_gather_pos, dim3(div_up(B * V, 256)), dim3(256), 0, st, (const float*)rows, vptr, corner_order, (int)B, V, F,
-                               grad_pos);
-    }
-    LS_HIP(hipGetLastError());
-    return LS_OK;
+    const bool ok = C >= 1 && color && rast && grad_out && (pos || V == 0) && ((tri && adj) || F == 0);
+    return rs_antialias_backward(inst(B, V, F), "ls_raster_antialias_backward", ok, color, C, rast, pos, tri, adj, H, W, grad_out, boost, order, seg,
+                                 vptr, corner_order, grad_color, grad_pos, ws, ws_bytes, device, stream);
 }
 
 // ---- range mode ---------------------------------------------------------------------------------------------------------------------------
@@ -942,50 +1014,22 @@ extern "C" int ls_range_workspace_bytes(int64_t B, int64_t N, int H, int W, int 
 
 extern "C" int ls_range_forward(const float* pos, int64_t V, const int32_t* tri, int64_t F, const int32_t* ranges, int64_t B, int64_t N, int H,
                                 int W, float* rast, void* ws, size_t ws_bytes, int device, void* stream) {
-    int rc = rg_check(B, N, V, F, H, W, "ls_range_forward");
-    if (rc) return rc;
-    const RsWs L = rs_layout_keys(B * H * W, N, 0);
-    LS_REQUIRE(rast && ws && ranges && ((pos && tri) || N == 0), LS_E_INVALID, "ls_range_forward: null argument");
-    LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_range_forward: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
-    DeviceGuard g(device);
-    LS_HIP(g.err);
-    return rs_forward(MapRange{ranges, (int)B}, pos, tri, B, N, V, F, H, W, rast, (char*)ws, L, (hipStream_t)stream);
+    return rs_forward(range(ranges, B, N, V, F), "ls_range_forward", rast && ws && ranges && ((pos && tri) || N == 0), pos, tri, H, W, rast, ws,
+                      ws_bytes, device, stream);
 }
 
 extern "C" int ls_range_pixel_order(const float* rast, const int32_t* ranges, int64_t B, int64_t N, int64_t F, int H, int W, int32_t* order,
                                     int32_t* seg, void* ws, size_t ws_bytes, int device, void* stream) {
-    int rc = rg_check(B, N, 0, F, H, W, "ls_range_pixel_order");
-    if (rc) return rc;
-    const RsWs L = rs_layout_keys(B * H * W, N, 0);
-    LS_REQUIRE(rast && ranges && order && seg && ws, LS_E_INVALID, "ls_range_pixel_order: null argument");
-    LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_range_pixel_order: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
-    DeviceGuard g(device);
-    LS_HIP(g.err);
-    return rs_pixel_order(MapRange{ranges, (int)B}, rast, B, N, F, H, W, order, seg, (char*)ws, L, (hipStream_t)stream);
+    return rs_pixel_order(range(ranges, B, N, 0, F), "ls_range_pixel_order", rast && ranges && order && seg && ws, rast, H, W, order, seg, ws,
+                          ws_bytes, device, stream);
 }
 
 extern "C" int ls_range_backward(const float* pos, int64_t V, const int32_t* tri, int64_t F, const int32_t* ranges, int64_t B, int64_t N, int H,
                                  int W, const float* grad_rast, const int32_t* order, const int32_t* seg, const int32_t* vptr,
                                  const int32_t* corner_order, float* grad_pos, void* ws, size_t ws_bytes, int device, void* stream) {
-    int rc = rg_check(B, N, V, F, H, W, "ls_range_backward");
-    if (rc) return rc;
-    const RsWs L = rs_layout_keys(B * H * W, N, 0);
-    LS_REQUIRE(grad_rast && ranges && order && seg && vptr && grad_pos && ws && (pos || V == 0) && ((tri && corner_order) || F == 0), LS_E_INVALID,
-               "ls_range_backward: null argument");
-    LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_range_backward: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
-    DeviceGuard g(device);
-    LS_HIP(g.err);
-    hipStream_t st = (hipStream_t)stream;
-    float* rows = (float*)((char*)ws + L.rows);
-    const MapRange map{ranges, (int)B};
-    if (N > 0) {
-        RowRaster<MapRange> r{map, pos, tri, grad_rast, V, F, H, W};
-        hipLaunchKernelGGL(k_rs_seg_sum<RowRaster<MapRange>>, dim3(div_up(N, 256)), dim3(256), 0, st, r, order, seg, N, 9, 0, rows);
-    }
-    if (V > 0)
-        hipLaunchKernelGGL(k_rg_gather_pos, dim3(div_up(V, 256)), dim3(256), 0, st, (const float*)rows, vptr, corner_order, ranges, (int)B, V, grad_pos);
-    LS_HIP(hipGetLastError());
-    return LS_OK;
+    const bool ok = grad_rast && ranges && order && seg && vptr && grad_pos && ws && (pos || V == 0) && ((tri && corner_order) || F == 0);
+    return rs_backward(range(ranges, B, N, V, F), "ls_range_backward", ok, pos, tri, H, W, grad_rast, order, seg, vptr, corner_order, grad_pos, ws,
+                       ws_bytes, device, stream);
 }
 
 extern "C" int ls_range_interpolate_backward(const float* rast, const int32_t* ranges, int64_t B, int64_t N, int H, int W, int64_t V, int C,
@@ -1000,23 +1044,15 @@ extern "C" int ls_range_interpolate_backward(const float* rast, const int32_t* r
     LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_range_interpolate_backward: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
     DeviceGuard g(device);
     LS_HIP(g.err);
-    hipStream_t st = (hipStream_t)stream;
-    float* rows = (float*)((char*)ws + L.rows);
-    if (N > 0)
-        for (int c = 0; c < C; ++c) {
-            RowInterp r{rast, grad_out, C, c};
-            hipLaunchKernelGGL(k_rs_seg_sum<RowInterp>, dim3(div_up(N, 256)), dim3(256), 0, st, r, order, seg, N, 3 * C, 3 * c, rows);
-        }
-    if (V * C > 0)
-        hipLaunchKernelGGL(k_rg_gather_attr, dim3(div_up(V * C, 256)), dim3(256), 0, st, (const float*)rows, vptr, corner_order, ranges, (int)B, V, C,
-                           grad_attr);
+    rs_interp_grad_attr(range(ranges, B, N, V, 0), rast, 1, C, grad_out, order, seg, vptr, corner_order, grad_attr, (float*)((char*)ws + L.rows),
+                        (hipStream_t)stream);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
 
 extern "C" int ls_range_adjacency_workspace_bytes(int64_t N, size_t* bytes) {
     LS_REQUIRE(bytes && N >= 0 && 3 * N < ((int64_t)1 << 31) - 1, LS_E_INVALID, "ls_range_adjacency_workspace_bytes: bad argument");
-    *bytes = 4 * (size_t)(3 * N) + sort_scratch_bytes(3 * N, true);       // the half-edge ids, the sort's scratch behind them
+    *bytes = rs_adjacency_bytes(N);
     return LS_OK;
 }
 
@@ -1028,33 +1064,14 @@ extern "C" int ls_range_adjacency(const int32_t* tri, int64_t F, const int32_t* 
     LS_REQUIRE(B >= 1 && F >= 0 && adj && ws && ranges && (tri || N == 0), LS_E_INVALID, "ls_range_adjacency: bad argument");
     LS_REQUIRE(ws_bytes >= need, LS_E_WORKSPACE, "ls_range_adjacency: workspace too small (%zu < %zu bytes)", ws_bytes, need);
     if (N == 0) return LS_OK;
-    DeviceGuard g(device);
-    LS_HIP(g.err);
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t n = 3 * N;
-    int* ord_a = (int*)ws;
-    const int* sorted = nullptr;
-    KeyItemEdge key{tri, MapRange{ranges, (int)B}};
-    rc = radix_argsort_words(key, n, 3, ord_a, sort_scratch_carve(ord_a + n, n, true), st, &sorted, radix_passes(B - 1));
-    if (rc) return rc;
-    hipLaunchKernelGGL((k_rs_adjacency<KeyItemEdge, 3>), dim3(div_up(n, 256)), dim3(256), 0, st, key, sorted, n, adj);
-    LS_HIP(hipGetLastError());
-    return LS_OK;
+    return rs_adjacency<KeyItemEdge, 3>(KeyItemEdge{tri, MapRange{ranges, (int)B}}, 3 * N, radix_passes(B - 1), adj, ws, device, stream);
 }
 
 extern "C" int ls_range_antialias(const float* color, int C, const float* rast, const float* pos, int64_t V, const int32_t* tri, int64_t F,
                                   const int32_t* ranges, int64_t B, int64_t N, int H, int W, const int32_t* adj, float* out, int device,
                                   void* stream) {
-    int rc = rg_check(B, N, V, F, H, W, "ls_range_antialias");
-    if (rc) return rc;
-    LS_REQUIRE(C >= 1 && color && rast && out && ranges && ((pos && tri && adj) || N == 0), LS_E_INVALID, "ls_range_antialias: bad argument");
-    DeviceGuard g(device);
-    LS_HIP(g.err);
-    hipStream_t st = (hipStream_t)stream;
-    AAMesh<MapRange> m{MapRange{ranges, (int)B}, pos, tri, adj, rast, V, F, H, W};
-    hipLaunchKernelGGL(k_aa_forward<MapRange>, dim3(div_up(B * H * W, 256)), dim3(256), 0, st, m, (int)B, color, C, out);
-    LS_HIP(hipGetLastError());
-    return LS_OK;
+    const bool ok = C >= 1 && color && rast && out && ranges && ((pos && tri && adj) || N == 0);
+    return rs_antialias(range(ranges, B, N, V, F), "ls_range_antialias", ok, color, C, rast, pos, tri, adj, H, W, out, device, stream);
 }
 
 extern "C" int ls_range_antialias_backward(const float* color, int C, const float* rast, const float* pos, int64_t V, const int32_t* tri, int64_t F,
@@ -1062,30 +1079,7 @@ extern "C" int ls_range_antialias_backward(const float* color, int C, const floa
                                            float boost, const int32_t* order, const int32_t* seg, const int32_t* vptr,
                                            const int32_t* corner_order, float* grad_color, float* grad_pos, void* ws, size_t ws_bytes, int device,
                                            void* stream) {
-    int rc = rg_check(B, N, V, F, H, W, "ls_range_antialias_backward");
-    if (rc) return rc;
-    const RsWs L = rs_layout_keys(B * H * W, N, 0);
-    LS_REQUIRE(C >= 1 && color && rast && grad_out && ranges && ((pos && tri && adj) || N == 0), LS_E_INVALID,
-               "ls_range_antialias_backward: bad argument");
-    LS_REQUIRE(!grad_pos || (order && seg && vptr && ws && (corner_order || F == 0)), LS_E_INVALID,
-               "ls_range_antialias_backward: grad_pos needs the pixel order, the corner ranking and a workspace");
-    LS_REQUIRE(!grad_pos || ws_bytes >= L.total, LS_E_WORKSPACE, "ls_range_antialias_backward: workspace too small (%zu < %zu bytes)", ws_bytes,
-               L.total);
-    DeviceGuard g(device);
-    LS_HIP(g.err);
-    hipStream_t st = (hipStream_t)stream;
-    AAMesh<MapRange> m{MapRange{ranges, (int)B}, pos, tri, adj, rast, V, F, H, W};
-    if (grad_color) hipLaunchKernelGGL(k_aa_grad_color<MapRange>, dim3(div_up(B * H * W, 256)), dim3(256), 0, st, m, (int)B, grad_out, C, grad_color);
-    if (grad_pos) {
-        float* rows = (float*)((char*)ws + L.rows);
-        if (N > 0) {
-            RowAA<MapRange> r{m, color, grad_out, C, boost};
-            hipLaunchKernelGGL(k_rs_seg_sum<RowAA<MapRange>>, dim3(div_up(N, 256)), dim3(256), 0, st, r, order, seg, N, 9, 0, rows);
-        }
-        if (V > 0)
-            hipLaunchKernelGGL(k_rg_gather_pos, dim3(div_up(V, 256)), dim3(256), 0, st, (const float*)rows, vptr, corner_order, ranges, (int)B, V,
-                               grad_pos);
-    }
-    LS_HIP(hipGetLastError());
-    return LS_OK;
+    const bool ok = C >= 1 && color && rast && grad_out && ranges && ((pos && tri && adj) || N == 0);
+    return rs_antialias_backward(range(ranges, B, N, V, F), "ls_range_antialias_backward", ok, color, C, rast, pos, tri, adj, H, W, grad_out, boost,
+                                 order, seg, vptr, corner_order, grad_color, grad_pos, ws, ws_bytes, device, stream);
 }

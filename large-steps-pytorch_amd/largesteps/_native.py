@@ -326,6 +326,39 @@ def retry_on_oom(fn):
     return wrapped
 
 
+class IdentityCache:
+    """What was computed once from a tensor OBJECT (the corner ranking and the edge adjacency of a face tensor, the device table of a
+    ranges tensor). An entry is valid only for the very tensor it was built from (weak reference), its version counter and data pointer,
+    and an optional tuple `extra` of whatever else the value depends on: a storage address is recycled by the caching allocator as soon
+    as a tensor dies, so it cannot be the identity. Entries of dead tensors are purged on insert, and 8 entries are the most kept."""
+    __slots__ = ("entries",)
+
+    def __init__(self):
+        self.entries = {}
+
+    def get(self, t, extra=()):
+        """the value stored for t, or None"""
+        hit = self.entries.get(id(t))
+        if hit is None:
+            return None
+        ref, version, ptr, ex, value = hit
+        if ref() is t and version == t._version and ptr == t.data_ptr() and ex == extra:
+            return value
+        del self.entries[id(t)]
+        return None
+
+    def put(self, t, value, extra=()):
+        for k in [k for k, h in self.entries.items() if h[0]() is None]:
+            del self.entries[k]
+        if len(self.entries) >= 8:
+            self.entries.clear()
+        try:
+            self.entries[id(t)] = (weakref.ref(t), t._version, t.data_ptr(), extra, value)
+        except TypeError:           # an object that cannot be weakly referenced: do not cache
+            pass
+        return value
+
+
 def stream_of(device):
     if _raw_stream is not None and device.index is not None:
         return ctypes.c_void_p(_raw_stream(device.index))

@@ -20,23 +20,18 @@ from torch.autograd import Function
 from . import _native
 
 
-# Per face TENSOR OBJECT: range check of the indices (syncs the host once) and the vertex-major ranking of the corners.
-# One-off integer plumbing per mesh connectivity (ls_corner_ranks: native radix sort): the 3 F corners grouped by
-# vertex, in ascending corner id (deterministic sums); cpos is the inverse permutation (corner -> rank), vptr the ranks
-# each vertex owns. An entry is valid only for the very tensor it was built from (weak reference + version counter):
-# a storage address is recycled by the caching allocator as soon as a face tensor dies, so it cannot be the identity.
-_plans = {}
+# Per face TENSOR OBJECT (_native.IdentityCache; shape, dtype and V are part of the entry): range check of the indices (syncs the host
+# once) and the vertex-major ranking of the corners. One-off integer plumbing per mesh connectivity (ls_corner_ranks: native radix sort):
+# the 3 F corners grouped by vertex, in ascending corner id (deterministic sums); cpos is the inverse permutation (corner -> rank), vptr
+# the ranks each vertex owns.
+_plans = _native.IdentityCache()
 
 
 def _plan(f, V):
-    key = id(f)
-    hit = _plans.get(key)
-    if hit is not None:
-        ref, version, shape, dtype, ptr, v_count, plan = hit
-        if ref() is f and version == f._version and shape == tuple(f.shape) and dtype == f.dtype and ptr == f.data_ptr() \
-                and v_count == V:
-            return plan
-        del _plans[key]
+    extra = (tuple(f.shape), f.dtype, V)
+    plan = _plans.get(f, extra)
+    if plan is not None:
+        return plan
     F = f.shape[0]
     n = ctypes.c_size_t(0)
     _native.check(_native.lib().ls_corner_ranks_workspace_bytes(F, V, ctypes.byref(n)))
@@ -46,21 +41,12 @@ def _plan(f, V):
     with torch.cuda.device(f.device):                  # range check + counting + stable radix sort by vertex id, all native
         _native.check(_native.lib().ls_corner_ranks(_native.ptr(f), f.element_size(), F, V, _native.ptr(vptr), _native.ptr(vcorner), _native.ptr(ws),
                                                     ws.numel(), f.device.index, _native.stream_of(f.device)))
-    for k in [k for k, h in _plans.items() if h[0]() is None]:      # entries of dead tensors
-        del _plans[k]
-    if len(_plans) >= 8:
-        _plans.clear()
     # the kernels read the connectivity six times per step: 4-byte indices (validated above) halve that traffic
     narrow = f.to(torch.int32) if (f.dtype == torch.int64 and V < 2 ** 31) else f
     # rank -> corner, the inverse of vcorner: what the vertex-major passes of the pair walk (one-off integer plumbing, like `narrow`)
     order = torch.empty_like(vcorner)
     order[vcorner.long()] = torch.arange(3 * F, dtype=torch.int32, device=f.device)
-    plan = (vptr, vcorner, narrow, order)
-    try:
-        _plans[key] = (weakref.ref(f), f._version, tuple(f.shape), f.dtype, f.data_ptr(), V, plan)
-    except TypeError:           # an object that cannot be weakly referenced: do not cache
-        pass
-    return plan
+    return _plans.put(f, (vptr, vcorner, narrow, order), extra)
 
 
 def _prep(verts, faces):

@@ -33,9 +33,14 @@ antialias, attr, color, rast[..., :2]) equals bit for bit the sum of the B slice
 from image 0's. Ranges may overlap, be unsorted, be empty (an all-zero image) or leave faces out; silhouettes are those of each image's
 own faces (a closed surface cut by a range has a boundary along the cut). The rast of a range-mode call carries its range table:
 `interpolate` and `antialias` must be given that very tensor.
+
+Above the kernels the two modes share one code path: `_Rasterize`, `_Interpolate` and `_Antialias` convert, allocate and save once, and ask
+the frame that the rast carries (`rast._largesteps_frame`) for what a mode supplies -- the number of keys and images, the workspace size,
+the shape rules of pos and tri, the edge adjacency and the native calls (`_InstancedFrame` knows F, `_RangeFrame` its range table). The
+frame also holds the pixel order of the backward passes, made at most once per version of the rast. A rast that no `rasterize` made (a
+clone, a fabricated tensor) gets a fresh instanced frame; a range frame is made by `rasterize` only.
 """
 import ctypes
-import weakref
 
 import numpy as np
 import torch
@@ -60,7 +65,7 @@ RasterizeCudaContext = RasterizeContext
 
 
 # ---- per face tensor: range check + corner ranking (normals.py's cache) and the edge adjacency ------------------------------------------
-_adjacency = {}
+_adjacency = _native.IdentityCache()
 
 
 def _faces(tri, V):
@@ -76,47 +81,36 @@ def _faces(tri, V):
     return f, narrow, vptr, order
 
 
-def _adjacent(f, narrow):
-    key = id(f)
-    hit = _adjacency.get(key)
-    if hit is not None:
-        ref, version, ptr, adj = hit
-        if ref() is f and version == f._version and ptr == f.data_ptr():
-            return adj
-        del _adjacency[key]
-    F = narrow.shape[0]
+def _scratch(dev, size_fn, *shape):
+    """the workspace whose size the native `size_fn` gives for `shape`"""
     n = ctypes.c_size_t(0)
-    _native.check(_native.lib().ls_raster_adjacency_workspace_bytes(F, ctypes.byref(n)))
-    ws = torch.empty(n.value, dtype=torch.uint8, device=f.device)
-    adj = torch.empty(max(3 * F, 1), dtype=torch.int32, device=f.device)
-    with torch.cuda.device(f.device):
-        _native.check(_native.lib().ls_raster_adjacency(_native.ptr(narrow), F, _native.ptr(adj), _native.ptr(ws), ws.numel(), f.device.index,
-                                                        _native.stream_of(f.device)))
-    for k in [k for k, h in _adjacency.items() if h[0]() is None]:
-        del _adjacency[k]
-    if len(_adjacency) >= 8:
-        _adjacency.clear()
-    try:
-        _adjacency[key] = (weakref.ref(f), f._version, f.data_ptr(), adj)
-    except TypeError:
-        pass
-    return adj
-
-
-def _workspace(B, F, H, W, C, dev):
-    n = ctypes.c_size_t(0)
-    _native.check(_native.lib().ls_raster_workspace_bytes(B, F, H, W, C, ctypes.byref(n)))
+    _native.check(size_fn(*shape, ctypes.byref(n)))
     return torch.empty(n.value, dtype=torch.uint8, device=dev)
 
 
-def _pos(pos):
+def _adjacent(f, narrow):
+    adj = _adjacency.get(f)
+    if adj is None:
+        F, dev = narrow.shape[0], f.device
+        ws = _scratch(dev, _native.lib().ls_raster_adjacency_workspace_bytes, F)
+        adj = torch.empty(max(3 * F, 1), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().ls_raster_adjacency(_native.ptr(narrow), F, _native.ptr(adj), _native.ptr(ws), ws.numel(), dev.index,
+                                                            _native.stream_of(dev)))
+        _adjacency.put(f, adj)
+    return adj
+
+
+def _pos(pos, shared=False):
+    """the clip-space positions detached, fp32 and contiguous: (B, V, 4), or the one (V, 4) of range mode (`shared`)"""
     _native.require_device(pos, "pos")
-    if pos.dim() != 3 or pos.shape[2] != 4:
-        raise ValueError(f"pos must be (B, V, 4) clip-space positions (instanced mode), got {tuple(pos.shape)}")
+    if pos.dim() != (2 if shared else 3) or pos.shape[-1] != 4:
+        raise ValueError(f"pos must be (V, 4) clip-space positions in range mode, got {tuple(pos.shape)}" if shared else
+                         f"pos must be (B, V, 4) clip-space positions (instanced mode), got {tuple(pos.shape)}")
     p = pos.detach()
     if p.dtype != torch.float32 or not p.is_contiguous():
         p = p.to(torch.float32).contiguous()
-    return p
+    return _aligned(p) if shared else p
 
 
 def _rast(rast):
@@ -127,153 +121,29 @@ def _rast(rast):
     return r if (r.dtype == torch.float32 and r.is_contiguous()) else r.to(torch.float32).contiguous()
 
 
-class _PixelOrder:
-    """The pixels of one rasterized frame sorted by (image, face) -- the order every backward sums in. Made at most once per frame, by
-    the first backward that needs it, and shared through the rast tensor."""
-    __slots__ = ("version", "F", "order", "seg")
-
-    def __init__(self, version, F):
-        self.version, self.F, self.order, self.seg = version, F, None, None
-
-    def get(self, r):
-        if self.order is None:
-            B, H, W, _ = r.shape
-            dev = r.device
-            order = torch.empty(B * H * W, dtype=torch.int32, device=dev)
-            seg = torch.empty(B * self.F + 1, dtype=torch.int32, device=dev)
-            ws = _workspace(B, self.F, H, W, 0, dev)
-            with torch.cuda.device(dev):
-                _native.check(_native.lib().ls_raster_pixel_order(_native.ptr(r), B, self.F, H, W, _native.ptr(order), _native.ptr(seg),
-                                                                  _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
-            self.order, self.seg = order, seg
-        return self.order, self.seg
-
-
-def _order_slot(rast, F):
-    slot = getattr(rast, "_largesteps_order", None)
-    if slot is not None and slot.version == rast._version and slot.F == F:
-        return slot
-    return _PixelOrder(rast._version, F)
-
-
-class _Rasterize(Function):
-    @staticmethod
-    def forward(ctx, pos, tri, H, W, slot):
-        p = _pos(pos)
-        B, V = p.shape[0], p.shape[1]
-        f, narrow, vptr, order = _faces(tri, V)
-        F, dev = narrow.shape[0], p.device
-        rast = torch.empty((B, H, W, 4), dtype=torch.float32, device=dev)
-        ws = _workspace(B, F, H, W, 0, dev)
-        with torch.cuda.device(dev):
-            _native.check(_native.lib().ls_raster_forward(_native.ptr(p), B, V, _native.ptr(narrow), F, H, W, _native.ptr(rast), _native.ptr(ws),
-                                                          ws.numel(), dev.index, _native.stream_of(dev)))
-        rast_db = torch.zeros((B, H, W, 4), dtype=torch.float32, device=dev)
-        ctx.mark_non_differentiable(rast_db)
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(p, narrow, vptr, order, rast)
-        ctx.slot = slot
-        ctx.HW = (H, W)
-        return rast, rast_db
-
-    @staticmethod
-    def backward(ctx, g_rast, g_db):
-        if g_rast is None or not ctx.needs_input_grad[0]:
-            return None, None, None, None, None
-        p, narrow, vptr, corner_order, rast = ctx.saved_tensors
-        B, V = p.shape[0], p.shape[1]
-        F, dev = narrow.shape[0], p.device
-        H, W = ctx.HW
-        g = g_rast.to(torch.float32).contiguous()
-        order, seg = ctx.slot.get(rast)
-        ws = _workspace(B, F, H, W, 0, dev)
-        gp = torch.empty_like(p)
-        with torch.cuda.device(dev):
-            _native.check(_native.lib().ls_raster_backward(_native.ptr(p), B, V, _native.ptr(narrow), F, H, W, _native.ptr(g), _native.ptr(order),
-                                                           _native.ptr(seg), _native.ptr(vptr), _native.ptr(corner_order), _native.ptr(gp),
-                                                           _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
-        return gp, None, None, None, None
-
-
-@_native.retry_on_oom
-def rasterize(glctx, pos, tri, resolution, ranges=None, grad_db=True):
-    """
-    Rasterize triangles (nvdiffrast.torch.rasterize, instanced and range mode). Returns (rast, rast_db).
-
-    glctx : RasterizeContext (ignored)
-    pos : (B, V, 4) fp32 clip-space positions on a HIP device; (V, 4) in range mode
-    tri : (F, 3) int32 or int64
-    resolution : (H, W), each in [1, 4096]
-    ranges : None (instanced mode), or range mode: a (B, 2) int32 CPU tensor of (start, count) rows with 0 <= start, 0 <= count and
-             start + count <= F. pos is then (V, 4), shared by the B images, and image b holds the faces tri[start_b : start_b + count_b]
-             with GLOBAL ids (face index in tri, plus one): bit for bit the instanced frame of pos[None] and that slice, start_b added to
-             the ids (the slice law of the module's docstring). Ranges may overlap, be unsorted or empty. The device copy of the table is
-             cached per ranges tensor (identity, version, data pointer): keep one tensor (`MeshBatch.ranges()`) and nothing is copied
-             from the host after the first call. The returned rast carries the table for `interpolate` and `antialias`; rast_db is
-             then a plain zero tensor (pixel differentials are not supported in range mode).
-    grad_db : ignored. rast_db holds zeros (rasterize computes no image-space derivatives) and asking for its gradient raises; it carries
-              the detached pos and tri, from which `interpolate(..., rast_db=rast_db, diff_attrs=...)` computes the differentials when
-              they are wanted (`pixel_differentials`).
-
-    rast (B, H, W, 4) = (u, v, z/w, triangle id + 1), 0 for background pixels. Coverage: a pixel is covered iff its centre lies in the
-    projected triangle (top-left rule, watertight along shared edges) and z/w is in [-1, 1] (near and far clipping); the nearest
-    covering triangle wins (ties: the lower id). The gradient of rast[..., 0:2] flows to pos; the gradient of the z/w channel is dropped.
-    """
-    H, W = (int(resolution[0]), int(resolution[1]))
-    if ranges is not None:
-        return _rasterize_range(pos, tri, H, W, resolution, ranges)
-    if not (1 <= H <= 4096 and 1 <= W <= 4096):
-        raise ValueError(f"resolution must be (H, W) with each in [1, 4096], got {tuple(resolution)}")
-    F = tri.shape[0] if isinstance(tri, torch.Tensor) and tri.dim() == 2 else 0
-    slot = _PixelOrder(0, F)
-    rast, rast_db = _Rasterize.apply(pos, tri, H, W, slot)
-    slot.version = rast._version
-    _attach_order(rast, slot)
-    rast_db._largesteps_db = _DbSource(pos, tri, rast_db._version)
-    return rast, rast_db
-
-
-def _attach_order(rast, slot):
-    rast._largesteps_order = slot
-
-
-# ---- range mode ------------------------------------------------------------------------------------------------------------------------
-_range_tables = {}
+# ---- range mode: the table of a ranges tensor --------------------------------------------------------------------------------------------
+_range_tables = _native.IdentityCache()
 
 
 class _RangeTable:
     """The device table (B, 3) = (start, count, item_ptr) of one ranges tensor, and the item adjacency of every face tensor it was used with
     (cached per (face tensor, ranges tensor) in the style of `_adjacent`)."""
-    __slots__ = ("B", "N", "F", "dev", "adj", "__weakref__")
+    __slots__ = ("B", "N", "F", "dev", "adj")
 
     def __init__(self, B, N, F, dev):
-        self.B, self.N, self.F, self.dev, self.adj = B, N, F, dev, {}
+        self.B, self.N, self.F, self.dev, self.adj = B, N, F, dev, _native.IdentityCache()
 
     def adjacency(self, f, narrow):
         """(3 N) int32: the item across each edge of each item within its image, -1 for none"""
-        key = id(f)
-        hit = self.adj.get(key)
-        if hit is not None:
-            ref, version, ptr, adj = hit
-            if ref() is f and version == f._version and ptr == f.data_ptr():
-                return adj
-            del self.adj[key]
-        dev = self.dev.device
-        n = ctypes.c_size_t(0)
-        _native.check(_native.lib().ls_range_adjacency_workspace_bytes(self.N, ctypes.byref(n)))
-        ws = torch.empty(n.value, dtype=torch.uint8, device=dev)
-        adj = torch.empty(max(3 * self.N, 1), dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            _native.check(_native.lib().ls_range_adjacency(_native.ptr(narrow), narrow.shape[0], _native.ptr(self.dev), self.B, self.N,
-                                                           _native.ptr(adj), _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
-        for k in [k for k, h in self.adj.items() if h[0]() is None]:
-            del self.adj[k]
-        if len(self.adj) >= 8:
-            self.adj.clear()
-        try:
-            self.adj[key] = (weakref.ref(f), f._version, f.data_ptr(), adj)
-        except TypeError:
-            pass
+        adj = self.adj.get(f)
+        if adj is None:
+            dev = self.dev.device
+            ws = _scratch(dev, _native.lib().ls_range_adjacency_workspace_bytes, self.N)
+            adj = torch.empty(max(3 * self.N, 1), dtype=torch.int32, device=dev)
+            with torch.cuda.device(dev):
+                _native.check(_native.lib().ls_range_adjacency(_native.ptr(narrow), narrow.shape[0], _native.ptr(self.dev), self.B, self.N,
+                                                               _native.ptr(adj), _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
+            self.adj.put(f, adj)
         return adj
 
 
@@ -302,102 +172,201 @@ def _check_ranges(ranges, F):
 
 def _range_table(ranges, F, dev):
     """the device table of `ranges`, validated against F faces; cached per ranges tensor (identity, version, data pointer)"""
-    key = id(ranges)
-    hit = _range_tables.get(key)
-    if hit is not None:
-        ref, version, ptr, tab = hit
-        if ref() is ranges and version == ranges._version and ptr == ranges.data_ptr() and tab.F == F and tab.dev.device == dev:
-            return tab
-        del _range_tables[key]
-    B, N = _check_ranges(ranges, F)
-    host = torch.empty((B, 3), dtype=torch.int32)
-    host[:, :2] = ranges
-    count = ranges[:, 1].to(torch.int64)
-    host[:, 2] = (torch.cumsum(count, 0) - count).to(torch.int32)
-    tab = _RangeTable(B, N, F, host.to(dev))
-    for k in [k for k, h in _range_tables.items() if h[0]() is None]:
-        del _range_tables[k]
-    if len(_range_tables) >= 8:
-        _range_tables.clear()
-    _range_tables[key] = (weakref.ref(ranges), ranges._version, ranges.data_ptr(), tab)
+    tab = _range_tables.get(ranges, (F, dev))
+    if tab is None:
+        B, N = _check_ranges(ranges, F)
+        host = torch.empty((B, 3), dtype=torch.int32)
+        host[:, :2] = ranges
+        count = ranges[:, 1].to(torch.int64)
+        host[:, 2] = (torch.cumsum(count, 0) - count).to(torch.int32)
+        tab = _range_tables.put(ranges, _RangeTable(B, N, F, host.to(dev)), (F, dev))
     return tab
 
 
-class _RangeFrame:
-    """What the rast of a range-mode `rasterize` carries: the range table and, made at most once per version of the rast by the first
-    backward that needs it, its pixels sorted by item -- the order every backward sums in."""
-    __slots__ = ("tab", "version", "order", "seg")
+# ---- the frame of a rast: what differs between the modes above the kernels ------------------------------------------------------------------
+class _Frame:
+    """What the rast of `rasterize` carries (`rast._largesteps_frame`), instanced or range mode. It owns the pixels of the frame sorted by
+    key ((image, face), or item) -- the order every backward sums in, made at most once per version of the rast by the first backward that
+    needs it -- and, in its two implementations, what a mode supplies: the number of keys and of images, the workspace, the shape rules
+    of pos and tri, the edge adjacency and the native calls. F: the faces of tri; tab: the `_RangeTable`, None when instanced."""
+    __slots__ = ("F", "tab", "version", "order", "seg")
 
-    def __init__(self, tab):
-        self.tab, self.version, self.order, self.seg = tab, None, None, None
+    def __init__(self, F, tab=None):
+        self.F, self.tab, self.version, self.order, self.seg = F, tab, None, None, None
 
     def pixel_order(self, r, version):
         if self.order is None or self.version != version:
-            tab = self.tab
             B, H, W, _ = r.shape
             dev = r.device
             order = torch.empty(B * H * W, dtype=torch.int32, device=dev)
-            seg = torch.empty(tab.N + 1, dtype=torch.int32, device=dev)
-            ws = _range_workspace(B, tab.N, H, W, 0, dev)
+            seg = torch.empty(self.keys(B) + 1, dtype=torch.int32, device=dev)
+            ws = self.workspace(B, H, W, 0, dev)
             with torch.cuda.device(dev):
-                _native.check(_native.lib().ls_range_pixel_order(_native.ptr(r), _native.ptr(tab.dev), B, tab.N, tab.F, H, W, _native.ptr(order),
-                                                                 _native.ptr(seg), _native.ptr(ws), ws.numel(), dev.index,
-                                                                 _native.stream_of(dev)))
+                self.sort_pixels(r, B, H, W, order, seg, ws, dev)
             self.order, self.seg, self.version = order, seg, version
         return self.order, self.seg
 
 
+class _InstancedFrame(_Frame):
+    """B views of one mesh: pos (B, V, 4), keys (image, face)"""
+    __slots__ = ()
+    pos = staticmethod(_pos)
+    faces = staticmethod(_faces)
+    adjacency = staticmethod(_adjacent)
+
+    def keys(self, B):
+        return B * self.F
+
+    def images(self, p):
+        return p.shape[0]
+
+    def workspace(self, B, H, W, C, dev):
+        n = ctypes.c_size_t(0)
+        _native.check(_native.lib().ls_raster_workspace_bytes(B, self.F, H, W, C, ctypes.byref(n)))
+        return torch.empty(n.value, dtype=torch.uint8, device=dev)
+
+    def sort_pixels(self, r, B, H, W, order, seg, ws, dev):
+        _native.check(_native.lib().ls_raster_pixel_order(_native.ptr(r), B, self.F, H, W, _native.ptr(order), _native.ptr(seg), _native.ptr(ws),
+                                                          ws.numel(), dev.index, _native.stream_of(dev)))
+
+    def rasterize(self, p, narrow, B, H, W, rast, ws, dev):
+        _native.check(_native.lib().ls_raster_forward(_native.ptr(p), B, p.shape[1], _native.ptr(narrow), narrow.shape[0], H, W, _native.ptr(rast),
+                                                      _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
+
+    def rasterize_backward(self, p, narrow, B, H, W, g, order, seg, vptr, corner_order, gp, ws, dev):
+        _native.check(_native.lib().ls_raster_backward(_native.ptr(p), B, p.shape[1], _native.ptr(narrow), narrow.shape[0], H, W, _native.ptr(g),
+                                                       _native.ptr(order), _native.ptr(seg), _native.ptr(vptr), _native.ptr(corner_order),
+                                                       _native.ptr(gp), _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
+
+    def interpolate_backward(self, a, r, narrow, g, vptr, corner_order, ga, gr, version):
+        (B, H, W, _), (Ba, V, C), dev = r.shape, a.shape, r.device
+        order = seg = ws = None
+        if ga is not None:
+            order, seg = self.pixel_order(r, version)
+            ws = self.workspace(B, H, W, C, dev)
+        _native.check(_native.lib().ls_raster_interpolate_backward(
+            _native.ptr(a), Ba, V, C, _native.ptr(r), B, H, W, _native.ptr(narrow), narrow.shape[0], _native.ptr(g), _native.ptr(order),
+            _native.ptr(seg), _native.ptr(vptr), _native.ptr(corner_order), _native.ptr(ga), _native.ptr(gr), _native.ptr(ws),
+            0 if ws is None else ws.numel(), dev.index, _native.stream_of(dev)))
+
+    def antialias(self, c, r, p, narrow, adj, B, H, W, out, dev):
+        C = c.shape[3]
+        _native.check(_native.lib().ls_raster_antialias(_native.ptr(c), C, _native.ptr(r), _native.ptr(p), B, p.shape[1], H, W, _native.ptr(narrow),
+                                                        narrow.shape[0], _native.ptr(adj), _native.ptr(out), dev.index, _native.stream_of(dev)))
+
+    def antialias_backward(self, c, r, p, narrow, adj, B, H, W, C, g, boost, order, seg, vptr, corner_order, gc, gp, ws, dev):
+        _native.check(_native.lib().ls_raster_antialias_backward(
+            _native.ptr(c), C, _native.ptr(r), _native.ptr(p), B, p.shape[1], H, W, _native.ptr(narrow), narrow.shape[0], _native.ptr(adj),
+            _native.ptr(g), boost, _native.ptr(order), _native.ptr(seg), _native.ptr(vptr), _native.ptr(corner_order), _native.ptr(gc),
+            _native.ptr(gp), _native.ptr(ws), 0 if ws is None else ws.numel(), dev.index, _native.stream_of(dev)))
+
+
+class _RangeFrame(_Frame):
+    """B images of the N items of a range table: one shared pos (V, 4), keys = items. Made by `rasterize` only."""
+    __slots__ = ()
+
+    def __init__(self, tab):
+        super().__init__(tab.F, tab)
+
+    def keys(self, B):
+        return self.tab.N
+
+    def images(self, p):
+        return self.tab.B
+
+    def pos(self, pos):
+        return _pos(pos, shared=True)
+
+    def faces(self, tri, V):
+        f, narrow, vptr, order = _faces(tri, V)
+        if narrow.shape[0] != self.F:
+            raise ValueError(f"tri has {narrow.shape[0]} faces, the range-mode rast was rasterized from {self.F}")
+        return f, narrow, vptr, order
+
+    def adjacency(self, f, narrow):
+        return self.tab.adjacency(f, narrow)
+
+    def workspace(self, B, H, W, C, dev):
+        n = ctypes.c_size_t(0)
+        _native.check(_native.lib().ls_range_workspace_bytes(B, self.tab.N, H, W, C, ctypes.byref(n)))
+        return torch.empty(n.value, dtype=torch.uint8, device=dev)
+
+    def sort_pixels(self, r, B, H, W, order, seg, ws, dev):
+        tab = self.tab
+        _native.check(_native.lib().ls_range_pixel_order(_native.ptr(r), _native.ptr(tab.dev), B, tab.N, tab.F, H, W, _native.ptr(order),
+                                                         _native.ptr(seg), _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
+
+    def rasterize(self, p, narrow, B, H, W, rast, ws, dev):
+        tab = self.tab
+        _native.check(_native.lib().ls_range_forward(_native.ptr(p), p.shape[0], _native.ptr(narrow), tab.F, _native.ptr(tab.dev), B, tab.N, H, W,
+                                                     _native.ptr(rast), _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
+
+    def rasterize_backward(self, p, narrow, B, H, W, g, order, seg, vptr, corner_order, gp, ws, dev):
+        tab = self.tab
+        _native.check(_native.lib().ls_range_backward(_native.ptr(p), p.shape[0], _native.ptr(narrow), tab.F, _native.ptr(tab.dev), B, tab.N, H, W,
+                                                      _native.ptr(g), _native.ptr(order), _native.ptr(seg), _native.ptr(vptr),
+                                                      _native.ptr(corner_order), _native.ptr(gp), _native.ptr(ws), ws.numel(), dev.index,
+                                                      _native.stream_of(dev)))
+
+    def interpolate_backward(self, a, r, narrow, g, vptr, corner_order, ga, gr, version):
+        (B, H, W, _), (_, V, C), dev, tab = r.shape, a.shape, r.device, self.tab
+        st = _native.stream_of(dev)
+        if gr is not None:          # ids are global and attr is shared: the instanced kernel as it is, as in the forward
+            _native.check(_native.lib().ls_raster_interpolate_backward(
+                _native.ptr(a), 1, V, C, _native.ptr(r), B, H, W, _native.ptr(narrow), narrow.shape[0], _native.ptr(g), None, None, None, None, None,
+                _native.ptr(gr), None, 0, dev.index, st))
+        if ga is not None:
+            order, seg = self.pixel_order(r, version)
+            ws = self.workspace(B, H, W, C, dev)
+            _native.check(_native.lib().ls_range_interpolate_backward(
+                _native.ptr(r), _native.ptr(tab.dev), B, tab.N, H, W, V, C, _native.ptr(g), _native.ptr(order), _native.ptr(seg), _native.ptr(vptr),
+                _native.ptr(corner_order), _native.ptr(ga), _native.ptr(ws), ws.numel(), dev.index, st))
+
+    def antialias(self, c, r, p, narrow, adj, B, H, W, out, dev):
+        C, tab = c.shape[3], self.tab
+        _native.check(_native.lib().ls_range_antialias(_native.ptr(c), C, _native.ptr(r), _native.ptr(p), p.shape[0], _native.ptr(narrow), tab.F,
+                                                       _native.ptr(tab.dev), B, tab.N, H, W, _native.ptr(adj), _native.ptr(out), dev.index,
+                                                       _native.stream_of(dev)))
+
+    def antialias_backward(self, c, r, p, narrow, adj, B, H, W, C, g, boost, order, seg, vptr, corner_order, gc, gp, ws, dev):
+        tab = self.tab
+        _native.check(_native.lib().ls_range_antialias_backward(
+            _native.ptr(c), C, _native.ptr(r), _native.ptr(p), p.shape[0], _native.ptr(narrow), tab.F, _native.ptr(tab.dev), B, tab.N, H, W,
+            _native.ptr(adj), _native.ptr(g), boost, _native.ptr(order), _native.ptr(seg), _native.ptr(vptr), _native.ptr(corner_order),
+            _native.ptr(gc), _native.ptr(gp), _native.ptr(ws), 0 if ws is None else ws.numel(), dev.index, _native.stream_of(dev)))
+
+
 def _range_frame(rast):
     """the range frame of a rast that a range-mode `rasterize` returned, None for any other tensor"""
-    frame = getattr(rast, "_largesteps_range", None)
-    if frame is None or not isinstance(rast, torch.Tensor) or rast.dim() != 4 or rast.shape[0] != frame.tab.B:
+    frame = getattr(rast, "_largesteps_frame", None)
+    if frame is None or frame.tab is None or not isinstance(rast, torch.Tensor) or rast.dim() != 4 or rast.shape[0] != frame.tab.B:
         return None
     return frame
 
 
-def _range_workspace(B, N, H, W, C, dev):
-    n = ctypes.c_size_t(0)
-    _native.check(_native.lib().ls_range_workspace_bytes(B, N, H, W, C, ctypes.byref(n)))
-    return torch.empty(n.value, dtype=torch.uint8, device=dev)
+def _instanced_frame(rast, tri):
+    """the instanced frame that rast carries for the F faces of tri, or a fresh one (a rast that no `rasterize` of this package made, or
+    one made from another F); the caller leaves it on rast once its call went through"""
+    F = tri.shape[0] if isinstance(tri, torch.Tensor) and tri.dim() == 2 else 0
+    frame = getattr(rast, "_largesteps_frame", None)
+    return frame if frame is not None and frame.tab is None and frame.F == F else _InstancedFrame(F)
 
 
-def _pos_shared(pos):
-    """the (V, 4) positions of range mode, detached, fp32 and contiguous"""
-    _native.require_device(pos, "pos")
-    if pos.dim() != 2 or pos.shape[1] != 4:
-        raise ValueError(f"pos must be (V, 4) clip-space positions in range mode, got {tuple(pos.shape)}")
-    p = pos.detach()
-    if p.dtype != torch.float32 or not p.is_contiguous():
-        p = p.to(torch.float32).contiguous()
-    return _aligned(p)
-
-
-def _range_faces(tri, V, tab):
-    f, narrow, vptr, order = _faces(tri, V)
-    if narrow.shape[0] != tab.F:
-        raise ValueError(f"tri has {narrow.shape[0]} faces, the range-mode rast was rasterized from {tab.F}")
-    return f, narrow, vptr, order
-
-
-class _RasterizeRange(Function):
+class _Rasterize(Function):
     @staticmethod
     def forward(ctx, pos, tri, H, W, frame):
-        p = _pos_shared(pos)
-        V, tab = p.shape[0], frame.tab
-        f, narrow, vptr, order = _range_faces(tri, V, tab)
-        B, N, F, dev = tab.B, tab.N, tab.F, p.device
+        p = frame.pos(pos)
+        f, narrow, vptr, order = frame.faces(tri, p.shape[-2])
+        B, dev = frame.images(p), p.device
         rast = torch.empty((B, H, W, 4), dtype=torch.float32, device=dev)
-        ws = _range_workspace(B, N, H, W, 0, dev)
+        ws = frame.workspace(B, H, W, 0, dev)
         with torch.cuda.device(dev):
-            _native.check(_native.lib().ls_range_forward(_native.ptr(p), V, _native.ptr(narrow), F, _native.ptr(tab.dev), B, N, H, W,
-                                                         _native.ptr(rast), _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
+            frame.rasterize(p, narrow, B, H, W, rast, ws, dev)
         rast_db = torch.zeros((B, H, W, 4), dtype=torch.float32, device=dev)
         ctx.mark_non_differentiable(rast_db)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(p, narrow, vptr, order, rast)
         ctx.frame = frame
-        ctx.HW = (H, W)
-        ctx.pos_shape = tuple(pos.shape)
         return rast, rast_db
 
     @staticmethod
@@ -405,22 +374,18 @@ class _RasterizeRange(Function):
         if g_rast is None or not ctx.needs_input_grad[0]:
             return None, None, None, None, None
         p, narrow, vptr, corner_order, rast = ctx.saved_tensors
-        tab = ctx.frame.tab
-        V, B, N, F, dev = p.shape[0], tab.B, tab.N, tab.F, p.device
-        H, W = ctx.HW
+        (B, H, W, _), dev, frame = rast.shape, p.device, ctx.frame
         g = g_rast.to(torch.float32).contiguous()
-        order, seg = ctx.frame.pixel_order(rast, rast._version)
-        ws = _range_workspace(B, N, H, W, 0, dev)
+        order, seg = frame.pixel_order(rast, rast._version)
+        ws = frame.workspace(B, H, W, 0, dev)
         gp = torch.empty_like(p)
         with torch.cuda.device(dev):
-            _native.check(_native.lib().ls_range_backward(_native.ptr(p), V, _native.ptr(narrow), F, _native.ptr(tab.dev), B, N, H, W,
-                                                          _native.ptr(g), _native.ptr(order), _native.ptr(seg), _native.ptr(vptr),
-                                                          _native.ptr(corner_order), _native.ptr(gp), _native.ptr(ws), ws.numel(), dev.index,
-                                                          _native.stream_of(dev)))
-        return gp.view(ctx.pos_shape), None, None, None, None
+            frame.rasterize_backward(p, narrow, B, H, W, g, order, seg, vptr, corner_order, gp, ws, dev)
+        return gp, None, None, None, None
 
 
-def _rasterize_range(pos, tri, H, W, resolution, ranges):
+def _range_frame_for(pos, tri, H, W, resolution, ranges):
+    """the checks of a range-mode `rasterize`, and its frame"""
     for t, what in ((pos, "pos"), (tri, "tri")):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{what} must be a torch.Tensor, got {type(t).__name__}")
@@ -443,113 +408,45 @@ def _rasterize_range(pos, tri, H, W, resolution, ranges):
                                   "(there is no CPU path in this package)")
     if tab.B * H * W >= 2 ** 31 - 1:
         raise OverflowError(f"{tab.B} images of {H} x {W} pixels: the kernels index pixels with int32")
-    frame = _RangeFrame(tab)
-    rast, rast_db = _RasterizeRange.apply(pos, tri, H, W, frame)
-    rast._largesteps_range = frame
+    return _RangeFrame(tab)
+
+
+@_native.retry_on_oom
+def rasterize(glctx, pos, tri, resolution, ranges=None, grad_db=True):
+    """
+    Rasterize triangles (nvdiffrast.torch.rasterize, instanced and range mode). Returns (rast, rast_db).
+
+    glctx : RasterizeContext (ignored)
+    pos : (B, V, 4) fp32 clip-space positions on a HIP device; (V, 4) in range mode
+    tri : (F, 3) int32 or int64
+    resolution : (H, W), each in [1, 4096]
+    ranges : None (instanced mode), or range mode: a (B, 2) int32 CPU tensor of (start, count) rows with 0 <= start, 0 <= count and
+             start + count <= F. pos is then (V, 4), shared by the B images, and image b holds the faces tri[start_b : start_b + count_b]
+             with GLOBAL ids (face index in tri, plus one): bit for bit the instanced frame of pos[None] and that slice, start_b added to
+             the ids (the slice law of the module's docstring). Ranges may overlap, be unsorted or empty. The device copy of the table is
+             cached per ranges tensor (identity, version, data pointer): keep one tensor (`MeshBatch.ranges()`) and nothing is copied
+             from the host after the first call. The returned rast carries the table for `interpolate` and `antialias`; rast_db is
+             then a plain zero tensor (pixel differentials are not supported in range mode).
+    grad_db : ignored. rast_db holds zeros (rasterize computes no image-space derivatives) and asking for its gradient raises; it carries
+              the detached pos and tri, from which `interpolate(..., rast_db=rast_db, diff_attrs=...)` computes the differentials when
+              they are wanted (`pixel_differentials`).
+
+    rast (B, H, W, 4) = (u, v, z/w, triangle id + 1), 0 for background pixels. Coverage: a pixel is covered iff its centre lies in the
+    projected triangle (top-left rule, watertight along shared edges) and z/w is in [-1, 1] (near and far clipping); the nearest
+    covering triangle wins (ties: the lower id). The gradient of rast[..., 0:2] flows to pos; the gradient of the z/w channel is dropped.
+    """
+    H, W = (int(resolution[0]), int(resolution[1]))
+    if ranges is not None:
+        frame = _range_frame_for(pos, tri, H, W, resolution, ranges)
+    else:
+        if not (1 <= H <= 4096 and 1 <= W <= 4096):
+            raise ValueError(f"resolution must be (H, W) with each in [1, 4096], got {tuple(resolution)}")
+        frame = _InstancedFrame(tri.shape[0] if isinstance(tri, torch.Tensor) and tri.dim() == 2 else 0)
+    rast, rast_db = _Rasterize.apply(pos, tri, H, W, frame)
+    rast._largesteps_frame = frame
+    if ranges is None:
+        rast_db._largesteps_db = _DbSource(pos, tri, rast_db._version)
     return rast, rast_db
-
-
-class _InterpolateRange(Function):
-    @staticmethod
-    def forward(ctx, attr, rast, tri, frame):
-        _native.require_device(attr, "attr")
-        r = _rast(rast)
-        B, H, W, _ = r.shape
-        a = (attr.unsqueeze(0) if attr.dim() == 2 else attr).detach()
-        if a.dtype != torch.float32 or not a.is_contiguous():
-            a = a.to(torch.float32).contiguous()
-        _, V, C = a.shape
-        f, narrow, vptr, order = _range_faces(tri, V, frame.tab)
-        F, dev = narrow.shape[0], r.device
-        out = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):          # ids are global and attr is shared: the instanced kernel as it is
-            _native.check(_native.lib().ls_raster_interpolate(_native.ptr(a), 1, V, C, _native.ptr(r), B, H, W, _native.ptr(narrow), F,
-                                                              _native.ptr(out), dev.index, _native.stream_of(dev)))
-        ctx.save_for_backward(a, r, narrow, vptr, order)
-        ctx.frame = frame
-        ctx.rast_version = rast._version
-        ctx.attr_shape = tuple(attr.shape)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        need_attr, need_rast = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if not (need_attr or need_rast):
-            return None, None, None, None
-        a, r, narrow, vptr, corner_order = ctx.saved_tensors
-        tab = ctx.frame.tab
-        B, H, W, _ = r.shape
-        _, V, C = a.shape
-        F, dev = narrow.shape[0], r.device
-        g = g.to(torch.float32).contiguous()
-        ga = torch.empty_like(a) if need_attr else None
-        gr = torch.empty((B, H, W, 4), dtype=torch.float32, device=dev) if need_rast else None
-        lib = _native.lib()
-        with torch.cuda.device(dev):
-            st = _native.stream_of(dev)
-            if need_rast:
-                _native.check(lib.ls_raster_interpolate_backward(
-                    _native.ptr(a), 1, V, C, _native.ptr(r), B, H, W, _native.ptr(narrow), F, _native.ptr(g), None, None, None, None, None,
-                    _native.ptr(gr), None, 0, dev.index, st))
-            if need_attr:
-                order, seg = ctx.frame.pixel_order(r, ctx.rast_version)
-                ws = _range_workspace(B, tab.N, H, W, C, dev)
-                _native.check(lib.ls_range_interpolate_backward(
-                    _native.ptr(r), _native.ptr(tab.dev), B, tab.N, H, W, V, C, _native.ptr(g), _native.ptr(order), _native.ptr(seg),
-                    _native.ptr(vptr), _native.ptr(corner_order), _native.ptr(ga), _native.ptr(ws), ws.numel(), dev.index, st))
-        return (ga.view(ctx.attr_shape) if need_attr else None), gr, None, None
-
-
-class _AntialiasRange(Function):
-    @staticmethod
-    def forward(ctx, color, rast, pos, tri, boost, frame):
-        _native.require_device(color, "color")
-        r = _rast(rast)
-        p = _pos_shared(pos)
-        B, H, W, _ = r.shape
-        if color.dim() != 4 or tuple(color.shape[:3]) != (B, H, W):
-            raise ValueError(f"color must be ({B}, {H}, {W}, C), got {tuple(color.shape)}")
-        c = color.detach()
-        if c.dtype != torch.float32 or not c.is_contiguous():
-            c = c.to(torch.float32).contiguous()
-        C, V, tab = c.shape[3], p.shape[0], frame.tab
-        f, narrow, vptr, order = _range_faces(tri, V, tab)
-        adj = tab.adjacency(f, narrow)
-        F, dev = narrow.shape[0], r.device
-        out = torch.empty_like(c)
-        with torch.cuda.device(dev):
-            _native.check(_native.lib().ls_range_antialias(_native.ptr(c), C, _native.ptr(r), _native.ptr(p), V, _native.ptr(narrow), F,
-                                                           _native.ptr(tab.dev), B, tab.N, H, W, _native.ptr(adj), _native.ptr(out), dev.index,
-                                                           _native.stream_of(dev)))
-        ctx.save_for_backward(c, r, p, narrow, adj, vptr, order)
-        ctx.boost = float(boost)
-        ctx.frame = frame
-        ctx.rast_version = rast._version
-        ctx.pos_shape = tuple(pos.shape)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        need_color, need_pos = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
-        if not (need_color or need_pos):
-            return None, None, None, None, None, None
-        c, r, p, narrow, adj, vptr, corner_order = ctx.saved_tensors
-        tab = ctx.frame.tab
-        B, H, W, C = c.shape
-        V, F, dev = p.shape[0], narrow.shape[0], c.device
-        g = g.to(torch.float32).contiguous()
-        gc = torch.empty_like(c) if need_color else None
-        gp = torch.empty_like(p) if need_pos else None
-        order = seg = ws = None
-        if need_pos:
-            order, seg = ctx.frame.pixel_order(r, ctx.rast_version)
-            ws = _range_workspace(B, tab.N, H, W, 0, dev)
-        with torch.cuda.device(dev):
-            _native.check(_native.lib().ls_range_antialias_backward(
-                _native.ptr(c), C, _native.ptr(r), _native.ptr(p), V, _native.ptr(narrow), F, _native.ptr(tab.dev), B, tab.N, H, W,
-                _native.ptr(adj), _native.ptr(g), ctx.boost, _native.ptr(order), _native.ptr(seg), _native.ptr(vptr), _native.ptr(corner_order),
-                _native.ptr(gc), _native.ptr(gp), _native.ptr(ws), 0 if ws is None else ws.numel(), dev.index, _native.stream_of(dev)))
-        return gc, None, (gp.view(ctx.pos_shape) if need_pos else None), None, None, None
 
 
 class _DbSource:
@@ -641,7 +538,7 @@ def _attr_da(attr, rast, tri, db, diff_attrs):
 
 class _Interpolate(Function):
     @staticmethod
-    def forward(ctx, attr, rast, tri, slot):
+    def forward(ctx, attr, rast, tri, frame):
         _native.require_device(attr, "attr")
         r = _rast(rast)
         B, H, W, _ = r.shape
@@ -657,14 +554,15 @@ class _Interpolate(Function):
         if a.dtype != torch.float32 or not a.is_contiguous():
             a = a.to(torch.float32).contiguous()
         Ba, V, C = a.shape
-        f, narrow, vptr, order = _faces(tri, V)
+        f, narrow, vptr, order = frame.faces(tri, V)
         F, dev = narrow.shape[0], r.device
         out = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev):          # in range mode too: ids are global and attr is shared (Ba = 1), the instanced kernel as it is
             _native.check(_native.lib().ls_raster_interpolate(_native.ptr(a), Ba, V, C, _native.ptr(r), B, H, W, _native.ptr(narrow), F,
                                                               _native.ptr(out), dev.index, _native.stream_of(dev)))
         ctx.save_for_backward(a, r, narrow, vptr, order)
-        ctx.slot = slot
+        ctx.frame = frame
+        ctx.rast_version = rast._version
         ctx.attr_shape = tuple(attr.shape)
         return out
 
@@ -674,21 +572,11 @@ class _Interpolate(Function):
         if not (need_attr or need_rast):
             return None, None, None, None
         a, r, narrow, vptr, corner_order = ctx.saved_tensors
-        B, H, W, _ = r.shape
-        Ba, V, C = a.shape
-        F, dev = narrow.shape[0], r.device
         g = g.to(torch.float32).contiguous()
         ga = torch.empty_like(a) if need_attr else None
-        gr = torch.empty((B, H, W, 4), dtype=torch.float32, device=dev) if need_rast else None
-        order = seg = ws = None
-        if need_attr:
-            order, seg = ctx.slot.get(r)
-            ws = _workspace(B, F, H, W, C, dev)
-        with torch.cuda.device(dev):
-            _native.check(_native.lib().ls_raster_interpolate_backward(
-                _native.ptr(a), Ba, V, C, _native.ptr(r), B, H, W, _native.ptr(narrow), F, _native.ptr(g), _native.ptr(order), _native.ptr(seg),
-                _native.ptr(vptr), _native.ptr(corner_order), _native.ptr(ga), _native.ptr(gr), _native.ptr(ws), 0 if ws is None else ws.numel(),
-                dev.index, _native.stream_of(dev)))
+        gr = torch.empty(r.shape, dtype=torch.float32, device=r.device) if need_rast else None
+        with torch.cuda.device(r.device):
+            ctx.frame.interpolate_backward(a, r, narrow, g, vptr, corner_order, ga, gr, ctx.rast_version)
         return (ga.view(ctx.attr_shape) if need_attr else None), gr, None, None
 
 
@@ -714,17 +602,15 @@ def interpolate(attr, rast, tri, rast_db=None, diff_attrs=None):
     if diff_attrs is not None and rast_db is None:
         raise ValueError("largesteps.render.interpolate: diff_attrs needs rast_db (the second output of rasterize)")
     frame = _range_frame(rast)
-    if frame is not None:
-        if diff_attrs is not None:
-            raise NotImplementedError("largesteps.render.interpolate: diff_attrs is not supported for a rast of range mode (ranges=...)")
-        if not isinstance(attr, torch.Tensor) or attr.dim() not in (2, 3) or (attr.dim() == 3 and attr.shape[0] != 1):
-            raise ValueError("attr must be (V, C) or (1, V, C) for a rast of range mode (the images share one vertex array), got "
-                             f"{tuple(attr.shape) if isinstance(attr, torch.Tensor) else type(attr).__name__}")
-        return _InterpolateRange.apply(attr, rast, tri, frame), None
-    F = tri.shape[0] if isinstance(tri, torch.Tensor) and tri.dim() == 2 else 0
-    slot = _order_slot(rast, F)
-    out = _Interpolate.apply(attr, rast, tri, slot)
-    _attach_order(rast, slot)
+    if frame is None:
+        frame = _instanced_frame(rast, tri)
+    elif diff_attrs is not None:
+        raise NotImplementedError("largesteps.render.interpolate: diff_attrs is not supported for a rast of range mode (ranges=...)")
+    elif not isinstance(attr, torch.Tensor) or attr.dim() not in (2, 3) or (attr.dim() == 3 and attr.shape[0] != 1):
+        raise ValueError("attr must be (V, C) or (1, V, C) for a rast of range mode (the images share one vertex array), got "
+                         f"{tuple(attr.shape) if isinstance(attr, torch.Tensor) else type(attr).__name__}")
+    out = _Interpolate.apply(attr, rast, tri, frame)
+    rast._largesteps_frame = frame
     if diff_attrs is None:
         return out, None
     with torch.no_grad():
@@ -733,29 +619,27 @@ def interpolate(attr, rast, tri, rast_db=None, diff_attrs=None):
 
 class _Antialias(Function):
     @staticmethod
-    def forward(ctx, color, rast, pos, tri, boost, slot):
+    def forward(ctx, color, rast, pos, tri, boost, frame):
         _native.require_device(color, "color")
         r = _rast(rast)
-        p = _pos(pos)
+        p = frame.pos(pos)
         B, H, W, _ = r.shape
         if color.dim() != 4 or tuple(color.shape[:3]) != (B, H, W):
             raise ValueError(f"color must be ({B}, {H}, {W}, C), got {tuple(color.shape)}")
-        if p.shape[0] != B:
+        if frame.images(p) != B:
             raise ValueError(f"pos has {p.shape[0]} batches for {B} images")
         c = color.detach()
         if c.dtype != torch.float32 or not c.is_contiguous():
             c = c.to(torch.float32).contiguous()
-        C, V = c.shape[3], p.shape[1]
-        f, narrow, vptr, order = _faces(tri, V)
-        adj = _adjacent(f, narrow)
-        F, dev = narrow.shape[0], r.device
-        out = torch.empty_like(c)
+        f, narrow, vptr, order = frame.faces(tri, p.shape[-2])
+        adj = frame.adjacency(f, narrow)
+        out, dev = torch.empty_like(c), r.device
         with torch.cuda.device(dev):
-            _native.check(_native.lib().ls_raster_antialias(_native.ptr(c), C, _native.ptr(r), _native.ptr(p), B, V, H, W, _native.ptr(narrow), F,
-                                                            _native.ptr(adj), _native.ptr(out), dev.index, _native.stream_of(dev)))
+            frame.antialias(c, r, p, narrow, adj, B, H, W, out, dev)
         ctx.save_for_backward(c, r, p, narrow, adj, vptr, order)
         ctx.boost = float(boost)
-        ctx.slot = slot
+        ctx.frame = frame
+        ctx.rast_version = rast._version
         return out
 
     @staticmethod
@@ -764,20 +648,16 @@ class _Antialias(Function):
         if not (need_color or need_pos):
             return None, None, None, None, None, None
         c, r, p, narrow, adj, vptr, corner_order = ctx.saved_tensors
-        B, H, W, C = c.shape
-        V, F, dev = p.shape[1], narrow.shape[0], c.device
+        (B, H, W, C), dev, frame = c.shape, c.device, ctx.frame
         g = g.to(torch.float32).contiguous()
         gc = torch.empty_like(c) if need_color else None
         gp = torch.empty_like(p) if need_pos else None
         order = seg = ws = None
         if need_pos:
-            order, seg = ctx.slot.get(r)
-            ws = _workspace(B, F, H, W, 0, dev)
+            order, seg = frame.pixel_order(r, ctx.rast_version)
+            ws = frame.workspace(B, H, W, 0, dev)
         with torch.cuda.device(dev):
-            _native.check(_native.lib().ls_raster_antialias_backward(
-                _native.ptr(c), C, _native.ptr(r), _native.ptr(p), B, V, H, W, _native.ptr(narrow), F, _native.ptr(adj), _native.ptr(g), ctx.boost,
-                _native.ptr(order), _native.ptr(seg), _native.ptr(vptr), _native.ptr(corner_order), _native.ptr(gc), _native.ptr(gp), _native.ptr(ws),
-                0 if ws is None else ws.numel(), dev.index, _native.stream_of(dev)))
+            frame.antialias_backward(c, r, p, narrow, adj, B, H, W, C, g, ctx.boost, order, seg, vptr, corner_order, gc, gp, ws, dev)
         return gc, None, gp, None, None, None
 
 
@@ -803,14 +683,13 @@ def antialias(color, rast, pos, tri, topology_hash=None, pos_gradient_boost=1.0)
         if frame is None:
             raise ValueError("largesteps.render.antialias: a (V, 4) pos is range mode and needs the range table that its rast carries: pass "
                              "the tensor that rasterize(..., ranges=...) returned (not a copy of it)")
-        return _AntialiasRange.apply(color, rast, pos, tri, float(pos_gradient_boost), frame)
-    if frame is not None:
+    elif frame is not None:
         raise ValueError(f"rast comes from a range-mode rasterize: pos must be the (V, 4) positions given to it, got "
                          f"{tuple(pos.shape) if isinstance(pos, torch.Tensor) else type(pos).__name__}")
-    F = tri.shape[0] if isinstance(tri, torch.Tensor) and tri.dim() == 2 else 0
-    slot = _order_slot(rast, F)
-    out = _Antialias.apply(color, rast, pos, tri, float(pos_gradient_boost), slot)
-    _attach_order(rast, slot)
+    else:
+        frame = _instanced_frame(rast, tri)
+    out = _Antialias.apply(color, rast, pos, tri, float(pos_gradient_boost), frame)
+    rast._largesteps_frame = frame
     return out
 
 

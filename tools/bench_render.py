@@ -81,7 +81,7 @@ for name in ("cfg2_bunny70k", "cfg4b_sphere1m"):
         case = {"mesh": name, "V": int(v.shape[0]), "F": int(f.shape[0]), "B": B}
         case["rasterize_fwd"] = timed(lambda: dr.rasterize(None, pos, tf, (RES, RES)))
         rast = dr.rasterize(None, pos, tf, (RES, RES))[0]
-        case["pixel_order"] = timed(lambda: dr._PixelOrder(0, tf.shape[0]).get(rast))
+        case["pixel_order"] = timed(lambda: dr._InstancedFrame(tf.shape[0]).pixel_order(rast, 0))
         p = pos.clone().requires_grad_(True)
         case["rasterize_fwd_bwd"] = timed(lambda: dr.rasterize(None, p, tf, (RES, RES))[0][..., :2].sum().backward())
         case["interpolate_fwd"] = timed(lambda: dr.interpolate(light, rast, tf))
