@@ -14,8 +14,9 @@
 // min(floor(lod + 0.5), Lmax). A pixel with a non-finite uv_da, bias, lod or level-0 texel coordinate outputs 0 and gives no gradient.
 //
 // Gradients, no float atomics. Per pixel: to uv from both levels; d out / d lod = sum_c g_c (c1_c - c0_c) where two levels were read
-// (zero where lod was clamped, where m == 0 and in nearest mode), which is the bias gradient and, through d lod / d uv_da, the uv_da
-// gradient (R == 0: d m / d A = d m / d B = 0.5, d m / d Cc = 0). To tex: every pixel is one item per level it read -- item p for l0,
+// (zero where lod was clamped, where m == 0 and in nearest mode; c_l here is the sum of the four taps times their weights, see
+// mip_level_grad), which is the bias gradient and, through d lod / d uv_da, the uv_da gradient (R == 0: d m / d A = d m / d B = 0.5,
+// d m / d Cc = 0). To tex: every pixel is one item per level it read -- item p for l0,
 // item N + p for l1 -- keyed by (level, base tap) as texture.hip keys a pixel by its base tap; ls_mip_order sorts the items (groupby.h) and
 // ls_mip_backward runs one thread per texel of EVERY level over the sorted items of the base positions that touch it, term
 // g (wx wy) w_level, a texel with more than 64 items by its whole wave. ls_mip_fold then adds, top down, 0.25f (0.5f) of every parent's
@@ -277,13 +278,16 @@ __global__ __launch_bounds__(256) void k_mip_forward(const float* __restrict__ t
 }
 
 // ---- per-pixel gradients: uv (N, 2) and d loss / d lod (N), both accumulated over the channel groups --------------------------------------
-// the uv gradient of one level and its bilinear read
+// the uv gradient of one level and its bilinear read. The read feeds d out / d lod = c1 - c0 and is summed by weights, not in the
+// forward's order t00 + (t10 - t00) fx: that form errs by a rounding of the LARGEST tap (a tap that reads 0 in zero mode leaves
+// t00 - t00 fx), the weighted sum by roundings of the weighted taps, which is what a difference of two reads needs.
 template <int CT>
 __device__ __forceinline__ void mip_level_grad(const float* __restrict__ level, const TxShape& sl, const float* __restrict__ uv, int64_t pix, int c0,
                                                const float (&go)[CT], float& gu, float& gv, float (&o)[CT]) {
     const TxCoord q = tx_coord(uv, pix, sl);
     const TxTaps<CT> a = tx_taps<CT>(level, q, pix, sl, c0);
     const float ofx = 1.0f - q.fx, ofy = 1.0f - q.fy;
+    const float w00 = ofx * ofy, w10 = q.fx * ofy, w01 = ofx * q.fy, w11 = q.fx * q.fy;
     float su = 0.0f, sv = 0.0f;
 #pragma unroll
     for (int c = 0; c < CT; ++c) {
@@ -291,9 +295,7 @@ __device__ __forceinline__ void mip_level_grad(const float* __restrict__ level, 
         const float dv = (a.t[1][0][c] - a.t[0][0][c]) * ofx + (a.t[1][1][c] - a.t[0][1][c]) * q.fx;
         su += go[c] * du;
         sv += go[c] * dv;
-        const float top = a.t[0][0][c] + (a.t[0][1][c] - a.t[0][0][c]) * q.fx;
-        const float bot = a.t[1][0][c] + (a.t[1][1][c] - a.t[1][0][c]) * q.fx;
-        o[c] = top + (bot - top) * q.fy;
+        o[c] = (a.t[0][0][c] * w00 + a.t[0][1][c] * w10) + (a.t[1][0][c] * w01 + a.t[1][1][c] * w11);
     }
     gu = (float)sl.Wt * su;
     gv = (float)sl.Ht * sv;

@@ -95,7 +95,7 @@ def texture(tex, uv, uv_da=None, bias=None, g=None, filter_mode="linear-mipmap-l
         out (B, H, W, C), dout_dlod (B, H, W, C) (c1 - c0 where two levels were read), lod (unclamped) and dlod (B, H, W),
         finite, two, flag (B, H, W) bool, l0 (B, H, W) int, f (B, H, W), base (B, H, W, 4) int, Lmax, levels
     and, when the upstream gradient g (B, H, W, C) is given,
-        grad_tex, grad_tex_abs, grad_tex_lod (Bt, Ht, Wt, C), grad_tex_n (Bt, Ht, Wt)
+        grad_tex, grad_tex_abs, grad_tex_lod (Bt, Ht, Wt, C), grad_tex_n (Bt, Ht, Wt), level_n (a (Bt, H_l, W_l) count per level)
         grad_uv, grad_uv_abs, grad_uv_lod (B, H, W, 2), grad_uv_n
         grad_bias, grad_bias_abs (B, H, W), grad_bias_n          (d loss / d lod)
         grad_uv_da, grad_uv_da_abs (B, H, W, 4), grad_uv_da_n
@@ -191,6 +191,7 @@ def texture(tex, uv, uv_da=None, bias=None, g=None, filter_mode="linear-mipmap-l
             uv_s = np.where((sign != 0)[..., None], uvc, coords(np.nan))
             Glod[l] = ts.texture(levels[l], uv_s, np.abs(g64) * r.dlod[..., None], "linear", boundary_mode, coords=coords).grad_tex_abs
     r.grad_uv_lod = np.abs(slope_uv) * r.dlod[..., None]
+    r.level_n = [n.copy() for n in Gn]          # the items of every texel of every level, before the levels are folded into level 0
     for l in range(Lmax - 1, -1, -1):
         shape = levels[l].shape
         up, coef = _up(G[l + 1], shape)

@@ -1,7 +1,8 @@
 """
 The mipmapped lookup and the pixel differentials of largesteps.render without a device: self-checks of the numpy statement
 (tests/mip_statement.py) -- level sizes, means, central finite differences of its own forward --, the flag cap of the device
-test's cases, and the public surface (argument checks, exported symbols, what must not move).
+test's cases (those of tests/texture_cases.py too, with the conditions they were built for), and the public surface (argument checks,
+exported symbols, what must not move).
 """
 import ctypes
 import os
@@ -269,3 +270,65 @@ def test_native_entry_points_are_exported_and_bound():
     assert lib.ls_mip_interpolate_da(null, 2, 3, 1, null, null, 3, 4, 4, null, 1, null, 0, null) == -1
     assert lib.ls_mip_order(null, null, null, 2, 4, 4, 1, 8, 8, 3, 1, 0, null, null, null, 0, 0, null) == -1
     assert lib.ls_mip_backward(null, null, 1, 8, 8, 0, 3, null, null, null, 2, 4, 4, 1, 0, null, null, null, null, null, null, null, null, 0, null) == -1
+
+
+def test_the_scale_cases_stay_under_the_flag_cap_and_meet_their_conditions():
+    """the cases of tests/test_mip_scale_gpu.py, from the statement alone"""
+    import texture_cases as tc
+
+    def offsets(shape, Lmax):
+        sizes = [shape[0] * max(shape[1] >> l, 1) * max(shape[2] >> l, 1) for l in range(Lmax + 1)]
+        return np.cumsum(sizes).tolist()
+
+    for name, (tex_shape, uv_shape, max_level) in tc.MIP_CASES.items():
+        tex, uv, da, bias, ml, g = tc.mip_case(name)
+        assert tex.shape == tex_shape and uv.shape == uv_shape + (2,) and ml == max_level and g.shape == uv_shape + tex_shape[3:]
+        for mode in ms.MODES:
+            # one boundary mode is enough: lod, the level choice, `flag` and `two` come from uv_da and the bias alone; the per-level counts
+            # checked below are those of clamp (the device test asserts the flag cap again for every boundary mode it runs)
+            r = ms.texture(tex, uv, da, bias, g, mode, "clamp", max_level)
+            linear = mode == "linear-mipmap-linear"
+            assert r.flag.mean() <= 0.02, (name, mode, r.flag.mean())
+            assert r.finite.all() and len(r.level_n) == r.Lmax + 1
+            # per-level counts: every item is counted once per tap, on its own level
+            assert sum(int(n.sum()) for n in r.level_n) == 4 * (int(r.finite.sum()) + int(r.two.sum()))
+            if name == "mip_threshold":
+                assert not r.flag.any() and da is None and r.Lmax == 5
+                n0, n1, n2 = (r.level_n[l][0] for l in range(3))
+                assert (n0 == 64).any() and (n0 == 65).any() and n2.max() > 64 and linear == bool(n1.max() > 64)
+                assert not any(n.any() for n in r.level_n[3:])
+                assert sorted(set(n0.ravel()[:64]) - {0}) == [1, 32, 33, 64, 65, 350]   # level 0's first wave: short, 64, and two long texels
+                want = tc.threshold_counts([((m + 1) // 2, i, j) for m, i, j in tc.MIP_THRESHOLD_CLUSTERS], *tex_shape[1:3])
+                assert np.array_equal(n0, want) and n0[4, 21] == 20 + 13 and n0[8, 27] == 20 + 12
+                assert r.two.sum() == (sum(m // 2 for m, _, _ in tc.MIP_THRESHOLD_CLUSTERS) if linear else 0)
+                assert offsets(tex_shape, 5) == [512, 640, 672, 680, 682, 683]          # level 2 lies in the third, partial workgroup
+            else:
+                assert (r.lod < 0).any() and (r.lod > r.Lmax).any() and (not linear or r.two.mean() > 0.5)
+                assert max(int(n.max()) for n in r.level_n) > 64
+        nk = tc.mip_keys(tex_shape, r.Lmax)
+        if name.startswith("three_pass"):
+            assert tc.texture_keys(tex_shape) >= 65536 and nk < 2 ** 24 and tc.radix_passes(nk) == 3
+        else:
+            assert tc.radix_passes(nk) == 2
+        if name.startswith("levels_straddle"):
+            # level 1 starts inside a workgroup (on a wave boundary: 2880 = 45 x 64), levels 2 and 3 inside a wave
+            assert r.Lmax == 3 and offsets(tex_shape, 3) == [2880, 3600, 3780, 3825] and 2880 % 256 and 3600 % 64 and 3780 % 64
+        if name.startswith("deep"):
+            assert r.Lmax == 9
+            thin = [lv.shape[1] == 1 or lv.shape[2] == 1 for lv in r.levels]
+            assert sum(thin) >= 4 and min(lv.shape[1] * lv.shape[2] for lv, t in zip(r.levels, thin) if t) == 1
+            assert all(n.any() for n in r.level_n)                                      # every thin level receives gradient of its own
+
+
+def test_the_bounds_hold_between_two_summation_orders_of_the_statement():
+    """as in tests/test_texture_cpu.py: the statement with its pixels reversed differs from itself by far less than the device bound, and
+    the bound stays a small fraction of an entry's terms at 861 items on one level-2 texel"""
+    import texture_cases as tc
+    tex, uv, da, bias, ml, g = tc.mip_case("mip_threshold")
+    a = ms.texture(tex, uv, da, bias, g, "linear-mipmap-linear", "clamp", ml)
+    b = ms.texture(tex, uv[:, ::-1, ::-1], da, bias[:, ::-1, ::-1], g[:, ::-1, ::-1], "linear-mipmap-linear", "clamp", ml)
+    assert np.array_equal(a.grad_tex_n, b.grad_tex_n) and a.level_n[2].max() == 861
+    bound = (a.grad_tex_n[..., None] + 16) * ms.U * a.grad_tex_abs + a.grad_tex_lod
+    diff = np.abs(a.grad_tex - b.grad_tex)
+    assert diff.max() > 0 and np.all(diff <= 1e-6 * bound)
+    assert bound.max() > 0 and np.all(bound <= 3e-4 * a.grad_tex_abs)

@@ -32,6 +32,7 @@ import mip_statement as ms  # noqa: E402
 import render_statement as rs  # noqa: E402
 import texture_statement as ts  # noqa: E402
 from render_scenes import clip, look_at, scene  # noqa: E402
+from texture_cases import scaled_da as _scaled_da  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0) if torch.cuda.is_available() else None
@@ -49,14 +50,6 @@ def oblique_quad():
     v = np.array([[-1, -1, 0], [1, -1, 0], [1, 1, 0], [-1, 1, 0]], np.float32)
     attr = np.array([[0.1, 0.05], [1.7, 0.2], [1.5, 1.9], [-0.2, 1.6]], np.float32)
     return clip(v, [look_at((1.8, 1.1, -1.9))], ar=24 / 20), np.array([[0, 1, 2], [0, 2, 3]]), attr, 20, 24
-
-
-def _scaled_da(rng, shape, Ht, Wt, lo, hi):
-    """uv_da whose lod (without bias) is uniform in [lo, hi): a random direction scaled to the wanted footprint"""
-    d = rng.standard_normal(shape + (4,))
-    want = rng.uniform(lo, hi, shape)
-    m = ms.footprint(d, Ht, Wt)[0]
-    return (d * np.sqrt(4.0 ** want / m)[..., None]).astype(np.float32)
 
 
 def case(name, device_chain=False):
@@ -184,7 +177,23 @@ def _torch_pyramid(t, Lmax):
     return levels
 
 
-@pytest.mark.parametrize("shape,max_level", [((2, 8, 8, 3), None), ((1, 2, 4, 4), None), ((1, 16, 16, 1), 2), ((1, 1, 1, 2), None), ((1, 32, 2, 5), None)])
+def _texel_centres(n):
+    """fp32 coordinates u_k, k < n, whose texel-space coordinate u_k n - 0.5 is exactly k in the device's fp32 arithmetic (fx = 0: the
+    lookup returns the texel's own bits): (k + 0.5) / n correctly rounded, or one of its neighbours. (torch divides by a scalar on
+    the device by multiplying with its reciprocal, which misses for sizes that are no power of two.) Such a number need not exist for
+    every k of every size; it does for the sizes used here. The check below multiplies and subtracts in two rounded steps, as the
+    device does because the library is built with -ffp-contract=off (csrc/Makefile); a contracted x n - 0.5 would be one fma and
+    this check would no longer describe it."""
+    k = np.arange(n, dtype=np.float32)
+    u = (k + np.float32(0.5)) / np.float32(n)
+    cands = np.stack([u] + [np.nextafter(u, np.float32(d)) for d in (np.inf, -np.inf)])
+    exact = cands * np.float32(n) - np.float32(0.5) == k
+    assert cands.dtype == np.float32 and exact.any(0).all(), n
+    return dev(cands[exact.argmax(0), np.arange(n)])
+
+
+@pytest.mark.parametrize("shape,max_level", [((2, 8, 8, 3), None), ((1, 2, 4, 4), None), ((1, 16, 16, 1), 2), ((1, 1, 1, 2), None), ((1, 32, 2, 5), None),
+                                             ((1, 64, 512, 3), None), ((1, 40, 72, 3), 3)])
 def test_pyramid_levels_are_the_plain_torch_means_bit_for_bit(shape, max_level):
     import largesteps.render as dr
     tex = dev(np.random.default_rng(4).standard_normal(shape).astype(np.float32))
@@ -193,8 +202,8 @@ def test_pyramid_levels_are_the_plain_torch_means_bit_for_bit(shape, max_level):
     assert mip.Lmax == len(want) - 1
     for l, level in enumerate(want):
         Hl, Wl = level.shape[1], level.shape[2]
-        jj, ii = torch.meshgrid(torch.arange(Hl, device=DEV), torch.arange(Wl, device=DEV), indexing="ij")
-        uv = torch.stack([(ii + 0.5) / Wl, (jj + 0.5) / Hl], -1)[None].expand(shape[0], -1, -1, -1).contiguous().float()
+        vv, uu = torch.meshgrid(_texel_centres(Hl), _texel_centres(Wl), indexing="ij")
+        uv = torch.stack([uu, vv], -1)[None].expand(shape[0], -1, -1, -1).contiguous()
         bias = torch.full((shape[0], Hl, Wl), float(l), device=DEV)
         for mode in ms.MODES:
             got = dr.texture(tex, uv, mip_level_bias=bias, mip=mip, filter_mode=mode, boundary_mode="clamp")

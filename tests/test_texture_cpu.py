@@ -1,7 +1,9 @@
 """
 largesteps.render.texture without a device: the numpy statement (tests/texture_statement.py) against central finite differences, against
 the plain-torch lookup CPU tensors get and the coordinates the reference hands to dr.texture (tests/golden/reference_render.npz), a
-few cases worked by hand, and the public surface (symbols, argument checks, the modes that stay unsupported).
+few cases worked by hand, and the public surface (symbols, argument checks, the modes that stay unsupported). And the statement's
+scatter against np.add.at (bit for bit), the conditions the cases of tests/texture_cases.py were built for, and the device bound against
+two summation orders of the statement itself.
 """
 import ctypes
 import os
@@ -181,3 +183,129 @@ def test_unsupported_modes_still_raise_and_cpu_tensors_keep_the_plain_lookup():
     for kw in (dict(filter_mode="nearest"), dict(boundary_mode="clamp"), dict(boundary_mode="zero")):
         with pytest.raises(NotImplementedError, match="HIP device"):
             texture(tex, uv, **kw)
+
+
+# ---- the statement's scatter, and the cases of tests/test_texture_scale_gpu.py ------------------------------------------------------------
+def _add_at_scatter(at, term, shape):
+    """texture_statement._scatter as it was first written: np.add.at into zeros, term by term"""
+    size, C = shape[0] * shape[1] * shape[2], shape[3]
+    grad, grad_abs, n = np.zeros((size, C)), np.zeros((size, C)), np.zeros(size, dtype=np.int64)
+    np.add.at(grad, at, term)
+    np.add.at(grad_abs, at, np.abs(term))
+    np.add.at(n, at, 1)
+    return grad.reshape(shape), grad_abs.reshape(shape), n.reshape(shape[:3])
+
+
+def _small_cases():
+    """the inputs of the tests above: (tex, uv, g)"""
+    rng = np.random.default_rng(11)
+    B, H, W, Ht, Wt, C = 2, 5, 7, 4, 6, 3
+    for linear in (False, True):
+        for Bt in (1, B):
+            yield rng.standard_normal((Bt, Ht, Wt, C)), _uv_inside_cells(rng, (B, H, W), Ht, Wt, linear), rng.standard_normal((B, H, W, C))
+    rng = np.random.default_rng(3)
+    golden = np.load(os.path.join(HERE, "golden", "reference_render.npz"))
+    cases = [(rng.standard_normal((Bt, Ht, Wt, C)).astype(np.float32), rng.uniform(-2.0, 3.0, (B, 9, 11, 2)).astype(np.float32))
+             for Bt, B, Ht, Wt, C in ((1, 3, 5, 8, 3), (2, 2, 7, 3, 4), (1, 1, 1, 1, 1))]
+    cases.append((golden["sh_envmap"][None], golden["bg_uvs"]))
+    for tex, uv in cases:
+        yield tex, uv, rng.standard_normal(uv.shape[:3] + (tex.shape[3],))
+    rng = np.random.default_rng(5)
+    yield rng.standard_normal((1, 4, 5, 2)), rng.uniform(-1, 2, (3, 6, 6, 2)), rng.standard_normal((3, 6, 6, 2))
+    yield rng.standard_normal((1, 4, 5, 2)), np.array([[[[np.nan, 0.5], [0.5, np.inf], [0.5, 0.5]]]]), np.ones((1, 1, 3, 2))
+
+
+def test_the_bincount_scatter_is_the_add_at_scatter_bit_for_bit(monkeypatch):
+    fast = [[ts.texture(tex, uv, g, f, b, coords=c) for f in ts.FILTERS for b in ts.BOUNDARIES for c in (np.float32, np.float64)]
+            for tex, uv, g in _small_cases()]
+    monkeypatch.setattr(ts, "_scatter", _add_at_scatter)
+    slow = [[ts.texture(tex, uv, g, f, b, coords=c) for f in ts.FILTERS for b in ts.BOUNDARIES for c in (np.float32, np.float64)]
+            for tex, uv, g in _small_cases()]
+    assert len(fast) == 10
+    for rf, rs_ in zip(fast, slow):
+        for x, y in zip(rf, rs_):
+            assert x.grad_tex_n.dtype == y.grad_tex_n.dtype and x.grad_tex.shape == y.grad_tex.shape
+            assert np.array_equal(x.grad_tex_n, y.grad_tex_n) and x.grad_tex_n.sum() > 0
+            assert np.array_equal(x.grad_tex, y.grad_tex) and np.array_equal(x.grad_tex_abs, y.grad_tex_abs)
+
+
+def test_the_scale_cases_meet_their_conditions():
+    import texture_cases as tc
+    assert [tc.radix_passes(nk) for nk in (0, 255, 256, 65535, 65536, 2 ** 24 - 1, 2 ** 24, 2 ** 31 - 3)] == [1, 1, 2, 2, 3, 3, 4, 4]
+    for name, (tex_shape, uv_shape, modes) in tc.TEXTURE_CASES.items():
+        nk = tc.texture_keys(tex_shape)
+        assert set(modes) <= set(tc.ALL_MODES)
+        tex, uv, g = tc.texture_case(name)
+        assert tex.shape == tex_shape and uv.shape == uv_shape + (2,) and g.shape == uv_shape + tex_shape[3:]
+        assert tex.dtype == uv.dtype == g.dtype == np.float32
+        if name != "threshold":                     # every boundary rule fires on both axes
+            assert uv.min() < -1.4 and uv.max() > 2.4
+        if name != "four_pass_4096_c1":
+            assert modes == tc.ALL_MODES
+        else:                                       # 16.7 M texels: one statement call, the mode whose border texels pile up
+            r = ts.texture(tex, uv, g, "linear", "clamp")
+            assert r.grad_tex.shape == tex_shape and r.grad_tex_n.dtype == np.int64 and r.finite.all()
+            assert r.grad_tex_n.sum() == 4 * uv[..., 0].size and r.grad_tex_n.max() > 700
+            assert r.grad_tex_n[0, 1:-1, 1:-1].max() <= 4 and (r.grad_tex_n[0, 1:-1, 1:-1] > 0).sum() > 200   # inside: a few texels, a few items each
+        if name.startswith("three_pass"):
+            assert 65536 <= nk < 2 ** 24 and tc.radix_passes(nk) == 3
+        if name.startswith("four_pass"):
+            assert nk == 4097 ** 2 >= 2 ** 24 and tc.radix_passes(nk) == 4 and modes == (("linear", "wrap"), ("linear", "clamp"))
+    assert tc.TEXTURE_CASES["wide_300x5_c3"][0][2] + 1 > 255 and 5 * 300 == 5 * 256 + 220
+    assert tc.TEXTURE_CASES["three_pass_own_b4_128x128_c4"][0] == (4, 128, 128, 4) and tc.TEXTURE_CASES["three_pass_own_b4_128x128_c4"][1][0] == 4
+    assert tc.TEXTURE_CASES["c32"][0][3] == 32 and tc.TEXTURE_CASES["c5"][0][3] == 5
+
+    # threshold: the counts the layout promises, where it promises them
+    Bt, Ht, Wt, C = tc.THRESHOLD_SHAPE
+    assert Ht * Wt == 960 and Ht * Wt - 3 * 256 == 192
+    cl = tc.THRESHOLD_CLUSTERS
+    single = [c for c in cl if c[0] not in (40, 25, 24)]
+    assert sorted(m for m, _, _ in single) == [1, 63, 64, 65, 65, 66, 127, 128, 129, 700]
+    for a, (_, i, j) in enumerate(cl):              # cells at least two texels apart, but for the two pairs; none touches the border
+        assert 1 <= i < Wt - 2 and 0 <= j < Ht - 2
+        for m2, i2, j2 in cl[a + 1:]:
+            assert abs(i - i2) >= 2 or abs(j - j2) >= 2 or (j == j2 and abs(i - i2) == 1 and m2 in (25, 24))
+    want = tc.threshold_counts(cl, Ht, Wt)
+    for boundary in ts.BOUNDARIES:
+        tex, uv, g = tc.texture_case("threshold", "linear")
+        r = ts.texture(tex, uv, g, "linear", boundary)
+        assert np.array_equal(r.grad_tex_n[0], want)
+        flat = r.grad_tex_n[0].ravel()
+        for m in (1, 63, 64, 65, 66, 127, 128, 129, 700):
+            assert (flat == m).any(), m
+        assert sorted(set(flat[:64]) - {0}) == [1, 64, 65, 129]                  # one wave: short, exactly 64, and two long texels
+        assert (flat[768:] == 65).sum() == 4 and (flat[896:] == 65).sum() == 2  # long texels in the last, partial workgroup and in its last wave
+        assert r.grad_tex_n[0, 10, 21] == 40 + 25 and r.grad_tex_n[0, 14, 31] == 40 + 24 and r.grad_tex_n[0, 10, 20] == 40
+        # strictly inside the cells: 0.1 of a texel from every border, in the fp32 arithmetic of the device
+        x, y = uv[..., 0] * np.float32(Wt) - np.float32(0.5), uv[..., 1] * np.float32(Ht) - np.float32(0.5)
+        for f in (x - np.floor(x), y - np.floor(y)):
+            assert f.min() > 0.09 and f.max() < 0.91
+        tex, uv, g = tc.texture_case("threshold", "nearest")
+        n = ts.texture(tex, uv, g, "nearest", boundary).grad_tex_n[0]
+        assert sorted(n[n > 0]) == sorted(m for m, _, _ in cl) and all(n[j, i] == m for m, i, j in cl)
+        assert np.array_equal(uv[..., 0] * np.float32(Wt), np.floor(uv[..., 0] * np.float32(Wt)) + np.float32(0.5))
+
+
+@pytest.mark.parametrize("name,filt,boundary", [("threshold", "linear", "wrap"), ("threshold", "nearest", "zero"), ("constant_uv", "linear", "wrap"),
+                                                ("three_pass_255x257_c3", "linear", "clamp")])
+def test_the_bounds_hold_between_two_summation_orders_of_the_statement(name, filt, boundary):
+    """the statement with fp32 coordinates, its pixels taken in reverse, is the same sum in another order: the two differ (fp64 is
+    not associative) by far less than the device bound, which at 700, 2048 and 4690 terms is still a small fraction of the entry's
+    terms -- the bound neither fails a correct sum nor admits a wrong term"""
+    import texture_cases as tc
+    if name == "constant_uv":
+        rng = np.random.default_rng(0)
+        tex, g = rng.standard_normal((1, 6, 4, 3)).astype(np.float32), rng.standard_normal((2, 32, 32, 3)).astype(np.float32)
+        uv = np.broadcast_to(np.float32([0.62, 0.4]), (2, 32, 32, 2)).copy()
+    else:
+        tex, uv, g = tc.texture_case(name, filt)
+    a = ts.texture(tex, uv, g, filt, boundary, coords=np.float32)
+    b = ts.texture(tex, uv[:, ::-1, ::-1], g[:, ::-1, ::-1], filt, boundary, coords=np.float32)
+    assert np.array_equal(a.grad_tex_n, b.grad_tex_n) and a.grad_tex_n.max() >= 700
+    bound = (a.grad_tex_n[..., None] + 16) * U * a.grad_tex_abs
+    diff = np.abs(a.grad_tex - b.grad_tex)
+    assert (diff.max() > 0 or filt == "nearest") and np.all(diff <= 1e-6 * bound)       # (nearest: sums of fp32 numbers, exact in fp64)
+    hit = a.grad_tex_n > 0
+    assert np.all(bound[hit] > 0) and not bound[~hit].any()
+    assert np.all(bound <= 3e-4 * a.grad_tex_abs)               # (4690 + 16) 2^-24 = 2.8e-4: dropping one term of a long texel is caught
+    assert np.array_equal(a.out, b.out[:, ::-1, ::-1]) and np.array_equal(a.grad_uv, b.grad_uv[:, ::-1, ::-1])
