@@ -15,6 +15,8 @@ What is restated (reference = rgl-epfl/large-steps-pytorch @ 0.2.2, paths relati
   solve.reference_cg            largesteps/solvers.py:58-126     ('CG', fp32, abs 1e-5 stop)
   solve.jacobi_pcg              fp64 statement of the algorithm the HIP PCG implements
   normals.face_normals / vertex_normals (+ *_backward)   scripts/geometry.py:91-110, :115-147 and their analytic gradients
+  normals.edge_norms / normalize_rows_backward / corner_terms / norm_gradients   the intermediates of that backward (the
+                                three global norms, g_raw, gN, the per-face gradient of the face normals) for tests of device buffers
   step.run / step.AdamUniform   the loop body of scripts/main.py:172-208 (no renderer) with largesteps/optimize.py:18-41
 
 Third-party dependency holding the default solver's arithmetic: `cholespy` (requirements.txt:1,
