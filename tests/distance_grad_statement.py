@@ -14,6 +14,12 @@ barycentric weights of the closest point and the two gradients, in numpy fp64, w
    is the sum of the terms of the corners that are this vertex (a repeated index receives both of its terms).
 The device adds the terms in fp32 in a fixed order; `gradients` adds them in fp64 and reports, per vertex, the sum of their magnitudes
 and the length of the device's fp32 chain, which is what the error bound of the device test is made of.
+3. Order. `ordered_gradients` adds them in fp32 in the device's order, so its result is the device's bit for bit. The key of a point is
+   its face, or F (the number of faces, "no group") for an I outside [0, F); the points are sorted stably by key, so a face's points
+   come in ascending point id, and those of key F are dropped. The nine-entry row of a face with m points starts from +0.0f; up to
+   m = 64 it is one chain over items 0, 1, ..., m - 1; a longer one is 64 lane chains, lane l over items l, l + 64, ..., then
+   v = v + v[lane ^ s] for s = 32, 16, 8, 4, 2, 1, and lane 0 is the row. A vertex adds, from +0.0f, the three entries of its corners
+   in rank order: corner c is entries 3 (c % 3) ... + 2 of row c // 3.
 """
 import numpy as np
 
@@ -116,13 +122,14 @@ def chain(m):
     return np.where(m <= 64, m, -(-m // 64) + 6)
 
 
-def gradients(P, V, F, I, C, g):
+def gradients(P, V, F, I, C, g, t=None):
     """dict: gP (n, 3) fp32; gV (nV, 3) fp64, the exact sum of the fp32 terms; abs (nV, 3) the sum of their magnitudes; depth (nV,) the
-    device's fp32 chain: the longest row chain among the vertex's faces plus the number of its corners"""
+    device's fp32 chain: the longest row chain among the vertex's faces plus the number of its corners. t: terms(P, V, F, I, C, g) of a
+    caller that has them already"""
     F = np.asarray(F, dtype=np.int64)
     I = np.asarray(I, dtype=np.int64)
     nV, nF = np.asarray(V).shape[0], F.shape[0]
-    tP, tV = terms(P, V, F, I, C, g)
+    tP, tV = terms(P, V, F, I, C, g) if t is None else t
     tV = tV.astype(np.float32).astype(np.float64)
     gV, ab = np.zeros((nV, 3)), np.zeros((nV, 3))
     for k in range(3):
@@ -133,3 +140,70 @@ def gradients(P, V, F, I, C, g):
     np.maximum.at(longest, F.reshape(-1), np.repeat(per_face, 3))
     corners = np.bincount(F.reshape(-1), minlength=nV)
     return {"gP": tP.astype(np.float32), "gV": gV, "abs": ab, "depth": longest + corners}
+
+
+def point_terms(P, C, g):
+    """rule 2 to the points alone, (n, 3) fp32: it needs no face, so a point whose I is outside [0, F) has its term too"""
+    return ((2.0 * np.asarray(g, dtype=np.float64))[:, None] * (_f64(P) - np.asarray(C, dtype=np.float64))).astype(np.float32)
+
+
+BUTTERFLY = (32, 16, 8, 4, 2, 1)
+
+
+def keys(I, nF):
+    """rule 3: the face of a point, or nF for an I outside [0, nF)"""
+    I = np.asarray(I, dtype=np.int64)
+    return np.where((I < 0) | (I >= nF), nF, I)
+
+
+def face_rows(t, key, nF, butterfly=BUTTERFLY):
+    """rule 3 up to the rows: t (n, 9) fp32, the terms of every point; key (n,) in [0, nF] -> (nF, 9) fp32. Vectorised over the faces,
+    looping over the position in the chain"""
+    t, key = np.asarray(t, dtype=np.float32), np.asarray(key, dtype=np.int64)
+    order = np.argsort(key, kind="stable")
+    order = order[key[order] < nF]
+    m = np.bincount(key[order], minlength=nF)
+    seg = np.r_[0, np.cumsum(m)]
+    t = t[order]
+    rows = np.zeros((nF, 9), dtype=np.float32)
+    short = m <= 64
+    for j in range(int(m[short].max(initial=0))):
+        a = np.nonzero(short & (m > j))[0]
+        rows[a] += t[seg[a] + j]
+    lng = np.nonzero(~short)[0]
+    if lng.size:
+        lanes = np.arange(64)
+        acc = np.zeros((lng.size, 64, 9), dtype=np.float32)
+        for r in range(-(-int(m[lng].max()) // 64)):
+            item = 64 * r + lanes
+            a, l = np.nonzero(item[None, :] < m[lng][:, None])
+            acc[a, l] += t[seg[lng[a]] + item[l]]
+        for s in butterfly:
+            acc = acc + acc[:, lanes ^ s]
+        rows[lng] = acc[:, 0]
+    return rows
+
+
+def vertex_sums(rows, vptr, corner_order):
+    """rule 3 from the rows on: (nV, 3) fp32, vectorised over the vertices, looping over the rank"""
+    vptr, corner_order = np.asarray(vptr, dtype=np.int64), np.asarray(corner_order, dtype=np.int64)
+    of_corner = rows.reshape(-1, 3)                  # corner c: entries 3 (c % 3) ... + 2 of row c // 3
+    cnt = np.diff(vptr)
+    gV = np.zeros((cnt.size, 3), dtype=np.float32)
+    for j in range(int(cnt.max(initial=0))):
+        a = np.nonzero(cnt > j)[0]
+        gV[a] += of_corner[corner_order[vptr[a] + j]]
+    return gV
+
+
+def ordered_gradients(P, V, F, I, C, g, vptr, corner_order, butterfly=BUTTERFLY, t=None):
+    """(nV, 3) fp32: the gradient to V with the bits of the device (rule 3). vptr (nV + 1,) and corner_order (3 nF,) are the corner
+    ranking: the corners of vertex v are corner_order[vptr[v] : vptr[v + 1]]. `butterfly` is there for the test that a different order
+    of the lane sums changes bits. t: the terms(...) of the points whose I is in [0, F), in their order, of a caller that has them"""
+    F = np.asarray(F, dtype=np.int64)
+    key = keys(I, F.shape[0])
+    ok = key < F.shape[0]
+    if t is None:
+        t = terms(np.asarray(P)[ok], V, F, key[ok], np.asarray(C)[ok], np.asarray(g)[ok])
+    tV = t[1].astype(np.float32).reshape(-1, 9)
+    return vertex_sums(face_rows(tV, key[ok], F.shape[0], butterfly), vptr, corner_order)
