@@ -775,6 +775,27 @@ int ls_range_antialias_backward(const float* color, int C, const float* rast, co
                                 float* grad_color, float* grad_pos, void* ws, size_t ws_bytes, int device, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Depth peeling of the rasterizer (largesteps/render.py: DepthPeeler; csrc/raster.hip): the layer behind a
+ * previous one, in both modes. prev_rast (B, H, W, 4): the rast of the previous layer, as ls_raster_forward / ls_range_forward or an
+ * earlier peel wrote it for the same pos, tri (ranges), H and W; it is only read, and must not be rast. The depth pass resolves a pixel
+ * by the smallest key (order bits of fp32 z/w) << 32 | face, and rast keeps exactly that z/w and face + 1: the peel admits a covering
+ * fragment only if its key is STRICTLY GREATER than the key of prev_rast at its pixel, and nothing where prev_rast is background or
+ * holds an id that is not one of the image's. The law:
+ *   layer l of a pixel (layer 0 = ls_raster_forward / ls_range_forward) is the l-th of the pixel's covering fragments in ascending
+ *   (order bits of z/w, face) order, bit for bit as the forward pass would write that fragment; all zeros once they are used up.
+ * Exact depth ties peel in face order; there is no epsilon. rast has the layout of the forward pass, so every other entry point
+ * (pixel order, the backwards, interpolation, antialiasing) takes a layer as it takes a frame. Sizes, limits, error codes and the
+ * workspace are those of ls_raster_forward (ls_raster_workspace_bytes) and ls_range_forward (ls_range_workspace_bytes); LS_E_INVALID
+ * also when prev_rast is NULL or equals rast. Neither allocates or synchronises, neither uses float atomics. ASYNC.
+ *   ls_peel_forward                 rast = the layer behind prev_rast, instanced mode.
+ *   ls_peel_range_forward           the same in range mode (global ids, the slice law layer by layer).
+ * --------------------------------------------------------------------------------------------- */
+int ls_peel_forward(const float* pos, int64_t B, int64_t V, const int32_t* tri, int64_t F, int H, int W, const float* prev_rast,
+                    float* rast, void* ws, size_t ws_bytes, int device, void* stream);
+int ls_peel_range_forward(const float* pos, int64_t V, const int32_t* tri, int64_t F, const int32_t* ranges, int64_t B, int64_t N, int H,
+                          int W, const float* prev_rast, float* rast, void* ws, size_t ws_bytes, int device, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Differentiable 2D texture lookup (largesteps/render.py: texture; the rules are stated in csrc/texture.hip and DESIGN.md section 2.7,
  * restated in numpy by tests/texture_statement.py). tex (Bt, Ht, Wt, C) fp32 with Bt 1 (shared by every image) or B, 1 <= Ht, Wt <= 8192,
  * 1 <= C <= 32; uv (B, H, W, 2) fp32, 8-byte aligned; out (B, H, W, C). filter: LS_TEXTURE_NEAREST / _LINEAR; boundary: LS_TEXTURE_WRAP /

@@ -31,9 +31,16 @@
 // pair (b, f), f in range b, numbered item_ptr[b] + f - start_b, N = sum count_b of them: the depth pass, the tile scan, the pixel-order
 // keys, seg, the face rows and the edge adjacency (per image: the neighbour across an edge WITHIN the slice) are all indexed by item.
 // Both modes run the same device functions and kernels, through a mapping (MapInst, MapRange) from keys to (image, face, pos batch).
+//
+// Depth peeling (ls_peel_*): the depth pass with a floor per pixel. The previous layer's rast holds, bit for bit, the z/w and the id its
+// pixel won with, i.e. its depth key; a covering fragment enters the minimum only if its key is STRICTLY GREATER than that key, and
+// nothing enters where the previous layer is background (or holds an id foreign to the image): background stays background. The law:
+// layer l of a pixel is the l-th of its covering fragments in ascending key order, (order bits of z/w, face id) -- exact depth ties
+// peel in face order, no epsilon. The peeling kernels are the two depth kernels instantiated with Peel<Map>; resolve is shared.
 #include "common.h"
 #include "groupby.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace ls {
 
@@ -180,6 +187,21 @@ struct MapRange {      // range mode: image b draws faces [start_b, start_b + co
     __device__ __forceinline__ int adj_face(int64_t b, int opp) const { return rt[3 * b] + (opp - rt[3 * b + 2]); }      // entries are items
 };
 
+// Depth peeling: a mode's map together with the previous layer, given to the two depth kernels in place of the map itself. floor_key:
+// the key that the previous layer's pixel won with (key_of maps -0 and +0 to one key and rast keeps z/w bit for bit), ~0 -- above every key --
+// where that pixel is background for image b; it reads the (z/w, id) half of the pixel's rast row. The kernels submit a fragment only
+// above the floor of its pixel; with a plain map the `if constexpr` is discarded and their source is what it was.
+template <class Map>
+struct Peel : Map {
+    const float* __restrict__ prev;
+    __device__ __forceinline__ u64 floor_key(int64_t pix, int64_t b, int64_t F) const {
+        const int id = this->id(prev, pix, b, F);
+        return id ? rs_key(prev[pix * 4 + 2], id - 1) : ~0ull;
+    }
+};
+template <class Map> struct is_peel { static constexpr bool value = false; };
+template <class Map> struct is_peel<Peel<Map>> { static constexpr bool value = true; };
+
 // one thread per key (b, f): small triangles rasterized here, large ones only counted in tiles
 template <class Map>
 __global__ __launch_bounds__(256) void k_rs_small(Map map, const float* __restrict__ pos, const int* __restrict__ tri, int64_t nk, int64_t V,
@@ -200,7 +222,11 @@ __global__ __launch_bounds__(256) void k_rs_small(Map map, const float* __restri
                 for (int x = x0; x <= x1; ++x) {
                     double E[3];
                     float zf;
-                    if (rs_cover(t, rs_centre(x, W), py, E, zf)) atomicMin(&img[(size_t)y * W + x], rs_key(zf, (int)f));
+                    if (rs_cover(t, rs_centre(x, W), py, E, zf)) {
+                        if constexpr (is_peel<Map>::value)
+                            if (!(rs_key(zf, (int)f) > map.floor_key((b * H + y) * W + x, b, F))) continue;
+                        atomicMin(&img[(size_t)y * W + x], rs_key(zf, (int)f));
+                    }
                 }
             }
         }
@@ -230,8 +256,11 @@ __global__ __launch_bounds__(256) void k_rs_large(Map map, const float* __restri
         if (x > x1 || y > y1) continue;
         double E[3];
         float zf;
-        if (rs_cover(t, rs_centre(x, W), rs_centre(y, H), E, zf))
+        if (rs_cover(t, rs_centre(x, W), rs_centre(y, H), E, zf)) {
+            if constexpr (is_peel<Map>::value)
+                if (!(rs_key(zf, (int)f) > map.floor_key((b * H + y) * W + x, b, F))) continue;
             atomicMin(&depth[((size_t)b * H + y) * W + x], rs_key(zf, (int)f));
+        }
     }
 }
 
@@ -756,13 +785,17 @@ void rs_gather_attr(const Range& m, const float* rows, const int32_t* vptr, cons
                            grad_attr);
 }
 
-template <class Map>
-int rs_forward(const Mode<Map>& m, const char* who, bool ok, const float* pos, const int32_t* tri, int H, int W, float* rast, void* ws, size_t ws_bytes,
-               int device, void* stream) {
+// PEEL: the layer behind `prev` (the rast of the layer before, of the same mode and sizes): the depth kernels get Peel<Map>; otherwise
+// prev is not looked at
+template <bool PEEL, class Map>
+int rs_forward(const Mode<Map>& m, const char* who, bool ok, const float* pos, const int32_t* tri, int H, int W, const float* prev, float* rast,
+               void* ws, size_t ws_bytes, int device, void* stream) {
     int rc = rs_check(m, H, W, who);
     if (rc) return rc;
     const RsWs L = rs_layout_keys(m.B * H * W, m.nk, 0);
     LS_REQUIRE(ok, LS_E_INVALID, "%s: null argument", who);
+    LS_REQUIRE(!PEEL || prev != rast, LS_E_INVALID, "%s: prev_rast and rast are the same buffer (the layer before is read while this one is written)",
+               who);
     LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, L.total);
     DeviceGuard g(device);
     LS_HIP(g.err);
@@ -774,10 +807,15 @@ int rs_forward(const Mode<Map>& m, const char* who, bool ok, const float* pos, c
     const int64_t N = m.B * H * W, nk = m.nk;
     LS_HIP(hipMemsetAsync(depth, 0xff, 8 * (size_t)N, st));
     if (nk > 0) {
-        hipLaunchKernelGGL(k_rs_small<Map>, dim3(div_up(nk, 256)), dim3(256), 0, st, m.map, pos, tri, nk, m.V, m.F, H, W, depth, tiles);
+        const auto dmap = [&] {
+            if constexpr (PEEL) return Peel<Map>{m.map, prev};
+            else return m.map;
+        }();
+        using DepthMap = std::remove_const_t<decltype(dmap)>;
+        hipLaunchKernelGGL(k_rs_small<DepthMap>, dim3(div_up(nk, 256)), dim3(256), 0, st, dmap, pos, tri, nk, m.V, m.F, H, W, depth, tiles);
         rc = exclusive_scan(tiles, nk, toff, (int*)(w + L.bsum), st);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_rs_large<Map>, dim3(RS_LARGE_GRID), dim3(256), 0, st, m.map, pos, tri, nk, m.V, m.F, H, W, (const int*)toff, depth);
+        hipLaunchKernelGGL(k_rs_large<DepthMap>, dim3(RS_LARGE_GRID), dim3(256), 0, st, dmap, pos, tri, nk, m.V, m.F, H, W, (const int*)toff, depth);
     }
     hipLaunchKernelGGL(k_rs_resolve<Map>, dim3(div_up(N, 256)), dim3(256), 0, st, m.map, pos, tri, (int)m.B, m.V, m.F, H, W, (const u64*)depth,
                        rast);
@@ -912,8 +950,8 @@ extern "C" int ls_raster_workspace_bytes(int64_t B, int64_t F, int H, int W, int
 
 extern "C" int ls_raster_forward(const float* pos, int64_t B, int64_t V, const int32_t* tri, int64_t F, int H, int W, float* rast, void* ws,
                                  size_t ws_bytes, int device, void* stream) {
-    return rs_forward(inst(B, V, F), "ls_raster_forward", rast && ws && (pos || V == 0) && (tri || F == 0), pos, tri, H, W, rast, ws, ws_bytes,
-                      device, stream);
+    return rs_forward<false>(inst(B, V, F), "ls_raster_forward", rast && ws && (pos || V == 0) && (tri || F == 0), pos, tri, H, W, nullptr, rast,
+                             ws, ws_bytes, device, stream);
 }
 
 extern "C" int ls_raster_pixel_order(const float* rast, int64_t B, int64_t F, int H, int W, int32_t* order, int32_t* seg, void* ws,
@@ -1014,8 +1052,8 @@ extern "C" int ls_range_workspace_bytes(int64_t B, int64_t N, int H, int W, int 
 
 extern "C" int ls_range_forward(const float* pos, int64_t V, const int32_t* tri, int64_t F, const int32_t* ranges, int64_t B, int64_t N, int H,
                                 int W, float* rast, void* ws, size_t ws_bytes, int device, void* stream) {
-    return rs_forward(range(ranges, B, N, V, F), "ls_range_forward", rast && ws && ranges && ((pos && tri) || N == 0), pos, tri, H, W, rast, ws,
-                      ws_bytes, device, stream);
+    return rs_forward<false>(range(ranges, B, N, V, F), "ls_range_forward", rast && ws && ranges && ((pos && tri) || N == 0), pos, tri, H, W,
+                             nullptr, rast, ws, ws_bytes, device, stream);
 }
 
 extern "C" int ls_range_pixel_order(const float* rast, const int32_t* ranges, int64_t B, int64_t N, int64_t F, int H, int W, int32_t* order,
@@ -1082,4 +1120,17 @@ extern "C" int ls_range_antialias_backward(const float* color, int C, const floa
     const bool ok = C >= 1 && color && rast && grad_out && ranges && ((pos && tri && adj) || N == 0);
     return rs_antialias_backward(range(ranges, B, N, V, F), "ls_range_antialias_backward", ok, color, C, rast, pos, tri, adj, H, W, grad_out, boost,
                                  order, seg, vptr, corner_order, grad_color, grad_pos, ws, ws_bytes, device, stream);
+}
+
+// ---- depth peeling: the layer behind prev_rast, both modes (the workspaces are ls_raster_workspace_bytes / ls_range_workspace_bytes) --------
+extern "C" int ls_peel_forward(const float* pos, int64_t B, int64_t V, const int32_t* tri, int64_t F, int H, int W, const float* prev_rast,
+                               float* rast, void* ws, size_t ws_bytes, int device, void* stream) {
+    const bool ok = prev_rast && rast && ws && (pos || V == 0) && (tri || F == 0);
+    return rs_forward<true>(inst(B, V, F), "ls_peel_forward", ok, pos, tri, H, W, prev_rast, rast, ws, ws_bytes, device, stream);
+}
+
+extern "C" int ls_peel_range_forward(const float* pos, int64_t V, const int32_t* tri, int64_t F, const int32_t* ranges, int64_t B, int64_t N,
+                                     int H, int W, const float* prev_rast, float* rast, void* ws, size_t ws_bytes, int device, void* stream) {
+    const bool ok = prev_rast && rast && ws && ranges && ((pos && tri) || N == 0);
+    return rs_forward<true>(range(ranges, B, N, V, F), "ls_peel_range_forward", ok, pos, tri, H, W, prev_rast, rast, ws, ws_bytes, device, stream);
 }

@@ -210,6 +210,9 @@ _SIGNATURES = {
     "ls_range_antialias_backward": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_int, c_int,
                                             c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_size_t, c_int, c_void_p]),
+    "ls_peel_forward": (c_int, [c_void_p, c_i64, c_i64, c_void_p, c_i64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "ls_peel_range_forward": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                      c_int, c_void_p]),
     "ls_texture_workspace_bytes": (c_int, [c_i64, c_int, c_int, ctypes.POINTER(c_size_t)]),
     "ls_texture_forward": (c_int, [c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "ls_texture_order": (c_int, [c_void_p, c_i64, c_int, c_int, c_i64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_int,

@@ -8,6 +8,8 @@ tests/render_statement.py):
     rast, rast_db = rasterize(ctx, pos, tri, resolution)       pos (B, V, 4) clip space, tri (F, 3) int32 / int64, resolution (H, W)
     rast, rast_db = rasterize(ctx, pos, tri, resolution, ranges=R)     range mode: pos (V, 4), R (B, 2) int32 CPU rows (start, count);
                                                                image b draws tri[start_b : start_b + count_b] (the slice law, below)
+    with DepthPeeler(ctx, pos, tri, resolution) as peeler:     depth peeling, both modes (ranges=R): each call of
+        rast, rast_db = peeler.rasterize_next_layer()          rasterize_next_layer() gives the surfaces behind the layer before (below)
     out, _ = interpolate(attr, rast, tri)                      attr (V, C), (1, V, C) or (B, V, C)
     color_aa = antialias(color, rast, pos, tri, pos_gradient_boost=1.0)
     texture(tex, uv, filter_mode='linear', boundary_mode='wrap')    tex (1 or B, Ht, Wt, C), uv (B, H, W, 2); nearest / linear, wrap / clamp /
@@ -34,6 +36,15 @@ from image 0's. Ranges may overlap, be unsorted, be empty (an all-zero image) or
 own faces (a closed surface cut by a range has a boundary along the cut). The rast of a range-mode call carries its range table:
 `interpolate` and `antialias` must be given that very tensor.
 
+Depth peeling (`DepthPeeler`, nvdiffrast's class) shows what lies behind the nearest surface: nested shells, the far side of a closed
+mesh, translucent targets, a thickness loss. Layer 0 is `rasterize` itself (the same native call, the same bits); layer l + 1 keeps, per
+pixel, the nearest covering fragment strictly behind the one layer l shows, in the order the depth pass resolves a pixel by: (z/w as
+fp32, face id). So layer l is the l-th covering fragment of the pixel in that order -- exact depth ties peel in face order, there is no
+epsilon -- and a pixel that ran out of fragments is background from then on. Every layer is a rast like any other (it carries its
+frame): `interpolate`, `antialias` and the pixel differentials take it unchanged, and the gradient of its u and v flows to pos through
+the backward of `rasterize`; which fragment a layer shows is a discrete choice and carries no gradient. The slice law holds layer by
+layer.
+
 Above the kernels the two modes share one code path: `_Rasterize`, `_Interpolate` and `_Antialias` convert, allocate and save once, and ask
 the frame that the rast carries (`rast._largesteps_frame`) for what a mode supplies -- the number of keys and images, the workspace size,
 the shape rules of pos and tri, the edge adjacency and the native calls (`_InstancedFrame` knows F, `_RangeFrame` its range table). The
@@ -49,7 +60,7 @@ from torch.autograd import Function
 from . import _native
 from .normals import _plan as _corner_plan
 
-__all__ = ["RasterizeContext", "RasterizeGLContext", "RasterizeCudaContext", "rasterize", "interpolate", "antialias", "texture",
+__all__ = ["RasterizeContext", "RasterizeGLContext", "RasterizeCudaContext", "rasterize", "DepthPeeler", "interpolate", "antialias", "texture",
            "texture_construct_mip", "pixel_differentials", "persp_proj", "SphericalHarmonics", "NVDRenderer"]
 
 
@@ -188,7 +199,8 @@ class _Frame:
     """What the rast of `rasterize` carries (`rast._largesteps_frame`), instanced or range mode. It owns the pixels of the frame sorted by
     key ((image, face), or item) -- the order every backward sums in, made at most once per version of the rast by the first backward that
     needs it -- and, in its two implementations, what a mode supplies: the number of keys and of images, the workspace, the shape rules
-    of pos and tri, the edge adjacency and the native calls. F: the faces of tri; tab: the `_RangeTable`, None when instanced."""
+    of pos and tri, the edge adjacency and the native calls (`rasterize`, and `rasterize_layer` behind a previous layer: depth peeling).
+    F: the faces of tri; tab: the `_RangeTable`, None when instanced. fresh(): another frame of the same mode, for another rast."""
     __slots__ = ("F", "tab", "version", "order", "seg")
 
     def __init__(self, F, tab=None):
@@ -214,6 +226,9 @@ class _InstancedFrame(_Frame):
     faces = staticmethod(_faces)
     adjacency = staticmethod(_adjacent)
 
+    def fresh(self):
+        return _InstancedFrame(self.F)
+
     def keys(self, B):
         return B * self.F
 
@@ -232,6 +247,10 @@ class _InstancedFrame(_Frame):
     def rasterize(self, p, narrow, B, H, W, rast, ws, dev):
         _native.check(_native.lib().ls_raster_forward(_native.ptr(p), B, p.shape[1], _native.ptr(narrow), narrow.shape[0], H, W, _native.ptr(rast),
                                                       _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
+
+    def rasterize_layer(self, p, narrow, B, H, W, prev, rast, ws, dev):
+        _native.check(_native.lib().ls_peel_forward(_native.ptr(p), B, p.shape[1], _native.ptr(narrow), narrow.shape[0], H, W, _native.ptr(prev),
+                                                    _native.ptr(rast), _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
 
     def rasterize_backward(self, p, narrow, B, H, W, g, order, seg, vptr, corner_order, gp, ws, dev):
         _native.check(_native.lib().ls_raster_backward(_native.ptr(p), B, p.shape[1], _native.ptr(narrow), narrow.shape[0], H, W, _native.ptr(g),
@@ -262,11 +281,14 @@ class _InstancedFrame(_Frame):
 
 
 class _RangeFrame(_Frame):
-    """B images of the N items of a range table: one shared pos (V, 4), keys = items. Made by `rasterize` only."""
+    """B images of the N items of a range table: one shared pos (V, 4), keys = items. Made by `rasterize` and `DepthPeeler` only."""
     __slots__ = ()
 
     def __init__(self, tab):
         super().__init__(tab.F, tab)
+
+    def fresh(self):
+        return _RangeFrame(self.tab)
 
     def keys(self, B):
         return self.tab.N
@@ -300,6 +322,12 @@ class _RangeFrame(_Frame):
         tab = self.tab
         _native.check(_native.lib().ls_range_forward(_native.ptr(p), p.shape[0], _native.ptr(narrow), tab.F, _native.ptr(tab.dev), B, tab.N, H, W,
                                                      _native.ptr(rast), _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
+
+    def rasterize_layer(self, p, narrow, B, H, W, prev, rast, ws, dev):
+        tab = self.tab
+        _native.check(_native.lib().ls_peel_range_forward(_native.ptr(p), p.shape[0], _native.ptr(narrow), tab.F, _native.ptr(tab.dev), B, tab.N, H,
+                                                          W, _native.ptr(prev), _native.ptr(rast), _native.ptr(ws), ws.numel(), dev.index,
+                                                          _native.stream_of(dev)))
 
     def rasterize_backward(self, p, narrow, B, H, W, g, order, seg, vptr, corner_order, gp, ws, dev):
         tab = self.tab
@@ -354,14 +382,17 @@ def _instanced_frame(rast, tri):
 
 class _Rasterize(Function):
     @staticmethod
-    def forward(ctx, pos, tri, H, W, frame):
+    def forward(ctx, pos, tri, H, W, frame, prev=None):
         p = frame.pos(pos)
         f, narrow, vptr, order = frame.faces(tri, p.shape[-2])
         B, dev = frame.images(p), p.device
         rast = torch.empty((B, H, W, 4), dtype=torch.float32, device=dev)
         ws = frame.workspace(B, H, W, 0, dev)
         with torch.cuda.device(dev):
-            frame.rasterize(p, narrow, B, H, W, rast, ws, dev)
+            if prev is None:
+                frame.rasterize(p, narrow, B, H, W, rast, ws, dev)
+            else:                         # depth peeling: the layer behind `prev`, the peeler's own copy of the layer before
+                frame.rasterize_layer(p, narrow, B, H, W, prev, rast, ws, dev)
         rast_db = torch.zeros((B, H, W, 4), dtype=torch.float32, device=dev)
         ctx.mark_non_differentiable(rast_db)
         ctx.set_materialize_grads(False)
@@ -372,7 +403,7 @@ class _Rasterize(Function):
     @staticmethod
     def backward(ctx, g_rast, g_db):
         if g_rast is None or not ctx.needs_input_grad[0]:
-            return None, None, None, None, None
+            return None, None, None, None, None, None
         p, narrow, vptr, corner_order, rast = ctx.saved_tensors
         (B, H, W, _), dev, frame = rast.shape, p.device, ctx.frame
         g = g_rast.to(torch.float32).contiguous()
@@ -381,7 +412,7 @@ class _Rasterize(Function):
         gp = torch.empty_like(p)
         with torch.cuda.device(dev):
             frame.rasterize_backward(p, narrow, B, H, W, g, order, seg, vptr, corner_order, gp, ws, dev)
-        return gp, None, None, None, None
+        return gp, None, None, None, None, None
 
 
 def _range_frame_for(pos, tri, H, W, resolution, ranges):
@@ -411,6 +442,24 @@ def _range_frame_for(pos, tri, H, W, resolution, ranges):
     return _RangeFrame(tab)
 
 
+def _frame_for(pos, tri, H, W, resolution, ranges):
+    """the frame of a `rasterize` call or of a `DepthPeeler`, after the checks that come before the Function's own"""
+    if ranges is not None:
+        return _range_frame_for(pos, tri, H, W, resolution, ranges)
+    if not (1 <= H <= 4096 and 1 <= W <= 4096):
+        raise ValueError(f"resolution must be (H, W) with each in [1, 4096], got {tuple(resolution)}")
+    return _InstancedFrame(tri.shape[0] if isinstance(tri, torch.Tensor) and tri.dim() == 2 else 0)
+
+
+def _rasterize(pos, tri, H, W, frame, prev=None):
+    """one frame through `_Rasterize`: the nearest surface, or (depth peeling) the one behind `prev`; the rast leaves with its frame"""
+    rast, rast_db = _Rasterize.apply(pos, tri, H, W, frame, prev)
+    rast._largesteps_frame = frame
+    if frame.tab is None:
+        rast_db._largesteps_db = _DbSource(pos, tri, rast_db._version)
+    return rast, rast_db
+
+
 @_native.retry_on_oom
 def rasterize(glctx, pos, tri, resolution, ranges=None, grad_db=True):
     """
@@ -436,17 +485,59 @@ def rasterize(glctx, pos, tri, resolution, ranges=None, grad_db=True):
     covering triangle wins (ties: the lower id). The gradient of rast[..., 0:2] flows to pos; the gradient of the z/w channel is dropped.
     """
     H, W = (int(resolution[0]), int(resolution[1]))
-    if ranges is not None:
-        frame = _range_frame_for(pos, tri, H, W, resolution, ranges)
-    else:
-        if not (1 <= H <= 4096 and 1 <= W <= 4096):
-            raise ValueError(f"resolution must be (H, W) with each in [1, 4096], got {tuple(resolution)}")
-        frame = _InstancedFrame(tri.shape[0] if isinstance(tri, torch.Tensor) and tri.dim() == 2 else 0)
-    rast, rast_db = _Rasterize.apply(pos, tri, H, W, frame)
-    rast._largesteps_frame = frame
-    if ranges is None:
-        rast_db._largesteps_db = _DbSource(pos, tri, rast_db._version)
-    return rast, rast_db
+    return _rasterize(pos, tri, H, W, _frame_for(pos, tri, H, W, resolution, ranges))
+
+
+class DepthPeeler:
+    """
+    Depth peeling (nvdiffrast.torch.DepthPeeler, instanced and range mode): the surfaces behind the nearest one, a layer per call.
+
+        with DepthPeeler(glctx, pos, tri, resolution) as peeler:
+            for _ in range(layers):
+                rast, rast_db = peeler.rasterize_next_layer()
+
+    The arguments are those of `rasterize`, checked as `rasterize` checks them (range mode: pos (V, 4) and ranges). Layer 0 is what
+    `rasterize` returns, bit for bit. Layer l + 1 holds, per pixel, the nearest covering fragment strictly behind the one in layer l, in
+    the order the depth pass resolves a pixel by -- (z/w as fp32, face id) -- so layer l is the pixel's l-th covering fragment in that
+    order: fragments at exactly the same depth peel one by one in face order, and nothing is skipped or repeated by an epsilon. A pixel
+    whose fragments are used up is background (all zeros) in every later layer, and so is a whole layer past the deepest one.
+
+    Each layer is computed from the peeler's own detached copy of the one before: editing a returned rast does not change later layers.
+    Every returned rast carries its frame, so `interpolate`, `antialias` and (instanced mode) `rast_db` with diff_attrs take it as they
+    take the rast of `rasterize`, and the gradient of rast[..., :2] of any layer flows to pos through the backward of `rasterize`;
+    which fragment a layer shows is a discrete choice without a gradient. In range mode the slice law holds for every layer. pos must
+    not be changed in place between layers (ValueError). No call synchronises with the host: a peeling render can be captured.
+    """
+
+    def __init__(self, glctx, pos, tri, resolution, ranges=None, grad_db=True):
+        H, W = (int(resolution[0]), int(resolution[1]))
+        frame = _frame_for(pos, tri, H, W, resolution, ranges)
+        frame.faces(tri, frame.pos(pos).shape[-2])          # what `_Rasterize` checks, here rather than at the first layer
+        self._args = (pos, tri, H, W)
+        self._frame, self._pos_version, self._prev = frame, pos._version, None
+        self._active = False                                # True inside the `with` block
+
+    def __enter__(self):
+        if self._args is None:
+            raise RuntimeError("largesteps.render.DepthPeeler: a peeler is used in one `with` block only")
+        self._active = True
+        return self
+
+    def __exit__(self, *exc):
+        self._active, self._args, self._frame, self._prev = False, None, None, None
+        return False
+
+    @_native.retry_on_oom
+    def rasterize_next_layer(self):
+        """(rast, rast_db) of the next layer, as `rasterize` returns them: first the nearest surface, then what lies behind it"""
+        if not self._active:
+            raise RuntimeError("largesteps.render.DepthPeeler.rasterize_next_layer: call it inside the peeler's `with` block")
+        pos, tri, H, W = self._args
+        if pos._version != self._pos_version:
+            raise ValueError("pos was changed in place after the DepthPeeler was made: the next layer would not lie behind the last one")
+        rast, rast_db = _rasterize(pos, tri, H, W, self._frame.fresh(), self._prev)
+        self._prev = rast.detach().clone()
+        return rast, rast_db
 
 
 class _DbSource:
