@@ -1465,6 +1465,8 @@ extern "C" int ls_direct_create(const ls_direct_arrays* A, int device, void* str
     LS_REQUIRE(A->h_nodes && A->h_perm && A->h_push_ptr && V > 0 && levels >= 1 && levels <= 30 && n_bnd >= 0 && n_front >= V &&
                (arity == 2 || arity == 4 || arity == 8), LS_E_INVALID, "ls_direct_create: bad argument");
     LS_REQUIRE(V < INT32_MAX && n_bnd < INT32_MAX && n_front * arity < INT32_MAX, LS_E_OVERFLOW, "ls_direct_create: plan exceeds int32 offsets");
+    // the tier's gathers address xb (n_bnd x k floats, k <= 4) with 32-bit byte offsets (nd_tier.h, pull_request)
+    LS_REQUIRE(n_bnd * (int64_t)(4 * sizeof(float)) <= (int64_t)UINT32_MAX, LS_E_OVERFLOW, "ls_direct_create: boundary vectors exceed 4 GB");
     *out = nullptr;
     CreatePlan T{levels, arity};
     T.level_off.resize((size_t)levels + 1);

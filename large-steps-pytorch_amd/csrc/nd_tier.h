@@ -143,33 +143,64 @@ __device__ __forceinline__ float bcast_lane(float v, int c) {
 // upd[(bnd_off + i) * K], in the array the down sweep later uses for x_bnd) and the parent gathers per front position through
 // a static pull list -- the slot scheme of the upper levels (arity x K floats per position, 12-byte pieces written by
 // different workgroup phases) moved ~80 MB of partial cache lines per sweep at 1M vertices.
+//
+// How the gather is written matters more than what it reads. `if (idx >= 0) v += xb[idx]` per child compiles to one predicated block
+// per child -- load, wait for EVERY load in flight, add -- and a block runs when any lane of the wave has that child: arity serial
+// round trips, and the first wait also drains whatever matrix batches were prefetched (tools/tier_isa_report.py counts them). So the
+// rows are REQUESTED unconditionally, all children back to back, an absent child from row 0 of xb (always a valid address; its value
+// is never used), and SUMMED by a select in child order: `has ? v + r : v` -- never `v + 0`, never a multiplication by a mask (row 0
+// may hold anything, and -0.0 + 0.0 changes a bit). The order and the operands of every sum are those of the per-child form.
+template <int K, int N>
+__device__ __forceinline__ void pull_request(const TierArgs& a, const int (&pl)[N], float (&r)[N][K]) {
+    // a 32-bit BYTE offset against the scalar base of xb (one register per address instead of a pair; ls_direct_create requires the
+    // array to stay below 4 GB)
+    const char* base = reinterpret_cast<const char*>(a.xb);
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+        const float* p = reinterpret_cast<const float*>(base + (unsigned)max(pl[c], 0) * (unsigned)(K * sizeof(float)));
+#pragma unroll
+        for (int q = 0; q < K; ++q) r[c][q] = p[q];
+    }
+}
+template <int K, int N>
+__device__ __forceinline__ void pull_sum(const int (&pl)[N], const float (&r)[N][K], float (&v)[K]) {
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+#pragma unroll
+        for (int q = 0; q < K; ++q) v[q] = pl[c] >= 0 ? v[q] + r[c][q] : v[q];
+    }
+}
+
+// Without indices in registers: the A indices of a front position are contiguous -- ONE round trip for all of them, a second one for
+// the rows (two instead of up to 2 A). Eight rows of K >= 3 columns in flight do not fit the kernel's 128 registers next to its two
+// matrix batches: arity 8 requests its rows in two halves of four (the eight indices still come together).
+template <int K, int A>
+__device__ __forceinline__ void pull_compact_n(const TierArgs& a, size_t f, float (&v)[K]) {
+    constexpr int G = A * K <= 16 ? A : 4;           // rows in flight together
+    int pl[A];
+#pragma unroll
+    for (int c = 0; c < A; ++c) pl[c] = a.pull[f * A + c];
+#pragma unroll
+    for (int c0 = 0; c0 < A; c0 += G) {
+        int pg[G];
+        float r[G][K];
+#pragma unroll
+        for (int c = 0; c < G; ++c) pg[c] = pl[c0 + c];
+        pull_request<K, G>(a, pg, r);
+        pull_sum<K, G>(pg, r, v);
+    }
+}
 template <int K>
 __device__ __forceinline__ void pull_compact(const TierArgs& a, size_t f, float (&v)[K]) {
 #pragma unroll
     for (int q = 0; q < K; ++q) v[q] = 0.0f;
-    const int* pl = a.pull + f * a.arity;
-    for (int c = 0; c < a.arity; ++c) {
-        const int idx = pl[c];
-        if (idx >= 0) {
-#pragma unroll
-            for (int q = 0; q < K; ++q) v[q] += a.xb[(size_t)idx * K + q];
-        }
-    }
+    if (a.arity == 4) pull_compact_n<K, 4>(a, f, v);                 // (ls_direct_create accepts the arities 2, 4 and 8)
+    else if (a.arity == 8) pull_compact_n<K, 8>(a, f, v);
+    else pull_compact_n<K, 2>(a, f, v);
 }
 
-// the same with the (static) pull indices already in registers: what is left behind a barrier is ONE round trip
-template <int K>
-__device__ __forceinline__ void pull_values(const TierArgs& a, const int (&pl)[4], float (&v)[K]) {
-#pragma unroll
-    for (int q = 0; q < K; ++q) v[q] = 0.0f;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        if (pl[c] >= 0) {
-#pragma unroll
-            for (int q = 0; q < K; ++q) v[q] += a.xb[(size_t)pl[c] * K + q];
-        }
-    }
-}
+// With the (static) pull indices already in registers (pull_indices, requested before the barrier) pull_request + pull_sum leave ONE
+// round trip behind the barrier: node_up requests the boundary row's children, the own row's children and the row of braw together.
 __device__ __forceinline__ void pull_indices(const TierArgs& a, size_t f, bool on, int (&pl)[4]) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) pl[c] = on ? a.pull[f * 4 + c] : -1;
@@ -349,6 +380,9 @@ __device__ __forceinline__ void sparse_row(const TierArgs& a, const LeafIdx& ix,
             for (int q = 0; q < K; ++q) u[q] = fmaf(e[t].val, vec4[e[t].idx * 4 + q], u[q]);
         }
     }
+    // the tail is one round trip per entry, and left so: the 1M plane has no such row in the up sweep and 4511 own rows (in 4304 of its
+    // 16384 leaves) in the down sweep, the closed 1M sphere 44 / 1454 rows, none longer than 6 (counted with the host planner); two
+    // entries per turn, requested together, were measured on the plane: down-sweep leaf phase 24.9 -> 25.2 us by the stamps -- not kept
     for (int p = ix.p0 + TIER_SPE; p < ix.p1; ++p) {
         const SpEnt z = a.sp_ent[p];
 #pragma unroll
@@ -386,7 +420,9 @@ __device__ __forceinline__ void leaf_up_compute(const TierArgs& a, const TierIte
 #pragma unroll
             for (int q = 0; q < K; ++q) out[dst + q] = u[q];
         }
-        for (int i = lane + 64; i < b; i += 64) {          // leaves with more than 64 boundary rows: no prefetch
+        // leaves with more than 64 boundary rows: no prefetch, one round trip per entry. Left so: the 1M plane has no such leaf, the
+        // closed 1M sphere ONE of 16384 -- nothing the benchmark's meshes could show
+        for (int i = lane + 64; i < b; i += 64) {
             const int p0 = a.sp_ptr[n.spb_off + i], p1 = a.sp_ptr[n.spb_off + i + 1], pp = a.ppos[n.bnd_off + i];
             float u[K];
 #pragma unroll
@@ -602,7 +638,8 @@ __device__ __forceinline__ void node_up_pre(const TierArgs& a, const TierItem& i
     // the boundary rows' hand-over (needed by the item that finishes the row chunk): its static indices too -- round 6's stamps show
     // dense phases of 8-quad items whose whole stream is in flight before the barrier; two dependent round trips behind it were
     // the phase, not something the stream hid
-    // (k = 4 columns: the four index registers across the barrier would be the kernel's 129th-130th VGPR -- it keeps the two-trip form)
+    // (k = 4 columns: the four index registers across the barrier would be the kernel's 129th-130th VGPR -- its boundary row goes
+    //  through pull_compact behind the barrier: indices, then rows; see node_up)
     if (K <= 3) pull_indices(a, (size_t)(it.front_off + it.s + i), inner && fin, P.plb);
 }
 
@@ -615,15 +652,34 @@ __device__ __forceinline__ void node_up(const TierArgs& a, const TierItem& it, D
     const bool row = i < b;
     float* sv4 = region;
     const float4* __restrict__ col = reinterpret_cast<const float4*>(a.u4 + it.w_off) + (row ? i : 0);
+    const bool fin = it.part == 0 && row && it.pfront_off >= 0;        // this item adds the children's hand-over (and, unsplit, stores)
+    const bool inner = !(it.flags & NODE_LEAF);
+    const bool pre4 = a.arity == 4 && inner;        // wave-uniform: the pull indices of P are this item's
+    // What waits for the previous phase, requested TOGETHER: the children's rows for this lane's boundary row (-> pass) and own row
+    // (-> u0), and the own row's right-hand side -- nine loads back to back behind the matrix batch B, ONE wait. (Absent children, and
+    // lanes without a row, read row 0: P.plo / P.plb are -1 there. B is requested first: its loads are predicated, and behind the
+    // rows the compiler puts them behind the rows' WAIT as well -- B's round trip would follow the rows' instead of sharing it.)
+    // k = 4 keeps a shorter form, THREE trips: the boundary row's four indices were not kept across the barrier (node_up_pre) and eight
+    // rows of four columns in flight do not fit the 128 registers (tried: 12 bytes of scratch). The boundary row goes through
+    // pull_compact (indices, then rows), then the own row's children and right-hand side together.
     float4 B[TIER_Q];                               // second batch of the matrix stream: in flight while the vector is assembled
     tier_prefetch<NT>(col, (size_t)b, (it.r0 >> 2) + TIER_Q, it.r1 >> 2, B);
-    float pass[K];
+    const int j0 = it.r0 + lane;
+    const bool own0 = pre4 && j0 < it.r1 && j0 < it.s;
+    float pass[K], u0[K], v0[K];
 #pragma unroll
-    for (int q = 0; q < K; ++q) pass[q] = 0.0f;
-    const bool fin = it.part == 0 && row && it.pfront_off >= 0;        // this item adds the children's hand-over (and, unsplit, stores)
-    const bool pre4 = a.arity == 4;
-    if (fin && !(it.flags & NODE_LEAF)) {
-        if (pre4 && K <= 3) pull_values<K>(a, P.plb, pass); else pull_compact<K>(a, (size_t)(it.front_off + it.s + i), pass);
+    for (int q = 0; q < K; ++q) pass[q] = u0[q] = v0[q] = 0.0f;
+    if (pre4) {
+        float rb[4][K], ro[4][K];
+        if (K <= 3) pull_request<K, 4>(a, P.plb, rb);
+        else if (fin) pull_compact_n<K, 4>(a, (size_t)(it.front_off + it.s + i), pass);
+        pull_request<K, 4>(a, P.plo, ro);
+#pragma unroll
+        for (int q = 0; q < K; ++q) v0[q] = a.braw[(size_t)(own0 ? it.own_start + j0 : 0) * K + q];
+        if (K <= 3) pull_sum<K, 4>(P.plb, rb, pass);
+        pull_sum<K, 4>(P.plo, ro, u0);
+    } else if (fin && inner) {
+        pull_compact<K>(a, (size_t)(it.front_off + it.s + i), pass);
     }
     for (int j = it.r0 + lane; j < it.r1; j += 64) {
         float v[K];
@@ -636,13 +692,15 @@ __device__ __forceinline__ void node_up(const TierArgs& a, const TierItem& it, D
             const size_t g = (size_t)a.perm[it.own_start + j];
 #pragma unroll
             for (int q = 0; q < K; ++q) v[q] = b_in[g * K + q];
-        } else {
+        } else if (pre4 && j == j0) {                 // requested at the item's entry
+#pragma unroll
+            for (int q = 0; q < K; ++q) v[q] = v0[q] - u0[q];
+        } else {                                      // a second 64-entry chunk of the range, or a tree of another arity
+            const size_t f = (size_t)(it.front_off + j);
 #pragma unroll
             for (int q = 0; q < K; ++q) v[q] = a.braw[(size_t)(it.own_start + j) * K + q];        // gathered at kernel start
-        }
-        if (!(it.flags & NODE_LEAF)) {
             float u[K];
-            if (pre4 && j == it.r0 + lane) pull_values<K>(a, P.plo, u); else pull_compact<K>(a, (size_t)(it.front_off + j), u);
+            pull_compact<K>(a, f, u);
 #pragma unroll
             for (int q = 0; q < K; ++q) v[q] -= u[q];
         }
@@ -804,8 +862,11 @@ __device__ __forceinline__ void node_down(const TierArgs& a, const TierItem& it,
 }
 
 // One workgroup per subtree. UP: phases run leaves -> tier root. DOWN: tier root -> leaves.
+// Register budget: 128 VGPRs, no scratch, for every instantiation (tools/tier_isa_report.py prints them) -- 16 waves per CU in each
+// shape: one 16-wave workgroup, two 8-wave ones (80 KB of LDS each) or four 4-wave ones. The second launch bound is waves per SIMD: 4
+// for the 4- and the 8-wave shape (an 8-wave kernel allowed 2 would take up to 256 registers and run ONE workgroup per CU).
 template <int K, bool UP, int W, bool NT>
-__global__ __launch_bounds__(64 * W, 16 / W) void k_nd_tier(TierArgs a, const float* __restrict__ b_in, float* __restrict__ x_out,
+__global__ __launch_bounds__(64 * W, W >= 16 ? 1 : 4) void k_nd_tier(TierArgs a, const float* __restrict__ b_in, float* __restrict__ x_out,
                                                               int tri_floats) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -832,6 +893,8 @@ __global__ __launch_bounds__(64 * W, 16 / W) void k_nd_tier(TierArgs a, const fl
     if (UP) {
         // right-hand side of the tier's inner-node rows, gathered once into the tree's numbering (braw): the dense items
         // read it from a static address instead of walking perm -> b behind a barrier
+        // (each row is the chain perm -> b -> store; running a thread's rows together -- all perm loads, then all b loads -- was measured:
+        //  header + gather done 2.44 -> 2.63 us by the stamps on the 1M plane, a thread has one or two rows -- not kept)
         const int n_dense = rl(hdr, 18);
         for (int r = threadIdx.x; r < n_dense; r += blockDim.x) {
             // the dense rows of a subtree are one range per level; ranges are listed as (start, count) pairs
