@@ -69,7 +69,9 @@ __global__ __launch_bounds__(BLOCK) void k_gather_corners(const int* __restrict_
     // the loads); the sum runs over them in rank order as before
     constexpr int GC = 8;
     float c[GC][3];
-    const int last = max(e1 - 1, e0);            // e1 == e0 (unreferenced vertex): a valid address, the value is not used
+    // e1 == e0 (unreferenced vertex): slot 0, which every corner buffer has (max(F, 1) x 3 slots); the value is not used. Not e0: the
+    // unreferenced vertices after the last referenced one have e0 == 3 F, one slot past the buffer
+    const int last = max(e1 - 1, 0);
 #pragma unroll
     for (int t = 0; t < GC; ++t) {
         const size_t e = (size_t)min(e0 + t, last);
