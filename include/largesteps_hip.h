@@ -35,6 +35,7 @@
  *                        and its autograd gradient
  *   ls_texture_*         nvdiffrast.torch.texture as scripts/render.py calls it (the backgrounds), with gradients to tex and uv
  *   ls_mip_*             the mipmap filter modes of nvdiffrast.torch.texture and the pixel differentials that choose their level
+ *   ls_cube_*            the cube-map mode of nvdiffrast.torch.texture (boundary_mode='cube'), with gradients to tex and the direction
  *   ls_mesh_distance_*   igl.point_mesh_squared_distance / igl.hausdorff (figures/comparison/generate_data.py: the error column)
  */
 #ifndef LARGESTEPS_HIP_H
@@ -870,6 +871,35 @@ int ls_mip_backward(const float* tex, const float* pyr, int64_t Bt, int Ht, int 
                     const float* bias, int64_t B, int H, int W, int mode, int boundary, const float* grad_out, const int32_t* order,
                     const int32_t* seg, float* grad_tex, float* grad_pyr, float* grad_uv, float* grad_lod, float* grad_uv_da, int device,
                     void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Differentiable cube-map lookup (largesteps/render.py: texture with boundary_mode='cube'; the rules are stated in csrc/cube.hip and
+ * DESIGN.md section 2.7, restated in numpy by tests/cube_statement.py). tex (Bt, 6, n, n, C) fp32 with Bt 1 (shared by every image) or B,
+ * faces in the order +x, -x, +y, -y, +z, -z, 1 <= n <= 8192, 1 <= C <= 32; uv (B, H, W, 3) fp32: a direction that need not be
+ * normalised; out (B, H, W, C). filter: LS_TEXTURE_NEAREST / _LINEAR. Linear taps that leave the face read the neighbouring face, a
+ * tap beyond a corner is dropped and its weight shared by the other three. A direction with a non-finite component or with all
+ * components zero gives output 0 and no gradient; every texel index is clamped into its range before an address is formed.
+ * LS_E_INVALID for bad sizes, modes or null pointers, LS_E_OVERFLOW when 4 B H W or 6 Bt n^2 + 1 does not fit int32. No entry point
+ * allocates or synchronises, none uses float atomics: outputs and gradients are bitwise reproducible. ASYNC.
+ *   ls_cube_workspace_bytes      workspace of ls_cube_order for B H W pixels (16-byte aligned).
+ *   ls_cube_forward              out.
+ *   ls_cube_order                order (4 B H W for LS_TEXTURE_LINEAR: item 4 pixel + 2 dy + dx; B H W for LS_TEXTURE_NEAREST) = the
+ *                                (pixel, tap) items sorted stably by their destination texel ((bt 6 + f) n + j) n + i, dropped taps and
+ *                                pixels without a gradient last; seg (6 Bt n^2 + 1) = the first sorted position of each key: the order
+ *                                grad_tex sums in. Depends on uv, the texture's SHAPE and the filter only.
+ *   ls_cube_backward             grad_tex (Bt, 6, n, n, C) (summed over the images when Bt = 1) and grad_uv (B, H, W, 3) (zero for
+ *                                LS_TEXTURE_NEAREST; the face choice is held fixed); either may be NULL, both are overwritten. order /
+ *                                seg: what ls_cube_order returned for the same uv, shapes and filter (needed for grad_tex only; the
+ *                                kernels index pixels through them without a range check).
+ * --------------------------------------------------------------------------------------------- */
+int ls_cube_workspace_bytes(int64_t B, int H, int W, size_t* bytes);
+int ls_cube_forward(const float* tex, int64_t Bt, int n, int C, const float* uv, int64_t B, int H, int W, int filter, float* out,
+                    int device, void* stream);
+int ls_cube_order(const float* uv, int64_t B, int H, int W, int64_t Bt, int n, int filter, int32_t* order, int32_t* seg, void* ws,
+                  size_t ws_bytes, int device, void* stream);
+int ls_cube_backward(const float* tex, int64_t Bt, int n, int C, const float* uv, int64_t B, int H, int W, int filter,
+                     const float* grad_out, const int32_t* order, const int32_t* seg, float* grad_tex, float* grad_uv, int device,
+                     void* stream);
 
 #ifdef __cplusplus
 }

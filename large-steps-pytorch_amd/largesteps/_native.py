@@ -231,6 +231,11 @@ _SIGNATURES = {
                              c_void_p, c_size_t, c_int, c_void_p]),
     "ls_mip_backward": (c_int, [c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int,
                                 c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "ls_cube_workspace_bytes": (c_int, [c_i64, c_int, c_int, ctypes.POINTER(c_size_t)]),
+    "ls_cube_forward": (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "ls_cube_order": (c_int, [c_void_p, c_i64, c_int, c_int, c_i64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "ls_cube_backward": (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_int, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -18,6 +18,9 @@ tests/render_statement.py):
     texture(tex, uv, uv_da, filter_mode='linear-mipmap-linear')     the mipmapped lookup (csrc/mip.hip, restated by tests/mip_statement.py);
                                                                texture_construct_mip(tex) builds a reusable pyramid, pixel_differentials(rast,
                                                                pos, tri) the differentials of the barycentrics themselves
+    texture(cube, dirs, boundary_mode='cube')                  the cube-map lookup: cube (1 or B, 6, n, n, C), dirs (B, H, W, 3) directions;
+                                                               nearest / linear, seamless across edges and corners (csrc/cube.hip, restated
+                                                               by tests/cube_statement.py)
 
 plus the renderer built on them: `persp_proj`, `SphericalHarmonics`, `NVDRenderer` (same constructor keys, same values as the
 reference's). Conventions: rast = (u, v, z/w, id + 1), 0 for background; an attribute interpolates as u a0 + v a1 + (1 - u - v) a2;
@@ -947,7 +950,8 @@ def texture_construct_mip(tex, max_mip_level=None, cube_mode=False):
     itself -- `texture` sends the gradient of every level back to tex on its own.
     """
     if cube_mode:
-        raise NotImplementedError("largesteps.render.texture_construct_mip: cube_mode=True (cube maps) is not supported")
+        raise NotImplementedError("largesteps.render.texture_construct_mip: cube_mode=True (mipmapped cube maps) is not supported; "
+                                  "texture(..., boundary_mode='cube') looks a cube map up without mipmaps")
     _check_tex(tex)
     Lmax = _mip_last_level(tex.shape[1], tex.shape[2], max_mip_level)
     if not tex.is_cuda:
@@ -1096,6 +1100,121 @@ def _texture_mip(tex, uv, uv_da, mip_level_bias, mip, mode, bnd, max_mip_level):
     return out
 
 
+class _CubeOrder:
+    """The (pixel, tap) items of one cube-map lookup sorted by their destination texel -- the order the gradient of the cube sums in
+    (four items per pixel for 'linear', one for 'nearest'). It depends on the directions, the cube's shape and the filter, not on the
+    texels' values: cached on the uv tensor exactly as `_TexelOrder` is."""
+    __slots__ = ("key", "order", "seg")
+
+    def __init__(self, key):
+        self.key, self.order, self.seg = key, None, None
+
+    def get(self, u, Bt, n, filt):
+        if self.order is None:
+            B, H, W, _ = u.shape
+            dev = u.device
+            ws = _scratch(dev, _native.lib().ls_cube_workspace_bytes, B, H, W)
+            order = torch.empty((4 if filt == 1 else 1) * B * H * W, dtype=torch.int32, device=dev)
+            seg = torch.empty(6 * Bt * n * n + 1, dtype=torch.int32, device=dev)
+            with torch.cuda.device(dev):
+                _native.check(_native.lib().ls_cube_order(_native.ptr(u), B, H, W, Bt, n, filt, _native.ptr(order), _native.ptr(seg),
+                                                          _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
+            self.order, self.seg = order, seg
+        return self.order, self.seg
+
+
+def _cube_order_slot(uv, Bt, n, filt):
+    if torch.cuda.is_current_stream_capturing():            # as for _TexelOrder: a replay sorts what it finds
+        return _CubeOrder(None)
+    key = (uv._version, uv.data_ptr(), tuple(uv.shape), tuple(uv.stride()), Bt, n, filt)
+    slot = getattr(uv, "_largesteps_cube_order", None)
+    if slot is not None and slot.key == key:
+        return slot
+    return _CubeOrder(key)
+
+
+class _TextureCube(Function):
+    @staticmethod
+    def forward(ctx, tex, uv, filt, slot):
+        t, u = _plain(tex, 16), _plain(uv, 4)
+        Bt, _, n, _, C = t.shape
+        B, H, W, _ = u.shape
+        dev = u.device
+        out = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().ls_cube_forward(_native.ptr(t), Bt, n, C, _native.ptr(u), B, H, W, filt, _native.ptr(out), dev.index,
+                                                        _native.stream_of(dev)))
+        ctx.save_for_backward(t, u)
+        ctx.filt = filt
+        ctx.slot = slot
+        ctx.shapes = (tuple(tex.shape), tuple(uv.shape))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        need_tex, need_uv = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_tex or need_uv):
+            return None, None, None, None
+        t, u = ctx.saved_tensors
+        filt = ctx.filt
+        Bt, _, n, _, C = t.shape
+        B, H, W, _ = u.shape
+        dev = u.device
+        g = _aligned(g.to(torch.float32).contiguous())
+        gt = torch.empty_like(t) if need_tex else None
+        gu = torch.empty_like(u) if need_uv else None
+        order = seg = None
+        if need_tex:
+            order, seg = ctx.slot.get(u, Bt, n, filt)
+        with torch.cuda.device(dev):
+            _native.check(_native.lib().ls_cube_backward(_native.ptr(t), Bt, n, C, _native.ptr(u), B, H, W, filt, _native.ptr(g),
+                                                         _native.ptr(order), _native.ptr(seg), _native.ptr(gt), _native.ptr(gu), dev.index,
+                                                         _native.stream_of(dev)))
+        return (gt.view(ctx.shapes[0]) if need_tex else None), (gu.view(ctx.shapes[1]) if need_uv else None), None, None
+
+
+def _texture_cube(tex, uv, filter_mode):
+    """texture(..., boundary_mode='cube'): the checks in the order the docstring of `texture` gives, then the native lookup"""
+    if any(isinstance(t, torch.Tensor) and not t.is_cuda for t in (tex, uv)):
+        raise NotImplementedError("largesteps.render.texture: boundary_mode='cube' (cube maps) needs a HIP device")
+    if filter_mode in _MIP_FILTER_MODES:
+        raise NotImplementedError(f"largesteps.render.texture: filter_mode={filter_mode!r} with boundary_mode='cube' (mipmapped cube maps) "
+                                  "is not supported; use 'linear' or 'nearest'")
+    if filter_mode not in _FILTER_MODES:
+        raise ValueError(f"filter_mode must be one of {sorted(_FILTER_MODES)}, got {filter_mode!r}")
+    for t, what in ((tex, "tex"), (uv, "uv")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what} must be a torch.Tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{what} must be float32, got {t.dtype}")
+    if tex.dim() != 5 or tex.shape[1] != 6 or tex.shape[2] != tex.shape[3]:
+        raise ValueError(f"a cube map must be (1 or B, 6, n, n, C) with square faces, got {tuple(tex.shape)}")
+    if uv.dim() != 4 or uv.shape[3] != 3:
+        raise ValueError(f"uv must be (B, H, W, 3) directions for boundary_mode='cube', got {tuple(uv.shape)}")
+    Bt, _, n, _, C = tex.shape
+    B, H, W, _ = uv.shape
+    if Bt not in (1, B):
+        raise ValueError(f"tex has {Bt} batches for {B} images")
+    if not 1 <= n <= TEXTURE_MAX_SIZE:
+        raise ValueError(f"a cube face must be between 1 and {TEXTURE_MAX_SIZE} texels a side, got {n}")
+    if not 1 <= C <= TEXTURE_MAX_CHANNELS:
+        raise ValueError(f"the texture must have between 1 and {TEXTURE_MAX_CHANNELS} channels, got {C}")
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError(f"uv must not be empty, got {tuple(uv.shape)}")
+    if 4 * B * H * W >= 2 ** 31 - 1:
+        raise OverflowError(f"uv has {B * H * W} pixels: the cube lookup indexes four items per pixel with int32")
+    if 6 * Bt * n * n >= 2 ** 31 - 2:
+        raise OverflowError(f"the cube maps have {6 * Bt * n * n} texels: the kernels index them with int32")
+    if tex.device != uv.device:
+        raise ValueError(f"tex is on {tex.device}, uv on {uv.device}")
+    filt = _FILTER_MODES[filter_mode]
+    slot = _cube_order_slot(uv, Bt, n, filt)
+    out = _TextureCube.apply(tex, uv, filt, slot)
+    if slot.key is not None:
+        uv._largesteps_cube_order = slot
+    return out
+
+
 def _texture_cpu(tex, uv):
     """the lookup in plain torch, linear + wrap, forward only: what a CPU tensor gets (the device kernel keeps this operation order)"""
     with torch.no_grad():
@@ -1124,8 +1243,22 @@ def texture(tex, uv, uv_da=None, mip_level_bias=None, mip=None, filter_mode='lin
 
     filter_mode : 'linear' (bilinear), 'nearest', 'auto' (= 'linear'), 'linear-mipmap-linear' (trilinear), 'linear-mipmap-nearest'.
     boundary_mode : 'wrap', 'clamp' or 'zero', applied to each tap index: modulo the size; clamped to [0, size - 1]; a tap outside
-                    reads 0 and receives no gradient. 'cube' raises NotImplementedError.
+                    reads 0 and receives no gradient. 'cube': a cube-map lookup by direction (below).
     uv_da, mip_level_bias, mip, max_mip_level : the mipmap modes' inputs (below); accepted and ignored by the other modes.
+
+    Cube maps (boundary_mode='cube', HIP device only; csrc/cube.hip, restated by tests/cube_statement.py). tex (1 or B, 6, n, n, C), faces
+    in the order +x, -x, +y, -y, +z, -z (OpenGL's), uv (B, H, W, 3): a direction d = (x, y, z) that need not be normalised.
+    filter_mode 'nearest', 'linear' or 'auto'; a mipmap filter mode raises NotImplementedError (mipmapped cube maps are not supported).
+    The major axis is x if |x| >= |y| and |x| >= |z|, else y if |y| >= |z|, else z; its sign picks the face, and with (sc, tc, ma) =
+    (-z, -y, x) (z, -y, x) (x, z, y) (x, -z, y) (x, -y, z) (-x, -y, z) for the six faces s = (sc / |ma| + 1) / 2, t = (tc / |ma| + 1) / 2
+    are the face coordinates, looked up as a 2D texture of n x n texels: a pixel whose four taps lie inside the face is bit for bit
+    texture(tex[:, f], (s, t), 'linear', 'clamp'). A linear tap one texel outside the face reads the texel of the neighbouring face
+    that contains the centre of that outside texel (filtering is seamless across the 12 edges); a tap outside in both directions (at
+    one of the 8 corners) has no texel, and its weight is shared evenly by the other three. A direction with a non-finite component, or
+    (0, 0, 0), gives 0 and no gradient. Gradients flow to tex and (linear) to uv -- with the face choice held fixed, perpendicular to d
+    -- without float atomics; the item order is cached per uv tensor and version. Checks, in this order: tensors that are not on a HIP
+    device raise NotImplementedError; types and dtypes (TypeError); tex (1 or B, 6, n, n, C) with square faces and uv (B, H, W, 3)
+    (ValueError); the batch, size and channel limits (ValueError) and 4 B H W, 6 Bt n^2 < 2^31 (OverflowError).
 
     Mipmap modes (HIP device only). uv_da (B, H, W, 4) = (du/dX, du/dY, dv/dX, dv/dY) in texture units per pixel (the second output of
     `interpolate(uv_attr, rast, tri, rast_db, diff_attrs='all')`), mip_level_bias (B, H, W); one may be None, not both. mip: a pyramid
@@ -1151,7 +1284,7 @@ def texture(tex, uv, uv_da=None, mip_level_bias=None, mip=None, filter_mode='lin
     if mipmapped and not (isinstance(uv, torch.Tensor) and uv.is_cuda and isinstance(tex, torch.Tensor) and tex.is_cuda):
         raise NotImplementedError(f"largesteps.render.texture: filter_mode={filter_mode!r} (mipmaps) needs a HIP device")
     if boundary_mode == 'cube':
-        raise NotImplementedError("largesteps.render.texture: boundary_mode='cube' (cube maps) is not supported")
+        return _texture_cube(tex, uv, filter_mode)
     if filter_mode not in _FILTER_MODES and not mipmapped:
         raise ValueError(f"filter_mode must be one of {sorted(_FILTER_MODES)}, got {filter_mode!r}")
     if boundary_mode not in _BOUNDARY_MODES:
