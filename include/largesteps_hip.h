@@ -676,6 +676,38 @@ int ls_mesh_distance_backward(void* handle, const float* P, int64_t n, const int
 int ls_mesh_distance_update(void* handle, const float* verts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Area-weighted points on a mesh surface and their gradient to the vertices (largesteps/sampling.py, and distance.chamfer_distance
+ * built on it). The rule is stated in csrc/sample.hip and DESIGN.md section 2.9, restated in numpy by tests/sample_statement.py, and
+ * the device answers with the same bits: fp64 areas from the fp32 corners quantised to 32 bits against the largest one, a 64-bit
+ * integer prefix sum, Philox4x32-10 keyed by `seed` with the counter (sample index, stream_id, 0), and square-root barycentric weights.
+ * A face without a finite positive area, or naming a vertex outside [0, V), is never drawn (no index is followed before it is checked).
+ * verts (V, 3) fp32, faces (F, 3) int32 / int64 (idx_bytes 4 / 8). LS_E_INVALID for a null pointer, a negative size or another
+ * idx_bytes; LS_E_OVERFLOW when n (within a workgroup of it), 3 F or offset + n reaches 2^31; LS_E_WORKSPACE for a workspace below
+ * ls_sample_workspace_bytes(F, n). No entry point allocates or synchronises, none uses float atomics: bitwise reproducible. ASYNC.
+ *   ls_sample_workspace_bytes   the workspace of either call below for F faces and n samples (256-byte aligned regions).
+ *   ls_sample_surface           P (n, 3) fp32 the points, I (n) int64 their faces, W (n, 3) fp32 their barycentric weights, for the
+ *                               samples offset .. offset + n - 1: the slice law -- samples [o, o + m) of any call are, bit for bit,
+ *                               what the call with offset = o, n = m returns. When no face can be drawn (F = 0 included): P = NaN,
+ *                               I = -1, W = 0, without an error.
+ *   ls_sample_surface_backward  gV (V, 3) fp32, overwritten: gV[v] = sum_i W[i][k] gP[i] over the samples whose face I[i] has v at
+ *                               corner k, from I and W as ls_sample_surface returned them (held fixed) and gP (n, 3) fp32. vptr (V + 1)
+ *                               and corner_order (3 F) are the ranking of ls_corner_ranks over the same faces (corner_order: rank ->
+ *                               corner, the inverse of its cpos), which carries the connectivity: `faces` itself is not read, and
+ *                               the kernels index through the ranking without a range check. Samples of a face are added in
+ *                               ascending i and a vertex's corners in rank order, in fp64, rounded to fp32 once. A sample whose I is
+ *                               outside [0, F) adds nothing.
+ * The 64-bit scan works in tiles of LS_SAMPLE_SCAN_TILE faces.
+ * --------------------------------------------------------------------------------------------- */
+#define LS_SAMPLE_SCAN_TILE 2048
+int ls_sample_workspace_bytes(int64_t F, int64_t n, size_t* bytes);
+int ls_sample_surface(const float* verts, const void* faces, int idx_bytes, int64_t F, int64_t V, int64_t n, uint64_t seed,
+                      uint32_t stream_id, uint64_t offset, float* P, int64_t* I, float* W, void* ws, size_t ws_bytes, int device,
+                      void* stream);
+int ls_sample_surface_backward(const void* faces, int idx_bytes, int64_t F, int64_t V, int64_t n, const int64_t* I, const float* W,
+                               const float* gP, const int32_t* vptr, const int32_t* corner_order, float* gV, void* ws, size_t ws_bytes,
+                               int device, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * AdamUniform step (optimize.py:18-41) on n contiguous fp32 elements, two kernels, no host sync:
  *   g1 = b1 g1 + (1-b1) g ; g2 = b2 g2 + (1-b2) g^2 ; p -= lr * (g1/(1-b1^t)) / (1e-8 + max sqrt(g2/(1-b2^t)))
  * scratch: at least 4096 bytes of device memory owned by the caller. ASYNC.

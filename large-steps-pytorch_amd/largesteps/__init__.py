@@ -10,6 +10,7 @@ largesteps/ 0.2.2). Same modules, symbols and call forms as the reference:
     from largesteps.normals import compute_face_normals, compute_vertex_normals     (reference: scripts/geometry.py)
     import largesteps.render as dr       (nvdiffrast.torch's rasterize / interpolate / antialias; NVDRenderer: scripts/render.py)
     from largesteps.distance import hausdorff, point_mesh_squared_distance   (igl's: the figures' error column)
+    from largesteps.sampling import sample_surface; from largesteps.distance import chamfer_distance   (mesh-to-mesh measures)
 
 Device work is done by hand-written HIP kernels for gfx950 in lib/liblargesteps_hip.so (C ABI in
 include/largesteps_hip.h); there is no CPU or stock-PyTorch fallback.

@@ -292,6 +292,54 @@ def point_mesh_squared_distance(P, V, F):
 
 
 @_native.retry_on_oom
+def chamfer_distance(VA, FA, VB, FB, n, seed=0):
+    """mean_a d^2(a, B) + mean_b d^2(b, A) over n area-weighted surface samples a of mesh A (largesteps.sampling.sample_surface with
+    `seed`, stream 0) and n samples b of mesh B (stream 1): a mesh-to-mesh measure that does not depend on where the vertices lie. A
+    0-dim float64 tensor on the meshes' device for tensor input, a float for numpy; NaN when a mesh has no face of positive area.
+    Bitwise reproducible.
+
+    With tensor input it is differentiable in VA and VB, each through both paths: through its own samples (their gradient to the
+    corners of the drawn faces) and through the faces closest to the other mesh's samples (module docstring). The face choice of the
+    sampler carries no gradient.
+
+    It builds two MeshDistance handles and releases them, so like point_mesh_squared_distance it synchronises and is not capturable;
+    a differentiable result keeps the handles until its graph is freed. In a loop keep the handles instead:
+
+        a, b = MeshDistance(VA, FA), MeshDistance(VB, FB)            # once
+        for it in range(steps):
+            a.update(VA)                                            # the mesh that moves
+            PA, _, _ = sample_surface(VA, FA, n, seed=it, stream=0)
+            PB, _, _ = sample_surface(VB, FB, n, seed=it, stream=1)
+            loss = b.squared_distance(PA)[0].mean() + a.squared_distance(PB)[0].mean()
+    """
+    from .sampling import _uint, sample_surface
+    if _uint(n, "n", 63) < 1:
+        raise ValueError("chamfer_distance: n must be at least 1")
+    _uint(seed, "seed", 64)
+    for name, X in (("VA", VA), ("FA", FA), ("VB", VB), ("FB", FB)):        # the type, dtype and shape checks, before any device work
+        (_as_faces(X) if name[0] == "F" else _as_points(X, name))
+    a = MeshDistance(VA, FA)
+    b = out = None
+    try:
+        b = MeshDistance(VB, FB)
+        if a.device != b.device:
+            raise RuntimeError(f"the meshes must be on one device: got {a.device} and {b.device}")
+        with torch.cuda.device(a.device):
+            # numpy positions: the handles' device copies, so that either kind of input takes one path to one value
+            PA, _, _ = sample_surface(VA if isinstance(VA, torch.Tensor) else a.V, a._f, n, seed=seed, stream=0)
+            PB, _, _ = sample_surface(VB if isinstance(VB, torch.Tensor) else b.V, b._f, n, seed=seed, stream=1)
+            out = b.squared_distance(PA)[0].mean() + a.squared_distance(PB)[0].mean()
+        if not (isinstance(VA, torch.Tensor) or isinstance(VB, torch.Tensor)):
+            out = float(out)
+        return out
+    finally:
+        if not (isinstance(out, torch.Tensor) and out.requires_grad):
+            a.close()
+            if b is not None:
+                b.close()
+
+
+@_native.retry_on_oom
 def hausdorff(VA, FA, VB, FB):
     """libigl's hausdorff(VA, FA, VB, FB): sqrt(max(max_a d^2(a, B), max_b d^2(b, A))) over every row of VA and VB as query points, a
     Python float. As in libigl this is vertex-to-surface (its documented known issue): a surface point that is not a vertex is not
