@@ -37,6 +37,7 @@
  *   ls_mip_*             the mipmap filter modes of nvdiffrast.torch.texture and the pixel differentials that choose their level
  *   ls_cube_*            the cube-map mode of nvdiffrast.torch.texture (boundary_mode='cube'), with gradients to tex and the direction
  *   ls_mesh_distance_*   igl.point_mesh_squared_distance / igl.hausdorff (figures/comparison/generate_data.py: the error column)
+ *   ls_mesh_ray_*        igl.ray_mesh_intersect, and what igl.ambient_occlusion is built from: rays against the mesh of a distance handle
  */
 #ifndef LARGESTEPS_HIP_H
 #define LARGESTEPS_HIP_H
@@ -674,6 +675,39 @@ int ls_mesh_distance_backward(void* handle, const float* P, int64_t n, const int
                               const int32_t* vptr, const int32_t* corner_order, float* gP, float* gV, void* ws, size_t ws_bytes,
                               void* stream);
 int ls_mesh_distance_update(void* handle, const float* verts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Rays against the mesh of a mesh-distance handle (libigl's ray_mesh_intersect, and what ambient_occlusion is built from;
+ * largesteps/raycast.py). The same handle answers distances and rays; ls_mesh_distance_update moves both. The rule is stated in
+ * csrc/raycast.hip and DESIGN.md section 2.10, restated in numpy by tests/ray_statement.py, and the device answers with the same bits:
+ * Woop, Benthin and Wald's watertight test in fp64 from the fp32 inputs; a hit needs tmin <= t <= tmax (both ends inclusive); the
+ * closest hit is the accepted face of smallest t, the lowest id on equal t; edges and vertices count as hits, a zero-area face is never
+ * hit, a direction with a non-finite component or all zero hits nothing. O, D (n, 3) fp32 origins and directions (D need not be unit:
+ * t is in units of |D|); trange (n, 2) fp64 (tmin, tmax) per ray, or NULL for [0, +inf].
+ *   ls_mesh_ray_closest   t (n) fp64, I (n) int64, W (n, 3) fp64 the barycentric weights of the hit on the corners of face I. A miss
+ *                         is t = +inf, I = -1, W = 0. Any of the three may be NULL.
+ *   ls_mesh_ray_any       hit (n) one byte per ray: 1 iff some face is accepted, which is I >= 0 of ls_mesh_ray_closest.
+ * The gradient of t (first order, the face held fixed; no gradient of W or I). With n = (b - a) x (c - a) of the hit face and
+ * q = n / (n . d): dt/do = -q, dt/dd = -t q, dt/dV[F[I, k]] = W[k] q, every term multiplied by the incoming gradient g in fp64 and rounded
+ * to fp32 once; a ray whose I is outside [0, F) adds nothing and gets zeros. The vertex gradient is summed as the distance's is: rays of
+ * a face in ascending id, a vertex's corners in the rank order of ls_corner_ranks, without float atomics: bitwise reproducible.
+ *   ls_mesh_ray_backward_workspace_bytes  the workspace of ls_mesh_ray_backward for n rays and F faces.
+ *   ls_mesh_ray_backward  O, D as the query took them, I, W, t as it returned them, g (n) fp64 the gradient of t; vptr (V + 1) and
+ *                         corner_order (3 F) as for ls_mesh_distance_backward. gO, gD (n, 3) fp32 and gV (V, 3) fp32 may each be NULL;
+ *                         W, vptr, corner_order and the workspace are needed for gV only.
+ * LS_E_INVALID for a null required pointer or n < 0, LS_E_OVERFLOW at 2^31 rays, LS_E_WORKSPACE for a workspace below
+ * ls_mesh_ray_backward_workspace_bytes(n, F); n = 0 is a no-op (gV is zeroed). No call allocates or synchronises: all ASYNC on `stream`.
+ * Queries and gradients on different streams may overlap each other and the distance queries of the same handle (they only read it);
+ * none may overlap ls_mesh_distance_update or ls_mesh_distance_destroy of that handle, and two calls that share a workspace must be
+ * ordered.
+ * --------------------------------------------------------------------------------------------- */
+int ls_mesh_ray_closest(void* handle, const float* O, const float* D, int64_t n, const double* trange, double* t, int64_t* I, double* W,
+                        void* stream);
+int ls_mesh_ray_any(void* handle, const float* O, const float* D, int64_t n, const double* trange, unsigned char* hit, void* stream);
+int ls_mesh_ray_backward_workspace_bytes(int64_t n, int64_t F, size_t* bytes);
+int ls_mesh_ray_backward(void* handle, const float* O, const float* D, int64_t n, const int64_t* I, const double* W, const double* t,
+                         const double* g, const int32_t* vptr, const int32_t* corner_order, float* gO, float* gD, float* gV, void* ws,
+                         size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Area-weighted points on a mesh surface and their gradient to the vertices (largesteps/sampling.py, and distance.chamfer_distance

@@ -1,7 +1,8 @@
 // distance.hip -- point-to-mesh squared distance and its directed maximum on the device (gfx950, wave64): libigl's
 // point_mesh_squared_distance / hausdorff, which the reference's figures call on every recorded step.
 //
-// The mesh (fp32 positions, int32 faces) is held by a handle with the LBVH of lbvh.h over its faces (leaf boxes exact: margin 0). A
+// The mesh (fp32 positions, int32 faces) is held by a handle (meshbvh.h; raycast.hip queries the same one) with the LBVH of lbvh.h over
+// its faces (leaf boxes exact: margin 0). A
 // query point p (fp32) walks it stacklessly. Everything after the load is fp64:
 //   * the leaf test is lbvh_point_tri (the remesher's region tests), guarded: a triangle whose area term |ab x ac|^2 is not positive,
 //     or whose region test gives a non-finite point, is measured as the closest of its segments ab, bc, ca (the first on a tie);
@@ -24,6 +25,7 @@
 #include "common.h"
 #include "groupby.h"
 #include "lbvh.h"
+#include "meshbvh.h"
 #include "meshface.h"
 #include <algorithm>
 #include <cmath>
@@ -33,7 +35,6 @@
 namespace ls {
 
 typedef unsigned long long u64;
-constexpr double MD_SLACK = 0x1p-40, MD_SHRINK = 1.0 - 0x1p-40;
 
 __device__ __forceinline__ double md_d2(const double p[3], const double r[3]) {
     const double dx = p[0] - r[0], dy = p[1] - r[1], dz = p[2] - r[2];
@@ -205,64 +206,6 @@ __global__ __launch_bounds__(BLOCK) void k_md_grad_points(const float* __restric
     const double s = 2.0 * g[i];
     for (int q = 0; q < 3; ++q) gP[3 * (size_t)i + q] = (float)(s * ((double)Q[3 * (size_t)i + q] - C[3 * (size_t)i + q]));
 }
-// the group-by key of a point: its face, or T ("no group") for an I outside [0, T)
-__global__ __launch_bounds__(BLOCK) void k_md_keys(const int64_t* __restrict__ I, int n, int T, int* __restrict__ keys) {
-    const int i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const int64_t f = I[i];
-    keys[i] = (f < 0 || f >= T) ? T : (int)f;
-}
-// rows[f][3 k + q] = sum over the points of face f, in sorted order, of fl32(-(2 g w_k) d_q): the G of seg_sum
-struct MdRows {
-    const float* __restrict__ Q; const double* __restrict__ C; const double* __restrict__ g; const double* __restrict__ W;
-    const int* __restrict__ order; const int* __restrict__ seg; float* __restrict__ rows;
-    __device__ __forceinline__ int count(int64_t key) const { return seg[key + 1] - seg[key]; }
-    __device__ __forceinline__ void walk(int64_t key, int start, int step, float (&acc)[9]) const {
-        const int e = seg[key + 1];
-        for (int j = seg[key] + start; j < e; j += step) {
-            const size_t i = (size_t)order[j];
-            const double s = 2.0 * g[i];
-            const double d[3] = {(double)Q[3 * i] - C[3 * i], (double)Q[3 * i + 1] - C[3 * i + 1], (double)Q[3 * i + 2] - C[3 * i + 2]};
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const double sw = s * W[3 * i + k];
-#pragma unroll
-                for (int q = 0; q < 3; ++q) acc[3 * k + q] += (float)(-(sw * d[q]));
-            }
-        }
-    }
-    __device__ __forceinline__ void store(int64_t key, const float (&acc)[9]) const {
-#pragma unroll
-        for (int q = 0; q < 9; ++q) rows[key * 9 + q] = acc[q];
-    }
-};
-__global__ __launch_bounds__(256) void k_md_face_rows(MdRows r, int64_t T) { seg_sum<9>(T, r); }
-// gV[v] = the (x, y, z) of the vertex's corners in its faces' rows, added in rank order (0 for a vertex without faces)
-__global__ __launch_bounds__(256) void k_md_gather_verts(const float* __restrict__ rows, const int* __restrict__ vptr, const int* __restrict__ order, int64_t V,
-                                                         float* __restrict__ gV) {
-    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (v >= V) return;
-    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
-    for (int r = vptr[v]; r < vptr[v + 1]; ++r) {
-        const int c = order[r];
-        const float* row = rows + (size_t)(c / 3) * 9 + 3 * (c % 3);
-        s0 += row[0]; s1 += row[1]; s2 += row[2];
-    }
-    gV[3 * v] = s0; gV[3 * v + 1] = s1; gV[3 * v + 2] = s2;
-}
-
-// ---- the handle ----------------------------------------------------------------------------------------------------------------
-struct MeshDistanceHandle {
-    int device = 0, V = 0, T = 0;
-    double slack = 0.0;
-    void* mem = nullptr;            // one device buffer holding every array below
-    size_t cap = 0;
-    float* pos = nullptr;
-    int* faces = nullptr;
-    int* small = nullptr;           // [0]: the index check's flag, [8..13]: the vertex box of lbvh_bounds
-    Lbvh bvh{};
-};
-
 }  // namespace ls
 
 using namespace ls;
@@ -386,26 +329,6 @@ extern "C" int ls_mesh_distance_weights(void* handle, const float* P, int64_t n,
     return LS_OK;
 }
 
-namespace {
-struct MdWs {          // the regions of the backward's workspace (sized from n and F alone)
-    size_t keys, order, seg, sort, W, rows, total;
-};
-MdWs md_layout(int64_t n, int64_t F) {
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const int64_t m = std::max<int64_t>(n, 1);
-    MdWs w;
-    size_t o = 0;
-    w.keys = o; o += al(4 * (size_t)m);
-    w.order = o; o += al(4 * (size_t)m);
-    w.seg = o; o += al(4 * (size_t)(F + 2));
-    w.sort = o; o += al(sort_scratch_bytes(m, true));
-    w.W = o; o += al(24 * (size_t)m);
-    w.rows = o; o += al(36 * (size_t)F);
-    w.total = o;
-    return w;
-}
-}  // namespace
-
 extern "C" int ls_mesh_distance_backward_workspace_bytes(int64_t n, int64_t F, size_t* bytes) {
     LS_REQUIRE(bytes && n >= 0 && F > 0, LS_E_INVALID, "ls_mesh_distance_backward_workspace_bytes: bad argument");
     LS_REQUIRE(n < INT32_MAX - BLOCK && 3 * F < INT32_MAX, LS_E_OVERFLOW, "ls_mesh_distance_backward_workspace_bytes: more than 2^31 points or corners");
@@ -436,11 +359,11 @@ extern "C" int ls_mesh_distance_backward(void* handle, const float* P, int64_t n
         double* W = (double*)(w + L.W);
         float* rows = (float*)(w + L.rows);
         hipLaunchKernelGGL(k_md_weights, dim3(div_up(n, BLOCK)), dim3(BLOCK), 0, st, P, (int)n, (const float*)H->pos, (const int*)H->faces, H->T, I, W);
-        hipLaunchKernelGGL(k_md_keys, dim3(div_up(n, BLOCK)), dim3(BLOCK), 0, st, I, (int)n, H->T, keys);
+        hipLaunchKernelGGL(k_md_keys<0>, dim3(div_up(n, BLOCK)), dim3(BLOCK), 0, st, I, (int)n, H->T, keys);
         int rc = group_by_key<true>(keys, n, H->T, order, seg, sort_scratch_carve(w + L.sort, n, true), st);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_md_face_rows, dim3(div_up(H->T, 256)), dim3(256), 0, st, MdRows{P, C, g, W, order, seg, rows}, (int64_t)H->T);
-        hipLaunchKernelGGL(k_md_gather_verts, dim3(div_up(H->V, 256)), dim3(256), 0, st, (const float*)rows, vptr, corner_order, (int64_t)H->V, gV);
+        hipLaunchKernelGGL(k_md_face_rows<MdRows>, dim3(div_up(H->T, 256)), dim3(256), 0, st, MdRows{P, C, g, W, order, seg, rows}, (int64_t)H->T);
+        hipLaunchKernelGGL(k_md_gather_verts<0>, dim3(div_up(H->V, 256)), dim3(256), 0, st, (const float*)rows, vptr, corner_order, (int64_t)H->V, gV);
     }
     LS_HIP(hipGetLastError());
     return LS_OK;

@@ -1,5 +1,5 @@
 // lbvh.h -- a linear BVH over the triangles of a mesh (fp32 positions (V, 3), int32 faces (T, 3) in [0, V)), shared by the remesher's
-// projection (remesh.hip) and the point-to-mesh distance (distance.hip).
+// projection (remesh.hip), the point-to-mesh distance (distance.hip) and the ray queries (raycast.hip, which walk it their own way).
 //
 // Build (lbvh_bounds, then lbvh_build): 30-bit Morton codes of the triangle centroids in the vertex box, the stable radix sort of
 // radix.h, Karras' hierarchy (internal node i of T - 1, leaves at T - 1 + i, leaf i = triangle tri[i]), a bottom-up refit of the

@@ -111,6 +111,11 @@ _SIGNATURES = {
     "ls_mesh_distance_backward": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_size_t, c_void_p]),
     "ls_mesh_distance_update": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "ls_mesh_ray_closest": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ls_mesh_ray_any": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p]),
+    "ls_mesh_ray_backward_workspace_bytes": (c_int, [c_i64, c_i64, ctypes.POINTER(c_size_t)]),
+    "ls_mesh_ray_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ls_sample_workspace_bytes": (c_int, [c_i64, c_i64, ctypes.POINTER(c_size_t)]),
     "ls_sample_surface": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_i64, c_i64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
