@@ -38,6 +38,7 @@
  *   ls_cube_*            the cube-map mode of nvdiffrast.torch.texture (boundary_mode='cube'), with gradients to tex and the direction
  *   ls_mesh_distance_*   igl.point_mesh_squared_distance / igl.hausdorff (figures/comparison/generate_data.py: the error column)
  *   ls_mesh_ray_*        igl.ray_mesh_intersect, and what igl.ambient_occlusion is built from: rays against the mesh of a distance handle
+ *   ls_mesh_winding_*    igl.winding_number / igl.fast_winding_number, the sign of igl.signed_distance: over the same handle
  */
 #ifndef LARGESTEPS_HIP_H
 #define LARGESTEPS_HIP_H
@@ -708,6 +709,32 @@ int ls_mesh_ray_backward_workspace_bytes(int64_t n, int64_t F, size_t* bytes);
 int ls_mesh_ray_backward(void* handle, const float* O, const float* D, int64_t n, const int64_t* I, const double* W, const double* t,
                          const double* g, const int32_t* vptr, const int32_t* corner_order, float* gO, float* gD, float* gV, void* ws,
                          size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The generalized winding number of points against the mesh of a mesh-distance handle (libigl's winding_number and
+ * fast_winding_number, and the sign of signed_distance; largesteps/distance.py). The rule is stated in csrc/winding.hip and DESIGN.md
+ * section 2.11 and restated in numpy by tests/winding_statement.py: per face the van Oosterom-Strackee solid angle over 4 pi in fp64
+ * from the fp32 inputs, 0 when its numerator is 0; per node of the handle's hierarchy the area-weighted centre p, a radius r and the
+ * moments of a three-term far field. A query walks the hierarchy in pre-order and takes a node's far field when |q - p| > beta r, a
+ * leaf's exact term otherwise, adding in visiting order: a result depends on (mesh, query, beta) alone. A query with a non-finite
+ * component gives NaN.
+ *   ls_mesh_winding_bytes    the size of the moment buffer of a mesh of F faces. The caller owns the buffer (8-byte aligned).
+ *   ls_mesh_winding_prepare  fills the buffer from the handle's current positions and hierarchy; again after ls_mesh_distance_update.
+ *   ls_mesh_winding_query    w (n) fp64 for P (n, 3) fp32, beta >= 1; beta = +inf is ls_mesh_winding_exact (moments may be NULL then).
+ *   ls_mesh_winding_exact    w (n) fp64: the sum over all faces in ascending id, no hierarchy.
+ *   ls_mesh_winding_arrays   copies to device arrays, each or NULL: left, right (F - 1), esc (2 F - 1), tri (F), box (2 F - 1, 6) fp32
+ *                            and mom (2 F - 1, 36) fp64 -- per node p (3), r, N (3), Ar, C (9), T (18: row i, columns jk = 00 01 02
+ *                            11 12 22), a pad. Internal node i of F - 1, leaf i at F - 1 + i holding face tri[i]. For the tests.
+ * LS_E_INVALID for a null required pointer, n < 0 or beta < 1 (or NaN), LS_E_OVERFLOW at 2^31 points; n = 0 is a no-op. No call
+ * allocates or synchronises: all ASYNC on `stream`. Queries only read the handle and the buffer; none may overlap
+ * ls_mesh_winding_prepare of that buffer or ls_mesh_distance_update / ls_mesh_distance_destroy of that handle.
+ * --------------------------------------------------------------------------------------------- */
+int ls_mesh_winding_bytes(int64_t F, size_t* bytes);
+int ls_mesh_winding_prepare(void* handle, void* moments, void* stream);
+int ls_mesh_winding_query(void* handle, const void* moments, const float* P, int64_t n, double beta, double* w, void* stream);
+int ls_mesh_winding_exact(void* handle, const float* P, int64_t n, double* w, void* stream);
+int ls_mesh_winding_arrays(void* handle, const void* moments, int32_t* left, int32_t* right, int32_t* esc, int32_t* tri, float* box,
+                           double* mom, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Area-weighted points on a mesh surface and their gradient to the vertices (largesteps/sampling.py, and distance.chamfer_distance

@@ -114,6 +114,11 @@ _SIGNATURES = {
     "ls_mesh_ray_closest": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ls_mesh_ray_any": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p]),
     "ls_mesh_ray_backward_workspace_bytes": (c_int, [c_i64, c_i64, ctypes.POINTER(c_size_t)]),
+    "ls_mesh_winding_bytes": (c_int, [c_i64, ctypes.POINTER(c_size_t)]),
+    "ls_mesh_winding_prepare": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "ls_mesh_winding_query": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_double, c_void_p, c_void_p]),
+    "ls_mesh_winding_exact": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p]),
+    "ls_mesh_winding_arrays": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ls_mesh_ray_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ls_sample_workspace_bytes": (c_int, [c_i64, c_i64, ctypes.POINTER(c_size_t)]),

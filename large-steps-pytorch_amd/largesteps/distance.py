@@ -32,6 +32,12 @@ differentiable result of `point_mesh_squared_distance` keeps its handle until it
 the device: let that graph go (drop the result and the tensors computed from it) outside any capture. A `MeshDistance` of your
 own is released by `close()` or its `with` block, when you choose.
 
+Inside or outside. `MeshDistance.winding_number(P, beta)` is the generalized winding number (Jacobson et al. 2013) by the tree walk of
+Barill et al. 2018 over the same LBVH (csrc/winding.hip), `signed_distance` the distance with its sign
+(negative inside): igl.fast_winding_number, igl.winding_number (beta = math.inf) and igl.signed_distance. Unlike ray parity or a
+pseudonormal sign it degrades gracefully on self-intersecting, folded and open meshes. The handle prepares the walk's node moments on
+the first winding query after construction or `update`; a handle that never asks pays nothing. Prepared, both queries are capturable.
+
 Input conventions follow remesh_botsch: numpy input (V float64 or float32, converted to fp32; F integer) runs on the current HIP device
 and returns numpy; tensor input (V and query points fp32, F int32 / int64, all on one HIP device) returns tensors on that device. CPU
 tensors raise.
@@ -149,6 +155,30 @@ class _SquaredDistance(Function):
         return gP, gV, None
 
 
+def _as_beta(beta):
+    if isinstance(beta, bool) or not isinstance(beta, (int, float, np.integer, np.floating)):
+        raise TypeError(f"beta must be a real number, got {type(beta).__name__}")
+    beta = float(beta)
+    if not beta >= 1.0:
+        raise ValueError(f"winding number: beta must be at least 1, got {beta}")
+    return beta
+
+
+class _SignedRoot(Function):
+    """S = s sqrt(sqrD), computed by the caller, with dS = coef dsqrD (coef = s / (2 sqrt(sqrD)), 0 where sqrD == 0)"""
+
+    @staticmethod
+    def forward(ctx, sqrD, S, coef):
+        ctx.save_for_backward(coef)
+        return S.clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        coef, = ctx.saved_tensors
+        return g * coef, None, None
+
+
 class MeshDistance:
     """The LBVH of one mesh (V, F) on a HIP device, for distance queries from any number of point sets: the figure's target mesh,
     built once and queried at every recorded step, or a moving mesh whose positions `update` replaces at every step. numpy (V, F) go
@@ -168,6 +198,7 @@ class MeshDistance:
         self._f = f
         self._ranks = None
         self._version = 0                  # bumped by update: a backward pass belongs to the positions of its forward pass
+        self._wn, self._wn_version = None, -1      # the winding walk's moments and the version they were prepared for
         self._remember(V)
         self._h = ctypes.c_void_p(0)
         with torch.cuda.device(self.device):
@@ -245,6 +276,64 @@ class MeshDistance:
             _native.check(_native.lib().ls_mesh_distance_max(self._h, _native.ptr(p), p.shape[0], _native.ptr(out), _native.stream_of(self.device)))
         return float(out) if p_np else out
 
+    def _moments(self):
+        """the moment buffer of the winding walk, prepared on the first winding query after construction or `update`"""
+        if self._wn_version != self._version:
+            if self._wn is None:
+                c = ctypes.c_size_t(0)
+                _native.check(_native.lib().ls_mesh_winding_bytes(self._f.shape[0], ctypes.byref(c)))
+                self._wn = torch.empty(c.value, dtype=torch.uint8, device=self.device)
+            with torch.cuda.device(self.device):
+                _native.check(_native.lib().ls_mesh_winding_prepare(self._h, _native.ptr(self._wn), _native.stream_of(self.device)))
+            self._wn_version = self._version
+        return self._wn
+
+    def _winding(self, p, beta):
+        if not self._h:
+            raise RuntimeError("mesh distance: query of a closed handle")
+        w = torch.empty(p.shape[0], dtype=torch.float64, device=self.device)
+        mom = None if beta == math.inf else self._moments()
+        with torch.cuda.device(self.device):
+            _native.check(_native.lib().ls_mesh_winding_query(self._h, _native.ptr(mom), _native.ptr(p), p.shape[0], beta, _native.ptr(w),
+                                                              _native.stream_of(self.device)))
+        return w
+
+    @_native.retry_on_oom
+    def winding_number(self, P, beta=2.0):
+        """w (n,) float64: the generalized winding number of the mesh around every row of P (libigl's fast_winding_number): 1 inside a
+        closed, outward-oriented mesh, 0 outside, -1 for the flipped orientation, k inside k nested copies, a fraction near an open
+        boundary; NaN for a row with a non-finite component. `beta` >= 1 is the accuracy of the tree walk: a node of the handle's LBVH
+        farther than beta times its radius answers with a three-term expansion of its faces (DESIGN.md section 2.11 has measured
+        errors; the default 2.0 is libigl's). beta = math.inf sums every face exactly (libigl's winding_number). A query lying in
+        the plane of a face, on an edge or on a vertex takes 0 from that face. Bitwise reproducible; not differentiable."""
+        beta = _as_beta(beta)
+        p, p_np = self._points(P)
+        w = self._winding(p, beta)
+        return w.cpu().numpy() if p_np else w
+
+    @_native.retry_on_oom
+    def signed_distance(self, P, beta=2.0):
+        """(S (n,) float64, I (n,) int64, C (n, 3) float64): libigl's signed_distance with the winding-number sign. I and C are those of
+        `squared_distance`; S = s sqrt(sqrD) with s = -1 where winding_number(P, beta) >= 0.5 (inside: negative, libigl's convention)
+        and +1 elsewhere; S is NaN where the winding number is. libigl scales the distance by 1 - 2 w instead; here |S| is the distance.
+        S is differentiable in P and in the handle's source V exactly as sqrD is, dS = s / (2 sqrt(sqrD)) dsqrD, and zero where
+        sqrD == 0; the winding number and the sign carry no gradient."""
+        beta = _as_beta(beta)
+        sqrD, I, C = self.squared_distance(P)
+        if isinstance(sqrD, torch.Tensor):
+            with torch.no_grad():
+                w = self._winding(_on(_as_points(P, "P")[0], self.device), beta)
+                d = torch.sqrt(sqrD.detach())
+                s = torch.where(w >= 0.5, -1.0, 1.0).to(torch.float64)
+                S = torch.where(torch.isnan(w), w, s * d)
+            if sqrD.requires_grad:
+                coef = torch.where(d > 0, s / (2.0 * d), torch.zeros_like(d))
+                S = _SignedRoot.apply(sqrD, S, coef)
+            return S, I, C
+        w = self.winding_number(P, beta)
+        S = np.where(w >= 0.5, -1.0, 1.0) * np.sqrt(sqrD)
+        return np.where(np.isnan(w), w, S), I, C
+
     def hausdorff(self, VA, FA):
         """hausdorff(VA, FA, V, F) of this mesh (V, F): only the other mesh's LBVH is built."""
         if (VA.shape[0] if isinstance(VA, torch.Tensor) else np.asarray(VA).shape[0]) == 0:
@@ -260,6 +349,7 @@ class MeshDistance:
         if self._h:
             _native.lib().ls_mesh_distance_destroy(self._h)
             self._h = ctypes.c_void_p(0)
+            self._wn, self._wn_version = None, -1
 
     def __del__(self):
         try:
@@ -285,6 +375,37 @@ def point_mesh_squared_distance(P, V, F):
     out = None
     try:
         out = m.squared_distance(P)
+        return out
+    finally:
+        if not (out is not None and isinstance(out[0], torch.Tensor) and out[0].requires_grad):
+            m.close()
+
+
+@_native.retry_on_oom
+def winding_number(V, F, P, beta=2.0):
+    """libigl's fast_winding_number(V, F, P) (and winding_number with beta = math.inf) -> w (n,) float64: MeshDistance.winding_number of
+    a handle built for this call. numpy input gives numpy, tensors give a tensor on their device."""
+    _as_beta(beta)
+    for name, X in (("V", V), ("P", P)):                # the type, dtype and shape checks, before any device work
+        _as_points(X, name)
+    _as_faces(F)
+    with MeshDistance(V, F) as m:
+        return m.winding_number(P, beta)
+
+
+@_native.retry_on_oom
+def signed_distance(P, V, F, beta=2.0):
+    """libigl's signed_distance(P, V, F) with the winding-number sign -> (S, I, C): MeshDistance.signed_distance of a handle built for
+    this call; negative inside. S is differentiable in tensors P and V that require grad; its graph then keeps the handle, as
+    point_mesh_squared_distance's does."""
+    _as_beta(beta)
+    for name, X in (("P", P), ("V", V)):
+        _as_points(X, name)
+    _as_faces(F)
+    m = MeshDistance(V, F)
+    out = None
+    try:
+        out = m.signed_distance(P, beta)
         return out
     finally:
         if not (out is not None and isinstance(out[0], torch.Tensor) and out[0].requires_grad):
