@@ -124,9 +124,14 @@ __device__ __forceinline__ T wave_sum(T x) {
     return x;   // valid in lane 0
 }
 
-// The same sum by an xor butterfly (32, 16, ... 1), returned in EVERY lane. The segmented sum of groupby.h is pinned to this order of
+// The same sum by an xor butterfly (32, 16, ... 1), in float or in double, returned in EVERY lane. The segmented sum of groupby.h is pinned to this order of
 // additions (bitwise-reproducible gradients): it is not interchangeable with wave_sum above.
 __device__ __forceinline__ float wave_sum_xor(float v) {
+#pragma unroll
+    for (int m = WAVE / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, WAVE);
+    return v;
+}
+__device__ __forceinline__ double wave_sum_xor(double v) {
 #pragma unroll
     for (int m = WAVE / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, WAVE);
     return v;

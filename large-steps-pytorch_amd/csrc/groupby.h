@@ -29,17 +29,18 @@ __global__ __launch_bounds__(256) void k_gb_segments(const int* __restrict__ sk,
 // The sum of one key per thread, keys [0, nkeys) over a grid of 256-thread workgroups. A key of at most 64 items is added by its own
 // thread, items in order; a longer one by its whole wave, lane l adding items l, l + 64, ... in order and wave_sum_xor adding the lanes.
 // G provides count(key), the number of items of the key; walk(key, start, step, acc), which adds items start, start + step, ... of the
-// key to acc[K] in order; store(key, acc), which writes the K sums. (Kernels here are templates only so that several units can include them.)
-template <int K, class G>
+// key to acc[K] in order; store(key, acc), which writes the K sums. A is the type the sums are formed in (wave_sum_xor has the same
+// butterfly for float and double). (Kernels here are templates only so that several units can include them.)
+template <int K, class G, class A = float>
 __device__ __forceinline__ void seg_sum(int64_t nkeys, const G& g) {
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const bool ok = k < nkeys;
     const bool lng = ok && g.count(k) > 64;
     if (ok && !lng) {
-        float acc[K];
+        A acc[K];
 #pragma unroll
-        for (int q = 0; q < K; ++q) acc[q] = 0.0f;
+        for (int q = 0; q < K; ++q) acc[q] = A(0);
         g.walk(k, 0, 1, acc);
         g.store(k, acc);
     }
@@ -48,9 +49,9 @@ __device__ __forceinline__ void seg_sum(int64_t nkeys, const G& g) {
         const int src = __ffsll((long long)m) - 1;
         m &= m - 1;
         const int64_t kk = (int64_t)blockIdx.x * 256 + (threadIdx.x & ~63) + src;
-        float acc[K];
+        A acc[K];
 #pragma unroll
-        for (int q = 0; q < K; ++q) acc[q] = 0.0f;
+        for (int q = 0; q < K; ++q) acc[q] = A(0);
         g.walk(kk, lane, 64, acc);
 #pragma unroll
         for (int q = 0; q < K; ++q) acc[q] = wave_sum_xor(acc[q]);

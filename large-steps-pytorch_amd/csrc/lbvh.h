@@ -1,11 +1,14 @@
 // lbvh.h -- a linear BVH over the triangles of a mesh (fp32 positions (V, 3), int32 faces (T, 3) in [0, V)), shared by the remesher's
-// projection (remesh.hip), the point-to-mesh distance (distance.hip) and the ray queries (raycast.hip, which walk it their own way).
+// projection (remesh.hip) and, through the handle of meshbvh.h (built in meshbvh.hip), by the point-to-mesh distance (distance.hip), the
+// ray queries (raycast.hip) and the winding number (winding.hip); the last two walk it their own way.
 //
 // Build (lbvh_bounds, then lbvh_build): 30-bit Morton codes of the triangle centroids in the vertex box, the stable radix sort of
 // radix.h, Karras' hierarchy (internal node i of T - 1, leaves at T - 1 + i, leaf i = triangle tri[i]), a bottom-up refit of the
 // leaves' corner boxes widened by `margin` (an atomic visit counter: the last child's thread goes on; min / max boxes are
 // order-independent) and escape links (the node that follows a node's subtree in the pre-order, -1 past the end). lbvh_walk visits
-// a query's candidates without a stack or scratch, templated on the query's bound and leaf test. Everything is deterministic.
+// a query's candidates without a stack or scratch, templated on the query's bound and leaf test. lbvh_climb is the bottom-up pass
+// of the refit, which the winding number's node moments (winding.hip) run again with another combine step; lbvh_point_tri is the
+// closest-point rule of every user, with the barycentric weights of the point on request. Everything is deterministic.
 // Kernels are templates only so that the header can be included by several translation units.
 #pragma once
 #include "common.h"
@@ -101,6 +104,22 @@ __global__ __launch_bounds__(BLOCK) void k_lbvh_karras(const unsigned* __restric
     left[i] = L; right[i] = R;
     parent[L] = i; parent[R] = i;
 }
+// The bottom-up pass from a finished leaf: at every internal node on the way to the root the thread that arrives FIRST stops (the
+// sibling's subtree is not done yet), the one that arrives second runs combine(node, left[node], right[node]) and goes on. The fence
+// before the atomic publishes what this thread wrote below the node, the fence after it orders the reads of what the sibling's thread
+// published; combine reads the children through volatile pointers. Which thread does a node's combine does not change its operands.
+template <class Combine>
+__device__ __forceinline__ void lbvh_climb(int leaf, const int* __restrict__ left, const int* __restrict__ right, const int* __restrict__ parent,
+                                           int* __restrict__ flag, Combine combine) {
+    int node = parent[leaf];
+    while (node >= 0) {
+        __threadfence();
+        if (atomicAdd(&flag[node], 1) == 0) return;       // the sibling's subtree is not done yet: its last thread goes on
+        __threadfence();
+        combine(node, left[node], right[node]);
+        node = parent[node];
+    }
+}
 template <int UNIT = 0>
 __global__ __launch_bounds__(BLOCK) void k_lbvh_refit(const float* __restrict__ P, const int* __restrict__ faces, const int* __restrict__ tri, int T,
                                                       float margin, const int* __restrict__ left, const int* __restrict__ right,
@@ -109,22 +128,17 @@ __global__ __launch_bounds__(BLOCK) void k_lbvh_refit(const float* __restrict__ 
     if (i >= T) return;
     const int f = tri[i];
     const float3 a = lbvh_ld(P, faces[3 * f]), b = lbvh_ld(P, faces[3 * f + 1]), c = lbvh_ld(P, faces[3 * f + 2]);
-    int node = T - 1 + i;
+    const int node = T - 1 + i;
     float* bx = box + 6 * (size_t)node;
     bx[0] = fminf(fminf(a.x, b.x), c.x) - margin; bx[1] = fminf(fminf(a.y, b.y), c.y) - margin; bx[2] = fminf(fminf(a.z, b.z), c.z) - margin;
     bx[3] = fmaxf(fmaxf(a.x, b.x), c.x) + margin; bx[4] = fmaxf(fmaxf(a.y, b.y), c.y) + margin; bx[5] = fmaxf(fmaxf(a.z, b.z), c.z) + margin;
     if (T == 1) return;
-    node = parent[node];
-    while (node >= 0) {
-        __threadfence();
-        if (atomicAdd(&flag[node], 1) == 0) return;       // the sibling's subtree is not done yet: its last thread goes on
-        __threadfence();
-        const volatile float* l = box + 6 * (size_t)left[node];
-        const volatile float* r = box + 6 * (size_t)right[node];
-        float* o = box + 6 * (size_t)node;
+    lbvh_climb(node, left, right, parent, flag, [&](int nd, int lc, int rc) {
+        const volatile float* l = box + 6 * (size_t)lc;
+        const volatile float* r = box + 6 * (size_t)rc;
+        float* o = box + 6 * (size_t)nd;
         for (int q = 0; q < 3; ++q) { o[q] = fminf(l[q], r[q]); o[3 + q] = fmaxf(l[3 + q], r[3 + q]); }
-        node = parent[node];
-    }
+    });
 }
 // escape link: the node that follows a node's subtree in the pre-order (left first), -1 past the end
 template <int UNIT = 0>
@@ -205,38 +219,56 @@ __device__ __forceinline__ void lbvh_walk(const int* __restrict__ left, const in
 
 __device__ __forceinline__ double lbvh_dd(double ax, double ay, double az, double bx, double by, double bz) { return (ax * bx + ay * by) + az * bz; }
 // closest point of p on triangle (a, b, c) in fp64: the region tests of tests/remesh_statement.py:point_triangle (no guard for a
-// degenerate triangle: the remesher's input has none, the distance path guards it in distance.hip)
-__device__ inline void lbvh_point_tri(const double p[3], const double a[3], const double b[3], const double c[3], double r[3]) {
+// degenerate triangle: the remesher's input has none, the distance path guards it in meshbvh.h). WW: also w[3], the weights of the
+// point on (a, b, c), from the quotient of the same branch (r is never rebuilt from them); the distance's gradient asks for them.
+template <bool WW = false>
+__device__ inline void lbvh_point_tri(const double p[3], const double a[3], const double b[3], const double c[3], double r[3], double* w = nullptr) {
     const double ab[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, ac[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
     const double ap[3] = {p[0] - a[0], p[1] - a[1], p[2] - a[2]};
     const double d1 = lbvh_dd(ab[0], ab[1], ab[2], ap[0], ap[1], ap[2]), d2 = lbvh_dd(ac[0], ac[1], ac[2], ap[0], ap[1], ap[2]);
-    if (d1 <= 0.0 && d2 <= 0.0) { r[0] = a[0]; r[1] = a[1]; r[2] = a[2]; return; }
+    if (d1 <= 0.0 && d2 <= 0.0) {
+        r[0] = a[0]; r[1] = a[1]; r[2] = a[2];
+        if constexpr (WW) { w[0] = 1.0; w[1] = 0.0; w[2] = 0.0; }
+        return;
+    }
     const double bp[3] = {p[0] - b[0], p[1] - b[1], p[2] - b[2]};
     const double d3 = lbvh_dd(ab[0], ab[1], ab[2], bp[0], bp[1], bp[2]), d4 = lbvh_dd(ac[0], ac[1], ac[2], bp[0], bp[1], bp[2]);
-    if (d3 >= 0.0 && d4 <= d3) { r[0] = b[0]; r[1] = b[1]; r[2] = b[2]; return; }
+    if (d3 >= 0.0 && d4 <= d3) {
+        r[0] = b[0]; r[1] = b[1]; r[2] = b[2];
+        if constexpr (WW) { w[0] = 0.0; w[1] = 1.0; w[2] = 0.0; }
+        return;
+    }
     const double vc = d1 * d4 - d3 * d2;
     if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {
         const double v = d1 / (d1 - d3);
         for (int q = 0; q < 3; ++q) r[q] = a[q] + ab[q] * v;
+        if constexpr (WW) { w[0] = 1.0 - v; w[1] = v; w[2] = 0.0; }
         return;
     }
     const double cp[3] = {p[0] - c[0], p[1] - c[1], p[2] - c[2]};
     const double d5 = lbvh_dd(ab[0], ab[1], ab[2], cp[0], cp[1], cp[2]), d6 = lbvh_dd(ac[0], ac[1], ac[2], cp[0], cp[1], cp[2]);
-    if (d6 >= 0.0 && d5 <= d6) { r[0] = c[0]; r[1] = c[1]; r[2] = c[2]; return; }
+    if (d6 >= 0.0 && d5 <= d6) {
+        r[0] = c[0]; r[1] = c[1]; r[2] = c[2];
+        if constexpr (WW) { w[0] = 0.0; w[1] = 0.0; w[2] = 1.0; }
+        return;
+    }
     const double vb = d5 * d2 - d1 * d6;
     if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {
-        const double w = d2 / (d2 - d6);
-        for (int q = 0; q < 3; ++q) r[q] = a[q] + ac[q] * w;
+        const double u = d2 / (d2 - d6);
+        for (int q = 0; q < 3; ++q) r[q] = a[q] + ac[q] * u;
+        if constexpr (WW) { w[0] = 1.0 - u; w[1] = 0.0; w[2] = u; }
         return;
     }
     const double va = d3 * d6 - d5 * d4;
     if (va <= 0.0 && d4 - d3 >= 0.0 && d5 - d6 >= 0.0) {
-        const double w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
-        for (int q = 0; q < 3; ++q) r[q] = b[q] + (c[q] - b[q]) * w;
+        const double u = (d4 - d3) / ((d4 - d3) + (d5 - d6));
+        for (int q = 0; q < 3; ++q) r[q] = b[q] + (c[q] - b[q]) * u;
+        if constexpr (WW) { w[0] = 0.0; w[1] = 1.0 - u; w[2] = u; }
         return;
     }
-    const double den = 1.0 / ((va + vb) + vc), v = vb * den, w = vc * den;
-    for (int q = 0; q < 3; ++q) r[q] = (a[q] + ab[q] * v) + ac[q] * w;
+    const double den = 1.0 / ((va + vb) + vc), v = vb * den, u = vc * den;
+    for (int q = 0; q < 3; ++q) r[q] = (a[q] + ab[q] * v) + ac[q] * u;
+    if constexpr (WW) { w[0] = (1.0 - v) - u; w[1] = v; w[2] = u; }
 }
 
 }  // namespace ls

@@ -29,7 +29,7 @@
 // The gradient of t (first order, the face held fixed; W and I carry none). With n = (b - a) x (c - a), q = n / (n . d) in fp64 from the
 // fp32 inputs and g the incoming gradient: dt/do = -q, dt/dd = -t q, dt/dV[F[I, k]] = w_k q; the terms -(g q), -((g t) q) and (g w_k) q are
 // rounded to fp32 once. A miss adds nothing; n . d = 0 gives what IEEE gives. The vertex gradient is summed exactly as the distance's
-// (meshbvh.h): rays grouped by face, seg_sum<9>, a thread per vertex in corner-rank order. No float atomics, no host synchronisation.
+// (md_vertex_grad of meshbvh.h): rays grouped by face, seg_sum<9>, a thread per vertex in corner-rank order. No float atomics, no host synchronisation.
 #include "common.h"
 #include "groupby.h"
 #include "lbvh.h"
@@ -69,8 +69,9 @@ __device__ __forceinline__ RcRay rc_ray(const float* __restrict__ O, const float
     return r;
 }
 // the rule on face f: true iff the face is hit (before the range test); t and the three edge functions over det
-__device__ __forceinline__ bool rc_face(const RcRay& r, const float* __restrict__ P, const int* __restrict__ faces, int f, double& t, double& U, double& V,
-                                        double& W, double& det) {
+__device__ __forceinline__ bool rc_face(const RcRay& r, const MeshView& m, int f, double& t, double& U, double& V, double& W, double& det) {
+    const float* __restrict__ P = m.P;
+    const int* __restrict__ faces = m.faces;
     const size_t va = 3 * (size_t)faces[3 * (size_t)f], vb = 3 * (size_t)faces[3 * (size_t)f + 1], vc = 3 * (size_t)faces[3 * (size_t)f + 2];
     const double Akx = (double)P[va + r.kx] - r.o[0], Aky = (double)P[va + r.ky] - r.o[1], Akz = (double)P[va + r.kz] - r.o[2];
     const double Bkx = (double)P[vb + r.kx] - r.o[0], Bky = (double)P[vb + r.ky] - r.o[1], Bkz = (double)P[vb + r.kz] - r.o[2];
@@ -105,21 +106,23 @@ __device__ __forceinline__ bool rc_box(const RcRay& r, const float* __restrict__
 // the walk of ray i. ANY: hit[i] = some face is accepted (the walk stops at the first); else t, I, W of the closest hit, any may be null
 template <bool ANY>
 __device__ __forceinline__ void rc_walk(const float* __restrict__ O, const float* __restrict__ D, int n, const double* __restrict__ trange,
-                                        const float* __restrict__ P, const int* __restrict__ faces, int T, const int* __restrict__ tri,
-                                        const float* __restrict__ box, const int* __restrict__ left, const int* __restrict__ esc,
-                                        const int* __restrict__ right, double slack, double* __restrict__ tout, int64_t* __restrict__ I,
-                                        double* __restrict__ Wout, unsigned char* __restrict__ hit) {
+                                        const MeshView& m, double* __restrict__ tout, int64_t* __restrict__ I, double* __restrict__ Wout,
+                                        unsigned char* __restrict__ hit) {
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
-    const RcRay r = rc_ray(O, D, (size_t)i, slack);
+    const int* __restrict__ left = m.left;
+    const int* __restrict__ right = m.right;
+    const int* __restrict__ esc = m.esc;
+    const float* __restrict__ box = m.box;
+    const RcRay r = rc_ray(O, D, (size_t)i, m.slack);
     const double tmin = trange ? trange[2 * (size_t)i] : 0.0, tmax = trange ? trange[2 * (size_t)i + 1] : rc_inf();
-    const int leaf0 = T - 1;
+    const int leaf0 = m.T - 1;
     double best = tmax, w0 = 0.0, w1 = 0.0, w2 = 0.0;
     int id = RC_NONE;
     auto leaf = [&](int node) {
-        const int f = tri[node - leaf0];
+        const int f = m.tri[node - leaf0];
         double t, U, V, W, det;
-        if (!rc_face(r, P, faces, f, t, U, V, W, det)) return;
+        if (!rc_face(r, m, f, t, U, V, W, det)) return;
         if (!(t >= tmin && t <= tmax)) return;
         if (t < best || (t == best && f < id)) { best = t; id = f; w0 = U / det; w1 = V / det; w2 = W / det; }
     };
@@ -153,28 +156,26 @@ __device__ __forceinline__ void rc_walk(const float* __restrict__ O, const float
     if (I) I[i] = found ? id : -1;
     if (Wout) { Wout[3 * (size_t)i] = found ? w0 : 0.0; Wout[3 * (size_t)i + 1] = found ? w1 : 0.0; Wout[3 * (size_t)i + 2] = found ? w2 : 0.0; }
 }
-// one thread per ray: the closest hit
+// one thread per ray: the closest hit (loose pointers, the view built here, for the reason given at k_md_query of distance.hip)
 __global__ __launch_bounds__(BLOCK) void k_ray_closest(const float* __restrict__ O, const float* __restrict__ D, int n, const double* __restrict__ trange,
                                                        const float* __restrict__ P, const int* __restrict__ faces, int T, const int* __restrict__ tri,
-                                                       const float* __restrict__ box, const int* __restrict__ left, const int* __restrict__ esc,
-                                                       const int* __restrict__ right, double slack, double* __restrict__ t, int64_t* __restrict__ I,
+                                                       const float* __restrict__ box, const int* __restrict__ left, const int* __restrict__ right,
+                                                       const int* __restrict__ esc, double slack, double* __restrict__ t, int64_t* __restrict__ I,
                                                        double* __restrict__ W) {
-    rc_walk<false>(O, D, n, trange, P, faces, T, tri, box, left, esc, right, slack, t, I, W, nullptr);
+    rc_walk<false>(O, D, n, trange, MeshView{P, faces, T, tri, box, left, right, esc, slack}, t, I, W, nullptr);
 }
 // one thread per ray: one byte, 1 iff some face is accepted
 __global__ __launch_bounds__(BLOCK) void k_ray_any(const float* __restrict__ O, const float* __restrict__ D, int n, const double* __restrict__ trange,
-                                                   const float* __restrict__ P, const int* __restrict__ faces, int T, const int* __restrict__ tri,
-                                                   const float* __restrict__ box, const int* __restrict__ left, const int* __restrict__ esc,
-                                                   double slack, unsigned char* __restrict__ hit) {
-    rc_walk<true>(O, D, n, trange, P, faces, T, tri, box, left, esc, nullptr, slack, nullptr, nullptr, nullptr, hit);
+                                                   const MeshView m, unsigned char* __restrict__ hit) {
+    rc_walk<true>(O, D, n, trange, m, nullptr, nullptr, nullptr, hit);
 }
 
 // ---- the gradient ----------------------------------------------------------------------------------------------------------------
 // n = (b - a) x (c - a) of face f, fp64
-__device__ __forceinline__ void rc_normal(const float* __restrict__ P, const int* __restrict__ faces, size_t f, double nrm[3]) {
-    const size_t va = 3 * (size_t)faces[3 * f], vb = 3 * (size_t)faces[3 * f + 1], vc = 3 * (size_t)faces[3 * f + 2];
-    const double ab[3] = {(double)P[vb] - (double)P[va], (double)P[vb + 1] - (double)P[va + 1], (double)P[vb + 2] - (double)P[va + 2]};
-    const double ac[3] = {(double)P[vc] - (double)P[va], (double)P[vc + 1] - (double)P[va + 1], (double)P[vc + 2] - (double)P[va + 2]};
+__device__ __forceinline__ void rc_normal(const MeshView& m, size_t f, double nrm[3]) {
+    double y[9];
+    mesh_corners(m, f, y);
+    const double ab[3] = {y[3] - y[0], y[4] - y[1], y[5] - y[2]}, ac[3] = {y[6] - y[0], y[7] - y[1], y[8] - y[2]};
     nrm[0] = ab[1] * ac[2] - ab[2] * ac[1];
     nrm[1] = ab[2] * ac[0] - ab[0] * ac[2];
     nrm[2] = ab[0] * ac[1] - ab[1] * ac[0];
@@ -185,16 +186,15 @@ __device__ __forceinline__ void rc_q(const float* __restrict__ D, size_t i, cons
     q[0] = nrm[0] / nd; q[1] = nrm[1] / nd; q[2] = nrm[2] / nd;
 }
 // gO[i] = fl32(-(g q)), gD[i] = fl32(-((g t) q)); zeros for a miss (an I outside [0, T))
-__global__ __launch_bounds__(BLOCK) void k_ray_grad_rays(const float* __restrict__ D, int n, const float* __restrict__ P, const int* __restrict__ faces, int T,
-                                                         const int64_t* __restrict__ I, const double* __restrict__ t, const double* __restrict__ g,
+__global__ __launch_bounds__(BLOCK) void k_ray_grad_rays(const float* __restrict__ D, int n, const MeshView m, const int64_t* __restrict__ I, const double* __restrict__ t, const double* __restrict__ g,
                                                          float* __restrict__ gO, float* __restrict__ gD) {
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
     const int64_t f = I[i];
     float o[3] = {0.0f, 0.0f, 0.0f}, d[3] = {0.0f, 0.0f, 0.0f};
-    if (f >= 0 && f < T) {
+    if (f >= 0 && f < m.T) {
         double nrm[3], q[3];
-        rc_normal(P, faces, (size_t)f, nrm);
+        rc_normal(m, (size_t)f, nrm);
         rc_q(D, (size_t)i, nrm, q);
         const double gi = g[i], gt = gi * t[i];
 #pragma unroll
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(BLOCK) void k_ray_grad_rays(const float* __restrict
 }
 // rows[f][3 k + c] = sum over the rays of face f, in sorted order, of fl32((g w_k) q_c): the G of seg_sum
 struct RcRows {
-    const float* __restrict__ D; const float* __restrict__ P; const int* __restrict__ faces; const double* __restrict__ g; const double* __restrict__ W;
+    const float* __restrict__ D; MeshView m; const double* __restrict__ g; const double* __restrict__ W;
     const int* __restrict__ order; const int* __restrict__ seg; float* __restrict__ rows;
     __device__ __forceinline__ int count(int64_t key) const { return seg[key + 1] - seg[key]; }
     __device__ __forceinline__ void walk(int64_t key, int start, int step, float (&acc)[9]) const {
@@ -216,7 +216,7 @@ struct RcRows {
         int j = seg[key] + start;
         if (j >= e) return;
         double nrm[3];
-        rc_normal(P, faces, (size_t)key, nrm);
+        rc_normal(m, (size_t)key, nrm);
         for (; j < e; j += step) {
             const size_t i = (size_t)order[j];
             double q[3];
@@ -248,9 +248,9 @@ extern "C" int ls_mesh_ray_closest(void* handle, const float* O, const float* D,
     if (n == 0 || (!t && !I && !W)) return LS_OK;
     DeviceGuard g(H->device);
     LS_HIP(g.err);
-    hipLaunchKernelGGL(k_ray_closest, dim3(div_up(n, BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, O, D, (int)n, trange, (const float*)H->pos,
-                       (const int*)H->faces, H->T, (const int*)H->bvh.tri, (const float*)H->bvh.box, (const int*)H->bvh.left, (const int*)H->bvh.esc,
-                       (const int*)H->bvh.right, H->slack, t, I, W);
+    const MeshView v = H->view();
+    hipLaunchKernelGGL(k_ray_closest, dim3(div_up(n, BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, O, D, (int)n, trange, v.P, v.faces, v.T, v.tri, v.box,
+                       v.left, v.right, v.esc, v.slack, t, I, W);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
@@ -262,9 +262,7 @@ extern "C" int ls_mesh_ray_any(void* handle, const float* O, const float* D, int
     if (n == 0) return LS_OK;
     DeviceGuard g(H->device);
     LS_HIP(g.err);
-    hipLaunchKernelGGL(k_ray_any, dim3(div_up(n, BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, O, D, (int)n, trange, (const float*)H->pos,
-                       (const int*)H->faces, H->T, (const int*)H->bvh.tri, (const float*)H->bvh.box, (const int*)H->bvh.left, (const int*)H->bvh.esc,
-                       H->slack, hit);
+    hipLaunchKernelGGL(k_ray_any, dim3(div_up(n, BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, O, D, (int)n, trange, H->view(), hit);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
@@ -272,7 +270,7 @@ extern "C" int ls_mesh_ray_any(void* handle, const float* O, const float* D, int
 extern "C" int ls_mesh_ray_backward_workspace_bytes(int64_t n, int64_t F, size_t* bytes) {
     LS_REQUIRE(bytes && n >= 0 && F > 0, LS_E_INVALID, "ls_mesh_ray_backward_workspace_bytes: bad argument");
     LS_REQUIRE(n < INT32_MAX - BLOCK && 3 * F < INT32_MAX, LS_E_OVERFLOW, "ls_mesh_ray_backward_workspace_bytes: more than 2^31 rays or corners");
-    *bytes = md_layout(n, F, false).total;
+    *bytes = md_layout(n, F, false, sizeof(float) * 9).total;
     return LS_OK;
 }
 
@@ -284,27 +282,17 @@ extern "C" int ls_mesh_ray_backward(void* handle, const float* O, const float* D
                "ls_mesh_ray_backward: the vertex gradient needs W, the corner ranking and a workspace");
     LS_REQUIRE(n < INT32_MAX - BLOCK, LS_E_OVERFLOW, "ls_mesh_ray_backward: more than 2^31 rays");
     MeshDistanceHandle* H = (MeshDistanceHandle*)handle;
-    const MdWs L = md_layout(n, H->T, false);
+    const MdWs L = md_layout(n, H->T, false, sizeof(float) * 9);
     LS_REQUIRE(!gV || ws_bytes >= L.total, LS_E_WORKSPACE, "ls_mesh_ray_backward: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
     DeviceGuard guard(H->device);
     LS_HIP(guard.err);
     const hipStream_t st = (hipStream_t)stream;
     if ((gO || gD) && n > 0)
-        hipLaunchKernelGGL(k_ray_grad_rays, dim3(div_up(n, BLOCK)), dim3(BLOCK), 0, st, D, (int)n, (const float*)H->pos, (const int*)H->faces, H->T, I, t, g, gO,
-                           gD);
+        hipLaunchKernelGGL(k_ray_grad_rays, dim3(div_up(n, BLOCK)), dim3(BLOCK), 0, st, D, (int)n, H->view(), I, t, g, gO, gD);
     if (gV && n == 0) LS_HIP(hipMemsetAsync(gV, 0, sizeof(float) * 3 * (size_t)H->V, st));
     if (gV && n > 0) {
-        char* w = (char*)ws;
-        int* keys = (int*)(w + L.keys);
-        int* order = (int*)(w + L.order);
-        int* seg = (int*)(w + L.seg);
-        float* rows = (float*)(w + L.rows);
-        hipLaunchKernelGGL(k_md_keys<0>, dim3(div_up(n, BLOCK)), dim3(BLOCK), 0, st, I, (int)n, H->T, keys);
-        int rc = group_by_key<true>(keys, n, H->T, order, seg, sort_scratch_carve(w + L.sort, n, true), st);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_md_face_rows<RcRows>, dim3(div_up(H->T, 256)), dim3(256), 0, st,
-                           RcRows{D, (const float*)H->pos, (const int*)H->faces, g, W, order, seg, rows}, (int64_t)H->T);
-        hipLaunchKernelGGL(k_md_gather_verts<0>, dim3(div_up(H->V, 256)), dim3(256), 0, st, (const float*)rows, vptr, corner_order, (int64_t)H->V, gV);
+        const MdCarved<float> c = md_carve<float>(ws, L, n);
+        if (int rc = md_vertex_grad<float>(I, n, H->T, H->V, RcRows{D, H->view(), g, W, c.order, c.seg, c.rows}, vptr, corner_order, gV, c, st)) return rc;
     }
     LS_HIP(hipGetLastError());
     return LS_OK;

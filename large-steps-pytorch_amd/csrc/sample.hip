@@ -20,11 +20,12 @@
 //
 // Gradient: gV[v] = sum_i W_ik gP_i over the samples whose face has v at corner k; I and W are held fixed. No float atomics: the samples
 // are grouped by face (groupby.h: stable, so ascending i within a face), nine fp64 sums per face are formed in that order (a thread up
-// to 64 samples, else the wave lane-strided and an xor butterfly: the order of groupby.h's seg_sum, in fp64), and a thread per vertex
-// adds the rows of its corners in the rank order of meshface.h in fp64 and rounds ONCE to fp32. Every product W_ik gP_i is exact in
-// fp64. Bitwise reproducible.
+// to 64 samples, else the wave lane-strided and an xor butterfly: groupby.h's seg_sum with an fp64 accumulator), and a thread per vertex
+// adds the rows of its corners in the rank order of meshface.h in fp64 and rounds ONCE to fp32 -- md_vertex_grad of meshbvh.h, the tail
+// of the distance's and the rays' gradients, with fp64 rows. Every product W_ik gP_i is exact in fp64. Bitwise reproducible.
 #include "common.h"
 #include "groupby.h"
+#include "meshbvh.h"
 #include "meshface.h"
 #include <algorithm>
 #include <cmath>
@@ -236,22 +237,10 @@ __global__ __launch_bounds__(BLOCK) void k_sp_sample(const float* __restrict__ v
 }
 
 // ---- gradient ----------------------------------------------------------------------------------------------------------------------
-// the group-by key of a sample: its face, or F ("no group") for an I outside [0, F)
-__global__ __launch_bounds__(BLOCK) void k_sp_keys(const int64_t* __restrict__ I, int n, int F, int* __restrict__ keys) {
-    const int i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const int64_t f = I[i];
-    keys[i] = (f < 0 || f >= F) ? F : (int)f;
-}
-
-__device__ __forceinline__ double sp_wave_sum_xor(double v) {
-#pragma unroll
-    for (int m = WAVE / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, WAVE);
-    return v;
-}
-
+// rows[f][3 k + q] = sum over the samples of face f, in sorted order, of W_ik gP_iq: the G of seg_sum, in fp64
 struct SpRows {
     const float* __restrict__ W; const float* __restrict__ gP; const int* __restrict__ order; const int* __restrict__ seg; double* __restrict__ rows;
+    __device__ __forceinline__ int count(int64_t key) const { return seg[key + 1] - seg[key]; }
     // adds the samples start, start + step, ... of face `key` to acc, in order
     __device__ __forceinline__ void walk(int64_t key, int start, int step, double (&acc)[9]) const {
         const int e = seg[key + 1];
@@ -272,48 +261,6 @@ struct SpRows {
     }
 };
 
-// rows[f][3 k + q] = sum over the samples of face f, in sorted order, of W_ik gP_iq: seg_sum of groupby.h in fp64
-__global__ __launch_bounds__(BLOCK) void k_sp_face_rows(SpRows r, int64_t F) {
-    const int64_t k = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    const int lane = threadIdx.x & (WAVE - 1);
-    const bool ok = k < F;
-    const bool lng = ok && r.seg[k + 1] - r.seg[k] > WAVE;
-    if (ok && !lng) {
-        double acc[9];
-#pragma unroll
-        for (int q = 0; q < 9; ++q) acc[q] = 0.0;
-        r.walk(k, 0, 1, acc);
-        r.store(k, acc);
-    }
-    unsigned long long m = __ballot(lng);
-    while (m) {                                       // (wave-uniform)
-        const int src = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        const int64_t kk = (int64_t)blockIdx.x * BLOCK + (threadIdx.x & ~(WAVE - 1)) + src;
-        double acc[9];
-#pragma unroll
-        for (int q = 0; q < 9; ++q) acc[q] = 0.0;
-        r.walk(kk, lane, WAVE, acc);
-#pragma unroll
-        for (int q = 0; q < 9; ++q) acc[q] = sp_wave_sum_xor(acc[q]);
-        if (lane == 0) r.store(kk, acc);
-    }
-}
-
-// gV[v] = fp32 of the fp64 sum, in rank order, of the rows of the vertex's corners (0 for a vertex without faces)
-__global__ __launch_bounds__(BLOCK) void k_sp_gather_verts(const double* __restrict__ rows, const int* __restrict__ vptr, const int* __restrict__ order,
-                                                           int64_t V, float* __restrict__ gV) {
-    const int64_t v = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (v >= V) return;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-    for (int r = vptr[v]; r < vptr[v + 1]; ++r) {
-        const int c = order[r];
-        const double* row = rows + (size_t)(c / 3) * 9 + 3 * (c % 3);
-        s0 += row[0]; s1 += row[1]; s2 += row[2];
-    }
-    gV[3 * v] = (float)s0; gV[3 * v + 1] = (float)s1; gV[3 * v + 2] = (float)s2;
-}
-
 }  // namespace ls
 
 using namespace ls;
@@ -321,13 +268,13 @@ using namespace ls;
 namespace {
 struct SpWs {          // the regions of the workspace: the forward's and the backward's overlap (a call is one or the other)
     size_t scal, cumq, lev1, lev2, tsum, fwd;           // forward: [0] amax bits, [1] Q; F, F / 16, F / 256 and tiles + 1 words
-    size_t keys, order, seg, sort, rows, bwd;           // backward
+    MdWs bwd;                                           // backward: md_vertex_grad's, with fp64 rows
     size_t total;
 };
 size_t sp_al(size_t x) { return (x + 255) & ~(size_t)255; }
 SpWs sp_layout(int64_t F, int64_t n) {
     SpWs w;
-    const int64_t m = std::max<int64_t>(n, 1), tiles = (F + SP_TILE - 1) / SP_TILE;
+    const int64_t tiles = (F + SP_TILE - 1) / SP_TILE;
     size_t o = 0;
     w.scal = o; o += sp_al(16);
     w.cumq = o; o += sp_al(8 * (size_t)std::max<int64_t>(F, 1));
@@ -335,14 +282,8 @@ SpWs sp_layout(int64_t F, int64_t n) {
     w.lev2 = o; o += sp_al(8 * (size_t)((F + SP_FAN2 - 1) / SP_FAN2 + 1));
     w.tsum = o; o += sp_al(8 * (size_t)(tiles + 1));
     w.fwd = o;
-    o = 0;
-    w.keys = o; o += sp_al(4 * (size_t)m);
-    w.order = o; o += sp_al(4 * (size_t)m);
-    w.seg = o; o += sp_al(4 * (size_t)(F + 2));
-    w.sort = o; o += sp_al(sort_scratch_bytes(m, true));
-    w.rows = o; o += sp_al(72 * (size_t)std::max<int64_t>(F, 1));
-    w.bwd = o;
-    w.total = std::max(w.fwd, w.bwd);
+    w.bwd = md_layout(n, F, false, sizeof(double) * 9);
+    w.total = std::max(w.fwd, w.bwd.total);
     return w;
 }
 // n is bounded below 2^31 - BLOCK: the sort's grids round it up to a workgroup
@@ -412,15 +353,8 @@ extern "C" int ls_sample_surface_backward(const void* faces, int idx_bytes, int6
         LS_HIP(hipMemsetAsync(gV, 0, sizeof(float) * 3 * (size_t)V, st));
         return LS_OK;
     }
-    char* w = (char*)ws;
-    int* keys = (int*)(w + L.keys);
-    int* order = (int*)(w + L.order);
-    int* seg = (int*)(w + L.seg);
-    double* rows = (double*)(w + L.rows);
-    hipLaunchKernelGGL(k_sp_keys, dim3(div_up(n, BLOCK)), dim3(BLOCK), 0, st, I, (int)n, (int)F, keys);
-    if (int rc = group_by_key<true>(keys, n, F, order, seg, sort_scratch_carve(w + L.sort, n, true), st)) return rc;
-    hipLaunchKernelGGL(k_sp_face_rows, dim3(div_up(F, BLOCK)), dim3(BLOCK), 0, st, SpRows{W, gP, order, seg, rows}, F);
-    hipLaunchKernelGGL(k_sp_gather_verts, dim3(div_up(V, BLOCK)), dim3(BLOCK), 0, st, (const double*)rows, vptr, corner_order, V, gV);
+    const MdCarved<double> c = md_carve<double>(ws, L.bwd, n);
+    if (int rc = md_vertex_grad<double>(I, n, F, V, SpRows{W, gP, c.order, c.seg, c.rows}, vptr, corner_order, gV, c, st)) return rc;
     LS_HIP(hipGetLastError());
     return LS_OK;
 }

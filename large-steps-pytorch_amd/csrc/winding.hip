@@ -20,7 +20,7 @@
 //   r = the distance from p to the farthest corner of the node's box as lbvh.h stores it (fp32 bounds, margin included): a query inside
 //       the box always has |q - p| <= r.
 // They are computed without per-node loops and deterministically: the leaves write raw moments about the centre o of the vertex box
-// (plainly additive), a bottom-up pass in the pattern of k_lbvh_refit adds left + right in that operand order (the thread that arrives
+// (plainly additive), the bottom-up pass of the refit (lbvh_climb of lbvh.h) adds left + right in that operand order (the thread that arrives
 // second does the addition; which thread that is does not change the sum), and a pass per node re-centres from o to p:
 //   C = C' - N (x) s,   T_ijk = T'_ijk - s_j C'_ik - s_k C'_ij + s_j s_k N_i,   s = p - o.
 // The re-centring cancels terms of size Ar R^k (R the diagonal of the mesh's box) down to Ar r^k: a relative error of (R / r)^2 2^-53 in
@@ -74,27 +74,24 @@ __device__ __forceinline__ void wn_origin(const unsigned* __restrict__ bb, doubl
 }
 
 // the raw moments about o: a thread per leaf writes its face's, then climbs; at an internal node the thread that finds its sibling done
-// adds left + right (the pattern of k_lbvh_refit). Slots: S = sum |a| c at WN_P, 0 at WN_R and the pad, N, Ar, C', T' in their places
-__global__ __launch_bounds__(BLOCK) void k_wn_raw(const float* __restrict__ P, const int* __restrict__ faces, const int* __restrict__ tri, int T,
-                                                  const unsigned* __restrict__ bb, const int* __restrict__ left, const int* __restrict__ right,
-                                                  const int* __restrict__ parent, int* __restrict__ flag, double* __restrict__ mom) {
-    const int i = blockIdx.x * BLOCK + threadIdx.x;
+// adds left + right (lbvh_climb). Slots: S = sum |a| c at WN_P, 0 at WN_R and the pad, N, Ar, C', T' in their places
+__global__ __launch_bounds__(BLOCK) void k_wn_raw(const MeshView mesh, const unsigned* __restrict__ bb, const int* __restrict__ parent,
+                                                  int* __restrict__ flag, double* __restrict__ mom) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x, T = mesh.T;
     if (i >= T) return;
     double o[3];
     wn_origin(bb, o);
-    const size_t f = (size_t)tri[i];
     double y[3][3];
+    mesh_corners(mesh, (size_t)mesh.tri[i], &y[0][0]);
 #pragma unroll
-    for (int v = 0; v < 3; ++v) {
-        const size_t p = 3 * (size_t)faces[3 * f + v];
+    for (int v = 0; v < 3; ++v)
 #pragma unroll
-        for (int k = 0; k < 3; ++k) y[v][k] = (double)P[p + k] - o[k];
-    }
+        for (int k = 0; k < 3; ++k) y[v][k] -= o[k];
     const double e1[3] = {y[1][0] - y[0][0], y[1][1] - y[0][1], y[1][2] - y[0][2]}, e2[3] = {y[2][0] - y[0][0], y[2][1] - y[0][1], y[2][2] - y[0][2]};
     const double a[3] = {0.5 * (e1[1] * e2[2] - e1[2] * e2[1]), 0.5 * (e1[2] * e2[0] - e1[0] * e2[2]), 0.5 * (e1[0] * e2[1] - e1[1] * e2[0])};
     const double ar = sqrt(lbvh_dd(a[0], a[1], a[2], a[0], a[1], a[2]));
     const double c[3] = {((y[0][0] + y[1][0]) + y[2][0]) / 3.0, ((y[0][1] + y[1][1]) + y[2][1]) / 3.0, ((y[0][2] + y[1][2]) + y[2][2]) / 3.0};
-    int node = T - 1 + i;
+    const int node = T - 1 + i;
     double* m = mom + (size_t)WN_STRIDE * node;
 #pragma unroll
     for (int k = 0; k < 3; ++k) { m[WN_P + k] = ar * c[k]; m[WN_N + k] = a[k]; }
@@ -111,17 +108,12 @@ __global__ __launch_bounds__(BLOCK) void k_wn_raw(const float* __restrict__ P, c
             }
         }
     if (T == 1) return;
-    node = parent[node];
-    while (node >= 0) {
-        __threadfence();
-        if (atomicAdd(&flag[node], 1) == 0) return;       // the sibling's subtree is not done yet: its last thread goes on
-        __threadfence();
-        const volatile double* l = mom + (size_t)WN_STRIDE * left[node];
-        const volatile double* r = mom + (size_t)WN_STRIDE * right[node];
-        double* out = mom + (size_t)WN_STRIDE * node;
+    lbvh_climb(node, mesh.left, mesh.right, parent, flag, [&](int nd, int lc, int rc) {
+        const volatile double* l = mom + (size_t)WN_STRIDE * lc;
+        const volatile double* r = mom + (size_t)WN_STRIDE * rc;
+        double* out = mom + (size_t)WN_STRIDE * nd;
         for (int q = 0; q < WN_STRIDE; ++q) out[q] = l[q] + r[q];
-        node = parent[node];
-    }
+    });
 }
 
 // a thread per node: p, r and the moments about p from the raw ones about o
@@ -193,56 +185,42 @@ __device__ __forceinline__ double wn_far(const double* __restrict__ m, const dou
 }
 
 // one thread per query: the walk
-__global__ __launch_bounds__(BLOCK) void k_wn_walk(const float* __restrict__ Q, int n, const float* __restrict__ P, const int* __restrict__ faces, int T,
-                                                   const int* __restrict__ tri, const int* __restrict__ left, const int* __restrict__ esc,
-                                                   const double* __restrict__ mom, double beta, double* __restrict__ w) {
+__global__ __launch_bounds__(BLOCK) void k_wn_walk(const float* __restrict__ Q, int n, const MeshView mesh, const double* __restrict__ mom, double beta,
+                                                   double* __restrict__ w) {
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
     const double q[3] = {(double)Q[3 * (size_t)i], (double)Q[3 * (size_t)i + 1], (double)Q[3 * (size_t)i + 2]};
     if (!(isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2]))) { w[i] = wn_nan(); return; }
-    const int leaf0 = T - 1;
+    const int leaf0 = mesh.T - 1;
     double acc = 0.0;
     int node = 0;
     while (node >= 0) {
         const double* m = mom + (size_t)WN_STRIDE * node;
         const double rho[3] = {m[WN_P] - q[0], m[WN_P + 1] - q[1], m[WN_P + 2] - q[2]};
         const double d2 = lbvh_dd(rho[0], rho[1], rho[2], rho[0], rho[1], rho[2]), d = sqrt(d2);
-        if (d > beta * m[WN_R]) { acc += wn_far(m, rho, d2, d) / WN_4PI; node = esc[node]; continue; }
+        if (d > beta * m[WN_R]) { acc += wn_far(m, rho, d2, d) / WN_4PI; node = mesh.esc[node]; continue; }
         if (node >= leaf0) {
-            const size_t f = (size_t)tri[node - leaf0];
-            double c[3][3];
-#pragma unroll
-            for (int v = 0; v < 3; ++v) {
-                const size_t p = 3 * (size_t)faces[3 * f + v];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) c[v][k] = (double)P[p + k];
-            }
-            acc += wn_face(q, c[0], c[1], c[2]);
-            node = esc[node];
-        } else node = left[node];
+            double c[9];
+            mesh_corners(mesh, (size_t)mesh.tri[node - leaf0], c);
+            acc += wn_face(q, c, c + 3, c + 6);
+            node = mesh.esc[node];
+        } else node = mesh.left[node];
     }
     w[i] = acc;
 }
 
 // the exact sum: a query per thread, tiles of WN_TILE faces' corners in LDS, added in ascending face id
-__global__ __launch_bounds__(WN_TILE) void k_wn_exact(const float* __restrict__ Q, int n, const float* __restrict__ P, const int* __restrict__ faces, int T,
-                                                      double* __restrict__ w) {
+__global__ __launch_bounds__(WN_TILE) void k_wn_exact(const float* __restrict__ Q, int n, const MeshView mesh, double* __restrict__ w) {
     __shared__ double tile[WN_TILE][9];
     const int i = blockIdx.x * WN_TILE + threadIdx.x;
     const size_t qi = (size_t)(i < n ? i : n - 1);
     const double q[3] = {(double)Q[3 * qi], (double)Q[3 * qi + 1], (double)Q[3 * qi + 2]};
+    const int T = mesh.T;
     double acc = 0.0;
     for (int base = 0; base < T; base += WN_TILE) {
         const int f = base + (int)threadIdx.x;
         __syncthreads();
-        if (f < T) {
-#pragma unroll
-            for (int v = 0; v < 3; ++v) {
-                const size_t p = 3 * (size_t)faces[3 * (size_t)f + v];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) tile[threadIdx.x][3 * v + k] = (double)P[p + k];
-            }
-        }
+        if (f < T) mesh_corners(mesh, (size_t)f, tile[threadIdx.x]);
         __syncthreads();
         const int m = min(WN_TILE, T - base);
         for (int t = 0; t < m; ++t) acc += wn_face(q, &tile[t][0], &tile[t][3], &tile[t][6]);
@@ -282,8 +260,7 @@ extern "C" int ls_mesh_winding_prepare(void* handle, void* moments, void* stream
     double* mom = (double*)((char*)moments + L.mom);
     int* flag = (int*)((char*)moments + L.flag);
     LS_HIP(hipMemsetAsync(flag, 0, sizeof(int) * (size_t)T, st));
-    hipLaunchKernelGGL(k_wn_raw, dim3(div_up(T, BLOCK)), dim3(BLOCK), 0, st, (const float*)H->pos, (const int*)H->faces, (const int*)H->bvh.tri, T,
-                       (const unsigned*)H->bvh.bb, (const int*)H->bvh.left, (const int*)H->bvh.right, (const int*)H->bvh.parent, flag, mom);
+    hipLaunchKernelGGL(k_wn_raw, dim3(div_up(T, BLOCK)), dim3(BLOCK), 0, st, H->view(), (const unsigned*)H->bvh.bb, (const int*)H->bvh.parent, flag, mom);
     hipLaunchKernelGGL(k_wn_centre, dim3(div_up(N, BLOCK)), dim3(BLOCK), 0, st, N, (const unsigned*)H->bvh.bb, (const float*)H->bvh.box, mom);
     LS_HIP(hipGetLastError());
     return LS_OK;
@@ -296,8 +273,7 @@ extern "C" int ls_mesh_winding_exact(void* handle, const float* P, int64_t n, do
     if (n == 0) return LS_OK;
     DeviceGuard g(H->device);
     LS_HIP(g.err);
-    hipLaunchKernelGGL(k_wn_exact, dim3(div_up(n, WN_TILE)), dim3(WN_TILE), 0, (hipStream_t)stream, P, (int)n, (const float*)H->pos, (const int*)H->faces,
-                       H->T, w);
+    hipLaunchKernelGGL(k_wn_exact, dim3(div_up(n, WN_TILE)), dim3(WN_TILE), 0, (hipStream_t)stream, P, (int)n, H->view(), w);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
@@ -311,8 +287,7 @@ extern "C" int ls_mesh_winding_query(void* handle, const void* moments, const fl
     if (n == 0) return LS_OK;
     DeviceGuard g(H->device);
     LS_HIP(g.err);
-    hipLaunchKernelGGL(k_wn_walk, dim3(div_up(n, BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, P, (int)n, (const float*)H->pos, (const int*)H->faces, H->T,
-                       (const int*)H->bvh.tri, (const int*)H->bvh.left, (const int*)H->bvh.esc,
+    hipLaunchKernelGGL(k_wn_walk, dim3(div_up(n, BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, P, (int)n, H->view(),
                        (const double*)((const char*)moments + wn_layout(H->T).mom), beta, w);
     LS_HIP(hipGetLastError());
     return LS_OK;

@@ -102,27 +102,22 @@ def _on(x, device):
     return torch.from_numpy(x).to(device)
 
 
-def _backward_workspace(n, F, dev):
+def _workspace(size_fn_name, *sizes, device):
+    """a uint8 buffer on `device` of as many bytes as the native size function of that name asks for `sizes`"""
     c = ctypes.c_size_t(0)
-    _native.check(_native.lib().ls_mesh_distance_backward_workspace_bytes(n, F, ctypes.byref(c)))
-    return torch.empty(c.value, dtype=torch.uint8, device=dev)
+    _native.check(getattr(_native.lib(), size_fn_name)(*sizes, ctypes.byref(c)))
+    return torch.empty(c.value, dtype=torch.uint8, device=device)
 
 
 @_native.retry_on_oom
 def _gradients(m, p, I, C, g, need_p, need_v):
     """(gP or None, gV or None) of one backward pass: its allocations and the native call"""
-    n, dev = p.shape[0], m.device
+    n = p.shape[0]
     g = g.to(torch.float64).contiguous()
     gP = torch.empty_like(p) if need_p else None
-    gV = vptr = order = ws = None
-    if need_v:
-        gV = torch.empty_like(m.V)
-        vptr, order = m._corner_ranks()
-        ws = _backward_workspace(n, m._f.shape[0], dev)
-    with torch.cuda.device(dev):
-        _native.check(_native.lib().ls_mesh_distance_backward(m._h, _native.ptr(p), n, _native.ptr(I), _native.ptr(C), _native.ptr(g),
-                                                              _native.ptr(vptr), _native.ptr(order), _native.ptr(gP), _native.ptr(gV),
-                                                              _native.ptr(ws), ws.numel() if ws is not None else 0, _native.stream_of(dev)))
+    gV, vptr, order, ws = m._vertex_grad_buffers("ls_mesh_distance_backward_workspace_bytes", n, need_v)
+    m._call("ls_mesh_distance_backward", _native.ptr(p), n, _native.ptr(I), _native.ptr(C), _native.ptr(g), _native.ptr(vptr), _native.ptr(order),
+            _native.ptr(gP), _native.ptr(gV), _native.ptr(ws), ws.numel() if ws is not None else 0)
     return gP, gV
 
 
@@ -145,12 +140,7 @@ class _SquaredDistance(Function):
     def backward(ctx, g, _gI, _gC):
         p, I, C = ctx.saved_tensors
         m = ctx.m
-        if not m._h:
-            raise RuntimeError("mesh distance: the handle of this forward pass was closed before its backward pass")
-        if m._version != ctx.version:
-            raise RuntimeError("mesh distance: the handle was updated after this forward pass; it no longer holds the positions the "
-                               "distances were computed from. Run the backward pass before MeshDistance.update")
-        m._check_source()
+        m._check_backward(ctx.version, "mesh distance", "distances", "MeshDistance")
         gP, gV = _gradients(m, p, I, C, g, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         return gP, gV, None
 
@@ -215,6 +205,43 @@ class MeshDistance:
             raise RuntimeError("mesh distance: the tensor V this handle was built from was changed in place; the handle still holds the "
                                "old positions. Call MeshDistance.update(V) after changing V")
 
+    def _check_backward(self, version, what, results, cls):
+        """the fences of a backward pass whose forward pass saw this handle at `version`: the handle still open, not updated since, its
+        source tensor not changed in place. `what`, `results` and `cls` are the words of the caller's messages"""
+        if not self._h:
+            raise RuntimeError(f"{what}: the handle of this forward pass was closed before its backward pass")
+        if self._version != version:
+            raise RuntimeError(f"{what}: the handle was updated after this forward pass; it no longer holds the positions the "
+                               f"{results} were computed from. Run the backward pass before {cls}.update")
+        self._check_source()
+
+    def _call(self, name, *args):
+        """the native function `name`(handle, *args, stream) on the handle's device and its current stream; raises what its status means"""
+        with torch.cuda.device(self.device):
+            _native.check(getattr(_native.lib(), name)(self._h, *args, _native.stream_of(self.device)))
+
+    @classmethod
+    def _for_call(cls, V, F, query):
+        """query(m) for a handle m built for this one call. The handle is closed on return unless the first result is a tensor that
+        requires grad: its graph then keeps the handle, which is released with the graph"""
+        m = cls(V, F)
+        out = None
+        try:
+            out = query(m)
+            return out
+        finally:
+            if not (out is not None and isinstance(out[0], torch.Tensor) and out[0].requires_grad):
+                m.close()
+
+    def _vertex_grad_buffers(self, size_fn_name, n, need_v):
+        """(gV, vptr, order, ws) of a backward pass over n items: the gradient to V, the corner ranking and the native workspace, or
+        four None when V needs no gradient"""
+        if not need_v:
+            return None, None, None, None
+        gV = torch.empty_like(self.V)
+        vptr, order = self._corner_ranks()
+        return gV, vptr, order, _workspace(size_fn_name, n, self._f.shape[0], device=self.device)
+
     def _corner_ranks(self):
         """(vptr, rank -> corner) of the faces, the summation order of the gradient to V (largesteps.normals._plan)"""
         if self._ranks is None:
@@ -232,8 +259,7 @@ class MeshDistance:
         if not self._h:
             raise RuntimeError("mesh distance: update of a closed handle")
         v = _on(v, self.device)
-        with torch.cuda.device(self.device):
-            _native.check(_native.lib().ls_mesh_distance_update(self._h, _native.ptr(v), _native.stream_of(self.device)))
+        self._call("ls_mesh_distance_update", _native.ptr(v))
         self.V = v
         self._version += 1
         self._remember(V)
@@ -262,9 +288,7 @@ class MeshDistance:
         sqrD = torch.empty(n, dtype=torch.float64, device=self.device)
         I = torch.empty(n, dtype=torch.int64, device=self.device)
         C = torch.empty((n, 3), dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            _native.check(_native.lib().ls_mesh_distance_query(self._h, _native.ptr(p), n, _native.ptr(sqrD), _native.ptr(I), _native.ptr(C),
-                                                               _native.stream_of(self.device)))
+        self._call("ls_mesh_distance_query", _native.ptr(p), n, _native.ptr(sqrD), _native.ptr(I), _native.ptr(C))
         return sqrD, I, C
 
     def max_squared_distance(self, P):
@@ -272,19 +296,15 @@ class MeshDistance:
         the device for a tensor (no synchronisation)."""
         p, p_np = self._points(P)
         out = torch.empty((), dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            _native.check(_native.lib().ls_mesh_distance_max(self._h, _native.ptr(p), p.shape[0], _native.ptr(out), _native.stream_of(self.device)))
+        self._call("ls_mesh_distance_max", _native.ptr(p), p.shape[0], _native.ptr(out))
         return float(out) if p_np else out
 
     def _moments(self):
         """the moment buffer of the winding walk, prepared on the first winding query after construction or `update`"""
         if self._wn_version != self._version:
             if self._wn is None:
-                c = ctypes.c_size_t(0)
-                _native.check(_native.lib().ls_mesh_winding_bytes(self._f.shape[0], ctypes.byref(c)))
-                self._wn = torch.empty(c.value, dtype=torch.uint8, device=self.device)
-            with torch.cuda.device(self.device):
-                _native.check(_native.lib().ls_mesh_winding_prepare(self._h, _native.ptr(self._wn), _native.stream_of(self.device)))
+                self._wn = _workspace("ls_mesh_winding_bytes", self._f.shape[0], device=self.device)
+            self._call("ls_mesh_winding_prepare", _native.ptr(self._wn))
             self._wn_version = self._version
         return self._wn
 
@@ -293,9 +313,7 @@ class MeshDistance:
             raise RuntimeError("mesh distance: query of a closed handle")
         w = torch.empty(p.shape[0], dtype=torch.float64, device=self.device)
         mom = None if beta == math.inf else self._moments()
-        with torch.cuda.device(self.device):
-            _native.check(_native.lib().ls_mesh_winding_query(self._h, _native.ptr(mom), _native.ptr(p), p.shape[0], beta, _native.ptr(w),
-                                                              _native.stream_of(self.device)))
+        self._call("ls_mesh_winding_query", _native.ptr(mom), _native.ptr(p), p.shape[0], beta, _native.ptr(w))
         return w
 
     @_native.retry_on_oom
@@ -371,14 +389,7 @@ def point_mesh_squared_distance(P, V, F):
     give tensors on their device. sqrD is differentiable in tensors P and V that require grad (module docstring); its graph then keeps
     the handle, which is released with the graph instead of on return. The release synchronises the device, so let the graph go (drop sqrD
     and the tensors computed from it) outside any stream capture; with a MeshDistance of your own, `close()` decides the moment."""
-    m = MeshDistance(V, F)
-    out = None
-    try:
-        out = m.squared_distance(P)
-        return out
-    finally:
-        if not (out is not None and isinstance(out[0], torch.Tensor) and out[0].requires_grad):
-            m.close()
+    return MeshDistance._for_call(V, F, lambda m: m.squared_distance(P))
 
 
 @_native.retry_on_oom
@@ -402,14 +413,7 @@ def signed_distance(P, V, F, beta=2.0):
     for name, X in (("P", P), ("V", V)):
         _as_points(X, name)
     _as_faces(F)
-    m = MeshDistance(V, F)
-    out = None
-    try:
-        out = m.signed_distance(P, beta)
-        return out
-    finally:
-        if not (out is not None and isinstance(out[0], torch.Tensor) and out[0].requires_grad):
-            m.close()
+    return MeshDistance._for_call(V, F, lambda m: m.signed_distance(P, beta))
 
 
 @_native.retry_on_oom

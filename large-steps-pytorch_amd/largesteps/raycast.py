@@ -30,7 +30,6 @@ body, after one eager warm-up pass (the first gradient to V builds the corner ra
 Input conventions are those of `distance`: numpy input runs on the current HIP device and returns numpy; tensors (O, D, V float32, F
 int32 / int64, on one HIP device) return tensors on that device. CPU tensors raise.
 """
-import ctypes
 import math
 
 import numpy as np
@@ -88,29 +87,17 @@ def _trange(tmin, tmax, n, dev):
     return tr
 
 
-def _backward_workspace(n, F, dev):
-    c = ctypes.c_size_t(0)
-    _native.check(_native.lib().ls_mesh_ray_backward_workspace_bytes(n, F, ctypes.byref(c)))
-    return torch.empty(c.value, dtype=torch.uint8, device=dev)
-
-
 @_native.retry_on_oom
 def _gradients(m, o, d, I, W, t, g, need_o, need_d, need_v):
     """(gO, gD, gV), each or None, of one backward pass: its allocations and the native call"""
-    n, dev = o.shape[0], m.device
+    n = o.shape[0]
     g = g.to(torch.float64).contiguous()
     gO = torch.empty_like(o) if need_o else None
     gD = torch.empty_like(d) if need_d else None
-    gV = vptr = order = ws = None
-    if need_v:
-        gV = torch.empty_like(m.V)
-        vptr, order = m._corner_ranks()
-        ws = _backward_workspace(n, m._f.shape[0], dev)
-    with torch.cuda.device(dev):
-        _native.check(_native.lib().ls_mesh_ray_backward(m._h, _native.ptr(o), _native.ptr(d), n, _native.ptr(I), _native.ptr(W), _native.ptr(t),
-                                                         _native.ptr(g), _native.ptr(vptr), _native.ptr(order), _native.ptr(gO), _native.ptr(gD),
-                                                         _native.ptr(gV), _native.ptr(ws), ws.numel() if ws is not None else 0,
-                                                         _native.stream_of(dev)))
+    gV, vptr, order, ws = m._vertex_grad_buffers("ls_mesh_ray_backward_workspace_bytes", n, need_v)
+    m._call("ls_mesh_ray_backward", _native.ptr(o), _native.ptr(d), n, _native.ptr(I), _native.ptr(W), _native.ptr(t), _native.ptr(g),
+            _native.ptr(vptr), _native.ptr(order), _native.ptr(gO), _native.ptr(gD), _native.ptr(gV), _native.ptr(ws),
+            ws.numel() if ws is not None else 0)
     return gO, gD, gV
 
 
@@ -133,12 +120,7 @@ class _Intersect(Function):
     def backward(ctx, g, _gI, _gW):
         o, d, t, I, W = ctx.saved_tensors
         m = ctx.m
-        if not m._h:
-            raise RuntimeError("ray mesh: the handle of this forward pass was closed before its backward pass")
-        if m._version != ctx.version:
-            raise RuntimeError("ray mesh: the handle was updated after this forward pass; it no longer holds the positions the "
-                               "hits were computed from. Run the backward pass before RayMesh.update")
-        m._check_source()
+        m._check_backward(ctx.version, "ray mesh", "hits", "RayMesh")
         gO, gD, gV = _gradients(m, o, d, I, W, t, g, *ctx.needs_input_grad[:3])
         return gO, gD, gV, None, None
 
@@ -159,9 +141,7 @@ class RayMesh(MeshDistance):
         t = torch.empty(n, dtype=torch.float64, device=self.device)
         I = torch.empty(n, dtype=torch.int64, device=self.device)
         W = torch.empty((n, 3), dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            _native.check(_native.lib().ls_mesh_ray_closest(self._h, _native.ptr(o), _native.ptr(d), n, _native.ptr(trange), _native.ptr(t),
-                                                            _native.ptr(I), _native.ptr(W), _native.stream_of(self.device)))
+        self._call("ls_mesh_ray_closest", _native.ptr(o), _native.ptr(d), n, _native.ptr(trange), _native.ptr(t), _native.ptr(I), _native.ptr(W))
         return t, I, W
 
     @_native.retry_on_oom
@@ -189,9 +169,7 @@ class RayMesh(MeshDistance):
         range, found by a walk that stops at the first accepted face. Not differentiable."""
         o, d, trange, was_np = self._rays(O, D, tmin, tmax)
         hit = torch.empty(o.shape[0], dtype=torch.bool, device=self.device)
-        with torch.cuda.device(self.device):
-            _native.check(_native.lib().ls_mesh_ray_any(self._h, _native.ptr(o), _native.ptr(d), o.shape[0], _native.ptr(trange), _native.ptr(hit),
-                                                        _native.stream_of(self.device)))
+        self._call("ls_mesh_ray_any", _native.ptr(o), _native.ptr(d), o.shape[0], _native.ptr(trange), _native.ptr(hit))
         return hit.cpu().numpy() if was_np else hit
 
 
@@ -202,14 +180,7 @@ def ray_mesh_intersect(O, D, V, F, tmin=0.0, tmax=math.inf):
     require grad; its graph then keeps the handle, which is released with the graph instead of on return. The release synchronises the
     device, so let the graph go outside any stream capture; with a RayMesh of your own, `close()` decides the moment."""
     _as_rays(O, D, tmin, tmax)                                        # the ray checks, before the handle is built
-    m = RayMesh(V, F)
-    out = None
-    try:
-        out = m.intersect(O, D, tmin, tmax)
-        return out
-    finally:
-        if not (out is not None and isinstance(out[0], torch.Tensor) and out[0].requires_grad):
-            m.close()
+    return RayMesh._for_call(V, F, lambda m: m.intersect(O, D, tmin, tmax))
 
 
 @_native.retry_on_oom

@@ -35,15 +35,13 @@ itself never follows such an index: the face just is not drawn).
 Input conventions follow largesteps.distance: tensor input (V float32, F int32 / int64, on one HIP device) returns tensors on that
 device; numpy input (V real, converted to float32; F integer) runs on the current HIP device and returns numpy. CPU tensors raise.
 """
-import ctypes
-
 import numpy as np
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _native
-from .distance import _as_faces, _as_points, _current_device, _on
+from .distance import _as_faces, _as_points, _current_device, _on, _workspace
 from .normals import _plan
 
 SCAN_TILE = 2048            # LS_SAMPLE_SCAN_TILE of the header: the faces one workgroup of the 64-bit scan owns
@@ -58,12 +56,6 @@ def _uint(x, what, bits):
     return x
 
 
-def _workspace(F, n, dev):
-    c = ctypes.c_size_t(0)
-    _native.check(_native.lib().ls_sample_workspace_bytes(F, n, ctypes.byref(c)))
-    return torch.empty(c.value, dtype=torch.uint8, device=dev)
-
-
 @_native.retry_on_oom
 def _forward(v, f, n, seed, stream, offset):
     dev = v.device
@@ -71,7 +63,7 @@ def _forward(v, f, n, seed, stream, offset):
     I = torch.empty(n, dtype=torch.int64, device=dev)
     W = torch.empty((n, 3), dtype=torch.float32, device=dev)
     if n:
-        ws = _workspace(f.shape[0], n, dev)
+        ws = _workspace("ls_sample_workspace_bytes", f.shape[0], n, device=dev)
         with torch.cuda.device(dev):
             _native.check(_native.lib().ls_sample_surface(_native.ptr(v), _native.ptr(f), f.element_size(), f.shape[0], v.shape[0], n, seed, stream,
                                                           offset, _native.ptr(P), _native.ptr(I), _native.ptr(W), _native.ptr(ws), ws.numel(),
@@ -86,7 +78,7 @@ def _backward(f, nv, I, W, gP):
         return torch.zeros((nv, 3), dtype=torch.float32, device=dev)
     gV = torch.empty((nv, 3), dtype=torch.float32, device=dev)
     vptr, _, _, order = _plan(f, nv)
-    ws = _workspace(f.shape[0], n, dev)
+    ws = _workspace("ls_sample_workspace_bytes", f.shape[0], n, device=dev)
     gP = gP.to(torch.float32).contiguous()
     with torch.cuda.device(dev):
         _native.check(_native.lib().ls_sample_surface_backward(_native.ptr(f), f.element_size(), f.shape[0], nv, n, _native.ptr(I), _native.ptr(W),

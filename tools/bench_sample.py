@@ -98,7 +98,7 @@ for spec in workloads:
     W = torch.empty((n, 3), dtype=torch.float32, device=dev)
     gP = torch.randn((n, 3), dtype=torch.float32, device=dev)
     gV = torch.empty_like(V)
-    ws = _workspace(nF, n, dev)
+    ws = _workspace("ls_sample_workspace_bytes", nF, n, device=dev)
     vptr, _, _, order = _plan(F, nV)
 
     def forward():

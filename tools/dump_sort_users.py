@@ -8,7 +8,13 @@ Covered: remove_duplicates; the CSR transpose of an unsymmetric matrix (backward
 normals, forward and backward; rasterize / interpolate / antialias forward and every gradient; texture forward and both gradients in
 every filter x boundary mode; hausdorff; one remesh_botsch iteration; the direct solver's first solve on the 70k mesh. The renderer's
 shapes hold faces and texels with more than 64 pixels and with fewer (asserted: per face from the rast ids of both images, per texel
-from the nearest texel of every pixel), so both arms of the segmented sum are compared."""
+from the nearest texel of every pixel), so both arms of the segmented sum are compared.
+The queries over one mesh and its LBVH (csrc/lbvh.h, meshbvh.h) on the 70k mesh: squared_distance with both gradients, the closest
+point's weights, max_squared_distance, RayMesh.intersect with its three gradients and occluded, winding_number at beta = 2 and exact,
+the hierarchy and the node moments, signed_distance with its gradients, sample_surface with its vertex gradient, chamfer_distance
+with both gradients, and the distance again after one update. The query points are 2^16 surface samples pushed along the normal to
+both sides with a share uniform in the grown box, and 1024 more around one face's centroid, so that some face owns more than 64 points
+and some face between 1 and 64 (asserted): both arms of the segmented sum again."""
 import os
 import sys
 
@@ -143,6 +149,86 @@ def dump(out):
                 tag = f"texture_{Ht}_{filt}_{bnd}"
                 save(tag + "_out", o), save(tag + "_grad_tex", tex.grad)
                 save(tag + "_grad_uv", uv.grad if uv.grad is not None else torch.zeros_like(uv))
+    # ---- the mesh queries: one handle over the 70k mesh
+    import math
+    from largesteps import _native
+    from largesteps.distance import chamfer_distance
+    from largesteps.raycast import RayMesh
+    from largesteps.sampling import sample_surface
+
+    V70, n = torch.from_numpy(v70).to(dev), 1 << 16
+    S, SI, _ = sample_surface(V70, tf, n, seed=1)
+    a, b, c = (V70[tf[SI, k]] for k in range(3))
+    nrm = torch.nn.functional.normalize(torch.linalg.cross(b - a, c - a), dim=1)
+    h = float(((a - b).norm(dim=1) + (b - c).norm(dim=1) + (c - a).norm(dim=1)).mean()) / 3.0
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(2)
+    share = torch.randint(0, 7, (n,), generator=gen, device=dev)
+    off = torch.tensor([0.25, -0.25, 1.0, -1.0, 4.0, -4.0, 0.0], device=dev)[share] * h
+    lo, hi = V70.min(0).values, V70.max(0).values
+    box = (lo + hi) / 2 + (torch.rand((n, 3), generator=gen, device=dev) * 1.5 - 0.75) * (hi - lo)
+    near = V70[tf[0].long()].mean(0) + dev_f32(rng.standard_normal((1024, 3))) * (0.05 * h)
+    P = torch.cat([torch.where((share == 6)[:, None], box, S + off[:, None] * nrm), near]).contiguous()
+    save("query_points", P)
+    D = ((lo + hi) / 2 - P) + dev_f32(rng.standard_normal(tuple(P.shape))) * (0.1 * float((hi - lo).norm()))
+
+    def grads(loss, *xs):
+        return [g if g is not None else torch.zeros_like(x) for g, x in zip(torch.autograd.grad(loss, xs, allow_unused=True), xs)]
+
+    Vg, Pg = V70.clone().requires_grad_(True), P.clone().requires_grad_(True)
+    with RayMesh(Vg, tf) as m:
+        sqrD, I, C = m.squared_distance(Pg)
+        per_face = np.bincount(I.cpu().numpy(), minlength=f70.shape[0])
+        assert per_face.max() > 64 and 0 < per_face[per_face > 0].min() <= 64, "the points must give faces of more and of fewer than 64 points"
+        gP, gV = grads((sqrD * weights(sqrD).double()).sum(), Pg, Vg)
+        save("distance_sqrD", sqrD), save("distance_I", I), save("distance_C", C), save("distance_grad_P", gP), save("distance_grad_V", gV)
+        W = torch.empty((P.shape[0], 3), dtype=torch.float64, device=dev)
+        m._call("ls_mesh_distance_weights", _native.ptr(P), P.shape[0], _native.ptr(I), _native.ptr(W))
+        save("distance_weights", W), save("distance_max", m.max_squared_distance(P))
+
+        Og, Dg = P.clone().requires_grad_(True), D.clone().requires_grad_(True)
+        t, RI, RW = m.intersect(Og, Dg)
+        hit = RI >= 0
+        print(f"rays: {int(hit.sum())} of {hit.shape[0]} hit, at most {int(np.bincount(RI[hit].cpu().numpy()).max())} on one face")
+        gO, gD, gV = grads((torch.where(hit, t, torch.zeros_like(t)) * weights(t).double()).sum(), Og, Dg, Vg)
+        save("ray_t", t), save("ray_I", RI), save("ray_W", RW), save("ray_grad_O", gO), save("ray_grad_D", gD), save("ray_grad_V", gV)
+        save("ray_occluded", m.occluded(P, D))
+
+        save("winding_beta2", m.winding_number(P, 2.0)), save("winding_exact", m.winding_number(P[:1 << 12], math.inf))
+        T70 = f70.shape[0]
+        i32 = dict(dtype=torch.int32, device=dev)
+        arrays = dict(left=torch.zeros(T70 - 1, **i32), right=torch.zeros(T70 - 1, **i32), esc=torch.zeros(2 * T70 - 1, **i32), tri=torch.zeros(T70, **i32),
+                      box=torch.zeros((2 * T70 - 1, 6), dtype=torch.float32, device=dev), mom=torch.zeros((2 * T70 - 1, 36), dtype=torch.float64, device=dev))
+        m._call("ls_mesh_winding_arrays", _native.ptr(m._moments()), *(_native.ptr(x) for x in arrays.values()))
+        for name, x in arrays.items():
+            save("lbvh_" + name, x)
+        Sd, _, _ = m.signed_distance(Pg)
+        gP, gV = grads((Sd * weights(Sd).double()).sum(), Pg, Vg)
+        save("signed_distance", Sd), save("signed_distance_grad_P", gP), save("signed_distance_grad_V", gV)
+
+        V2 = dev_f32(synthetic.perturb(v70.astype(np.float64), radial=0.02, seed=3))
+        m.update(V2)
+        sqrD, I, C = m.squared_distance(P)
+        save("updated_sqrD", sqrD), save("updated_I", I), save("updated_C", C)
+
+    SP, SI, SW = sample_surface(Vg, tf, n, seed=5)
+    gV, = grads((SP * weights(SP)).sum(), Vg)
+    per_face = np.bincount(SI.cpu().numpy(), minlength=f70.shape[0])
+    print(f"samples: at most {per_face.max()} on one face")
+    save("sample_P", SP), save("sample_I", SI), save("sample_W", SW), save("sample_grad_V", gV)
+    # a mesh of few faces: every face draws far more than 64 samples, the wave-strided arm of the fp64 segmented sum
+    vq, fq = synthetic.icosphere(2)
+    Vq, Fq = dev_f32(vq).requires_grad_(True), torch.from_numpy(fq).to(dev)
+    SP, SI, _ = sample_surface(Vq, Fq, n, seed=6)
+    assert np.bincount(SI.cpu().numpy()).min() > 64
+    save("sample_few_faces_P", SP), save("sample_few_faces_grad_V", grads((SP * weights(SP)).sum(), Vq)[0])
+
+    VB = V2.clone().requires_grad_(True)
+    ch = chamfer_distance(Vg, tf, VB, tf, 1 << 14, seed=4)
+    gA, gB = grads(ch, Vg, VB)
+    save("chamfer", ch), save("chamfer_grad_VA", gA), save("chamfer_grad_VB", gB)
+    del ch, Sd, sqrD, t
+
     torch.cuda.synchronize()
     print(f"wrote {len(os.listdir(out))} files to {out} with {os.environ.get('LARGESTEPS_HIP_LIB', 'the package library')}")
     return 0
