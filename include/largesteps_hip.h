@@ -39,6 +39,7 @@
  *   ls_mesh_distance_*   igl.point_mesh_squared_distance / igl.hausdorff (figures/comparison/generate_data.py: the error column)
  *   ls_mesh_ray_*        igl.ray_mesh_intersect, and what igl.ambient_occlusion is built from: rays against the mesh of a distance handle
  *   ls_mesh_winding_*    igl.winding_number / igl.fast_winding_number, the sign of igl.signed_distance: over the same handle
+ *   ls_mesh_selfx_*      igl.fast_find_self_intersections: which faces of the handle's mesh cut through each other
  */
 #ifndef LARGESTEPS_HIP_H
 #define LARGESTEPS_HIP_H
@@ -735,6 +736,35 @@ int ls_mesh_winding_query(void* handle, const void* moments, const float* P, int
 int ls_mesh_winding_exact(void* handle, const float* P, int64_t n, double* w, void* stream);
 int ls_mesh_winding_arrays(void* handle, const void* moments, int32_t* left, int32_t* right, int32_t* esc, int32_t* tri, float* box,
                            double* mom, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The self-intersections of the mesh of a mesh-distance handle (libigl's fast_find_self_intersections; largesteps/distance.py). The
+ * rule is stated in csrc/selfx.hip and DESIGN.md section 2.12 and restated in numpy by tests/selfx_statement.py: a segment (p, q)
+ * crosses a face iff the ray rule above, with o = p and d = q - p formed in fp64, accepts the face with 0 <= t <= 1 (edges and vertices
+ * count, det == 0 never hits, d == 0 hits nothing). For faces f < g, s = the number of equal (corner of f, corner of g) index pairs
+ * among the nine: s >= 2 is never reported; s == 1 is reported iff the edge of f opposite the shared corner crosses g or the edge of g
+ * opposite it crosses f; s == 0 iff one of the three edges of f crosses g or one of the three edges of g crosses f. And a pair is
+ * reported only if the corner boxes of f and g (the smallest and largest of the three fp32 corners per axis) are within 2 e of each other
+ * on all three axes, e = 2^-40 x the largest |coordinate| of the vertices: apart on an axis iff lo_g - e > hi_f + e or
+ * hi_g + e < lo_f - e in fp64, false on a NaN. A real crossing always passes this clause; it leaves out what the segment test accepts on
+ * rounding alone between far-apart faces of an exactly flat sheet. Coplanar overlaps are not reported (det == 0; in a tilted plane
+ * whose shear rounds, det is a rounding error and coplanar faces with near boxes can be); faces without a common index that touch at a
+ * point or along a segment are.
+ *   ls_mesh_selfx_count            counts (F) int32: counts[f] = the number of reported pairs (f, g) with g > f; total (int64, device)
+ *                                  = their sum, the number of pairs; flags (F) one byte per face, or NULL: 1 iff the face is in some
+ *                                  reported pair (zeroed first). ASYNC, capturable: no allocation, no synchronisation.
+ *   ls_mesh_selfx_workspace_bytes  the workspace of ls_mesh_selfx_pairs for F faces and k pairs (256-byte aligned regions).
+ *   ls_mesh_selfx_pairs            pairs (k, 2) int64 = the reported pairs (f, g), f < g, sorted lexicographically, from `counts` as
+ *                                  ls_mesh_selfx_count filled them for the handle's current positions and k = its total. A pair past
+ *                                  its face's count or past k is dropped, never written; counts of another mesh leave rows of
+ *                                  zeros. k = 0 is a no-op. ASYNC.
+ * LS_E_INVALID for a null required pointer or a negative size, LS_E_OVERFLOW when 3 F or 2 k reaches 2^31, LS_E_WORKSPACE for a
+ * workspace below ls_mesh_selfx_workspace_bytes(F, k). The result depends on the mesh alone, not on the hierarchy: bitwise
+ * reproducible. The calls only read the handle; none may overlap ls_mesh_distance_update or ls_mesh_distance_destroy of it.
+ * --------------------------------------------------------------------------------------------- */
+int ls_mesh_selfx_count(void* handle, int32_t* counts, int64_t* total, unsigned char* flags, void* stream);
+int ls_mesh_selfx_workspace_bytes(int64_t F, int64_t k, size_t* bytes);
+int ls_mesh_selfx_pairs(void* handle, const int32_t* counts, int64_t k, int64_t* pairs, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Area-weighted points on a mesh surface and their gradient to the vertices (largesteps/sampling.py, and distance.chamfer_distance

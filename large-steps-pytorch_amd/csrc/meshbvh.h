@@ -1,5 +1,5 @@
 // meshbvh.h -- what the queries against one mesh share (distance.hip: point-to-mesh distance; raycast.hip: ray casting; winding.hip:
-// winding number; sample.hip: the gradient tail only). Three things:
+// winding number; selfx.hip: self-intersections; sample.hip: the gradient tail only). Three things:
 //   * the handle that owns a device copy of the mesh and the LBVH of lbvh.h over its faces (created, updated and destroyed in
 //     meshbvh.hip), and MeshView, what a query kernel reads of it, passed by value;
 //   * the guarded closest point of a query point on a face, with its barycentric weights on request;

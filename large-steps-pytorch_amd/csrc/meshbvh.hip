@@ -1,6 +1,6 @@
 // meshbvh.hip -- the handle of meshbvh.h: a device copy of one mesh (fp32 positions, int32 faces, the face indices checked) and the LBVH
-// of lbvh.h over its faces (leaf boxes exact: margin 0), in one buffer of the scratch pool. distance.hip, raycast.hip and winding.hip
-// query it; `update` replaces the positions and rebuilds the hierarchy in the same buffer. The entry points keep the names of the
+// of lbvh.h over its faces (leaf boxes exact: margin 0), in one buffer of the scratch pool. distance.hip, raycast.hip, winding.hip and
+// selfx.hip query it; `update` replaces the positions and rebuilds the hierarchy in the same buffer. The entry points keep the names of the
 // first query that had a handle, the distance.
 #include "common.h"
 #include "lbvh.h"

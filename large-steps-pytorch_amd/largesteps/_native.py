@@ -119,6 +119,9 @@ _SIGNATURES = {
     "ls_mesh_winding_query": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_double, c_void_p, c_void_p]),
     "ls_mesh_winding_exact": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p]),
     "ls_mesh_winding_arrays": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ls_mesh_selfx_count": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ls_mesh_selfx_workspace_bytes": (c_int, [c_i64, c_i64, ctypes.POINTER(c_size_t)]),
+    "ls_mesh_selfx_pairs": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ls_mesh_ray_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ls_sample_workspace_bytes": (c_int, [c_i64, c_i64, ctypes.POINTER(c_size_t)]),

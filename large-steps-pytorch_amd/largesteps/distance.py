@@ -38,6 +38,22 @@ Barill et al. 2018 over the same LBVH (csrc/winding.hip)
 pseudonormal sign it degrades gracefully on self-intersecting, folded and open meshes. The handle prepares the walk's node moments on
 the first winding query after construction or `update`; a handle that never asks pays nothing. Prepared, both queries are capturable.
 
+Does the mesh cut through itself? `MeshDistance.self_intersections()` lists the pairs of faces that do, `self_intersecting_faces()` marks
+their faces and `count_self_intersections()` counts the pairs without synchronising (a per-step metric): igl.fast_find_self_intersections
+(csrc/selfx.hip; tests/selfx_statement.py restates the rule). A pair of faces that share no vertex index is
+reported iff an edge of one crosses the other, by the watertight segment test of the ray queries in fp64; a pair that shares one index
+iff the edge opposite the shared corner of one crosses the other; a pair that shares two or three never. And a pair is reported only if
+the corner boxes of its two faces come within 2 e of each other on every axis, e = 2^-40 x the largest |coordinate| of V: a real crossing
+always does, and the clause leaves out what the segment test accepts on rounding alone between far-apart faces of an exactly flat
+sheet. Consequences:
+  * coplanar overlaps are not reported, a sheet folded flat onto itself included: a segment in a face's plane has det == 0. That is
+    exact where the arithmetic is (a plane along the axes, coordinates on a grid); in a tilted plane whose shear rounds, det is a
+    rounding error and coplanar faces with near boxes can be reported on it, the same ones on every run and in any face order;
+  * two faces that touch at a point or along a segment ARE reported when they share no index: run the query on the de-duplicated mesh
+    (largesteps.meshops.remove_duplicates, the reference's function of that name);
+  * an edge that passes exactly through the common edge of two faces is reported against at least one of them.
+The result depends on the mesh alone and is bitwise reproducible; none of the three is differentiable.
+
 Input conventions follow remesh_botsch: numpy input (V float64 or float32, converted to fp32; F integer) runs on the current HIP device
 and returns numpy; tensor input (V and query points fp32, F int32 / int64, all on one HIP device) returns tensors on that device. CPU
 tensors raise.
@@ -183,6 +199,7 @@ class MeshDistance:
         if v.shape[0] == 0:
             raise ValueError("mesh distance: the mesh has no vertices")
         self.device = _current_device() if v_np else v.device
+        self._numpy = v_np                 # the queries that take no points return numpy for a handle built from numpy; update keeps it
         self.V = _on(v, self.device)
         f = _on(f, self.device)
         self._f = f
@@ -352,6 +369,48 @@ class MeshDistance:
         S = np.where(w >= 0.5, -1.0, 1.0) * np.sqrt(sqrD)
         return np.where(np.isnan(w), w, S), I, C
 
+    def _selfx_count(self, with_flags):
+        """(counts (F,) int32, total 0-dim int64, flags (F,) uint8 or None) of the count pass; no synchronisation"""
+        if not self._h:
+            raise RuntimeError("mesh distance: query of a closed handle")
+        F = self._f.shape[0]
+        counts = torch.empty(F, dtype=torch.int32, device=self.device)
+        total = torch.empty((), dtype=torch.int64, device=self.device)
+        flags = torch.empty(F, dtype=torch.uint8, device=self.device) if with_flags else None
+        self._call("ls_mesh_selfx_count", _native.ptr(counts), _native.ptr(total), _native.ptr(flags))
+        return counts, total, flags
+
+    @_native.retry_on_oom
+    def count_self_intersections(self):
+        """The number of pairs of faces that cut through each other (module docstring; `self_intersections` lists them): a 0-dim int64
+        tensor on the handle's device, an int for a handle built from numpy. With a tensor handle it does not synchronise and, after
+        one eager warm-up call, can be captured in a torch.cuda.graph: a metric to read at every step. Not differentiable."""
+        total = self._selfx_count(False)[1]
+        return int(total) if self._numpy else total
+
+    @_native.retry_on_oom
+    def self_intersecting_faces(self):
+        """(F,) bool: True for every face in some pair of `self_intersections` -- the `intersect` vector of libigl's
+        fast_find_self_intersections. A tensor on the handle's device (no synchronisation), numpy for a handle built from numpy.
+        Not differentiable."""
+        flags = self._selfx_count(True)[2].to(torch.bool)
+        return flags.cpu().numpy() if self._numpy else flags
+
+    @_native.retry_on_oom
+    def self_intersections(self):
+        """IF (k, 2) int64: the pairs of faces (f, g), f < g, that cut through each other, sorted lexicographically; (0, 2) when there
+        are none. The rule and what follows from it (coplanar overlaps are not reported, touching faces without a common index are)
+        is in the module docstring. One count pass, one host read of k (synchronises), one fill pass. A tensor on the handle's device,
+        numpy for a handle built from numpy (`update` with either kind of V does not change that). Bitwise reproducible;
+        not differentiable."""
+        counts, total, _ = self._selfx_count(False)
+        k = int(total)
+        pairs = torch.empty((k, 2), dtype=torch.int64, device=self.device)
+        if k:
+            ws = _workspace("ls_mesh_selfx_workspace_bytes", self._f.shape[0], k, device=self.device)
+            self._call("ls_mesh_selfx_pairs", _native.ptr(counts), k, _native.ptr(pairs), _native.ptr(ws), ws.numel())
+        return pairs.cpu().numpy() if self._numpy else pairs
+
     def hausdorff(self, VA, FA):
         """hausdorff(VA, FA, V, F) of this mesh (V, F): only the other mesh's LBVH is built."""
         if (VA.shape[0] if isinstance(VA, torch.Tensor) else np.asarray(VA).shape[0]) == 0:
@@ -414,6 +473,39 @@ def signed_distance(P, V, F, beta=2.0):
         _as_points(X, name)
     _as_faces(F)
     return MeshDistance._for_call(V, F, lambda m: m.signed_distance(P, beta))
+
+
+def _mesh_checks(V, F):
+    """the type, dtype and shape checks of a mesh, before any device work"""
+    _as_points(V, "V")
+    _as_faces(F)
+
+
+@_native.retry_on_oom
+def self_intersections(V, F):
+    """IF (k, 2) int64, the pairs of faces of the mesh (V, F) that cut through each other: MeshDistance.self_intersections of a handle
+    built for this call. numpy input gives numpy, tensors give a tensor on their device. Not differentiable."""
+    _mesh_checks(V, F)
+    return MeshDistance._for_call(V, F, lambda m: (m.self_intersections(),))[0]
+
+
+@_native.retry_on_oom
+def count_self_intersections(V, F):
+    """The number of pairs of `self_intersections(V, F)` without listing them: MeshDistance.count_self_intersections of a handle built
+    for this call (building it synchronises; keep a handle and `update` it for a per-step metric). An int for numpy input, a 0-dim
+    int64 tensor for tensors. Not differentiable."""
+    _mesh_checks(V, F)
+    return MeshDistance._for_call(V, F, lambda m: (m.count_self_intersections(),))[0]
+
+
+@_native.retry_on_oom
+def fast_find_self_intersections(V, F):
+    """libigl's fast_find_self_intersections(V, F) -> (found, intersect): found is a bool, True iff some pair of faces cut through each
+    other, and intersect (F,) bool marks every face of such a pair (numpy for numpy input, a tensor on their device for tensors).
+    Synchronises (found comes to the host). Not differentiable."""
+    _mesh_checks(V, F)
+    intersect = MeshDistance._for_call(V, F, lambda m: (m.self_intersecting_faces(),))[0]
+    return bool(intersect.any()), intersect
 
 
 @_native.retry_on_oom
