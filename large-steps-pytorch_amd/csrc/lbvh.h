@@ -2,7 +2,9 @@
 // projection (remesh.hip) and, through the handle of meshbvh.h (built in meshbvh.hip), by the point-to-mesh distance (distance.hip), the
 // ray queries (raycast.hip) and the winding number (winding.hip); the last two walk it their own way.
 //
-// Build (lbvh_bounds, then lbvh_build): 30-bit Morton codes of the triangle centroids in the vertex box, the stable radix sort of
+// Build (lbvh_bounds, then lbvh_build): 30-bit Morton codes of the triangle centroids in the vertex box (the box of every row of P, a
+// NaN coordinate passed over; an axis that is all NaN has a NaN box and the extent 1; a centroid's cell is its place in the box times
+// 1024, clamped to [0, 1023] as a float and then truncated, so that a NaN centroid lands in cell 0), the stable radix sort of
 // radix.h, Karras' hierarchy (internal node i of T - 1, leaves at T - 1 + i, leaf i = triangle tri[i]), a bottom-up refit of the
 // leaves' corner boxes widened by `margin` (an atomic visit counter: the last child's thread goes on; min / max boxes are
 // order-independent) and escape links (the node that follows a node's subtree in the pre-order, -1 past the end). lbvh_walk visits
@@ -41,7 +43,12 @@ __global__ __launch_bounds__(BLOCK) void k_lbvh_bbox(const float* __restrict__ P
     __syncthreads();
     unsigned mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
     for (int v = blockIdx.x * BLOCK + threadIdx.x; v < V; v += gridDim.x * BLOCK)
-        for (int q = 0; q < 3; ++q) { const unsigned k = key_of(P[3 * (size_t)v + q]); mn[q] = min(mn[q], k); mx[q] = max(mx[q], k); }
+        for (int q = 0; q < 3; ++q) {
+            const float x = P[3 * (size_t)v + q];
+            if (!(x == x)) continue;                  // a NaN is passed over, as fminf / fmaxf pass it over in the node boxes
+            const unsigned k = key_of(x);
+            mn[q] = min(mn[q], k); mx[q] = max(mx[q], k);
+        }
     for (int q = 0; q < 3; ++q) { atomicMin(&s[q], mn[q]); atomicMax(&s[3 + q], mx[q]); }
     __syncthreads();
     if (threadIdx.x < 3) atomicMin(&box[threadIdx.x], s[threadIdx.x]);
@@ -65,7 +72,7 @@ __global__ __launch_bounds__(BLOCK) void k_lbvh_morton(const float* __restrict__
     for (int k = 0; k < 3; ++k) {
         const float lo = __uint_as_float(lbvh_key_inv(box[k])), hi = __uint_as_float(lbvh_key_inv(box[3 + k]));
         const float ext = hi - lo > 0.0f ? hi - lo : 1.0f;
-        q[k] = (unsigned)min(max((int)((cen[k] - lo) / ext * 1024.0f), 0), 1023);
+        q[k] = (unsigned)(int)fminf(fmaxf((cen[k] - lo) / ext * 1024.0f, 0.0f), 1023.0f);      // clamped in float: the cast is defined, a NaN gives 0
     }
     code[f] = (int)((lbvh_expand(q[0]) << 2) | (lbvh_expand(q[1]) << 1) | lbvh_expand(q[2]));
 }
@@ -155,7 +162,8 @@ __global__ __launch_bounds__(BLOCK) void k_lbvh_escape(const int* __restrict__ l
     esc[i] = e;
 }
 
-// the box of the V vertices (min and max per axis, fp32) into lo / hi on the host; also left in a.bb for lbvh_build. SYNC.
+// the box of the V vertices (min and max per axis, fp32, NaNs passed over; NaN on an axis without a number) into lo / hi on the host;
+// also left in a.bb for lbvh_build. SYNC.
 static inline int lbvh_bounds(const float* P, int V, const Lbvh& a, hipStream_t st, float lo[3], float hi[3]) {
     const unsigned init[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
     LS_HIP(hipMemcpyAsync(a.bb, init, sizeof(init), hipMemcpyHostToDevice, st));

@@ -18,7 +18,8 @@ namespace ls {
 constexpr double MD_SLACK = 0x1p-40, MD_SHRINK = 1.0 - 0x1p-40;
 
 // ---- the view --------------------------------------------------------------------------------------------------------------------
-// the mesh and the arrays of its hierarchy that the walks read (lbvh.h has their sizes); slack: MD_SLACK x the largest coordinate
+// the mesh and the arrays of its hierarchy that the walks read (lbvh.h has their sizes); slack: MD_SLACK x the largest |coordinate|
+// that is not a NaN
 struct MeshView {
     const float* __restrict__ P;
     const int* __restrict__ faces;

@@ -40,8 +40,10 @@ static int md_build(MeshDistanceHandle* H, hipStream_t st) {
     float lo[3], hi[3];
     int rc = lbvh_bounds(H->pos, H->V, H->bvh, st, lo, hi);
     if (rc) return rc;
-    double M = 0.0;
-    for (int q = 0; q < 3; ++q) M = std::max(M, std::max(std::fabs((double)lo[q]), std::fabs((double)hi[q])));
+    double M = 0.0;         // the largest |coordinate| that is not a NaN (lbvh_bounds passes NaNs over), 0 when there is none
+    for (int q = 0; q < 3; ++q)
+        for (const float x : {lo[q], hi[q]})
+            if (x == x) M = std::max(M, std::fabs((double)x));
     H->slack = MD_SLACK * M;
     if ((rc = lbvh_build(H->pos, H->faces, H->T, 0.0f, H->bvh, st))) return rc;
     LS_HIP(hipStreamSynchronize(st));

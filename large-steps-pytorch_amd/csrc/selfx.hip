@@ -16,7 +16,7 @@
 //   s == 0: reported iff one of the three edges of f crosses g, or one of the three edges of g crosses f.
 // The box clause. A pair is reported only if the corner boxes of f and g are within 2 e of each other on all three axes: the box of a
 // face is the fminf / fmaxf of its three fp32 corners (the leaf boxes of the handle's LBVH, margin 0), e = the handle's slack, 2^-40 x
-// the largest |coordinate| of the vertices. On an axis the boxes are apart iff lo_g - e > hi_f + e or hi_g + e < lo_f - e, each side
+// the largest |coordinate| of the vertices (a NaN passed over). On an axis the boxes are apart iff lo_g - e > hi_f + e or hi_g + e < lo_f - e, each side
 // rounded once in fp64; a comparison with a NaN is false, so such a pair is not apart. The clause is symmetric in f and g. It is part of
 // the rule, not a shortcut of the walk: where the pair rule accepts with numbers that mean something, the segment passes within a few
 // fp64 roundings of the face, far inside e; but on an exactly flat sheet whose shear rounds it accepts on rounding alone (U = W = 0,

@@ -17,7 +17,8 @@ of the device code in its order (the build has -ffp-contract=off), as a brute fo
      s == 0: reported iff one of the three edges of f crosses g, or one of the three edges of g crosses f.
 3. The box clause. A pair is reported only if the corner boxes of f and g are within 2 e of each other on all three axes. The corner
    box of a face is the smallest and largest of its three fp32 corners per axis (fmin / fmax: a NaN corner is passed over), widened to
-   fp64; e = 2^-40 x the largest |coordinate| of V (every row, referenced by a face or not; the product is exact). On an axis the boxes
+   fp64; e = 2^-40 x the largest |coordinate| of V (every row, referenced by a face or not; a NaN coordinate is passed over here as
+   in the boxes; the product is exact). On an axis the boxes
    are apart iff lo_g - e > hi_f + e or hi_g + e < lo_f - e, each side rounded once in fp64; a comparison with a NaN is false, so such a
    pair is not apart. The clause is symmetric in f and g. Where rule 2 accepts with numbers that mean something, the segment passes
    within a few fp64 roundings of the face, far inside e, and the clause changes nothing; it decides the pairs rule 2 accepts on rounding
@@ -73,8 +74,8 @@ def crosses(p, q, a, b, c):
 
 
 def slack(V):
-    """e of rule 3: 2^-40 x the largest |coordinate| of V"""
-    return 2.0 ** -40 * float(np.abs(_f64(V)).max())
+    """e of rule 3: 2^-40 x the largest |coordinate| of V, a NaN passed over (0 when every coordinate is one)"""
+    return 2.0 ** -40 * float(np.fmax.reduce(np.abs(_f64(V)).reshape(-1), initial=0.0))
 
 
 def boxes_near(V, F, fi, gi):
