@@ -27,9 +27,9 @@
 // Corners. A tap with both indices out of range has no texel (at most one of the four): its weight w_c is split evenly over the other
 // three, w'_k = w_k + w_c / 3 (OpenGL's seamless rule: the missing texel is the mean of the three).
 //
-// Arithmetic. No dropped tap: top = t00 + (t10 - t00) fx, bot = t01 + (t11 - t01) fx, out = top + (bot - top) fy -- the order of
-// texture.hip, so a pixel whose four taps lie inside one face is bit for bit the 2-D linear + clamp lookup of that face at (s, t). With
-// a dropped tap: out = sum of w'_k t_k over the three remaining taps in ascending tap id, from 0.
+// Arithmetic. No dropped tap: top = t00 + (t10 - t00) fx, bot = t01 + (t11 - t01) fx, out = top + (bot - top) fy -- tx_blend of
+// textaps.h, the order of texture.hip, so a pixel whose four taps lie inside one face is bit for bit the 2-D linear + clamp lookup of
+// that face at (s, t). With a dropped tap: out = sum of w'_k t_k over the three remaining taps in ascending tap id, from 0.
 //
 // Gradient to uv (linear only; zero for nearest), face choice held fixed. With the dropped tap's texel replaced by ((ta + tb) + tc) / 3
 // of the other three (ascending tap id) the lookup is bilinear in all cases, so per channel du = (t10 - t00)(1 - fy) + (t11 - t01) fy,
@@ -43,11 +43,7 @@
 // with one thread per texel: term g w'_tap per item, items in sorted order, a texel with more than 64 items by its whole wave. For
 // Bt = 1 the pixels of all images feed the one texture in ascending pixel index. 4 N items, no inverse seam map: the simple layout (it
 // is mip.hip's 2 N items, doubled). Fixed order everywhere: bitwise reproducible. No entry point allocates or synchronises.
-#include "common.h"
-#include "groupby.h"
 #include "textaps.h"
-#include <algorithm>
-#include <type_traits>
 
 namespace ls {
 
@@ -208,11 +204,7 @@ __global__ __launch_bounds__(256) void k_cube_forward(const float* __restrict__ 
             for (int c = 0; c < CT; ++c) o[c] = t[0][c];
         } else if (q.drop < 0) {
 #pragma unroll
-            for (int c = 0; c < CT; ++c) {
-                const float top = t[0][c] + (t[1][c] - t[0][c]) * q.fx;
-                const float bot = t[2][c] + (t[3][c] - t[2][c]) * q.fx;
-                o[c] = top + (bot - top) * q.fy;
-            }
+            for (int c = 0; c < CT; ++c) o[c] = tx_blend(t[0][c], t[1][c], t[2][c], t[3][c], q.fx, q.fy);
         } else {
 #pragma unroll
             for (int k = 0; k < 4; ++k)
@@ -254,12 +246,7 @@ __global__ __launch_bounds__(256) void k_cube_backward_uv(const float* __restric
             const float ofx = 1.0f - q.fx, ofy = 1.0f - q.fy;
             float su = 0.0f, sv = 0.0f;
 #pragma unroll
-            for (int c = 0; c < CT; ++c) {
-                const float du = (t[1][c] - t[0][c]) * ofy + (t[3][c] - t[2][c]) * q.fy;
-                const float dv = (t[2][c] - t[0][c]) * ofx + (t[3][c] - t[1][c]) * q.fx;
-                su += go[c] * du;
-                sv += go[c] * dv;
-            }
+            for (int c = 0; c < CT; ++c) tx_blend_grad(t[0][c], t[1][c], t[2][c], t[3][c], q.fx, ofx, q.fy, ofy, go[c], su, sv);
             const float gsc = 0.5f * ((float)s.n * su) / q.ama, gtc = 0.5f * ((float)s.n * sv) / q.ama;
             const float gma = -(gsc * q.qs + gtc * q.qt);
             float gx, gy, gz;
@@ -286,7 +273,7 @@ __global__ __launch_bounds__(256) void k_cube_keys(const float* __restrict__ uv,
     k4.y = (q.finite && q.drop != 1) ? base + q.texel[1] : nk;
     k4.z = (q.finite && q.drop != 2) ? base + q.texel[2] : nk;
     k4.w = (q.finite && q.drop != 3) ? base + q.texel[3] : nk;
-    *reinterpret_cast<int4*>(keys + 4 * (size_t)pix) = k4;          // (the key buffer is 256-byte aligned: cube_layout)
+    *reinterpret_cast<int4*>(keys + 4 * (size_t)pix) = k4;          // (the key buffer is 256-byte aligned: tx_order_layout)
 }
 
 // ---- backward to tex: the gradient of one texel per key, summed by seg_sum of groupby.h ----------------------------------------------------
@@ -328,21 +315,6 @@ using namespace ls;
 
 namespace {
 
-struct CubeWs {
-    size_t keys, sort, total;
-};
-
-// the order's workspace for N pixels: always sized for the four items per pixel of linear filtering
-CubeWs cube_layout(int64_t N) {
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    CubeWs w;
-    size_t o = 0;
-    w.keys = o; o += al(4 * (size_t)(4 * N));
-    w.sort = o; o += al(sort_scratch_bytes(4 * N, true));
-    w.total = o;
-    return w;
-}
-
 int cube_check(int64_t Bt, int n, int C, int64_t B, int H, int W, int filter, const char* who, CubeShape* s) {
     LS_REQUIRE(B >= 1 && H >= 1 && W >= 1 && (Bt == 1 || Bt == B) && n >= 1 && n <= TX_MAX_SIZE && C >= 1 && C <= TX_MAX_C, LS_E_INVALID,
                "%s: bad sizes (tex %lld x 6 x %d x %d x %d, uv %lld x %d x %d)", who, (long long)Bt, n, n, C, (long long)B, H, W);
@@ -355,26 +327,13 @@ int cube_check(int64_t Bt, int n, int C, int64_t B, int H, int W, int filter, co
     return LS_OK;
 }
 
-template <class Launch>
-void cube_groups(int C, Launch launch) {
-    for (int c0 = 0; c0 < C; c0 += 4)
-        switch (std::min(4, C - c0)) {
-        case 1: launch(c0, std::integral_constant<int, 1>()); break;
-        case 2: launch(c0, std::integral_constant<int, 2>()); break;
-        case 3: launch(c0, std::integral_constant<int, 3>()); break;
-        default: launch(c0, std::integral_constant<int, 4>()); break;
-        }
-}
-
-bool cube_aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 }  // namespace
 
 extern "C" int ls_cube_workspace_bytes(int64_t B, int H, int W, size_t* bytes) {
     LS_REQUIRE(bytes && B >= 1 && H >= 1 && W >= 1, LS_E_INVALID, "ls_cube_workspace_bytes: bad argument");
     LS_REQUIRE(B < ((int64_t)1 << 31) && B * (int64_t)H * W < (((int64_t)1 << 31) - 1) / 4, LS_E_OVERFLOW,
                "ls_cube_workspace_bytes: 4 B H W does not fit int32");
-    *bytes = cube_layout(B * (int64_t)H * W).total;
+    *bytes = tx_order_layout(4 * B * (int64_t)H * W).total;
     return LS_OK;
 }
 
@@ -384,12 +343,12 @@ extern "C" int ls_cube_forward(const float* tex, int64_t Bt, int n, int C, const
     int rc = cube_check(Bt, n, C, B, H, W, filter, "ls_cube_forward", &s);
     if (rc) return rc;
     LS_REQUIRE(tex && uv && out, LS_E_INVALID, "ls_cube_forward: null argument");
-    s.vec4 = C == 4 && cube_aligned(tex, 16) && cube_aligned(out, 16);
+    s.vec4 = C == 4 && tx_aligned(tex, 16) && tx_aligned(out, 16);
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(div_up(s.N, 256)), block(256);
-    cube_groups(C, [&](int c0, auto ct) { hipLaunchKernelGGL(k_cube_forward<decltype(ct)::value>, grid, block, 0, st, tex, uv, s, c0, out); });
+    tx_groups(C, [&](int c0, auto ct) { hipLaunchKernelGGL(k_cube_forward<decltype(ct)::value>, grid, block, 0, st, tex, uv, s, c0, out); });
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
@@ -399,18 +358,16 @@ extern "C" int ls_cube_order(const float* uv, int64_t B, int H, int W, int64_t B
     CubeShape s;
     int rc = cube_check(Bt, n, 1, B, H, W, filter, "ls_cube_order", &s);
     if (rc) return rc;
-    const CubeWs L = cube_layout(s.N);
+    const TxOrderWs L = tx_order_layout(4 * s.N);        // always sized for the four items per pixel of linear filtering
     LS_REQUIRE(uv && order && seg && ws, LS_E_INVALID, "ls_cube_order: null argument");
-    LS_REQUIRE(cube_aligned(ws, 16), LS_E_INVALID, "ls_cube_order: the workspace must be 16-byte aligned");
+    LS_REQUIRE(tx_aligned(ws, 16), LS_E_INVALID, "ls_cube_order: the workspace must be 16-byte aligned");
     LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_cube_order: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)ws;
     const int64_t items = filter == TX_LINEAR ? 4 * s.N : s.N, nk = 6 * (int64_t)s.Bt * s.n * s.n;
-    int* keys = (int*)(w + L.keys);
-    hipLaunchKernelGGL(k_cube_keys, dim3(div_up(s.N, 256)), dim3(256), 0, st, uv, s, (int)nk, keys);
-    return group_by_key<true>(keys, items, nk, order, seg, sort_scratch_carve(w + L.sort, items, true), st);
+    hipLaunchKernelGGL(k_cube_keys, dim3(div_up(s.N, 256)), dim3(256), 0, st, uv, s, (int)nk, tx_order_keys(ws, L));
+    return tx_order_finish(ws, L, items, nk, order, seg, st);
 }
 
 extern "C" int ls_cube_backward(const float* tex, int64_t Bt, int n, int C, const float* uv, int64_t B, int H, int W, int filter,
@@ -420,17 +377,17 @@ extern "C" int ls_cube_backward(const float* tex, int64_t Bt, int n, int C, cons
     int rc = cube_check(Bt, n, C, B, H, W, filter, "ls_cube_backward", &s);
     if (rc) return rc;
     LS_REQUIRE(tex && uv && grad_out && (!grad_tex || (order && seg)), LS_E_INVALID, "ls_cube_backward: null argument");
-    s.vec4 = C == 4 && cube_aligned(tex, 16) && cube_aligned(grad_out, 16) && (!grad_tex || cube_aligned(grad_tex, 16));
+    s.vec4 = C == 4 && tx_aligned(tex, 16) && tx_aligned(grad_out, 16) && (!grad_tex || tx_aligned(grad_tex, 16));
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
     if (grad_uv) {
         const dim3 grid(div_up(s.N, 256)), block(256);
-        cube_groups(C, [&](int c0, auto ct) { hipLaunchKernelGGL(k_cube_backward_uv<decltype(ct)::value>, grid, block, 0, st, tex, uv, grad_out, s, c0, grad_uv); });
+        tx_groups(C, [&](int c0, auto ct) { hipLaunchKernelGGL(k_cube_backward_uv<decltype(ct)::value>, grid, block, 0, st, tex, uv, grad_out, s, c0, grad_uv); });
     }
     if (grad_tex) {
         const dim3 grid(div_up((int64_t)s.Bt * 6 * s.n * s.n, 256)), block(256);
-        cube_groups(C, [&](int c0, auto ct) { hipLaunchKernelGGL(k_cube_backward_tex<decltype(ct)::value>, grid, block, 0, st, uv, grad_out, order, seg, s, c0, grad_tex); });
+        tx_groups(C, [&](int c0, auto ct) { hipLaunchKernelGGL(k_cube_backward_tex<decltype(ct)::value>, grid, block, 0, st, uv, grad_out, order, seg, s, c0, grad_tex); });
     }
     LS_HIP(hipGetLastError());
     return LS_OK;

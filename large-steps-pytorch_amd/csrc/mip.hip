@@ -17,8 +17,9 @@
 // (zero where lod was clamped, where m == 0 and in nearest mode; c_l here is the sum of the four taps times their weights, see
 // mip_level_grad), which is the bias gradient and, through d lod / d uv_da, the uv_da gradient (R == 0: d m / d A = d m / d B = 0.5,
 // d m / d Cc = 0). To tex: every pixel is one item per level it read -- item p for l0,
-// item N + p for l1 -- keyed by (level, base tap) as texture.hip keys a pixel by its base tap; ls_mip_order sorts the items (groupby.h) and
-// ls_mip_backward runs one thread per texel of EVERY level over the sorted items of the base positions that touch it, term
+// item N + p for l1 -- keyed by (level, base tap) as texture.hip keys a pixel by its base tap (tx_base, tx_base_key of textaps.h plus the
+// keys of the levels before); ls_mip_order sorts the items (groupby.h) and ls_mip_backward runs one thread per texel of EVERY level
+// over the sorted items of the base positions that touch it (tx_texel_walk of textaps.h, the walk of the plain texture), term
 // g (wx wy) w_level, a texel with more than 64 items by its whole wave. ls_mip_fold then adds, top down, 0.25f (0.5f) of every parent's
 // gradient to each of its children: a pure gather. Fixed order everywhere: bitwise reproducible. No entry point allocates or synchronises.
 //
@@ -26,12 +27,8 @@
 // adjugate, a_k(Xn, Yn) = a_k.x Xn + a_k.y Yn + a_k.z, s = a_0 + a_1 + a_2, u = a_0 / s, v = a_1 / s, and
 // du/dXn = (a_0.x - u (a_0.x + a_1.x + a_2.x)) / s, likewise v and Yn; times 2 / W (2 / H) per pixel. Computed in fp64 like the coverage
 // test of raster.hip, stored as fp32. Background and degenerate faces (s or the determinant zero or non-finite) give 0.
-#include "common.h"
-#include "groupby.h"
 #include "meshface.h"
 #include "textaps.h"
-#include <algorithm>
-#include <type_traits>
 
 namespace ls {
 
@@ -133,11 +130,7 @@ __device__ __forceinline__ void mip_sample(const float* __restrict__ level, cons
     const TxCoord q = tx_coord(uv, pix, sl);
     const TxTaps<CT> a = tx_taps<CT>(level, q, pix, sl, c0);
 #pragma unroll
-    for (int c = 0; c < CT; ++c) {
-        const float top = a.t[0][0][c] + (a.t[0][1][c] - a.t[0][0][c]) * q.fx;
-        const float bot = a.t[1][0][c] + (a.t[1][1][c] - a.t[1][0][c]) * q.fx;
-        o[c] = top + (bot - top) * q.fy;
-    }
+    for (int c = 0; c < CT; ++c) o[c] = tx_blend(a.t[0][0][c], a.t[0][1][c], a.t[1][0][c], a.t[1][1][c], q.fx, q.fy);
 }
 
 // ---- pyramid: one thread per float of the coarser level (build) or of the finer level (fold) ---------------------------------------------
@@ -291,10 +284,7 @@ __device__ __forceinline__ void mip_level_grad(const float* __restrict__ level, 
     float su = 0.0f, sv = 0.0f;
 #pragma unroll
     for (int c = 0; c < CT; ++c) {
-        const float du = (a.t[0][1][c] - a.t[0][0][c]) * ofy + (a.t[1][1][c] - a.t[1][0][c]) * q.fy;
-        const float dv = (a.t[1][0][c] - a.t[0][0][c]) * ofx + (a.t[1][1][c] - a.t[0][1][c]) * q.fx;
-        su += go[c] * du;
-        sv += go[c] * dv;
+        tx_blend_grad(a.t[0][0][c], a.t[0][1][c], a.t[1][0][c], a.t[1][1][c], q.fx, ofx, q.fy, ofy, go[c], su, sv);
         o[c] = (a.t[0][0][c] * w00 + a.t[0][1][c] * w10) + (a.t[1][0][c] * w01 + a.t[1][1][c] * w11);
     }
     gu = (float)sl.Wt * su;
@@ -380,92 +370,46 @@ __global__ __launch_bounds__(256) void k_mip_keys(const float* __restrict__ uv, 
         const TxShape sl = mip_level_shape(s, l);
         const TxCoord q = tx_coord(uv, pix, sl);
         int i = q.i0, j = q.j0;
-        if (s.boundary == TX_WRAP) {
-            tx_fold(i, sl.Wt, TX_WRAP);
-            tx_fold(j, sl.Ht, TX_WRAP);
-        } else if (s.boundary == TX_CLAMP) {
-            i = min(max(i, -1), sl.Wt - 1);
-            j = min(max(j, -1), sl.Ht - 1);
-        } else {
-            ok = i >= -1 && i < sl.Wt && j >= -1 && j < sl.Ht;
-        }
+        ok = tx_base(i, j, sl);
         const int bt = s.Bt == 1 ? 0 : (int)(pix / s.HW);
-        if (ok) key = (int)(mip_keys_before(s, l) + ((int64_t)bt * (sl.Ht + 1) + (j + 1)) * (sl.Wt + 1) + (i + 1));
+        if (ok) key = (int)(mip_keys_before(s, l) + tx_base_key(bt, j, i, sl));
     }
     keys[it] = key;
 }
 
 // ---- backward to the pyramid: one thread per texel of every level ------------------------------------------------------------------------
-// slot q < 4 of the base positions along one axis whose tap falls on texel i of n (texture.hip's tx_slot, linear filtering)
-__device__ __forceinline__ bool mip_slot(int q, int i, int n, int boundary, int& base, int& tap) {
-    if (q == 0) { base = i; tap = 0; return true; }
-    if (q == 1) { base = (boundary == TX_WRAP && i == 0) ? n - 1 : i - 1; tap = 1; return true; }
-    if (boundary != TX_CLAMP) return false;
-    if (q == 2) { base = -1; tap = 0; return i == 0; }
-    base = n - 1; tap = 1;
-    return i == n - 1;
-}
+// item p < N is pixel p at its level l0, item N + p pixel p at l0 + 1: its weight has the factor 1 - f or f where two levels were read
+struct MipItem {
+    const float* __restrict__ uv; const float* __restrict__ uv_da; const float* __restrict__ bias;
+    MipShape s;                 // (by value: through a reference the conversions of mip_lod are not hoisted out of the walk's loops)
+    __device__ __forceinline__ bool operator()(int it, int64_t& pix, float& f) const {
+        const bool which = it >= s.N;
+        pix = which ? it - s.N : it;
+        const MipLod L = mip_lod(uv, uv_da, bias, pix, s);
+        f = which ? L.f : 1.0f - L.f;
+        return L.two;
+    }
+};
 
-struct MipTexel { int l, bt, j, i; };
-
+// the gradient of one texel of one level per key: tx_texel_walk of textaps.h over the level's keys
 template <int CT>
 struct MipTexelSum {
     const float* __restrict__ uv; const float* __restrict__ uv_da; const float* __restrict__ bias; const float* __restrict__ g;
     const int* __restrict__ order; const int* __restrict__ seg;
     MipShape s; int c0; float* __restrict__ gtex; float* __restrict__ gpyr;
 
-    __device__ __forceinline__ MipTexel texel(int64_t k) const {
-        MipTexel t;
-        t.l = 0;
-        int64_t n = (int64_t)s.Bt * s.Ht * s.Wt;
-        while (k >= n && t.l < s.Lmax) {               // (k < the texels of all levels: the loop ends at the texel's level)
-            k -= n;
-            ++t.l;
-            n = (int64_t)s.Bt * mip_side(s.Ht, t.l) * mip_side(s.Wt, t.l);
-        }
-        const int Wl = mip_side(s.Wt, t.l), Hl = mip_side(s.Ht, t.l);
-        const int64_t row = k / Wl;
-        t.i = (int)(k - row * Wl);
-        t.bt = (int)(row / Hl);
-        t.j = (int)(row - (int64_t)t.bt * Hl);
-        return t;
-    }
-
     template <bool COUNT>
     __device__ __forceinline__ int64_t visit(int64_t k, int start, int step, float (&acc)[CT]) const {
-        const MipTexel t = texel(k);
-        const TxShape sl = mip_level_shape(s, t.l);
-        const int64_t k0 = mip_keys_before(s, t.l);
-        int64_t total = 0;
-#pragma unroll
-        for (int qy = 0; qy < 4; ++qy) {
-            int by, ty;
-            if (!mip_slot(qy, t.j, sl.Ht, s.boundary, by, ty)) continue;
-#pragma unroll
-            for (int qx = 0; qx < 4; ++qx) {
-                int bx, tx;
-                if (!mip_slot(qx, t.i, sl.Wt, s.boundary, bx, tx)) continue;
-                const int64_t key = k0 + ((int64_t)t.bt * (sl.Ht + 1) + (by + 1)) * (sl.Wt + 1) + (bx + 1);
-                const int b = seg[key], e = seg[key + 1];
-                if constexpr (COUNT) total += e - b;
-                else {
-                    for (int p = b + start; p < e; p += step) {
-                        const int64_t it = order[p];
-                        const bool which = it >= s.N;
-                        const int64_t pix = which ? it - s.N : it;
-                        const MipLod L = mip_lod(uv, uv_da, bias, pix, s);
-                        const TxCoord q = tx_coord(uv, pix, sl);
-                        float w = (tx ? q.fx : 1.0f - q.fx) * (ty ? q.fy : 1.0f - q.fy);
-                        if (L.two) w = w * (which ? L.f : 1.0f - L.f);
-                        float go[CT];
-                        tx_load<CT>(g + (size_t)pix * s.C + c0, s.vec4 != 0, go);
-#pragma unroll
-                        for (int c = 0; c < CT; ++c) acc[c] += go[c] * w;
-                    }
-                }
-            }
+        int l = 0;
+        int64_t n = (int64_t)s.Bt * s.Ht * s.Wt;
+        while (k >= n && l < s.Lmax) {                 // (k < the texels of all levels: the loop ends at the texel's level)
+            k -= n;
+            ++l;
+            n = (int64_t)s.Bt * mip_side(s.Ht, l) * mip_side(s.Wt, l);
         }
-        return total;
+        const TxShape sl = mip_level_shape(s, l);
+        return tx_texel_walk<CT, COUNT>(tx_texel(k, sl), sl, mip_keys_before(s, l), MipItem{uv, uv_da, bias, s}, uv, g, order, seg, c0, start,
+                                        step, acc);
     }
     __device__ __forceinline__ int64_t count(int64_t k) const {
         float none[CT];
@@ -491,23 +435,6 @@ __global__ __launch_bounds__(256) void k_mip_backward_tex(const float* __restric
 using namespace ls;
 
 namespace {
-
-struct MipWs {
-    size_t keys, sort, total;
-};
-
-// the order's workspace for N pixels: always sized for the two items per pixel of linear-mipmap-linear
-MipWs mip_layout(int64_t N) {
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    MipWs w;
-    size_t o = 0;
-    w.keys = o; o += al(4 * (size_t)(2 * N));
-    w.sort = o; o += al(sort_scratch_bytes(2 * N, true));
-    w.total = o;
-    return w;
-}
-
-bool mip_aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 int mip_check_tex(int64_t Bt, int Ht, int Wt, int C, int Lmax, const char* who) {
     LS_REQUIRE(Bt >= 1 && Ht >= 1 && Wt >= 1 && Ht <= TX_MAX_SIZE && Wt <= TX_MAX_SIZE && C >= 1 && C <= TX_MAX_C && Bt < ((int64_t)1 << 31),
@@ -539,17 +466,6 @@ int mip_check(int64_t Bt, int Ht, int Wt, int C, int Lmax, int64_t B, int H, int
     return LS_OK;
 }
 
-template <class Launch>
-void mip_groups(int C, Launch launch) {
-    for (int c0 = 0; c0 < C; c0 += 4)
-        switch (std::min(4, C - c0)) {
-        case 1: launch(c0, std::integral_constant<int, 1>()); break;
-        case 2: launch(c0, std::integral_constant<int, 2>()); break;
-        case 3: launch(c0, std::integral_constant<int, 3>()); break;
-        default: launch(c0, std::integral_constant<int, 4>()); break;
-        }
-}
-
 int mip_check_raster(int64_t B, int64_t V, int64_t F, int H, int W, const char* who) {
     LS_REQUIRE(B >= 1 && V >= 0 && F >= 0 && H >= 1 && W >= 1 && H <= 4096 && W <= 4096, LS_E_INVALID, "%s: bad sizes (B %lld V %lld F %lld H %d W %d)",
                who, (long long)B, (long long)V, (long long)F, H, W);
@@ -563,7 +479,7 @@ int mip_check_raster(int64_t B, int64_t V, int64_t F, int H, int W, const char* 
 extern "C" int ls_mip_workspace_bytes(int64_t B, int H, int W, size_t* bytes) {
     LS_REQUIRE(bytes && B >= 1 && H >= 1 && W >= 1, LS_E_INVALID, "ls_mip_workspace_bytes: bad argument");
     LS_REQUIRE(2 * B * (int64_t)H * W < ((int64_t)1 << 31) - 1, LS_E_OVERFLOW, "ls_mip_workspace_bytes: 2 B H W does not fit int32");
-    *bytes = mip_layout(B * (int64_t)H * W).total;
+    *bytes = tx_order_layout(2 * B * (int64_t)H * W).total;
     return LS_OK;
 }
 
@@ -614,7 +530,7 @@ extern "C" int ls_mip_pixel_differentials(const float* rast, const float* pos, i
     int rc = mip_check_raster(B, V, F, H, W, "ls_mip_pixel_differentials");
     if (rc) return rc;
     LS_REQUIRE(rast && out && (pos || V == 0) && (tri || F == 0), LS_E_INVALID, "ls_mip_pixel_differentials: null argument");
-    LS_REQUIRE(mip_aligned(pos, 16) && mip_aligned(out, 16), LS_E_INVALID, "ls_mip_pixel_differentials: pos and out must be 16-byte aligned");
+    LS_REQUIRE(tx_aligned(pos, 16) && tx_aligned(out, 16), LS_E_INVALID, "ls_mip_pixel_differentials: pos and out must be 16-byte aligned");
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipLaunchKernelGGL(k_mip_pixel_diff, dim3(div_up(B * (int64_t)H * W, 256)), dim3(256), 0, (hipStream_t)stream, rast, pos, tri, (int)B, V, F, H, W,
@@ -630,7 +546,7 @@ extern "C" int ls_mip_interpolate_da(const float* attr, int64_t attr_batch, int6
     LS_REQUIRE(C >= 1 && (attr_batch == 1 || attr_batch == B), LS_E_INVALID, "ls_mip_interpolate_da: C %d, attribute batch %lld of %lld", C,
                (long long)attr_batch, (long long)B);
     LS_REQUIRE(rast && rast_db && out && (attr || V == 0) && (tri || F == 0), LS_E_INVALID, "ls_mip_interpolate_da: null argument");
-    LS_REQUIRE(mip_aligned(rast_db, 16) && mip_aligned(out, 8), LS_E_INVALID, "ls_mip_interpolate_da: rast_db must be 16-byte, out 8-byte aligned");
+    LS_REQUIRE(tx_aligned(rast_db, 16) && tx_aligned(out, 8), LS_E_INVALID, "ls_mip_interpolate_da: rast_db must be 16-byte, out 8-byte aligned");
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipLaunchKernelGGL(k_mip_interp_da, dim3(div_up(B * (int64_t)H * W, 256)), dim3(256), 0, (hipStream_t)stream, attr, (int)attr_batch, V, C, rast,
@@ -645,13 +561,13 @@ extern "C" int ls_mip_forward(const float* tex, const float* pyr, int64_t Bt, in
     int rc = mip_check(Bt, Ht, Wt, C, Lmax, B, H, W, mode, boundary, "ls_mip_forward", &s);
     if (rc) return rc;
     LS_REQUIRE(tex && (pyr || Lmax == 0) && uv && out && (uv_da || bias), LS_E_INVALID, "ls_mip_forward: null argument");
-    LS_REQUIRE(mip_aligned(uv, 8) && mip_aligned(uv_da, 16), LS_E_INVALID, "ls_mip_forward: uv must be 8-byte, uv_da 16-byte aligned");
-    s.vec4 = C == 4 && mip_aligned(tex, 16) && mip_aligned(pyr, 16) && mip_aligned(out, 16);
+    LS_REQUIRE(tx_aligned(uv, 8) && tx_aligned(uv_da, 16), LS_E_INVALID, "ls_mip_forward: uv must be 8-byte, uv_da 16-byte aligned");
+    s.vec4 = C == 4 && tx_aligned(tex, 16) && tx_aligned(pyr, 16) && tx_aligned(out, 16);
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(div_up(s.N, 256)), block(256);
-    mip_groups(C, [&](int c0, auto ct) {
+    tx_groups(C, [&](int c0, auto ct) {
         hipLaunchKernelGGL(k_mip_forward<decltype(ct)::value>, grid, block, 0, st, tex, pyr, uv, uv_da, bias, s, c0, out);
     });
     LS_HIP(hipGetLastError());
@@ -663,18 +579,16 @@ extern "C" int ls_mip_order(const float* uv, const float* uv_da, const float* bi
     MipShape s;
     int rc = mip_check(Bt, Ht, Wt, 1, Lmax, B, H, W, mode, boundary, "ls_mip_order", &s);
     if (rc) return rc;
-    const MipWs L = mip_layout(s.N);
+    const TxOrderWs L = tx_order_layout(2 * s.N);        // always sized for the two items per pixel of linear-mipmap-linear
     LS_REQUIRE(uv && (uv_da || bias) && order && seg && ws, LS_E_INVALID, "ls_mip_order: null argument");
-    LS_REQUIRE(mip_aligned(uv, 8) && mip_aligned(uv_da, 16), LS_E_INVALID, "ls_mip_order: uv must be 8-byte, uv_da 16-byte aligned");
+    LS_REQUIRE(tx_aligned(uv, 8) && tx_aligned(uv_da, 16), LS_E_INVALID, "ls_mip_order: uv must be 8-byte, uv_da 16-byte aligned");
     LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_mip_order: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)ws;
     const int64_t n = mode == MIP_LINEAR ? 2 * s.N : s.N, nk = mip_keys_before(s, Lmax + 1);
-    int* keys = (int*)(w + L.keys);
-    hipLaunchKernelGGL(k_mip_keys, dim3(div_up(n, 256)), dim3(256), 0, st, uv, uv_da, bias, s, n, nk, keys);
-    return group_by_key<true>(keys, n, nk, order, seg, sort_scratch_carve(w + L.sort, n, true), st);
+    hipLaunchKernelGGL(k_mip_keys, dim3(div_up(n, 256)), dim3(256), 0, st, uv, uv_da, bias, s, n, nk, tx_order_keys(ws, L));
+    return tx_order_finish(ws, L, n, nk, order, seg, st);
 }
 
 extern "C" int ls_mip_backward(const float* tex, const float* pyr, int64_t Bt, int Ht, int Wt, int C, int Lmax, const float* uv, const float* uv_da,
@@ -687,15 +601,15 @@ extern "C" int ls_mip_backward(const float* tex, const float* pyr, int64_t Bt, i
     LS_REQUIRE(tex && (pyr || Lmax == 0) && uv && grad_out && (uv_da || bias), LS_E_INVALID, "ls_mip_backward: null argument");
     LS_REQUIRE(!grad_tex || (order && seg && (grad_pyr || Lmax == 0)), LS_E_INVALID, "ls_mip_backward: grad_tex needs order, seg and grad_pyr");
     LS_REQUIRE(!grad_uv_da || (grad_lod && uv_da), LS_E_INVALID, "ls_mip_backward: grad_uv_da needs uv_da and grad_lod");
-    LS_REQUIRE(mip_aligned(uv, 8) && mip_aligned(uv_da, 16) && mip_aligned(grad_uv, 8) && mip_aligned(grad_uv_da, 16), LS_E_INVALID,
+    LS_REQUIRE(tx_aligned(uv, 8) && tx_aligned(uv_da, 16) && tx_aligned(grad_uv, 8) && tx_aligned(grad_uv_da, 16), LS_E_INVALID,
                "ls_mip_backward: uv and grad_uv must be 8-byte, uv_da and grad_uv_da 16-byte aligned");
-    s.vec4 = C == 4 && mip_aligned(tex, 16) && mip_aligned(pyr, 16) && mip_aligned(grad_out, 16) && mip_aligned(grad_tex, 16) && mip_aligned(grad_pyr, 16);
+    s.vec4 = C == 4 && tx_aligned(tex, 16) && tx_aligned(pyr, 16) && tx_aligned(grad_out, 16) && tx_aligned(grad_tex, 16) && tx_aligned(grad_pyr, 16);
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
     if (grad_uv || grad_lod) {
         const dim3 grid(div_up(s.N, 256)), block(256);
-        mip_groups(C, [&](int c0, auto ct) {
+        tx_groups(C, [&](int c0, auto ct) {
             hipLaunchKernelGGL(k_mip_backward_pixel<decltype(ct)::value>, grid, block, 0, st, tex, pyr, uv, uv_da, bias, grad_out, s, c0, grad_uv, grad_lod);
         });
         if (grad_uv_da)
@@ -704,7 +618,7 @@ extern "C" int ls_mip_backward(const float* tex, const float* pyr, int64_t Bt, i
     if (grad_tex) {
         const int64_t nt = mip_texels_before(s, Lmax + 1);
         const dim3 grid(div_up(nt, 256)), block(256);
-        mip_groups(C, [&](int c0, auto ct) {
+        tx_groups(C, [&](int c0, auto ct) {
             hipLaunchKernelGGL(k_mip_backward_tex<decltype(ct)::value>, grid, block, 0, st, uv, uv_da, bias, grad_out, order, seg, s, c0, nt, grad_tex,
                                grad_pyr);
         });

@@ -26,11 +26,11 @@
 // (size - 1, tap 1) for the last texel in clamp mode -- and adds g (wx wy) over each position's pixels in sorted order. A texel with
 // more than 64 pixels in all is summed by its whole wave, lane-strided per position, then an xor butterfly: a fixed order either way,
 // so every gradient is bitwise reproducible. No entry point allocates or synchronises.
-#include "common.h"
-#include "groupby.h"
+//
+// The taps, the blend and its (du, dv), the base tap and its key, the texel walk and the host side of the order (channel groups,
+// workspace layout, group-by tail) are in textaps.h, shared with mip.hip and cube.hip; this file keeps the kernels, the nearest
+// branch of the key and the entry points.
 #include "textaps.h"
-#include <algorithm>
-#include <type_traits>
 
 namespace ls {
 
@@ -45,11 +45,7 @@ __global__ __launch_bounds__(256) void k_tx_forward(const float* __restrict__ te
     float o[CT];
     if (s.filter == TX_LINEAR) {
 #pragma unroll
-        for (int c = 0; c < CT; ++c) {
-            const float top = a.t[0][0][c] + (a.t[0][1][c] - a.t[0][0][c]) * q.fx;
-            const float bot = a.t[1][0][c] + (a.t[1][1][c] - a.t[1][0][c]) * q.fx;
-            o[c] = q.finite ? top + (bot - top) * q.fy : 0.0f;
-        }
+        for (int c = 0; c < CT; ++c) o[c] = q.finite ? tx_blend(a.t[0][0][c], a.t[0][1][c], a.t[1][0][c], a.t[1][1][c], q.fx, q.fy) : 0.0f;
     } else {
 #pragma unroll
         for (int c = 0; c < CT; ++c) o[c] = a.t[0][0][c];
@@ -73,12 +69,8 @@ __global__ __launch_bounds__(256) void k_tx_backward_uv(const float* __restrict_
             const float ofx = 1.0f - q.fx, ofy = 1.0f - q.fy;
             float su = 0.0f, sv = 0.0f;
 #pragma unroll
-            for (int c = 0; c < CT; ++c) {
-                const float du = (a.t[0][1][c] - a.t[0][0][c]) * ofy + (a.t[1][1][c] - a.t[1][0][c]) * q.fy;
-                const float dv = (a.t[1][0][c] - a.t[0][0][c]) * ofx + (a.t[1][1][c] - a.t[0][1][c]) * q.fx;
-                su += go[c] * du;
-                sv += go[c] * dv;
-            }
+            for (int c = 0; c < CT; ++c)
+                tx_blend_grad(a.t[0][0][c], a.t[0][1][c], a.t[1][0][c], a.t[1][1][c], q.fx, ofx, q.fy, ofy, go[c], su, sv);
             acc.x += (float)s.Wt * su;
             acc.y += (float)s.Ht * sv;
         }
@@ -98,88 +90,26 @@ __global__ __launch_bounds__(256) void k_tx_keys(const float* __restrict__ uv, T
     if (s.filter == TX_NEAREST) {
         ok = tx_fold(i, s.Wt, s.boundary) && ok;
         ok = tx_fold(j, s.Ht, s.boundary) && ok;
-    } else if (s.boundary == TX_WRAP) {
-        tx_fold(i, s.Wt, TX_WRAP);
-        tx_fold(j, s.Ht, TX_WRAP);
-    } else if (s.boundary == TX_CLAMP) {
-        i = min(max(i, -1), s.Wt - 1);
-        j = min(max(j, -1), s.Ht - 1);
     } else {
-        ok = ok && i >= -1 && i < s.Wt && j >= -1 && j < s.Ht;
+        ok = tx_base(i, j, s) && ok;
     }
     const int bt = s.Bt == 1 ? 0 : (int)(pix / s.HW);
-    keys[pix] = ok ? (int)(((int64_t)bt * (s.Ht + 1) + (j + 1)) * (s.Wt + 1) + (i + 1)) : (int)tx_nkeys(s);
+    keys[pix] = ok ? (int)tx_base_key(bt, j, i, s) : (int)tx_nkeys(s);
 }
 
 // ---- backward to tex: one thread per texel ------------------------------------------------------------------------------------------------
-// slot q < 4 of the base positions along one axis whose tap falls on texel i of n: (base, tap); false = the slot is empty
-__device__ __forceinline__ bool tx_slot(int q, int i, int n, int filter, int boundary, int& base, int& tap) {
-    if (q == 0) { base = i; tap = 0; return true; }
-    if (filter == TX_NEAREST) return false;
-    if (q == 1) { base = (boundary == TX_WRAP && i == 0) ? n - 1 : i - 1; tap = 1; return true; }
-    if (boundary != TX_CLAMP) return false;
-    if (q == 2) { base = -1; tap = 0; return i == 0; }
-    base = n - 1; tap = 1;
-    return i == n - 1;
-}
-
-struct TxTexel { int bt, j, i; };
-
-// the pixels of the texel's base positions: their number (COUNT) or their weighted gradients added to acc, pixels start, start + step, ...
-// of every position
-template <int CT, bool COUNT>
-__device__ __forceinline__ int64_t tx_texel_walk(const TxTexel& t, const TxShape& s, const float* __restrict__ uv, const float* __restrict__ g,
-                                             const int* __restrict__ order, const int* __restrict__ seg, int c0, int start, int step, float (&acc)[CT]) {
-    int64_t total = 0;
-#pragma unroll
-    for (int qy = 0; qy < 4; ++qy) {
-        int by, ty;
-        if (!tx_slot(qy, t.j, s.Ht, s.filter, s.boundary, by, ty)) continue;
-#pragma unroll
-        for (int qx = 0; qx < 4; ++qx) {
-            int bx, tx;
-            if (!tx_slot(qx, t.i, s.Wt, s.filter, s.boundary, bx, tx)) continue;
-            const int64_t key = ((int64_t)t.bt * (s.Ht + 1) + (by + 1)) * (s.Wt + 1) + (bx + 1);
-            const int b = seg[key], e = seg[key + 1];
-            if constexpr (COUNT) total += e - b;
-            else {
-                for (int p = b + start; p < e; p += step) {
-                    const int pix = order[p];
-                    float w = 1.0f;
-                    if (s.filter == TX_LINEAR) {
-                        const TxCoord q = tx_coord(uv, pix, s);
-                        w = (tx ? q.fx : 1.0f - q.fx) * (ty ? q.fy : 1.0f - q.fy);
-                    }
-                    float go[CT];
-                    tx_load<CT>(g + (size_t)pix * s.C + c0, s.vec4 != 0, go);
-#pragma unroll
-                    for (int c = 0; c < CT; ++c) acc[c] += go[c] * w;
-                }
-            }
-        }
-    }
-    return total;
-}
-
-// the gradient of one texel per key, summed by seg_sum of groupby.h: a texel's items are the pixels of up to 16 base positions
+// the gradient of one texel per key, summed by seg_sum of groupby.h: a texel's items are the pixels of up to 16 base positions, walked
+// by tx_texel_walk of textaps.h (no key offset, no further factor in the weight)
 template <int CT>
 struct TxTexelSum {
     const float* __restrict__ uv; const float* __restrict__ g; const int* __restrict__ order; const int* __restrict__ seg;
     TxShape s; int c0; float* __restrict__ gtex;
-    __device__ __forceinline__ TxTexel texel(int64_t k) const {
-        TxTexel t;
-        const int64_t row = k / s.Wt;
-        t.i = (int)(k - row * s.Wt);
-        t.bt = (int)(row / s.Ht);
-        t.j = (int)(row - (int64_t)t.bt * s.Ht);
-        return t;
-    }
     __device__ __forceinline__ int64_t count(int64_t k) const {
         float none[CT];
-        return tx_texel_walk<CT, true>(texel(k), s, uv, g, order, seg, c0, 0, 1, none);
+        return tx_texel_walk<CT, true>(tx_texel(k, s), s, 0, TxPixelItem(), uv, g, order, seg, c0, 0, 1, none);
     }
     __device__ __forceinline__ void walk(int64_t k, int start, int step, float (&acc)[CT]) const {
-        tx_texel_walk<CT, false>(texel(k), s, uv, g, order, seg, c0, start, step, acc);
+        tx_texel_walk<CT, false>(tx_texel(k, s), s, 0, TxPixelItem(), uv, g, order, seg, c0, start, step, acc);
     }
     __device__ __forceinline__ void store(int64_t k, const float (&acc)[CT]) const { tx_store<CT>(gtex + (size_t)k * s.C + c0, s.vec4 != 0, acc); }
 };
@@ -196,20 +126,6 @@ using namespace ls;
 
 namespace {
 
-struct TxWs {
-    size_t keys, sort, total;
-};
-
-TxWs tx_layout(int64_t N) {
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    TxWs w;
-    size_t o = 0;
-    w.keys = o; o += al(4 * (size_t)N);
-    w.sort = o; o += al(sort_scratch_bytes(N, true));          // the pixel order sorts with carried keys
-    w.total = o;
-    return w;
-}
-
 int tx_check(int64_t Bt, int Ht, int Wt, int C, int64_t B, int H, int W, int filter, int boundary, const char* who, TxShape* s) {
     LS_REQUIRE(B >= 1 && H >= 1 && W >= 1 && (Bt == 1 || Bt == B) && Ht >= 1 && Wt >= 1 && Ht <= TX_MAX_SIZE && Wt <= TX_MAX_SIZE && C >= 1 &&
                    C <= TX_MAX_C,
@@ -224,26 +140,12 @@ int tx_check(int64_t Bt, int Ht, int Wt, int C, int64_t B, int H, int W, int fil
     return LS_OK;
 }
 
-// the channels in groups of at most four: one launch per group, launch(c0, std::integral_constant<int, CT>) for its CT channels from c0
-template <class Launch>
-void tx_groups(int C, Launch launch) {
-    for (int c0 = 0; c0 < C; c0 += 4)
-        switch (std::min(4, C - c0)) {
-        case 1: launch(c0, std::integral_constant<int, 1>()); break;
-        case 2: launch(c0, std::integral_constant<int, 2>()); break;
-        case 3: launch(c0, std::integral_constant<int, 3>()); break;
-        default: launch(c0, std::integral_constant<int, 4>()); break;
-        }
-}
-
-bool tx_aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 }  // namespace
 
 extern "C" int ls_texture_workspace_bytes(int64_t B, int H, int W, size_t* bytes) {
     LS_REQUIRE(bytes && B >= 1 && H >= 1 && W >= 1, LS_E_INVALID, "ls_texture_workspace_bytes: bad argument");
     LS_REQUIRE(B * (int64_t)H * W < ((int64_t)1 << 31) - 1, LS_E_OVERFLOW, "ls_texture_workspace_bytes: B H W does not fit int32");
-    *bytes = tx_layout(B * (int64_t)H * W).total;
+    *bytes = tx_order_layout(B * (int64_t)H * W).total;
     return LS_OK;
 }
 
@@ -269,18 +171,15 @@ extern "C" int ls_texture_order(const float* uv, int64_t B, int H, int W, int64_
     TxShape s;
     int rc = tx_check(Bt, Ht, Wt, 1, B, H, W, filter, boundary, "ls_texture_order", &s);
     if (rc) return rc;
-    const TxWs L = tx_layout(s.N);
+    const TxOrderWs L = tx_order_layout(s.N);
     LS_REQUIRE(uv && order && seg && ws, LS_E_INVALID, "ls_texture_order: null argument");
     LS_REQUIRE(tx_aligned(uv, 8), LS_E_INVALID, "ls_texture_order: uv must be 8-byte aligned");
     LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_texture_order: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)ws;
-    const int64_t N = s.N, nk = (int64_t)s.Bt * (s.Ht + 1) * (s.Wt + 1);
-    int* keys = (int*)(w + L.keys);
-    hipLaunchKernelGGL(k_tx_keys, dim3(div_up(N, 256)), dim3(256), 0, st, uv, s, keys);
-    return group_by_key<true>(keys, N, nk, order, seg, sort_scratch_carve(w + L.sort, N, true), st);
+    hipLaunchKernelGGL(k_tx_keys, dim3(div_up(s.N, 256)), dim3(256), 0, st, uv, s, tx_order_keys(ws, L));
+    return tx_order_finish(ws, L, s.N, (int64_t)s.Bt * (s.Ht + 1) * (s.Wt + 1), order, seg, st);
 }
 
 extern "C" int ls_texture_backward(const float* tex, int64_t Bt, int Ht, int Wt, int C, const float* uv, int64_t B, int H, int W, int filter,

@@ -54,7 +54,9 @@ the shape rules of pos and tri, the edge adjacency and the native calls (`_Insta
 frame also holds the pixel order of the backward passes, made at most once per version of the rast. A rast that no `rasterize` made (a
 clone, a fabricated tensor) gets a fresh instanced frame; a range frame is made by `rasterize` only.
 """
+import collections
 import ctypes
+import functools
 
 import numpy as np
 import torch
@@ -102,6 +104,16 @@ def _scratch(dev, size_fn, *shape):
     return torch.empty(n.value, dtype=torch.uint8, device=dev)
 
 
+def _plain(t, align):
+    """detached, contiguous and aligned for the kernels' vector loads (float2 / float4 rows: torch's allocations are 256-byte aligned, a
+    view into one need not be); None stays None"""
+    if t is None:
+        return None
+    d = t.detach()
+    d = d if d.is_contiguous() else d.contiguous()
+    return d if d.data_ptr() % align == 0 else d.clone()
+
+
 def _adjacent(f, narrow):
     adj = _adjacency.get(f)
     if adj is None:
@@ -124,7 +136,7 @@ def _pos(pos, shared=False):
     p = pos.detach()
     if p.dtype != torch.float32 or not p.is_contiguous():
         p = p.to(torch.float32).contiguous()
-    return _aligned(p) if shared else p
+    return _plain(p, 16) if shared else p
 
 
 def _rast(rast):
@@ -579,7 +591,7 @@ def pixel_differentials(rast, pos, tri):
     F, dev = narrow.shape[0], r.device
     out = torch.empty((B, H, W, 4), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        _native.check(_native.lib().ls_mip_pixel_differentials(_native.ptr(r), _native.ptr(_aligned(p)), B, V, _native.ptr(narrow), F, H, W,
+        _native.check(_native.lib().ls_mip_pixel_differentials(_native.ptr(r), _native.ptr(_plain(p, 16)), B, V, _native.ptr(narrow), F, H, W,
                                                                _native.ptr(out), dev.index, _native.stream_of(dev)))
     return out
 
@@ -592,8 +604,7 @@ def _resolve_db(rast_db, rast):
     if src is None or src.version != rast_db._version:
         if tuple(rast_db.shape) != tuple(rast.shape):
             raise ValueError(f"rast_db must have the shape of rast {tuple(rast.shape)}, got {tuple(rast_db.shape)}")
-        d = rast_db.detach()
-        return _aligned(d if (d.dtype == torch.float32 and d.is_contiguous()) else d.to(torch.float32).contiguous())
+        return _plain(rast_db.detach().to(torch.float32), 16)
     if src.pos._version != src.pos_version:
         raise ValueError("pos was changed in place after rasterize: its rast_db can no longer give the pixel differentials")
     if torch.cuda.is_current_stream_capturing():
@@ -794,88 +805,122 @@ TEXTURE_MAX_SIZE = 8192                                                 # texels
 TEXTURE_MAX_CHANNELS = 32
 
 
-class _TexelOrder:
-    """The pixels of one uv image sorted by their base tap -- the order the texture gradient sums in. It depends on uv, the texture's
-    shape and the two modes, not on the texture's values: made at most once per uv tensor and version, by the first backward that
-    needs it, and shared through the uv tensor (a fixed uv -- backgrounds, texture fitting on fixed geometry -- sorts once)."""
-    __slots__ = ("key", "order", "seg")
+def _mip_keys(Bt, Ht, Wt, Lmax, mode, bnd):
+    return Bt * sum((max(Ht >> l, 1) + 1) * (max(Wt >> l, 1) + 1) for l in range(Lmax + 1))
 
-    def __init__(self, key):
-        self.key, self.order, self.seg = key, None, None
 
-    def get(self, u, Bt, Ht, Wt, filt, bnd):
+# What differs between the three lookups above the kernels. For the item order: the attribute it is cached under on the uv tensor (one
+# each, so that a uv used by two kinds of lookup keeps both orders), how many leading arguments are the tensors whose versions form the
+# key, the native workspace and order functions, the items per pixel and the number of keys (both from the integers that follow the
+# tensors: the texture's sizes and the modes). For `_Texture`: the native lookup, (Bt, sizes) of a texture's shape, uv's alignment.
+_Lookup = collections.namedtuple("_Lookup", "attr tensors workspace order items nkeys forward backward dims uv_align", defaults=(None,) * 4)
+_TEXEL = _Lookup("_largesteps_texel_order", 1, "ls_texture_workspace_bytes", "ls_texture_order", lambda Bt, Ht, Wt, filt, bnd: 1,
+                 lambda Bt, Ht, Wt, filt, bnd: Bt * (Ht + 1) * (Wt + 1), "ls_texture_forward", "ls_texture_backward", lambda shape: shape[:3], 16)
+_MIP = _Lookup("_largesteps_mip_order", 3, "ls_mip_workspace_bytes", "ls_mip_order", lambda Bt, Ht, Wt, Lmax, mode, bnd: 2 if mode == 1 else 1, _mip_keys)
+_CUBE = _Lookup("_largesteps_cube_order", 1, "ls_cube_workspace_bytes", "ls_cube_order", lambda Bt, n, filt: 4 if filt == 1 else 1,
+                lambda Bt, n, filt: 6 * Bt * n * n, "ls_cube_forward", "ls_cube_backward", lambda shape: (shape[0], shape[2]), 4)
+
+
+class _Order:
+    """The items of one lookup in the order the gradient to the texels sums them in: the pixels of a uv image sorted by their base tap
+    (`_TEXEL`), its (pixel, level) items sorted by (level, base tap) (`_MIP`: two items per pixel for 'linear-mipmap-linear'), its
+    (pixel, tap) items sorted by their destination texel (`_CUBE`: four items per pixel for 'linear'). It depends on uv (and uv_da and the
+    bias), the texture's shape and the modes, not on the texture's values: made at most once per uv tensor and version, by the first
+    backward that needs it, and shared through the uv tensor (a fixed uv -- backgrounds, texture fitting on fixed geometry -- sorts
+    once)."""
+    __slots__ = ("kind", "key", "order", "seg")
+
+    def __init__(self, kind, key):
+        self.kind, self.key, self.order, self.seg = kind, key, None, None
+
+    def get(self, *args):
+        """args: the kind's tensors as the kernels get them (uv first), then the integers of its native order function"""
         if self.order is None:
-            B, H, W, _ = u.shape
-            dev = u.device
-            n = ctypes.c_size_t(0)
-            _native.check(_native.lib().ls_texture_workspace_bytes(B, H, W, ctypes.byref(n)))
-            ws = torch.empty(n.value, dtype=torch.uint8, device=dev)
-            order = torch.empty(B * H * W, dtype=torch.int32, device=dev)
-            seg = torch.empty(Bt * (Ht + 1) * (Wt + 1) + 1, dtype=torch.int32, device=dev)
+            kind, lib = self.kind, _native.lib()
+            tensors, conf = args[:kind.tensors], args[kind.tensors:]
+            B, H, W, _ = tensors[0].shape
+            dev = tensors[0].device
+            ws = _scratch(dev, getattr(lib, kind.workspace), B, H, W)
+            order = torch.empty(kind.items(*conf) * B * H * W, dtype=torch.int32, device=dev)
+            seg = torch.empty(kind.nkeys(*conf) + 1, dtype=torch.int32, device=dev)
             with torch.cuda.device(dev):
-                _native.check(_native.lib().ls_texture_order(_native.ptr(u), B, H, W, Bt, Ht, Wt, filt, bnd, _native.ptr(order), _native.ptr(seg),
-                                                             _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
+                _native.check(getattr(lib, kind.order)(*map(_native.ptr, tensors), B, H, W, *conf, _native.ptr(order), _native.ptr(seg),
+                                                       _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
             self.order, self.seg = order, seg
         return self.order, self.seg
 
 
-def _texel_order_slot(uv, Bt, Ht, Wt, filt, bnd):
-    key = (uv._version, uv.data_ptr(), tuple(uv.shape), tuple(uv.stride()), Bt, Ht, Wt, filt, bnd)
+_TexelOrder, _CubeOrder = functools.partial(_Order, _TEXEL), functools.partial(_Order, _CUBE)
+
+
+def _order_slot(kind, tensors, conf):
     # while a graph is being captured the order is neither taken from the tensor nor left on it: a replay must sort the uv it finds
     # (a captured body may read a uv that is updated in place between replays), and memory of the graph's pool must not outlive it
     if torch.cuda.is_current_stream_capturing():
-        return _TexelOrder(None)
-    slot = getattr(uv, "_largesteps_texel_order", None)
+        return _Order(kind, None)
+    key = sum(((None,) if t is None else (t._version, t.data_ptr(), tuple(t.shape), tuple(t.stride())) for t in tensors), ()) + tuple(conf)
+    slot = getattr(tensors[0], kind.attr, None)
     if slot is not None and slot.key == key:
         return slot
-    return _TexelOrder(key)
+    return _Order(kind, key)
 
 
-def _aligned(t):
-    """float2 / float4 rows: torch's allocations are 256-byte aligned, a view into one need not be"""
-    return t if t.data_ptr() % 16 == 0 else t.clone()
+def _lookup(kind, fn, tensors, conf, *args):
+    """fn.apply(*args, slot) with the order slot of (tensors, conf); the slot stays on uv = tensors[0] if it has a key"""
+    slot = _order_slot(kind, tensors, conf)
+    out = fn.apply(*args, slot)
+    if slot.key is not None:
+        setattr(tensors[0], kind.attr, slot)
+    return out
+
+
+def _grad_buffers(g, *wanted):
+    """the upstream gradient made plain, then an empty gradient like t for every (t, needed) with needed set, else None"""
+    return (_plain(g.to(torch.float32), 16),) + tuple(torch.empty_like(t) if needed else None for t, needed in wanted)
+
+
+def _views(grads, shapes):
+    """the gradients in the shapes the caller's tensors had"""
+    return tuple(None if x is None else x.view(shape) for x, shape in zip(grads, shapes))
 
 
 class _Texture(Function):
+    """the plain 2D lookup (`_TEXEL`) and the cube-map lookup (`_CUBE`); modes = (filter, boundary) and (filter,)"""
     @staticmethod
-    def forward(ctx, tex, uv, filt, bnd, slot):
-        t, u = tex.detach(), uv.detach()
-        t = _aligned(t if t.is_contiguous() else t.contiguous())
-        u = _aligned(u if u.is_contiguous() else u.contiguous())
-        Bt, Ht, Wt, C = t.shape
+    def forward(ctx, tex, uv, kind, modes, slot):
+        t, u = _plain(tex, 16), _plain(uv, kind.uv_align)
+        dims, C = kind.dims(t.shape), t.shape[-1]
         B, H, W, _ = u.shape
         dev = u.device
         out = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _native.check(_native.lib().ls_texture_forward(_native.ptr(t), Bt, Ht, Wt, C, _native.ptr(u), B, H, W, filt, bnd, _native.ptr(out),
-                                                           dev.index, _native.stream_of(dev)))
+            _native.check(getattr(_native.lib(), kind.forward)(_native.ptr(t), *dims, C, _native.ptr(u), B, H, W, *modes, _native.ptr(out),
+                                                               dev.index, _native.stream_of(dev)))
         ctx.save_for_backward(t, u)
-        ctx.modes = (filt, bnd)
+        ctx.conf = (kind, dims, modes)
         ctx.slot = slot
         ctx.shapes = (tuple(tex.shape), tuple(uv.shape))
         return out
 
     @staticmethod
     def backward(ctx, g):
-        need_tex, need_uv = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_tex, need_uv = ctx.needs_input_grad[:2]
         if not (need_tex or need_uv):
-            return None, None, None, None, None
+            return (None,) * 5
         t, u = ctx.saved_tensors
-        filt, bnd = ctx.modes
-        Bt, Ht, Wt, C = t.shape
+        kind, dims, modes = ctx.conf
+        C = t.shape[-1]
         B, H, W, _ = u.shape
         dev = u.device
-        g = _aligned(g.to(torch.float32).contiguous())
-        gt = torch.empty_like(t) if need_tex else None
-        gu = torch.empty_like(u) if need_uv else None
+        g, gt, gu = _grad_buffers(g, (t, need_tex), (u, need_uv))
         order = seg = None
         if need_tex:
-            order, seg = ctx.slot.get(u, Bt, Ht, Wt, filt, bnd)
+            order, seg = ctx.slot.get(u, *dims, *modes)
         with torch.cuda.device(dev):
-            _native.check(_native.lib().ls_texture_backward(_native.ptr(t), Bt, Ht, Wt, C, _native.ptr(u), B, H, W, filt, bnd, _native.ptr(g),
-                                                            _native.ptr(order), _native.ptr(seg), _native.ptr(gt), _native.ptr(gu), dev.index,
-                                                            _native.stream_of(dev)))
-        return (gt.view(ctx.shapes[0]) if need_tex else None), (gu.view(ctx.shapes[1]) if need_uv else None), None, None, None
+            _native.check(getattr(_native.lib(), kind.backward)(_native.ptr(t), *dims, C, _native.ptr(u), B, H, W, *modes, _native.ptr(g),
+                                                                _native.ptr(order), _native.ptr(seg), _native.ptr(gt), _native.ptr(gu),
+                                                                dev.index, _native.stream_of(dev)))
+        return _views((gt, gu), ctx.shapes) + (None, None, None)
 
 
 def _mip_last_level(Ht, Wt, max_mip_level=None):
@@ -956,59 +1001,7 @@ def texture_construct_mip(tex, max_mip_level=None, cube_mode=False):
     Lmax = _mip_last_level(tex.shape[1], tex.shape[2], max_mip_level)
     if not tex.is_cuda:
         raise NotImplementedError("largesteps.render.texture_construct_mip: the mipmap pyramid needs a HIP device")
-    t = tex.detach()
-    t = _aligned(t if t.is_contiguous() else t.contiguous())
-    return _Mip(tex, Lmax, _build_pyramid(t, Lmax))
-
-
-def _version_key(t):
-    return None if t is None else (t._version, t.data_ptr(), tuple(t.shape), tuple(t.stride()))
-
-
-class _MipOrder:
-    """The (pixel, level) items of one mipmapped lookup sorted by (level, base tap) -- the order the gradient of the pyramid sums in. It
-    depends on uv, uv_da, the bias, the texture's shape and the modes, not on the texture's values: cached on the uv tensor like
-    `_TexelOrder`, keyed by the versions of all three tensors."""
-    __slots__ = ("key", "order", "seg")
-
-    def __init__(self, key):
-        self.key, self.order, self.seg = key, None, None
-
-    def get(self, u, da, b, Bt, Ht, Wt, Lmax, mode, bnd):
-        if self.order is None:
-            B, H, W, _ = u.shape
-            dev = u.device
-            n = ctypes.c_size_t(0)
-            _native.check(_native.lib().ls_mip_workspace_bytes(B, H, W, ctypes.byref(n)))
-            ws = torch.empty(n.value, dtype=torch.uint8, device=dev)
-            order = torch.empty((2 if mode == 1 else 1) * B * H * W, dtype=torch.int32, device=dev)
-            nk = Bt * sum((max(Ht >> l, 1) + 1) * (max(Wt >> l, 1) + 1) for l in range(Lmax + 1))
-            seg = torch.empty(nk + 1, dtype=torch.int32, device=dev)
-            with torch.cuda.device(dev):
-                _native.check(_native.lib().ls_mip_order(_native.ptr(u), _native.ptr(da), _native.ptr(b), B, H, W, Bt, Ht, Wt, Lmax, mode, bnd,
-                                                         _native.ptr(order), _native.ptr(seg), _native.ptr(ws), ws.numel(), dev.index,
-                                                         _native.stream_of(dev)))
-            self.order, self.seg = order, seg
-        return self.order, self.seg
-
-
-def _mip_order_slot(uv, uv_da, bias, Bt, Ht, Wt, Lmax, mode, bnd):
-    if torch.cuda.is_current_stream_capturing():            # as for _TexelOrder: a replay sorts what it finds
-        return _MipOrder(None)
-    key = (_version_key(uv), _version_key(uv_da), _version_key(bias), Bt, Ht, Wt, Lmax, mode, bnd)
-    slot = getattr(uv, "_largesteps_mip_order", None)
-    if slot is not None and slot.key == key:
-        return slot
-    return _MipOrder(key)
-
-
-def _plain(t, align):
-    """detached, fp32-contiguous and aligned for the kernels' vector loads (None stays None)"""
-    if t is None:
-        return None
-    d = t.detach()
-    d = d if d.is_contiguous() else d.contiguous()
-    return d if d.data_ptr() % align == 0 else d.clone()
+    return _Mip(tex, Lmax, _build_pyramid(_plain(tex, 16), Lmax))
 
 
 class _TextureMip(Function):
@@ -1040,10 +1033,7 @@ class _TextureMip(Function):
         Bt, Ht, Wt, C = t.shape
         B, H, W, _ = u.shape
         dev = u.device
-        g = _aligned(g.to(torch.float32).contiguous())
-        gt = torch.empty_like(t) if need_tex else None
-        gpyr = torch.empty_like(pyr) if need_tex else None
-        gu = torch.empty_like(u) if need_uv else None
+        g, gt, gpyr, gu = _grad_buffers(g, (t, need_tex), (pyr, need_tex), (u, need_uv))
         glod = torch.empty((B, H, W), dtype=torch.float32, device=dev) if (need_da or need_bias) else None
         gda = torch.empty_like(da) if need_da else None
         order = seg = None
@@ -1057,9 +1047,7 @@ class _TextureMip(Function):
                                               _native.ptr(gpyr), _native.ptr(gu), _native.ptr(glod), _native.ptr(gda), dev.index, st))
             if need_tex and Lmax > 0:
                 _native.check(lib.ls_mip_fold(_native.ptr(gt), Bt, Ht, Wt, C, Lmax, _native.ptr(gpyr), dev.index, st))
-        s_tex, s_uv, s_da, s_b = ctx.shapes
-        return ((gt.view(s_tex) if need_tex else None), (gu.view(s_uv) if need_uv else None), (gda.view(s_da) if need_da else None),
-                (glod.view(s_b) if need_bias else None), None, None, None, None, None)
+        return _views((gt, gu, gda, glod if need_bias else None), ctx.shapes) + (None,) * 5
 
 
 def _check_mip_inputs(uv, uv_da, mip_level_bias):
@@ -1093,84 +1081,44 @@ def _texture_mip(tex, uv, uv_da, mip_level_bias, mip, mode, bnd, max_mip_level):
         pyr = mip.pyr
     else:
         Lmax, pyr = _mip_last_level(Ht, Wt, max_mip_level), None
-    slot = _mip_order_slot(uv, uv_da, mip_level_bias, Bt, Ht, Wt, Lmax, mode, bnd)
-    out = _TextureMip.apply(tex, uv, uv_da, mip_level_bias, pyr, Lmax, mode, bnd, slot)
-    if slot.key is not None:
-        uv._largesteps_mip_order = slot
-    return out
+    return _lookup(_MIP, _TextureMip, (uv, uv_da, mip_level_bias), (Bt, Ht, Wt, Lmax, mode, bnd), tex, uv, uv_da, mip_level_bias, pyr, Lmax, mode, bnd)
 
 
-class _CubeOrder:
-    """The (pixel, tap) items of one cube-map lookup sorted by their destination texel -- the order the gradient of the cube sums in
-    (four items per pixel for 'linear', one for 'nearest'). It depends on the directions, the cube's shape and the filter, not on the
-    texels' values: cached on the uv tensor exactly as `_TexelOrder` is."""
-    __slots__ = ("key", "order", "seg")
-
-    def __init__(self, key):
-        self.key, self.order, self.seg = key, None, None
-
-    def get(self, u, Bt, n, filt):
-        if self.order is None:
-            B, H, W, _ = u.shape
-            dev = u.device
-            ws = _scratch(dev, _native.lib().ls_cube_workspace_bytes, B, H, W)
-            order = torch.empty((4 if filt == 1 else 1) * B * H * W, dtype=torch.int32, device=dev)
-            seg = torch.empty(6 * Bt * n * n + 1, dtype=torch.int32, device=dev)
-            with torch.cuda.device(dev):
-                _native.check(_native.lib().ls_cube_order(_native.ptr(u), B, H, W, Bt, n, filt, _native.ptr(order), _native.ptr(seg),
-                                                          _native.ptr(ws), ws.numel(), dev.index, _native.stream_of(dev)))
-            self.order, self.seg = order, seg
-        return self.order, self.seg
-
-
-def _cube_order_slot(uv, Bt, n, filt):
-    if torch.cuda.is_current_stream_capturing():            # as for _TexelOrder: a replay sorts what it finds
-        return _CubeOrder(None)
-    key = (uv._version, uv.data_ptr(), tuple(uv.shape), tuple(uv.stride()), Bt, n, filt)
-    slot = getattr(uv, "_largesteps_cube_order", None)
-    if slot is not None and slot.key == key:
-        return slot
-    return _CubeOrder(key)
-
-
-class _TextureCube(Function):
-    @staticmethod
-    def forward(ctx, tex, uv, filt, slot):
-        t, u = _plain(tex, 16), _plain(uv, 4)
-        Bt, _, n, _, C = t.shape
-        B, H, W, _ = u.shape
-        dev = u.device
-        out = torch.empty((B, H, W, C), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _native.check(_native.lib().ls_cube_forward(_native.ptr(t), Bt, n, C, _native.ptr(u), B, H, W, filt, _native.ptr(out), dev.index,
-                                                        _native.stream_of(dev)))
-        ctx.save_for_backward(t, u)
-        ctx.filt = filt
-        ctx.slot = slot
-        ctx.shapes = (tuple(tex.shape), tuple(uv.shape))
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        need_tex, need_uv = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if not (need_tex or need_uv):
-            return None, None, None, None
-        t, u = ctx.saved_tensors
-        filt = ctx.filt
-        Bt, _, n, _, C = t.shape
-        B, H, W, _ = u.shape
-        dev = u.device
-        g = _aligned(g.to(torch.float32).contiguous())
-        gt = torch.empty_like(t) if need_tex else None
-        gu = torch.empty_like(u) if need_uv else None
-        order = seg = None
-        if need_tex:
-            order, seg = ctx.slot.get(u, Bt, n, filt)
-        with torch.cuda.device(dev):
-            _native.check(_native.lib().ls_cube_backward(_native.ptr(t), Bt, n, C, _native.ptr(u), B, H, W, filt, _native.ptr(g),
-                                                         _native.ptr(order), _native.ptr(seg), _native.ptr(gt), _native.ptr(gu), dev.index,
-                                                         _native.stream_of(dev)))
-        return (gt.view(ctx.shapes[0]) if need_tex else None), (gu.view(ctx.shapes[1]) if need_uv else None), None, None
+def _check_lookup(tex, uv, cube):
+    """what `texture` checks of tex and uv for the 2D lookups and for the cube lookup, in the order its docstring gives"""
+    for t, what in ((tex, "tex"), (uv, "uv")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what} must be a torch.Tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{what} must be float32, got {t.dtype}")
+    if cube:
+        if tex.dim() != 5 or tex.shape[1] != 6 or tex.shape[2] != tex.shape[3]:
+            raise ValueError(f"a cube map must be (1 or B, 6, n, n, C) with square faces, got {tuple(tex.shape)}")
+        if uv.dim() != 4 or uv.shape[3] != 3:
+            raise ValueError(f"uv must be (B, H, W, 3) directions for boundary_mode='cube', got {tuple(uv.shape)}")
+    else:
+        if tex.dim() != 4:
+            raise ValueError(f"tex must be (1 or B, Ht, Wt, C), got {tuple(tex.shape)}")
+        if uv.dim() != 4 or uv.shape[3] != 2:
+            raise ValueError(f"uv must be (B, H, W, 2), got {tuple(uv.shape)}")
+    Bt, (Ht, Wt, C) = tex.shape[0], tex.shape[-3:]
+    B, H, W, _ = uv.shape
+    if Bt not in (1, B):
+        raise ValueError(f"tex has {Bt} batches for {B} images")
+    if not (1 <= Ht <= TEXTURE_MAX_SIZE and 1 <= Wt <= TEXTURE_MAX_SIZE):
+        raise ValueError(f"a cube face must be between 1 and {TEXTURE_MAX_SIZE} texels a side, got {Ht}" if cube else
+                         f"the texture must be between 1 and {TEXTURE_MAX_SIZE} texels a side, got {Ht} x {Wt}")
+    if not 1 <= C <= TEXTURE_MAX_CHANNELS:
+        raise ValueError(f"the texture must have between 1 and {TEXTURE_MAX_CHANNELS} channels, got {C}")
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError(f"uv must not be empty, got {tuple(uv.shape)}")
+    if (4 if cube else 1) * B * H * W >= 2 ** 31 - 1:
+        raise OverflowError(f"uv has {B * H * W} pixels: " + ("the cube lookup indexes four items per pixel with int32" if cube else
+                                                              "the kernels index them with int32"))
+    if cube and 6 * Bt * Ht * Ht >= 2 ** 31 - 2:
+        raise OverflowError(f"the cube maps have {6 * Bt * Ht * Ht} texels: the kernels index them with int32")
+    if tex.device != uv.device:
+        raise ValueError(f"tex is on {tex.device}, uv on {uv.device}")
 
 
 def _texture_cube(tex, uv, filter_mode):
@@ -1182,37 +1130,9 @@ def _texture_cube(tex, uv, filter_mode):
                                   "is not supported; use 'linear' or 'nearest'")
     if filter_mode not in _FILTER_MODES:
         raise ValueError(f"filter_mode must be one of {sorted(_FILTER_MODES)}, got {filter_mode!r}")
-    for t, what in ((tex, "tex"), (uv, "uv")):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{what} must be a torch.Tensor, got {type(t).__name__}")
-        if t.dtype != torch.float32:
-            raise TypeError(f"{what} must be float32, got {t.dtype}")
-    if tex.dim() != 5 or tex.shape[1] != 6 or tex.shape[2] != tex.shape[3]:
-        raise ValueError(f"a cube map must be (1 or B, 6, n, n, C) with square faces, got {tuple(tex.shape)}")
-    if uv.dim() != 4 or uv.shape[3] != 3:
-        raise ValueError(f"uv must be (B, H, W, 3) directions for boundary_mode='cube', got {tuple(uv.shape)}")
-    Bt, _, n, _, C = tex.shape
-    B, H, W, _ = uv.shape
-    if Bt not in (1, B):
-        raise ValueError(f"tex has {Bt} batches for {B} images")
-    if not 1 <= n <= TEXTURE_MAX_SIZE:
-        raise ValueError(f"a cube face must be between 1 and {TEXTURE_MAX_SIZE} texels a side, got {n}")
-    if not 1 <= C <= TEXTURE_MAX_CHANNELS:
-        raise ValueError(f"the texture must have between 1 and {TEXTURE_MAX_CHANNELS} channels, got {C}")
-    if B < 1 or H < 1 or W < 1:
-        raise ValueError(f"uv must not be empty, got {tuple(uv.shape)}")
-    if 4 * B * H * W >= 2 ** 31 - 1:
-        raise OverflowError(f"uv has {B * H * W} pixels: the cube lookup indexes four items per pixel with int32")
-    if 6 * Bt * n * n >= 2 ** 31 - 2:
-        raise OverflowError(f"the cube maps have {6 * Bt * n * n} texels: the kernels index them with int32")
-    if tex.device != uv.device:
-        raise ValueError(f"tex is on {tex.device}, uv on {uv.device}")
+    _check_lookup(tex, uv, True)
     filt = _FILTER_MODES[filter_mode]
-    slot = _cube_order_slot(uv, Bt, n, filt)
-    out = _TextureCube.apply(tex, uv, filt, slot)
-    if slot.key is not None:
-        uv._largesteps_cube_order = slot
-    return out
+    return _lookup(_CUBE, _Texture, (uv,), (tex.shape[0], tex.shape[2], filt), tex, uv, _CUBE, (filt,))
 
 
 def _texture_cpu(tex, uv):
@@ -1289,29 +1209,8 @@ def texture(tex, uv, uv_da=None, mip_level_bias=None, mip=None, filter_mode='lin
         raise ValueError(f"filter_mode must be one of {sorted(_FILTER_MODES)}, got {filter_mode!r}")
     if boundary_mode not in _BOUNDARY_MODES:
         raise ValueError(f"boundary_mode must be one of {sorted(_BOUNDARY_MODES)}, got {boundary_mode!r}")
-    for t, what in ((tex, "tex"), (uv, "uv")):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{what} must be a torch.Tensor, got {type(t).__name__}")
-        if t.dtype != torch.float32:
-            raise TypeError(f"{what} must be float32, got {t.dtype}")
-    if tex.dim() != 4:
-        raise ValueError(f"tex must be (1 or B, Ht, Wt, C), got {tuple(tex.shape)}")
-    if uv.dim() != 4 or uv.shape[3] != 2:
-        raise ValueError(f"uv must be (B, H, W, 2), got {tuple(uv.shape)}")
-    Bt, Ht, Wt, C = tex.shape
-    B, H, W, _ = uv.shape
-    if Bt not in (1, B):
-        raise ValueError(f"tex has {Bt} batches for {B} images")
-    if not (1 <= Ht <= TEXTURE_MAX_SIZE and 1 <= Wt <= TEXTURE_MAX_SIZE):
-        raise ValueError(f"the texture must be between 1 and {TEXTURE_MAX_SIZE} texels a side, got {Ht} x {Wt}")
-    if not 1 <= C <= TEXTURE_MAX_CHANNELS:
-        raise ValueError(f"the texture must have between 1 and {TEXTURE_MAX_CHANNELS} channels, got {C}")
-    if B < 1 or H < 1 or W < 1:
-        raise ValueError(f"uv must not be empty, got {tuple(uv.shape)}")
-    if B * H * W >= 2 ** 31 - 1:
-        raise OverflowError(f"uv has {B * H * W} pixels: the kernels index them with int32")
-    if tex.device != uv.device:
-        raise ValueError(f"tex is on {tex.device}, uv on {uv.device}")
+    _check_lookup(tex, uv, False)
+    Bt, Ht, Wt, _ = tex.shape
     if mipmapped:
         return _texture_mip(tex, uv, uv_da, mip_level_bias, mip, _MIP_FILTER_MODES[filter_mode], _BOUNDARY_MODES[boundary_mode], max_mip_level)
     filt, bnd = _FILTER_MODES[filter_mode], _BOUNDARY_MODES[boundary_mode]
@@ -1320,11 +1219,7 @@ def texture(tex, uv, uv_da=None, mip_level_bias=None, mip=None, filter_mode='lin
             raise NotImplementedError("largesteps.render.texture: CPU tensors get filter_mode='linear' with boundary_mode='wrap' only; "
                                       "every other mode needs a HIP device")
         return _texture_cpu(tex, uv)
-    slot = _texel_order_slot(uv, Bt, Ht, Wt, filt, bnd)
-    out = _Texture.apply(tex, uv, filt, bnd, slot)
-    if slot.key is not None:
-        uv._largesteps_texel_order = slot
-    return out
+    return _lookup(_TEXEL, _Texture, (uv,), (Bt, Ht, Wt, filt, bnd), tex, uv, _TEXEL, (filt, bnd))
 
 
 def persp_proj(fov_x=45, ar=1, near=0.1, far=100, device=None):

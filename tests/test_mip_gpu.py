@@ -350,6 +350,40 @@ def test_changing_uv_da_in_place_invalidates_the_cached_order():
     assert np.array_equal(t.grad.cpu().numpy(), _run(tex, uv, d.cpu().numpy(), bias, g, 'linear-mipmap-linear', 'wrap', None)[1])
 
 
+def test_a_level_of_the_pyramid_is_read_exactly_as_a_plain_texture():
+    """With mip_level_bias all zero and no uv_da the level of detail is 0 and level 0 alone is read: both mip modes return the bits of
+    texture(tex, uv, 'linear', boundary) -- forward, gradient to tex and gradient to uv -- with max_mip_level=0 and with the full pyramid
+    (the fold then adds the zero gradients of the upper levels), and the gradient to the bias is exactly zero. uv is uniform in [-1, 2],
+    so taps fall outside under every boundary mode; 2048 pixels give the 8 x 8 texture more than 64 items per texel (the wave-wide sum)
+    and the 64 x 64 textures fewer."""
+    import largesteps.render as dr
+    rng = np.random.default_rng(11)
+    uv = rng.uniform(-1.0, 2.0, (2, 32, 32, 2)).astype(np.float32)
+
+    def bits(x):
+        return x.contiguous().view(torch.int32)
+
+    for Bt, Ht in ((1, 8), (2, 64)):
+        for C in (3, 4, 5):
+            tex = rng.standard_normal((Bt, Ht, Ht, C)).astype(np.float32)
+            g = dev(rng.standard_normal((2, 32, 32, C)).astype(np.float32))
+            for boundary in ts.BOUNDARIES:
+                t, c = dev(tex).requires_grad_(True), dev(uv).requires_grad_(True)
+                want = dr.texture(t, c, filter_mode='linear', boundary_mode=boundary)
+                (want * g).sum().backward()
+                for mode in ms.MODES:
+                    for max_level in (0, None):
+                        tm, cm = dev(tex).requires_grad_(True), dev(uv).requires_grad_(True)
+                        bias = torch.zeros((2, 32, 32), dtype=torch.float32, device=DEV).requires_grad_(True)
+                        got = dr.texture(tm, cm, mip_level_bias=bias, filter_mode=mode, boundary_mode=boundary, max_mip_level=max_level)
+                        (got * g).sum().backward()
+                        what = (Bt, Ht, C, boundary, mode, max_level)
+                        assert torch.equal(bits(got), bits(want)), ("forward",) + what
+                        assert torch.equal(bits(tm.grad), bits(t.grad)), ("grad tex",) + what
+                        assert torch.equal(bits(cm.grad), bits(c.grad)), ("grad uv",) + what
+                        assert bias.grad is not None and torch.count_nonzero(bias.grad) == 0, ("grad bias",) + what
+
+
 def _chain_device(tp, tf, ta, tt, H, W):
     import largesteps.render as dr
     rast, rast_db = dr.rasterize(None, tp, tf, (H, W))

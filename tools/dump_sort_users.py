@@ -6,9 +6,12 @@ two directories hold the same bytes:
     python tools/dump_sort_users.py compare out_a out_b                        (exit status 1 when a file differs or is missing)
 Covered: remove_duplicates; the CSR transpose of an unsymmetric matrix (backward of to_differential); corner_ranks through the
 normals, forward and backward; rasterize / interpolate / antialias forward and every gradient; texture forward and both gradients in
-every filter x boundary mode; hausdorff; one remesh_botsch iteration; the direct solver's first solve on the 70k mesh. The renderer's
-shapes hold faces and texels with more than 64 pixels and with fewer (asserted: per face from the rast ids of both images, per texel
-from the nearest texel of every pixel), so both arms of the segmented sum are compared.
+every filter x boundary mode; the mipmapped lookup (both mip modes x the boundary modes x uv_da, bias or both x a pyramid given or
+built in the call) and the cube lookup (both filters, directions across seams and at corners), forward and every gradient, each for
+1, 4 and 5 channels (one channel group, the float4 rows, two groups); hausdorff; one remesh_botsch iteration; the direct solver's
+first solve on the 70k mesh. The renderer's shapes hold faces and texels with more than 64 pixels and with fewer (asserted: per face
+from the rast ids of both images, per texel from the nearest texel of every pixel, per pyramid and cube texel from the item order
+itself), so both arms of the segmented sum are compared.
 The queries over one mesh and its LBVH (csrc/lbvh.h, meshbvh.h) on the 70k mesh: squared_distance with both gradients, the closest
 point's weights, max_squared_distance, RayMesh.intersect with its three gradients and occluded, winding_number at beta = 2 and exact,
 the hierarchy and the node moments, signed_distance with its gradients, sample_surface with its vertex gradient, chamfer_distance
@@ -149,6 +152,67 @@ def dump(out):
                 tag = f"texture_{Ht}_{filt}_{bnd}"
                 save(tag + "_out", o), save(tag + "_grad_tex", tex.grad)
                 save(tag + "_grad_uv", uv.grad if uv.grad is not None else torch.zeros_like(uv))
+
+    def grad_or_zero(x):
+        return x.grad if x.grad is not None else torch.zeros_like(x)
+
+    # ---- mipmapped texture: the same two sizes; uv_da spreads the pixels' footprints over every level, the bias alone does too
+    def mip_items_per_texel(seg, Ht, Lmax):
+        """wrap mode, one batch entry: texel i of a level gets the items of base positions i and i - 1 (wrapped) along each axis"""
+        cnt, k, per = np.diff(seg.cpu().numpy().astype(np.int64)), 0, []
+        for l in range(Lmax + 1):
+            h = max(Ht >> l, 1)
+            c = cnt[k:k + (h + 1) * (h + 1)].reshape(h + 1, h + 1)[1:, 1:]
+            k += (h + 1) * (h + 1)
+            per.append((c + np.roll(c, 1, 0) + np.roll(c, 1, 1) + np.roll(np.roll(c, 1, 0), 1, 1)).ravel())
+        return np.concatenate(per)
+
+    for Ht in (8, 256):
+        Lfull = int(np.log2(Ht))
+        da_np = rng.standard_normal((2, 64, 64, 4)) * 2.0 ** rng.uniform(-1.0, Lfull + 1.0, (2, 64, 64, 1)) / Ht
+        lod_inputs = {"both": (da_np, rng.uniform(-1.0, 1.0, (2, 64, 64))), "da": (da_np, None),
+                      "bias": (None, rng.uniform(-1.0, Lfull + 1.0, (2, 64, 64)))}
+        for C in (1, 4, 5):
+            tex_np = rng.random((1, Ht, Ht, C))
+            for mode in ("linear-mipmap-nearest", "linear-mipmap-linear"):
+                for bnd in ("wrap", "clamp", "zero"):
+                    for how, (da_a, bias_a) in lod_inputs.items():
+                        for prebuilt in (False, True):
+                            tex, uv = dev_f32(tex_np).requires_grad_(True), dev_f32(uv_np).requires_grad_(True)
+                            da = None if da_a is None else dev_f32(da_a).requires_grad_(True)
+                            bias = None if bias_a is None else dev_f32(bias_a).requires_grad_(True)
+                            mip = dr.texture_construct_mip(tex) if prebuilt else None
+                            o = dr.texture(tex, uv, uv_da=da, mip_level_bias=bias, mip=mip, filter_mode=mode, boundary_mode=bnd)
+                            (o * weights(o)).sum().backward()
+                            if bnd == "wrap" and C == 1 and not prebuilt:
+                                items = mip_items_per_texel(uv._largesteps_mip_order.seg, Ht, Lfull)
+                                assert items.max() > 64 and (Ht == 8 or 0 < items[items > 0].min() <= 64), \
+                                    f"texels of the {Ht} x {Ht} pyramid: {items.min()} .. {items.max()} items"
+                            tag = f"mip_{Ht}_c{C}_{mode.split('-')[-1]}_{bnd}_{how}_{'given' if prebuilt else 'built'}"
+                            save(tag + "_out", o), save(tag + "_grad_tex", tex.grad), save(tag + "_grad_uv", grad_or_zero(uv))
+                            if da is not None:
+                                save(tag + "_grad_uv_da", grad_or_zero(da))
+                            if bias is not None:
+                                save(tag + "_grad_bias", grad_or_zero(bias))
+
+    # ---- cube map: 4 x 4 faces under 2 x 64 x 64 directions (hundreds of items a texel) and 64 x 64 faces (mostly none or a few);
+    # the last 512 directions of each image hug the 8 corners and the 12 edges, so taps cross seams and one of four is dropped
+    dirs_np = rng.standard_normal((2, 64 * 64, 3))
+    near = rng.integers(0, 2, (2, 512, 3)) * 2.0 - 1.0
+    near[:, 256:, :] *= np.where(rng.integers(0, 3, (2, 256, 1)) == np.arange(3), rng.uniform(-1.0, 1.0, (2, 256, 1)), 1.0)      # edges
+    dirs_np[:, -512:] = (near + 0.02 * rng.standard_normal(near.shape)) * rng.uniform(0.5, 2.0, (2, 512, 1))
+    dirs_np = dirs_np.reshape(2, 64, 64, 3)
+    for n in (4, 64):
+        for C in (1, 4, 5):
+            tex_np = rng.random((1, 6, n, n, C))
+            for filt in ("nearest", "linear"):
+                tex, d = dev_f32(tex_np).requires_grad_(True), dev_f32(dirs_np).requires_grad_(True)
+                o = dr.texture(tex, d, filter_mode=filt, boundary_mode="cube")
+                (o * weights(o)).sum().backward()
+                items = np.diff(d._largesteps_cube_order.seg.cpu().numpy().astype(np.int64))      # keyed by destination texel
+                assert (items.max() > 64) if n == 4 else (0 < items[items > 0].min() <= 64), f"texels of 6 x {n} x {n}: {items.min()} .. {items.max()} items"
+                tag = f"cube_{n}_c{C}_{filt}"
+                save(tag + "_out", o), save(tag + "_grad_tex", tex.grad), save(tag + "_grad_uv", grad_or_zero(d))
     # ---- the mesh queries: one handle over the 70k mesh
     import math
     from largesteps import _native
