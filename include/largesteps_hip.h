@@ -40,6 +40,7 @@
  *   ls_mesh_ray_*        igl.ray_mesh_intersect, and what igl.ambient_occlusion is built from: rays against the mesh of a distance handle
  *   ls_mesh_winding_*    igl.winding_number / igl.fast_winding_number, the sign of igl.signed_distance: over the same handle
  *   ls_mesh_selfx_*      igl.fast_find_self_intersections: which faces of the handle's mesh cut through each other
+ *   ls_iso_*             igl.marching_tets on the Kuhn split of a regular grid: a level set as a mesh, with the gradient to the field
  */
 #ifndef LARGESTEPS_HIP_H
 #define LARGESTEPS_HIP_H
@@ -765,6 +766,42 @@ int ls_mesh_winding_arrays(void* handle, const void* moments, int32_t* left, int
 int ls_mesh_selfx_count(void* handle, int32_t* counts, int64_t* total, unsigned char* flags, void* stream);
 int ls_mesh_selfx_workspace_bytes(int64_t F, int64_t k, size_t* bytes);
 int ls_mesh_selfx_pairs(void* handle, const int32_t* counts, int64_t k, int64_t* pairs, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The level set S = iso of a scalar field on a regular grid as a triangle mesh, and the gradient of its vertices in the field
+ * (largesteps/levelset.py). The rule is stated in csrc/isosurf.hip and DESIGN.md section 2.13 and restated in numpy by
+ * tests/isosurf_statement.py, and the device answers with the same bits: marching tetrahedra on the Kuhn split. S (nx, ny, nz) fp32,
+ * node (i, j, k) at origin + spacing * (i, j, k) with id (i ny + j) nz + k; every cube of 8 nodes is cut into the 6 tets c, c + e_a,
+ * c + e_a + e_b, c + (1, 1, 1), one per permutation of the axes in lexicographic order, whose edges run along the 7 directions 100 010 001
+ * 110 011 101 111 = slots 0..6 and belong to the node they start at. A node is low iff S < iso (a NaN is high); an edge is live iff
+ * both ends are finite and exactly one is low; a cube with a non-finite corner emits nothing; a grid with a side of 1 has no cubes
+ * and no vertices. One vertex per live edge, ordered by (node, slot) through an exclusive scan of the popcounts of the nodes' 7-bit
+ * live masks: no sort, no atomics. With a the owner and b = a + d, in fp32: t = (iso - S[a]) / (S[b] - S[a]) clamped to [0, 1],
+ * x = origin_x + spacing_x * ((float)i_a + t d_x). Faces are ordered by (cube, tet, triangle) through a second scan, by a 16-case
+ * table, each with its normal from the low side to the high side.
+ *   ls_iso_workspace_bytes  the workspace of the three calls below for an (nx, ny, nz) grid (256-byte aligned regions): the masks, the
+ *                           counts and the two offset arrays.
+ *   ls_iso_count            fills the workspace and totals (int64[2], device) = (the number of vertices, the number of faces).
+ *                           ASYNC, capturable: no allocation, no synchronisation.
+ *   ls_iso_fill             V (n, 3) fp32 the vertices, E (n) int64 = 8 node + slot, the grid edge of each vertex (or NULL), F (m, 3) int64
+ *                           the faces, from the workspace as ls_iso_count filled it for the same S and iso. origin[3] and spacing[3]
+ *                           are host arrays. A vertex past n or a face past m is dropped, never written. n = m = 0 is a no-op. ASYNC.
+ *   ls_iso_backward         gS (nx, ny, nz) fp32, overwritten: the gradient of sum <gV, V> in S for gV (n, 3) fp32. Per live edge, in fp64
+ *                           from the fp32 inputs: D = S[b] - S[a], t = (iso - S[a]) / D (no term unless 0 <= t <= 1), e = spacing * d,
+ *                           term_a = (-(1 - t) / D) <gV, e>, term_b = (-t / D) <gV, e>. A node adds the term_a of its 7 slots in order, then
+ *                           the term_b of the 7 edges owned by node - d in slot order, in fp64, rounded to fp32 once: no float
+ *                           atomics, bitwise reproducible. A vertex past n adds nothing; n = 0 zeroes gS. ASYNC, capturable.
+ * LS_E_INVALID for a null required pointer, a side below 1, a negative n or m, or a spacing that is not positive and finite;
+ * LS_E_OVERFLOW when 8 x the nodes or 12 x the cubes reaches 2^31; LS_E_WORKSPACE for a workspace below ls_iso_workspace_bytes.
+ * ls_iso_fill and ls_iso_backward only read the workspace; none may overlap an ls_iso_count on it.
+ * --------------------------------------------------------------------------------------------- */
+int ls_iso_workspace_bytes(int64_t nx, int64_t ny, int64_t nz, size_t* bytes);
+int ls_iso_count(const float* S, int64_t nx, int64_t ny, int64_t nz, float iso, void* ws, size_t ws_bytes, int64_t* totals, int device,
+                 void* stream);
+int ls_iso_fill(const float* S, int64_t nx, int64_t ny, int64_t nz, float iso, const float* origin, const float* spacing, const void* ws,
+                size_t ws_bytes, int64_t n, int64_t m, float* V, int64_t* E, int64_t* F, int device, void* stream);
+int ls_iso_backward(const float* S, int64_t nx, int64_t ny, int64_t nz, float iso, const float* origin, const float* spacing,
+                    const void* ws, size_t ws_bytes, int64_t n, const float* gV, float* gS, int device, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Area-weighted points on a mesh surface and their gradient to the vertices (largesteps/sampling.py, and distance.chamfer_distance

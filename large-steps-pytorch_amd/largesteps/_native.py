@@ -122,6 +122,12 @@ _SIGNATURES = {
     "ls_mesh_selfx_count": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ls_mesh_selfx_workspace_bytes": (c_int, [c_i64, c_i64, ctypes.POINTER(c_size_t)]),
     "ls_mesh_selfx_pairs": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ls_iso_workspace_bytes": (c_int, [c_i64, c_i64, c_i64, ctypes.POINTER(c_size_t)]),
+    "ls_iso_count": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_float, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
+    "ls_iso_fill": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_i64, c_i64, c_void_p,
+                            c_void_p, c_void_p, c_int, c_void_p]),
+    "ls_iso_backward": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_i64, c_void_p,
+                                c_void_p, c_int, c_void_p]),
     "ls_mesh_ray_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ls_sample_workspace_bytes": (c_int, [c_i64, c_i64, ctypes.POINTER(c_size_t)]),
