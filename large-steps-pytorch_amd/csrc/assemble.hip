@@ -24,30 +24,37 @@ namespace ls {
 // ------------------------------------------------------------------------------------------------
 // workspace layout (shared by ls_assemble_pattern and ls_assemble_fill; depends on V and F only)
 // ------------------------------------------------------------------------------------------------
-struct AsmLayout {
-    size_t flags, chain_rows, cnt, slot_ptr, row_off, diag, tile_cnt, tile_off, corner_off, slot_col, slot_val, comp, total;
-    int64_t nslots, tiles;
-    AsmLayout(int64_t V, int64_t F) {
-        auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-        nslots = 6 * F;
-        tiles = (V + TILE_ROWS - 1) / TILE_ROWS;
-        size_t o = 0;
-        // what has to be ZERO when the kernels start comes first: one memset over [0, slot_ptr)
-        flags = o;     o = al(o + 64);
-        chain_rows = o;  o = al(o + 8 * (size_t)((V + 1) / 4096 + 4));   // single-pass scan of the row counters: ticket + one word per 4096 rows
-        cnt = o;       o = al(o + 4 * (size_t)(V + 2));        // (k_count reserves for vertex pairs with 64-bit atomics: one entry of slack)
-        slot_ptr = o;  o = al(o + 4 * (size_t)(V + 1));
-        row_off = o;   o = al(o + 4 * (size_t)(V + 1));        // offset of a row's first entry inside its tile's compact block
-        diag = o;      o = al(o + 4 * (size_t)(V + 1));
-        tile_cnt = o;  o = al(o + 4 * (size_t)(tiles + 1));    // entries of a 256-row tile
-        tile_off = o;  o = al(o + 4 * (size_t)(tiles + 1));    // ... and their exclusive scan: where the tile's rows start in the CSR arrays
-        corner_off = o; o = al(o + 4 * (size_t)(3 * F) + 64);  // where a face corner's two slots sit inside its vertex' row (k_count)
-        slot_col = o;  o = al(o + 4 * (size_t)nslots + 64);    // (+ 64: a row's last 16-byte quad may reach two slots past the array)
-        slot_val = o;  o = al(o + 4 * (size_t)nslots + 64);
-        comp = o;      o = al(o + 8 * (size_t)(nslots + V));   // final rows, tile by tile: tile t at entry slot_ptr[256 t] + 256 t ({col, value bits})
-        total = o;
-    }
+struct AsmWs {
+    int* flags;
+    unsigned long long* chain_rows;
+    int *cnt, *slot_ptr, *row_off;
+    float* diag;
+    int *tile_cnt, *tile_off, *corner_off, *slot_col;
+    float* slot_val;
+    int2* comp;
+    size_t total;
 };
+// (ls_assemble_fill holds the workspace const: it carves it the same way and hands every region to its kernel as const)
+static AsmWs asm_carve(const void* workspace, int64_t V, int64_t F) {
+    const size_t nslots = 6 * (size_t)F, tiles = (size_t)((V + TILE_ROWS - 1) / TILE_ROWS), pad = 16;       // pad: 64 bytes of ints
+    WsWalk w(workspace);
+    AsmWs r;
+    // what has to be ZERO when the kernels start comes first: one memset over [flags, slot_ptr)
+    r.flags = w.take<int>(16);
+    r.chain_rows = w.take<unsigned long long>((size_t)((V + 1) / 4096 + 4));       // single-pass scan of the row counters: ticket + one word per 4096 rows
+    r.cnt = w.take<int>((size_t)(V + 2));              // (k_count reserves for vertex pairs with 64-bit atomics: one entry of slack)
+    r.slot_ptr = w.take<int>((size_t)(V + 1));
+    r.row_off = w.take<int>((size_t)(V + 1));          // offset of a row's first entry inside its tile's compact block
+    r.diag = w.take<float>((size_t)(V + 1));
+    r.tile_cnt = w.take<int>(tiles + 1);               // entries of a 256-row tile
+    r.tile_off = w.take<int>(tiles + 1);               // ... and their exclusive scan: where the tile's rows start in the CSR arrays
+    r.corner_off = w.take<int>(3 * (size_t)F + pad);   // where a face corner's two slots sit inside its vertex' row (k_count)
+    r.slot_col = w.take<int>(nslots + pad);            // (+ pad: a row's last 16-byte quad may reach two slots past the array)
+    r.slot_val = w.take<float>(nslots + pad);
+    r.comp = w.take<int2>(nslots + (size_t)V);         // final rows, tile by tile: tile t at entry slot_ptr[256 t] + 256 t ({col, value bits})
+    r.total = w.bytes();
+    return r;
+}
 
 // ------------------------------------------------------------------------------------------------
 // exclusive scan of int32 (three kernels; the middle one is a single workgroup)
@@ -664,7 +671,7 @@ extern "C" int ls_assemble_workspace_bytes(int64_t V, int64_t F, size_t* h_bytes
     LS_REQUIRE(h_bytes && V >= 0 && F >= 0, LS_E_INVALID, "ls_assemble_workspace_bytes: bad argument");
     LS_REQUIRE(V < (int64_t)2000000000 && 6 * F < (int64_t)2000000000, LS_E_OVERFLOW,
                "mesh too large for the int32 index space (V=%lld F=%lld)", (long long)V, (long long)F);
-    *h_bytes = AsmLayout(V, F).total;
+    *h_bytes = asm_carve(nullptr, V, F).total;
     return LS_OK;
 }
 
@@ -677,54 +684,37 @@ extern "C" int ls_assemble_pattern(const void* faces, int idx_bytes, int64_t F, 
     LS_REQUIRE(kind == LS_LAPLACIAN_UNIFORM || kind == LS_LAPLACIAN_COT, LS_E_INVALID, "unknown Laplacian kind %d", kind);
     LS_REQUIRE(kind == LS_LAPLACIAN_UNIFORM || verts || F == 0, LS_E_INVALID, "cotangent Laplacian needs vertex positions");
     LS_REQUIRE(V < (int64_t)2000000000 && 6 * F < (int64_t)2000000000, LS_E_OVERFLOW, "mesh too large for int32 indices");
-    const AsmLayout L(V, F);
-    LS_REQUIRE(workspace_bytes >= L.total, LS_E_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, L.total);
+    const AsmWs w = asm_carve(workspace, V, F);
+    LS_REQUIRE(workspace_bytes >= w.total, LS_E_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, w.total);
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    int* cnt = (int*)(ws + L.cnt);
-    int* slot_ptr = (int*)(ws + L.slot_ptr);
-    int* corner_off = (int*)(ws + L.corner_off);
-    int* row_off = (int*)(ws + L.row_off);
-    unsigned long long* chain_rows = (unsigned long long*)(ws + L.chain_rows);
-    int* tile_cnt = (int*)(ws + L.tile_cnt);
-    int* tile_off = (int*)(ws + L.tile_off);
-    int2* comp = (int2*)(ws + L.comp);
-    float* diag = (float*)(ws + L.diag);
-    int* flags = (int*)(ws + L.flags);
-    int* slot_col = (int*)(ws + L.slot_col);
-    float* slot_val = (float*)(ws + L.slot_val);
 
-    // flags, the scan's chain and cnt are contiguous: one memset
-    LS_HIP(hipMemsetAsync(ws, 0, L.slot_ptr, st));
+    // flags, the scan's chain and cnt are contiguous: one memset up to slot_ptr
+    LS_HIP(hipMemsetAsync(w.flags, 0, (size_t)((char*)w.slot_ptr - (char*)w.flags), st));
     if (V == 0) { LS_HIP(hipMemsetAsync(rowptr, 0, 4, st)); *h_nnz = 0; LS_HIP(hipStreamSynchronize(st)); return LS_OK; }
     const int fgrid = F ? (int)std::min<int64_t>(div_up(F, BLOCK), 8192) : 1;
-    if (F) {
-        const int cgrid = div_up(F, BLOCK * CNT_FPT);
-        if (idx_bytes == 4) hipLaunchKernelGGL(k_count<int32_t>, dim3(cgrid), dim3(BLOCK), 0, st, (const int32_t*)faces, F, V, cnt, corner_off, flags);
-        else hipLaunchKernelGGL(k_count<int64_t>, dim3(cgrid), dim3(BLOCK), 0, st, (const int64_t*)faces, F, V, cnt, corner_off, flags);
-    }
-    int rc = exclusive_scan_chained(cnt, V, slot_ptr, chain_rows, st);
+    if (F)
+        LS_IDX(idx_bytes, hipLaunchKernelGGL(k_count<IDX>, dim3(div_up(F, BLOCK * CNT_FPT)), dim3(BLOCK), 0, st, (const IDX*)faces, F, V, w.cnt,
+                                             w.corner_off, w.flags));
+    int rc = exclusive_scan_chained(w.cnt, V, w.slot_ptr, w.chain_rows, st);
     if (rc) return rc;
     if (F) {
-        const bool cot = kind == LS_LAPLACIAN_COT;
-        if (idx_bytes == 4) {
-            if (cot) hipLaunchKernelGGL((k_scatter<int32_t, true>), dim3(fgrid), dim3(BLOCK), 0, st, (const int32_t*)faces, F, V, verts, slot_ptr, (const int*)corner_off, slot_col, slot_val);
-            else hipLaunchKernelGGL((k_scatter<int32_t, false>), dim3(fgrid), dim3(BLOCK), 0, st, (const int32_t*)faces, F, V, verts, slot_ptr, (const int*)corner_off, slot_col, slot_val);
-        } else {
-            if (cot) hipLaunchKernelGGL((k_scatter<int64_t, true>), dim3(fgrid), dim3(BLOCK), 0, st, (const int64_t*)faces, F, V, verts, slot_ptr, (const int*)corner_off, slot_col, slot_val);
-            else hipLaunchKernelGGL((k_scatter<int64_t, false>), dim3(fgrid), dim3(BLOCK), 0, st, (const int64_t*)faces, F, V, verts, slot_ptr, (const int*)corner_off, slot_col, slot_val);
-        }
+        if (kind == LS_LAPLACIAN_COT)
+            LS_IDX(idx_bytes, hipLaunchKernelGGL((k_scatter<IDX, true>), dim3(fgrid), dim3(BLOCK), 0, st, (const IDX*)faces, F, V, verts, w.slot_ptr,
+                                                 (const int*)w.corner_off, w.slot_col, w.slot_val));
+        else
+            LS_IDX(idx_bytes, hipLaunchKernelGGL((k_scatter<IDX, false>), dim3(fgrid), dim3(BLOCK), 0, st, (const IDX*)faces, F, V, verts, w.slot_ptr,
+                                                 (const int*)w.corner_off, w.slot_col, w.slot_val));
     }
     const int vgrid = div_up(V, TILE_ROWS);
-    if (kind == LS_LAPLACIAN_COT) hipLaunchKernelGGL(k_row_merge<true>, dim3(vgrid), dim3(BLOCK), 0, st, V, slot_ptr, slot_col, slot_val, a, b, comp, row_off, tile_cnt, diag);
-    else hipLaunchKernelGGL(k_row_merge<false>, dim3(vgrid), dim3(BLOCK), 0, st, V, slot_ptr, slot_col, slot_val, a, b, comp, row_off, tile_cnt, diag);
-    hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(1024), 0, st, (const int*)tile_cnt, vgrid, tile_off);
-    hipLaunchKernelGGL(k_rowptr, dim3(vgrid), dim3(BLOCK), 0, st, V, (const int*)tile_off, (const int*)row_off, rowptr, flags);
+    if (kind == LS_LAPLACIAN_COT) hipLaunchKernelGGL(k_row_merge<true>, dim3(vgrid), dim3(BLOCK), 0, st, V, w.slot_ptr, w.slot_col, w.slot_val, a, b, w.comp, w.row_off, w.tile_cnt, w.diag);
+    else hipLaunchKernelGGL(k_row_merge<false>, dim3(vgrid), dim3(BLOCK), 0, st, V, w.slot_ptr, w.slot_col, w.slot_val, a, b, w.comp, w.row_off, w.tile_cnt, w.diag);
+    hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(1024), 0, st, (const int*)w.tile_cnt, vgrid, w.tile_off);
+    hipLaunchKernelGGL(k_rowptr, dim3(vgrid), dim3(BLOCK), 0, st, V, (const int*)w.tile_off, (const int*)w.row_off, rowptr, w.flags);
     LS_HIP(hipGetLastError());
     int h[2] = {0, 0};
-    LS_HIP(hipMemcpyAsync(h, flags, 8, hipMemcpyDeviceToHost, st));
+    LS_HIP(hipMemcpyAsync(h, w.flags, 8, hipMemcpyDeviceToHost, st));
     LS_HIP(hipStreamSynchronize(st));
     LS_REQUIRE(h[0] == 0, LS_E_INDEX, "a face index is outside [0, %lld)", (long long)V);
     *h_nnz = h[1];
@@ -736,15 +726,13 @@ extern "C" int ls_assemble_fill(const void* workspace, size_t workspace_bytes, i
                                 void* stream) {
     LS_REQUIRE(workspace && rowptr && V >= 0 && F >= 0 && nnz >= 0 && (nnz == 0 || (col && val)), LS_E_INVALID,
                "ls_assemble_fill: null pointer or negative size");
-    const AsmLayout L(V, F);
-    LS_REQUIRE(workspace_bytes >= L.total, LS_E_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, L.total);
+    const AsmWs w = asm_carve(workspace, V, F);
+    LS_REQUIRE(workspace_bytes >= w.total, LS_E_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, w.total);
     if (V == 0) return LS_OK;
     DeviceGuard g(device);
     LS_HIP(g.err);
-    const char* ws = (const char*)workspace;
-    hipLaunchKernelGGL(k_emit, dim3(div_up(V, TILE_ROWS)), dim3(BLOCK), 0, (hipStream_t)stream, V,
-                       (const int*)(ws + L.slot_ptr), (const int2*)(ws + L.comp), (const int*)(ws + L.row_off),
-                       (const float*)(ws + L.diag), rowptr, col, val, coo_idx, coo_idx ? coo_idx + nnz : nullptr, dinv);
+    hipLaunchKernelGGL(k_emit, dim3(div_up(V, TILE_ROWS)), dim3(BLOCK), 0, (hipStream_t)stream, V, (const int*)w.slot_ptr, (const int2*)w.comp,
+                       (const int*)w.row_off, (const float*)w.diag, rowptr, col, val, coo_idx, coo_idx ? coo_idx + nnz : nullptr, dinv);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
@@ -761,12 +749,13 @@ extern "C" int ls_csr_from_coo(const int64_t* coo_rows, const int64_t* coo_cols,
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
-    auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-    char* ws = (char*)scratch;
-    int* cnt = (int*)ws;
-    int* flags = (int*)(ws + al(4 * (size_t)(V + 1)));
-    int* bsum = flags + 16;
-    LS_HIP(hipMemsetAsync(ws, 0, al(4 * (size_t)(V + 1)) + 64, st));
+    // the walk stays below `need`, the header's documented bound (which rounds the same regions up generously)
+    WsWalk w(scratch);
+    int* cnt = w.take<int>((size_t)(V + 1));
+    int* flags = w.take<int>(16, 64);
+    int* bsum = w.take<int>((size_t)scan_scratch_ints(V), 4);
+    LS_REQUIRE(w.bytes() <= need, LS_E_WORKSPACE, "ls_csr_from_coo: the scratch bound %zu is below the carve %zu", need, w.bytes());
+    LS_HIP(hipMemsetAsync(cnt, 0, (size_t)((char*)bsum - (char*)cnt), st));       // cnt and flags are adjacent: one memset up to bsum
     if (dinv && V) LS_HIP(hipMemsetAsync(dinv, 0, 4 * (size_t)V, st));
     if (nnz) hipLaunchKernelGGL(k_coo_hist, dim3((int)std::min<int64_t>(div_up(nnz, BLOCK), 8192)), dim3(BLOCK), 0, st,
                                 coo_rows, coo_cols, vals, nnz, V, cnt, col, dinv, flags);
@@ -832,25 +821,30 @@ __global__ __launch_bounds__(256) void k_dedup_faces(const IdxT* __restrict__ fa
 
 namespace {
 
-// The workspaces of the three users of the radix sort below: the caller's own regions as named byte offsets behind a 256-byte aligned
-// base (the + 256 of `total`), then the sort's scratch (radix.h), whose bsum also serves the entry point's own scan over V elements.
-struct DedupWs { size_t ord_a, flag, uid, sort, total; };
-DedupWs dedup_layout(int64_t V) {
-    const size_t n = 4 * (size_t)V;
-    return {0, n, 2 * n, 3 * n + 4, 3 * n + 4 + sort_scratch_bytes(V, true, V) + 256};          // uid: V + 1
+// The workspaces of the three users of the radix sort below: the caller's base is rounded up to 256 bytes here (the + 256 of `total`
+// pays for it), the entry point's own regions are packed at 4 bytes behind it, then comes the sort's scratch (radix.h), whose bsum also
+// serves the entry point's own scan over V elements.
+struct DedupWs { int *ord_a, *flag, *uid; SortScratch sort; size_t total; };
+DedupWs dedup_carve(void* workspace, int64_t V) {
+    WsWalk w(ws_align_base(workspace));
+    int *ord_a = w.take<int>((size_t)V, 4), *flag = w.take<int>((size_t)V, 4), *uid = w.take<int>((size_t)(V + 1), 4);
+    const SortScratch sort = sort_scratch_take(w, V, true, V, 4);
+    return {ord_a, flag, uid, sort, w.bytes() + 256};
 }
 // n ids ranked by keys in [0, V): ord_a, the key counts (V + 1, the last one the range flag), `own` more ints of the caller, the sort's scratch
-struct RankWs { size_t ord_a, cnt, own, sort, total; };
-RankWs rank_layout(int64_t n, int64_t V, int64_t own) {
-    const size_t cnt = 4 * (size_t)n, o = cnt + 4 * (size_t)(V + 1), sort = o + 4 * (size_t)own;
-    return {0, cnt, o, sort, sort + sort_scratch_bytes(n, false, V) + 256};
+struct RankWs { int *ord_a, *cnt, *own; SortScratch sort; size_t total; };
+RankWs rank_carve(void* workspace, int64_t n, int64_t V, int64_t own) {
+    WsWalk w(ws_align_base(workspace));
+    int *ord_a = w.take<int>((size_t)n, 4), *cnt = w.take<int>((size_t)(V + 1), 4), *mine = w.take<int>((size_t)own, 4);
+    const SortScratch sort = sort_scratch_take(w, n, false, V, 4);
+    return {ord_a, cnt, mine, sort, w.bytes() + 256};
 }
 
 }  // namespace
 
 extern "C" int ls_remove_duplicates_workspace_bytes(int64_t V, size_t* h_bytes) {
     LS_REQUIRE(h_bytes && V >= 0, LS_E_INVALID, "ls_remove_duplicates_workspace_bytes: bad argument");
-    *h_bytes = dedup_layout(V).total;
+    *h_bytes = dedup_carve(nullptr, V).total;
     return LS_OK;
 }
 
@@ -859,18 +853,13 @@ extern "C" int ls_remove_duplicates(const float* verts, int64_t V, const void* f
                                     void* stream) {
     LS_REQUIRE(h_n_unique && V >= 0 && F >= 0 && V < INT32_MAX && (V == 0 || (verts && unique_verts && inverse)) &&
                (F == 0 || (faces && new_faces && (idx_bytes == 4 || idx_bytes == 8))), LS_E_INVALID, "ls_remove_duplicates: bad argument");
-    const DedupWs L = dedup_layout(V);
-    LS_REQUIRE(workspace && ws_bytes >= L.total, LS_E_WORKSPACE, "ls_remove_duplicates: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
+    const auto [ord_a, flag, uid, ss, total] = dedup_carve(workspace, V);          // uid: V + 1
+    LS_REQUIRE(workspace && ws_bytes >= total, LS_E_WORKSPACE, "ls_remove_duplicates: workspace too small (%zu < %zu bytes)", ws_bytes, total);
     *h_n_unique = 0;
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
     if (V == 0) { LS_REQUIRE(F == 0, LS_E_INDEX, "ls_remove_duplicates: faces without vertices"); return LS_OK; }
-    char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    int* ord_a = (int*)(w + L.ord_a);
-    int* flag = (int*)(w + L.flag);
-    int* uid = (int*)(w + L.uid);              // V + 1
-    const SortScratch ss = sort_scratch_carve(w + L.sort, V, true);
     const int* src = nullptr;
     {
         KeyVerts key{verts};                   // three 32-bit key words (z, y, x), each gathered once and carried through its four byte passes
@@ -886,8 +875,8 @@ extern "C" int ls_remove_duplicates(const float* verts, int64_t V, const void* f
     if (F) {
         LS_HIP(hipMemsetAsync(bad, 0, sizeof(int), st));
         const int64_t m = 3 * F;
-        if (idx_bytes == 4) hipLaunchKernelGGL(k_dedup_faces<int32_t>, dim3(div_up(m, 256)), dim3(256), 0, st, (const int32_t*)faces, m, V, (const int64_t*)inverse, new_faces, bad);
-        else hipLaunchKernelGGL(k_dedup_faces<int64_t>, dim3(div_up(m, 256)), dim3(256), 0, st, (const int64_t*)faces, m, V, (const int64_t*)inverse, new_faces, bad);
+        LS_IDX(idx_bytes, hipLaunchKernelGGL(k_dedup_faces<IDX>, dim3(div_up(m, 256)), dim3(256), 0, st, (const IDX*)faces, m, V, (const int64_t*)inverse,
+                                             new_faces, bad));
     }
     LS_HIP(hipGetLastError());
     int h[2] = {0, 0};
@@ -936,21 +925,18 @@ __global__ __launch_bounds__(256) void k_invert_order(const int* __restrict__ or
 
 extern "C" int ls_csr_transpose_workspace_bytes(int64_t V, int64_t nnz, size_t* h_bytes) {
     LS_REQUIRE(h_bytes && V >= 0 && nnz >= 0, LS_E_INVALID, "ls_csr_transpose_workspace_bytes: bad argument");
-    *h_bytes = rank_layout(nnz, V, 0).total;
+    *h_bytes = rank_carve(nullptr, nnz, V, 0).total;
     return LS_OK;
 }
 
 extern "C" int ls_csr_transpose(const int32_t* rowptr, const int32_t* col, const float* val, int64_t V, int64_t nnz, int32_t* t_rowptr,
                                 int32_t* t_col, float* t_val, void* workspace, size_t ws_bytes, int device, void* stream) {
     LS_REQUIRE(rowptr && t_rowptr && V > 0 && nnz >= 0 && nnz < INT32_MAX && (nnz == 0 || (col && val && t_col && t_val)), LS_E_INVALID, "ls_csr_transpose: bad argument");
-    const RankWs L = rank_layout(nnz, V, 0);
-    LS_REQUIRE(workspace && ws_bytes >= L.total, LS_E_WORKSPACE, "ls_csr_transpose: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
+    const auto [ord_a, cnt, own, ss, total] = rank_carve(workspace, nnz, V, 0);
+    LS_REQUIRE(workspace && ws_bytes >= total, LS_E_WORKSPACE, "ls_csr_transpose: workspace too small (%zu < %zu bytes)", ws_bytes, total);
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    int *ord_a = (int*)(w + L.ord_a), *cnt = (int*)(w + L.cnt);
-    const SortScratch ss = sort_scratch_carve(w + L.sort, nnz, false);
     LS_HIP(hipMemsetAsync(cnt, 0, sizeof(int) * (V + 1), st));
     if (nnz) hipLaunchKernelGGL(k_count_keys, dim3(div_up(nnz, 256)), dim3(256), 0, st, (const int*)col, nnz, V, cnt, cnt + V);
     int rc = exclusive_scan(cnt, V, t_rowptr, ss.bsum, st);
@@ -972,7 +958,7 @@ extern "C" int ls_csr_transpose(const int32_t* rowptr, const int32_t* col, const
 
 extern "C" int ls_corner_ranks_workspace_bytes(int64_t F, int64_t V, size_t* h_bytes) {
     LS_REQUIRE(h_bytes && F >= 0 && V >= 0, LS_E_INVALID, "ls_corner_ranks_workspace_bytes: bad argument");
-    *h_bytes = rank_layout(3 * F, V, 3 * F).total;
+    *h_bytes = rank_carve(nullptr, 3 * F, V, 3 * F).total;
     return LS_OK;
 }
 
@@ -981,18 +967,14 @@ extern "C" int ls_corner_ranks(const void* faces, int idx_bytes, int64_t F, int6
     LS_REQUIRE(vptr && V >= 0 && F >= 0 && 3 * F < INT32_MAX && (F == 0 || (faces && cpos && (idx_bytes == 4 || idx_bytes == 8))), LS_E_INVALID,
                "ls_corner_ranks: bad argument");
     const int64_t n = 3 * F;
-    const RankWs L = rank_layout(n, V, n);
-    LS_REQUIRE(workspace && ws_bytes >= L.total, LS_E_WORKSPACE, "ls_corner_ranks: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
+    const auto [ord_a, cnt, keys, ss, total] = rank_carve(workspace, n, V, n);     // keys: the face corners as int32
+    LS_REQUIRE(workspace && ws_bytes >= total, LS_E_WORKSPACE, "ls_corner_ranks: workspace too small (%zu < %zu bytes)", ws_bytes, total);
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    int *ord_a = (int*)(w + L.ord_a), *cnt = (int*)(w + L.cnt), *keys = (int*)(w + L.own);        // keys: the face corners as int32
-    const SortScratch ss = sort_scratch_carve(w + L.sort, n, false);
     LS_HIP(hipMemsetAsync(cnt, 0, sizeof(int) * (V + 1), st));
     if (n) {
-        if (idx_bytes == 4) hipLaunchKernelGGL(k_faces_to_i32<int32_t>, dim3(div_up(n, 256)), dim3(256), 0, st, (const int32_t*)faces, n, V, keys);
-        else hipLaunchKernelGGL(k_faces_to_i32<int64_t>, dim3(div_up(n, 256)), dim3(256), 0, st, (const int64_t*)faces, n, V, keys);
+        LS_IDX(idx_bytes, hipLaunchKernelGGL(k_faces_to_i32<IDX>, dim3(div_up(n, 256)), dim3(256), 0, st, (const IDX*)faces, n, V, keys));
         hipLaunchKernelGGL(k_count_keys, dim3(div_up(n, 256)), dim3(256), 0, st, (const int*)keys, n, V, cnt, cnt + V);
     }
     int rc = exclusive_scan(cnt, V, (int*)vptr, ss.bsum, st);

@@ -273,7 +273,7 @@ __global__ __launch_bounds__(256) void k_cube_keys(const float* __restrict__ uv,
     k4.y = (q.finite && q.drop != 1) ? base + q.texel[1] : nk;
     k4.z = (q.finite && q.drop != 2) ? base + q.texel[2] : nk;
     k4.w = (q.finite && q.drop != 3) ? base + q.texel[3] : nk;
-    *reinterpret_cast<int4*>(keys + 4 * (size_t)pix) = k4;          // (the key buffer is 256-byte aligned: tx_order_layout)
+    *reinterpret_cast<int4*>(keys + 4 * (size_t)pix) = k4;          // (the key buffer is 256-byte aligned: tx_order_carve)
 }
 
 // ---- backward to tex: the gradient of one texel per key, summed by seg_sum of groupby.h ----------------------------------------------------
@@ -333,7 +333,7 @@ extern "C" int ls_cube_workspace_bytes(int64_t B, int H, int W, size_t* bytes) {
     LS_REQUIRE(bytes && B >= 1 && H >= 1 && W >= 1, LS_E_INVALID, "ls_cube_workspace_bytes: bad argument");
     LS_REQUIRE(B < ((int64_t)1 << 31) && B * (int64_t)H * W < (((int64_t)1 << 31) - 1) / 4, LS_E_OVERFLOW,
                "ls_cube_workspace_bytes: 4 B H W does not fit int32");
-    *bytes = tx_order_layout(4 * B * (int64_t)H * W).total;
+    *bytes = tx_order_carve(nullptr, 4 * B * (int64_t)H * W).total;
     return LS_OK;
 }
 
@@ -358,7 +358,7 @@ extern "C" int ls_cube_order(const float* uv, int64_t B, int H, int W, int64_t B
     CubeShape s;
     int rc = cube_check(Bt, n, 1, B, H, W, filter, "ls_cube_order", &s);
     if (rc) return rc;
-    const TxOrderWs L = tx_order_layout(4 * s.N);        // always sized for the four items per pixel of linear filtering
+    const TxOrderWs L = tx_order_carve(ws, 4 * s.N);       // always sized for the four items per pixel of linear filtering
     LS_REQUIRE(uv && order && seg && ws, LS_E_INVALID, "ls_cube_order: null argument");
     LS_REQUIRE(tx_aligned(ws, 16), LS_E_INVALID, "ls_cube_order: the workspace must be 16-byte aligned");
     LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_cube_order: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
@@ -366,8 +366,8 @@ extern "C" int ls_cube_order(const float* uv, int64_t B, int H, int W, int64_t B
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
     const int64_t items = filter == TX_LINEAR ? 4 * s.N : s.N, nk = 6 * (int64_t)s.Bt * s.n * s.n;
-    hipLaunchKernelGGL(k_cube_keys, dim3(div_up(s.N, 256)), dim3(256), 0, st, uv, s, (int)nk, tx_order_keys(ws, L));
-    return tx_order_finish(ws, L, items, nk, order, seg, st);
+    hipLaunchKernelGGL(k_cube_keys, dim3(div_up(s.N, 256)), dim3(256), 0, st, uv, s, (int)nk, L.keys);
+    return tx_order_finish(L, items, nk, order, seg, st);
 }
 
 extern "C" int ls_cube_backward(const float* tex, int64_t Bt, int n, int C, const float* uv, int64_t B, int H, int W, int filter,

@@ -184,7 +184,7 @@ extern "C" int ls_mesh_distance_weights(void* handle, const float* P, int64_t n,
 extern "C" int ls_mesh_distance_backward_workspace_bytes(int64_t n, int64_t F, size_t* bytes) {
     LS_REQUIRE(bytes && n >= 0 && F > 0, LS_E_INVALID, "ls_mesh_distance_backward_workspace_bytes: bad argument");
     LS_REQUIRE(n < INT32_MAX - BLOCK && 3 * F < INT32_MAX, LS_E_OVERFLOW, "ls_mesh_distance_backward_workspace_bytes: more than 2^31 points or corners");
-    *bytes = md_layout(n, F, true, sizeof(float) * 9).total;
+    *bytes = md_carve<float>(nullptr, n, F, true).total;
     return LS_OK;
 }
 
@@ -196,15 +196,14 @@ extern "C" int ls_mesh_distance_backward(void* handle, const float* P, int64_t n
                "ls_mesh_distance_backward: the vertex gradient needs I, the corner ranking and a workspace");
     LS_REQUIRE(n < INT32_MAX - BLOCK, LS_E_OVERFLOW, "ls_mesh_distance_backward: more than 2^31 query points");
     MeshDistanceHandle* H = (MeshDistanceHandle*)handle;
-    const MdWs L = md_layout(n, H->T, true, sizeof(float) * 9);
-    LS_REQUIRE(!gV || ws_bytes >= L.total, LS_E_WORKSPACE, "ls_mesh_distance_backward: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
+    const MdCarved<float> c = md_carve<float>(ws, n, H->T, true);
+    LS_REQUIRE(!gV || ws_bytes >= c.total, LS_E_WORKSPACE, "ls_mesh_distance_backward: workspace too small (%zu < %zu bytes)", ws_bytes, c.total);
     DeviceGuard guard(H->device);
     LS_HIP(guard.err);
     const hipStream_t st = (hipStream_t)stream;
     if (gP && n > 0) hipLaunchKernelGGL(k_md_grad_points, dim3(div_up(n, BLOCK)), dim3(BLOCK), 0, st, P, C, g, (int)n, gP);
     if (gV && n == 0) LS_HIP(hipMemsetAsync(gV, 0, sizeof(float) * 3 * (size_t)H->V, st));
     if (gV && n > 0) {
-        const MdCarved<float> c = md_carve<float>(ws, L, n);
         hipLaunchKernelGGL(k_md_weights, dim3(div_up(n, BLOCK)), dim3(BLOCK), 0, st, P, (int)n, H->view(), I, c.W);
         if (int rc = md_vertex_grad<float>(I, n, H->T, H->V, MdRows{P, C, g, c.W, c.order, c.seg, c.rows}, vptr, corner_order, gV, c, st)) return rc;
     }

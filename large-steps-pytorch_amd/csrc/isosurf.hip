@@ -31,6 +31,7 @@
 // threads are consecutive k: the 8 corner loads of a wave are 8 contiguous rows, each re-read from the caches by the 7 neighbours that
 // share it. Only threads next to the level set go on to the tables and to the offsets of their neighbours.
 #include "common.h"
+#include "workspace.h"
 #include <cmath>
 
 namespace ls {
@@ -226,20 +227,20 @@ __global__ __launch_bounds__(BLOCK) void k_iso_backward(const float* __restrict_
 }
 
 struct IsoWs {          // the regions of the workspace
-    size_t mask, ncnt, offs, ccnt, coffs, bsum, total;
+    unsigned char* mask;
+    int *ncnt, *offs, *ccnt, *coffs, *bsum;
+    size_t total;
 };
-static inline IsoWs iso_layout(int64_t N, int64_t Nc) {
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    IsoWs w;
-    size_t o = 0;
-    w.mask = o; o += al((size_t)N);
-    w.ncnt = o; o += al(4 * (size_t)N);
-    w.offs = o; o += al(4 * (size_t)(N + 1));
-    w.ccnt = o; o += al(4 * (size_t)(Nc > 0 ? Nc : 1));
-    w.coffs = o; o += al(4 * (size_t)(Nc + 1));
-    w.bsum = o; o += al(4 * (size_t)scan_scratch_ints(N));
-    w.total = o;
-    return w;
+// ls_iso_fill and ls_iso_backward hold the workspace const: they carve it the same way and hand every region to their kernels as const
+static inline IsoWs iso_carve(const void* ws, int64_t N, int64_t Nc) {
+    WsWalk w(ws);
+    unsigned char* mask = w.take<unsigned char>((size_t)N);
+    int* ncnt = w.take<int>((size_t)N);
+    int* offs = w.take<int>((size_t)(N + 1));
+    int* ccnt = w.take<int>((size_t)(Nc > 0 ? Nc : 1));
+    int* coffs = w.take<int>((size_t)(Nc + 1));
+    int* bsum = w.take<int>((size_t)scan_scratch_ints(N));
+    return {mask, ncnt, offs, ccnt, coffs, bsum, w.bytes()};
 }
 // LS_OK and the sizes, or the code of a grid that cannot be
 static int iso_sizes(const char* who, int64_t nx, int64_t ny, int64_t nz, int64_t* N, int64_t* Nc) {
@@ -266,7 +267,7 @@ extern "C" int ls_iso_workspace_bytes(int64_t nx, int64_t ny, int64_t nz, size_t
     LS_REQUIRE(bytes, LS_E_INVALID, "ls_iso_workspace_bytes: null argument");
     int64_t N, Nc;
     if (int rc = iso_sizes("ls_iso_workspace_bytes", nx, ny, nz, &N, &Nc)) return rc;
-    *bytes = iso_layout(N, Nc).total;
+    *bytes = iso_carve(nullptr, N, Nc).total;
     return LS_OK;
 }
 
@@ -275,20 +276,17 @@ extern "C" int ls_iso_count(const float* S, int64_t nx, int64_t ny, int64_t nz, 
     LS_REQUIRE(S && ws && totals, LS_E_INVALID, "ls_iso_count: null argument");
     int64_t N, Nc;
     if (int rc = iso_sizes("ls_iso_count", nx, ny, nz, &N, &Nc)) return rc;
-    const IsoWs L = iso_layout(N, Nc);
+    const IsoWs L = iso_carve(ws, N, Nc);
     LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_iso_count: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
     DeviceGuard guard(device);
     LS_HIP(guard.err);
     const hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)ws;
-    unsigned char* mask = (unsigned char*)(w + L.mask);
-    int *ncnt = (int*)(w + L.ncnt), *offs = (int*)(w + L.offs), *ccnt = (int*)(w + L.ccnt), *coffs = (int*)(w + L.coffs), *bsum = (int*)(w + L.bsum);
     const IsoGrid g{(int)nx, (int)ny, (int)nz, (int)N, (int)Nc, iso};
-    hipLaunchKernelGGL(k_iso_classify, dim3(div_up(N, BLOCK)), dim3(BLOCK), 0, st, S, g, mask, ncnt, ccnt);
+    hipLaunchKernelGGL(k_iso_classify, dim3(div_up(N, BLOCK)), dim3(BLOCK), 0, st, S, g, L.mask, L.ncnt, L.ccnt);
     LS_HIP(hipGetLastError());
-    if (int rc = exclusive_scan(ncnt, N, offs, bsum, st)) return rc;
-    if (int rc = exclusive_scan(ccnt, Nc, coffs, bsum, st)) return rc;
-    hipLaunchKernelGGL(k_iso_totals, dim3(1), dim3(1), 0, st, (const int*)offs, (const int*)coffs, (int)N, (int)Nc, totals);
+    if (int rc = exclusive_scan(L.ncnt, N, L.offs, L.bsum, st)) return rc;
+    if (int rc = exclusive_scan(L.ccnt, Nc, L.coffs, L.bsum, st)) return rc;
+    hipLaunchKernelGGL(k_iso_totals, dim3(1), dim3(1), 0, st, (const int*)L.offs, (const int*)L.coffs, (int)N, (int)Nc, totals);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
@@ -301,16 +299,15 @@ extern "C" int ls_iso_fill(const float* S, int64_t nx, int64_t ny, int64_t nz, f
     int64_t N, Nc;
     if (int rc = iso_sizes("ls_iso_fill", nx, ny, nz, &N, &Nc)) return rc;
     LS_REQUIRE(n < ((int64_t)1 << 31) && m < ((int64_t)1 << 31), LS_E_OVERFLOW, "ls_iso_fill: 2^31 rows or more");
-    const IsoWs L = iso_layout(N, Nc);
+    const IsoWs L = iso_carve(ws, N, Nc);
     LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_iso_fill: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
     if (n == 0 && m == 0) return LS_OK;
     DeviceGuard guard(device);
     LS_HIP(guard.err);
-    const char* w = (const char*)ws;
     const IsoGrid g{(int)nx, (int)ny, (int)nz, (int)N, (int)Nc, iso};
     hipLaunchKernelGGL(k_iso_fill, dim3(div_up(N, BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, S, g, Iso3{origin[0], origin[1], origin[2]},
-                       Iso3{spacing[0], spacing[1], spacing[2]}, (const unsigned char*)(w + L.mask), (const int*)(w + L.offs),
-                       (const int*)(w + L.coffs), (int)n, (int)m, V, E, F);
+                       Iso3{spacing[0], spacing[1], spacing[2]}, (const unsigned char*)L.mask, (const int*)L.offs,
+                       (const int*)L.coffs, (int)n, (int)m, V, E, F);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
@@ -322,7 +319,7 @@ extern "C" int ls_iso_backward(const float* S, int64_t nx, int64_t ny, int64_t n
     int64_t N, Nc;
     if (int rc = iso_sizes("ls_iso_backward", nx, ny, nz, &N, &Nc)) return rc;
     LS_REQUIRE(n < ((int64_t)1 << 31), LS_E_OVERFLOW, "ls_iso_backward: 2^31 rows or more");
-    const IsoWs L = iso_layout(N, Nc);
+    const IsoWs L = iso_carve(ws, N, Nc);
     LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_iso_backward: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
     DeviceGuard guard(device);
     LS_HIP(guard.err);
@@ -331,10 +328,9 @@ extern "C" int ls_iso_backward(const float* S, int64_t nx, int64_t ny, int64_t n
         LS_HIP(hipMemsetAsync(gS, 0, sizeof(float) * (size_t)N, st));
         return LS_OK;
     }
-    const char* w = (const char*)ws;
     const IsoGrid g{(int)nx, (int)ny, (int)nz, (int)N, (int)Nc, iso};
     hipLaunchKernelGGL(k_iso_backward, dim3(div_up(N, BLOCK)), dim3(BLOCK), 0, st, S, g, Iso3{spacing[0], spacing[1], spacing[2]},
-                       (const unsigned char*)(w + L.mask), (const int*)(w + L.offs), (int)n, gV, gS);
+                       (const unsigned char*)L.mask, (const int*)L.offs, (int)n, gV, gS);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }

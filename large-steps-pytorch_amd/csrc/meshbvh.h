@@ -120,37 +120,27 @@ __global__ __launch_bounds__(256) void k_md_gather_verts(const A* __restrict__ r
     gV[3 * v] = (float)s0; gV[3 * v + 1] = (float)s1; gV[3 * v + 2] = (float)s2;
 }
 
-struct MdWs {          // the regions of a backward's workspace (sized from n and F alone)
-    size_t keys, order, seg, sort, W, rows, total;
-};
-// with_w: a region for the (n, 3) fp64 weights (the distance computes them in its backward; the rays and the sampler are given them);
-// row_bytes: 9 sums per face in the accumulator's type
-static inline MdWs md_layout(int64_t n, int64_t F, bool with_w, size_t row_bytes) {
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const int64_t m = std::max<int64_t>(n, 1);
-    MdWs w;
-    size_t o = 0;
-    w.keys = o; o += al(4 * (size_t)m);
-    w.order = o; o += al(4 * (size_t)m);
-    w.seg = o; o += al(4 * (size_t)(F + 2));
-    w.sort = o; o += al(sort_scratch_bytes(m, true));
-    w.W = o; o += with_w ? al(24 * (size_t)m) : 0;
-    w.rows = o; o += al(row_bytes * (size_t)std::max<int64_t>(F, 1));
-    w.total = o;
-    return w;
-}
-// the workspace carved: what md_vertex_grad runs in, and what the G of a caller points into (order, seg, rows; W for the distance)
+// a backward's workspace (sized from n and F alone), carved: what md_vertex_grad runs in, and what the G of a caller points into (order,
+// seg, rows; W for the distance)
 template <class A>
 struct MdCarved {
     int *keys, *order, *seg;
     SortScratch sort;
     double* W;
     A* rows;
+    size_t total;
 };
+// with_w: a region for the (n, 3) fp64 weights (the distance computes them in its backward; the rays and the sampler are given them);
+// A: the accumulator's type, 9 sums per face
 template <class A>
-static inline MdCarved<A> md_carve(void* ws, const MdWs& L, int64_t n) {
-    char* w = (char*)ws;
-    return {(int*)(w + L.keys), (int*)(w + L.order), (int*)(w + L.seg), sort_scratch_carve(w + L.sort, n, true), (double*)(w + L.W), (A*)(w + L.rows)};
+static inline MdCarved<A> md_carve(void* ws, int64_t n, int64_t F, bool with_w) {
+    const int64_t m = std::max<int64_t>(n, 1);
+    WsWalk w(ws);
+    int *keys = w.take<int>((size_t)m), *order = w.take<int>((size_t)m), *seg = w.take<int>((size_t)(F + 2));
+    const SortScratch sort = sort_scratch_take(w, m, true);
+    double* W = w.take<double>(with_w ? 3 * (size_t)m : 0);
+    A* rows = w.take<A>(9 * (size_t)std::max<int64_t>(F, 1));
+    return {keys, order, seg, sort, W, rows, w.bytes()};
 }
 // gV (V, 3) from the terms G of n >= 1 items with faces I in a mesh of F faces and V vertices: face keys, the stable group-by, the
 // face rows in A, the gather in the corner ranking (vptr, corner_order). g reads c.order and c.seg and stores into c.rows. ASYNC.

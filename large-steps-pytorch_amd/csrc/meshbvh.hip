@@ -12,27 +12,35 @@
 
 using namespace ls;
 
-// carves the handle's arrays out of one buffer (256-byte aligned) of the scratch pool
+// the handle's arrays as the regions (256-byte aligned) of one buffer at `base`; returns the buffer's size
+static size_t md_carve_handle(MeshDistanceHandle* H, void* base) {
+    const size_t T = (size_t)H->T, N = 2 * T - 1;
+    Lbvh& b = H->bvh;
+    WsWalk w(base);
+    H->pos = w.take<float>(3 * (size_t)H->V);
+    H->faces = w.take<int>(3 * T);
+    H->small = w.take<int>(16);
+    b.code = w.take<int>(T);
+    b.ord_a = w.take<int>(T);
+    b.sort = sort_scratch_take(w, H->T, false);
+    b.tri = w.take<int>(T);
+    b.scode = w.take<unsigned>(T);
+    b.left = w.take<int>(T);
+    b.right = w.take<int>(T);
+    b.parent = w.take<int>(N);
+    b.esc = w.take<int>(N);
+    b.rflag = w.take<int>(T);
+    b.box = w.take<float>(6 * N);
+    b.bb = base ? (unsigned*)(H->small + 8) : nullptr;
+    return w.bytes();
+}
+// the handle's buffer from the scratch pool: measure, allocate, carve
 static int md_alloc(MeshDistanceHandle* H) {
-    const int64_t T = H->T, N = 2 * T - 1;
-    void* sort = nullptr;
-    void** slot[] = {(void**)&H->pos, (void**)&H->faces, (void**)&H->small, (void**)&H->bvh.code, (void**)&H->bvh.ord_a, &sort,
-                     (void**)&H->bvh.tri, (void**)&H->bvh.scode, (void**)&H->bvh.left, (void**)&H->bvh.right, (void**)&H->bvh.parent,
-                     (void**)&H->bvh.esc, (void**)&H->bvh.rflag, (void**)&H->bvh.box};
-    const int64_t bytes[] = {12 * (int64_t)H->V, 12 * T, 4 * 16, 4 * T, 4 * T, (int64_t)sort_scratch_bytes(T, false),
-                             4 * T, 4 * T, 4 * T, 4 * T, 4 * N, 4 * N, 4 * T, 24 * N};
-    size_t total = 0;
-    for (int64_t b : bytes) total += ((size_t)b + 255) & ~(size_t)255;
+    const size_t total = md_carve_handle(H, nullptr);
     void* p = pool_take(H->device, total, &H->cap);
     if (!p) { LS_HIP(pool_alloc(H->device, &p, total)); H->cap = total; }
     H->mem = p;
-    size_t off = 0;
-    for (int k = 0; k < (int)(sizeof(bytes) / sizeof(bytes[0])); ++k) {
-        *slot[k] = (char*)p + off;
-        off += ((size_t)bytes[k] + 255) & ~(size_t)255;
-    }
-    H->bvh.sort = sort_scratch_carve(sort, T, false);
-    H->bvh.bb = (unsigned*)(H->small + 8);
+    md_carve_handle(H, p);
     return LS_OK;
 }
 // the bounds, the slack and the LBVH of the positions in H->pos, in the handle's buffer; the stream is synchronised

@@ -26,6 +26,7 @@
 //   average backward     g read from device memory: each edge adds (g / 3 / F) (p_a - p_b) / |p_a - p_b| to its ends (0 for a
 //                        zero-length edge), written per corner and gathered as above.
 #include "meshface.h"
+#include "workspace.h"
 
 namespace ls {
 
@@ -268,10 +269,18 @@ __global__ __launch_bounds__(BLOCK) void k_edge_length_bwd(const float* __restri
 
 using namespace ls;
 
+// the partial sums of the average edge length | one 3-vector per corner (backward passes): packed at natural alignment
+struct GeomWs { double* part; float* corner; size_t total; };
+static GeomWs carve(void* workspace, int64_t F) {
+    WsWalk w(workspace);
+    double* part = w.take<double>(MESH_MAXG, 8);
+    float* corner = w.take<float>(9 * (size_t)std::max<int64_t>(F, 1), 4);
+    return {part, corner, w.bytes()};
+}
+
 extern "C" int ls_meshgeom_workspace_bytes(int64_t F, int64_t V, size_t* h_bytes) {
     LS_REQUIRE(h_bytes && F >= 0 && V >= 0, LS_E_INVALID, "ls_meshgeom_workspace_bytes: bad argument");
-    // the partial sums of the average edge length | one 3-vector per corner (backward passes)
-    *h_bytes = sizeof(double) * MESH_MAXG + sizeof(float) * 9 * (size_t)std::max<int64_t>(F, 1);
+    *h_bytes = carve(nullptr, F).total;
     return LS_OK;
 }
 
@@ -299,7 +308,7 @@ extern "C" int ls_massmatrix_voronoi_backward(const float* verts, const void* fa
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
-    float* corner = (float*)((double*)workspace + MESH_MAXG);
+    float* corner = carve(workspace, F).corner;
     if (F > 0)
         LS_IDX(idx_bytes, hipLaunchKernelGGL(k_voronoi_mass_bwd<IDX>, dim3(div_up(F, BLOCK)), dim3(BLOCK), 0, st, verts, (const IDX*)faces, F,
                                              g_mass, cpos, corner));
@@ -317,7 +326,7 @@ extern "C" int ls_average_edge_length(const float* verts, const void* faces, int
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
-    double* part = (double*)workspace;
+    double* part = carve(workspace, F).part;
     const int G = F > 0 ? reduce_grid(F) : 0;
     if (G > 0)
         LS_IDX(idx_bytes, hipLaunchKernelGGL(k_edge_length_partials<IDX>, dim3(G), dim3(BLOCK), 0, st, verts, (const IDX*)faces, F, part));
@@ -336,7 +345,7 @@ extern "C" int ls_average_edge_length_backward(const float* verts, const void* f
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
-    float* corner = (float*)((double*)workspace + MESH_MAXG);
+    float* corner = carve(workspace, F).corner;
     if (F > 0)
         LS_IDX(idx_bytes, hipLaunchKernelGGL(k_edge_length_bwd<IDX>, dim3(div_up(F, BLOCK)), dim3(BLOCK), 0, st, verts, (const IDX*)faces, F,
                                              g_out, cpos, corner));

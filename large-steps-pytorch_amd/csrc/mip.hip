@@ -479,7 +479,7 @@ int mip_check_raster(int64_t B, int64_t V, int64_t F, int H, int W, const char* 
 extern "C" int ls_mip_workspace_bytes(int64_t B, int H, int W, size_t* bytes) {
     LS_REQUIRE(bytes && B >= 1 && H >= 1 && W >= 1, LS_E_INVALID, "ls_mip_workspace_bytes: bad argument");
     LS_REQUIRE(2 * B * (int64_t)H * W < ((int64_t)1 << 31) - 1, LS_E_OVERFLOW, "ls_mip_workspace_bytes: 2 B H W does not fit int32");
-    *bytes = tx_order_layout(2 * B * (int64_t)H * W).total;
+    *bytes = tx_order_carve(nullptr, 2 * B * (int64_t)H * W).total;
     return LS_OK;
 }
 
@@ -579,7 +579,7 @@ extern "C" int ls_mip_order(const float* uv, const float* uv_da, const float* bi
     MipShape s;
     int rc = mip_check(Bt, Ht, Wt, 1, Lmax, B, H, W, mode, boundary, "ls_mip_order", &s);
     if (rc) return rc;
-    const TxOrderWs L = tx_order_layout(2 * s.N);        // always sized for the two items per pixel of linear-mipmap-linear
+    const TxOrderWs L = tx_order_carve(ws, 2 * s.N);       // always sized for the two items per pixel of linear-mipmap-linear
     LS_REQUIRE(uv && (uv_da || bias) && order && seg && ws, LS_E_INVALID, "ls_mip_order: null argument");
     LS_REQUIRE(tx_aligned(uv, 8) && tx_aligned(uv_da, 16), LS_E_INVALID, "ls_mip_order: uv must be 8-byte, uv_da 16-byte aligned");
     LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_mip_order: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
@@ -587,8 +587,8 @@ extern "C" int ls_mip_order(const float* uv, const float* uv_da, const float* bi
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = mode == MIP_LINEAR ? 2 * s.N : s.N, nk = mip_keys_before(s, Lmax + 1);
-    hipLaunchKernelGGL(k_mip_keys, dim3(div_up(n, 256)), dim3(256), 0, st, uv, uv_da, bias, s, n, nk, tx_order_keys(ws, L));
-    return tx_order_finish(ws, L, n, nk, order, seg, st);
+    hipLaunchKernelGGL(k_mip_keys, dim3(div_up(n, 256)), dim3(256), 0, st, uv, uv_da, bias, s, n, nk, L.keys);
+    return tx_order_finish(L, n, nk, order, seg, st);
 }
 
 extern "C" int ls_mip_backward(const float* tex, const float* pyr, int64_t Bt, int Ht, int Wt, int C, int Lmax, const float* uv, const float* uv_da,

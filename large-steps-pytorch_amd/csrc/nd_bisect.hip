@@ -444,26 +444,30 @@ static std::string nd_embed_device_impl(void* ctx, int64_t V) {
     hipStream_t st = A.st;
     int dev = 0;
     (void)hipGetDevice(&dev);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    size_t o_d[4];
-    for (int k = 0; k < 4; ++k) o_d[k] = take(sizeof(int) * V);
     const int n_cnt = BFS_MAX_LEVELS + 2 * BFS_CHUNK + 8;
-    const size_t o_q0 = take(sizeof(int) * V), o_q1 = take(sizeof(int) * V), o_done = take(V), o_cnt = take(sizeof(int) * n_cnt), o_best = take(16), o_first = take(16);
-    size_t cap = off, ecap = sizeof(double) * 3 * (size_t)V;
-    char* base = (char*)pool_take(dev, off, &cap);
-    if (!base && pool_alloc(dev, (void**)&base, off) != hipSuccess) return "nd_embed_device: out of device memory";
+    // one allocation (256-byte aligned regions): four distance arrays, two queues, the done flags, the level counters, two scalars
+    int *d[4], *q[2], *cnt, *first;
+    unsigned char* done;
+    unsigned long long* best;
+    auto carve = [&](void* at) {
+        WsWalk w(at);
+        for (int k = 0; k < 4; ++k) d[k] = w.take<int>((size_t)V);
+        for (int k = 0; k < 2; ++k) q[k] = w.take<int>((size_t)V);
+        done = w.take<unsigned char>((size_t)V);
+        cnt = w.take<int>(n_cnt);
+        best = w.take<unsigned long long>(2);
+        first = w.take<int>(4);
+        return w.bytes();
+    };
+    const size_t need = carve(nullptr);
+    size_t cap = need, ecap = sizeof(double) * 3 * (size_t)V;
+    char* base = (char*)pool_take(dev, need, &cap);
+    if (!base && pool_alloc(dev, (void**)&base, need) != hipSuccess) return "nd_embed_device: out of device memory";
+    carve(base);
     struct Free { char* p; size_t bytes; int dev; hipStream_t st; ~Free() { (void)hipStreamSynchronize(st); if (!pool_give(dev, p, bytes)) (void)hipFree(p); } } guard{base, cap, dev, st};
     double* emb = (double*)pool_take(dev, ecap, &ecap);
     if (!emb && pool_alloc(dev, (void**)&emb, ecap) != hipSuccess) return "nd_embed_device: out of device memory";
     A.d_emb = emb; A.d_emb_cap = ecap;               // (owned by the context from here on, whatever this function returns)
-    int* d[4];
-    for (int k = 0; k < 4; ++k) d[k] = (int*)(base + o_d[k]);
-    int* q[2] = {(int*)(base + o_q0), (int*)(base + o_q1)};
-    unsigned char* done = (unsigned char*)(base + o_done);
-    int* cnt = (int*)(base + o_cnt);
-    unsigned long long* best = (unsigned long long*)(base + o_best);
-    int* first = (int*)(base + o_first);
     const unsigned gv = (unsigned)div_up(std::max<int64_t>(V, n_cnt), BLOCK);
     bool failed = false, to_host = false;
     struct Sweep { int levels, last; int64_t visited; };           // levels = index of the last non-empty level
@@ -553,40 +557,49 @@ std::string nd_bisect_device(void* ctx, int64_t V, int D, int smooth, const doub
     const int NA = (minsep && has_pos && embedded) ? 6 : 3;
     const int max_dom = 1 << (D - 1), nb = div_up(V, BCH);
     // one allocation: positions (two copies), 3 x 2 lists, state, node, end-point flags, per-domain tables, scan scratch, sort scratch
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_pos = take(sizeof(double) * 3 * V), o_pos2 = take(sizeof(double) * 3 * V);
-    const size_t o_pos3 = NA == 6 ? take(sizeof(double) * 3 * V) : 0;
-    size_t o_L[2 * NAX];
-    for (int k = 0; k < 2 * NA; ++k) o_L[k] = take(sizeof(int) * V);
-    const size_t o_state = take(sizeof(long long) * V), o_node = take(sizeof(long long) * V), o_endp = take(V);
-    const size_t o_seg0 = take(sizeof(int) * (2 * (size_t)max_dom + 2)), o_seg1 = take(sizeof(int) * (2 * (size_t)max_dom + 2));
-    const size_t o_ax = take(sizeof(int) * max_dom), o_half = take(sizeof(int) * max_dom), o_ecnt = take(sizeof(int) * 2 * (size_t)max_dom),
-                 o_use1 = take(sizeof(int) * max_dom), o_b0 = take(sizeof(int) * max_dom), o_b1 = take(sizeof(int) * max_dom);
-    const size_t o_bsum = take(sizeof(unsigned long long) * NA * (size_t)nb);
-    const size_t o_sideb = minsep ? take(sizeof(unsigned) * V) : 0, o_cutb = minsep ? take(V) : 0, o_ecnt6 = minsep ? take(sizeof(int) * 2 * NAX * (size_t)max_dom) : 0;
-    const size_t o_sort = take(sort_scratch_bytes(V, true));                 // the coordinate sorts carry their key words
+    double *pos, *pos2, *posB;
+    int *L[2 * NAX], *seg[2];
+    long long *state, *d_node;
+    Round tables{};                           // the rounds' tables: the same pointers in every round
+    SortScratch ss;
+    auto carve = [&](void* at) {
+        const size_t n = (size_t)V, dom = (size_t)max_dom;
+        WsWalk w(at);
+        pos = w.take<double>(3 * n);
+        pos2 = w.take<double>(3 * n);
+        posB = NA == 6 ? w.take<double>(3 * n) : nullptr;
+        for (int k = 0; k < 2 * NA; ++k) L[k] = w.take<int>(n);
+        state = w.take<long long>(n);
+        d_node = w.take<long long>(n);
+        tables.endp = w.take<unsigned char>(n);
+        for (int k = 0; k < 2; ++k) seg[k] = w.take<int>(2 * dom + 2);
+        tables.ax = w.take<int>(dom);
+        tables.half = w.take<int>(dom);
+        tables.ecnt = w.take<int>(2 * dom);
+        tables.use1 = w.take<int>(dom);
+        tables.base0 = w.take<int>(dom);
+        tables.base1 = w.take<int>(dom);
+        tables.bsum = w.take<unsigned long long>(NA * (size_t)nb);
+        tables.sidebits = minsep ? w.take<unsigned>(n) : nullptr;
+        tables.cutbits = minsep ? w.take<unsigned char>(n) : nullptr;
+        tables.ecnt6 = minsep ? w.take<int>(2 * NAX * dom) : nullptr;
+        ss = sort_scratch_take(w, V, true);                         // the coordinate sorts carry their key words
+        return w.bytes();
+    };
+    const size_t need = carve(nullptr);
     int dev = 0;
     (void)hipGetDevice(&dev);
-    size_t cap = off;
-    char* base = (char*)pool_take(dev, off, &cap);                  // (the pool of large buffers of direct.hip: a remesh loop comes back with the same size)
-    if (!base && pool_alloc(dev, (void**)&base, off) != hipSuccess) return "nd_bisect_device: out of device memory";
+    size_t cap = need;
+    char* base = (char*)pool_take(dev, need, &cap);                 // (the pool of large buffers of direct.hip: a remesh loop comes back with the same size)
+    if (!base && pool_alloc(dev, (void**)&base, need) != hipSuccess) return "nd_bisect_device: out of device memory";
+    carve(base);
     struct Free {
         char* p; size_t bytes; int dev; hipStream_t st;
         ~Free() { (void)hipStreamSynchronize(st); if (!pool_give(dev, p, bytes)) (void)hipFree(p); }
     } guard{base, cap, dev, st};
-    double* pos = (double*)(base + o_pos);
-    double* pos2 = (double*)(base + o_pos2);
-    int* L[2 * NAX];
-    for (int k = 0; k < 2 * NA; ++k) L[k] = (int*)(base + o_L[k]);
-    const SortScratch ss = sort_scratch_carve(base + o_sort, V, true);
-    long long* state = (long long*)(base + o_state);
-    long long* d_node = (long long*)(base + o_node);
-    int* seg[2] = {(int*)(base + o_seg0), (int*)(base + o_seg1)};
     // ---- positions ------------------------------------------------------------------------------------------------------------------
     // axes 0-2: the caller's positions, averaged; without positions the embedding (averaged under the trial-cut rule only: the plain
     // embedding is what the longest-axis rounds are pinned to). Axes 3-5 (NA == 6): the embedding, averaged.
-    double* posB = NA == 6 ? (double*)(base + o_pos3) : nullptr;
     auto smooth_passes = [&](double*& p, double*& scratch, int passes) {
         for (int it = 0; it < passes; ++it) {
             hipLaunchKernelGGL(k_smooth, dim3(div_up(V, BLOCK)), dim3(BLOCK), 0, st, A.d_rowptr, A.d_col, V, (const double*)p, scratch);
@@ -620,16 +633,11 @@ std::string nd_bisect_device(void* ctx, int64_t V, int D, int smooth, const doub
     hipLaunchKernelGGL(k_init, dim3(div_up(V, BLOCK)), dim3(BLOCK), 0, st, V, state, seg[0]);
     // ---- D rounds ---------------------------------------------------------------------------------------------------------------------
     for (int r = 0; r < D; ++r) {
-        Round R;
+        Round R = tables;
         R.n_dom = 1 << r; R.NA = NA;
         R.seg = seg[r & 1]; R.seg_next = seg[(r + 1) & 1];
         for (int k = 0; k < NAX; ++k) { R.L[k] = k < NA ? Lc[k] : nullptr; R.Ln[k] = k < NA ? Lo[k] : nullptr; }
-        R.pos = pos; R.pos2 = posB; R.state = state; R.endp = (unsigned char*)(base + o_endp);
-        R.sidebits = minsep ? (unsigned*)(base + o_sideb) : nullptr; R.cutbits = minsep ? (unsigned char*)(base + o_cutb) : nullptr;
-        R.ecnt6 = minsep ? (int*)(base + o_ecnt6) : nullptr;
-        R.ax = (int*)(base + o_ax); R.half = (int*)(base + o_half); R.ecnt = (int*)(base + o_ecnt); R.use1 = (int*)(base + o_use1);
-        R.base0 = (int*)(base + o_b0); R.base1 = (int*)(base + o_b1);
-        R.bsum = (unsigned long long*)(base + o_bsum); R.nb = nb;
+        R.pos = pos; R.pos2 = posB; R.state = state; R.nb = nb;
         const int gv = div_up(V, BLOCK);
         if (minsep) {
             if (hipMemsetAsync(R.sidebits, 0, sizeof(unsigned) * V, st) != hipSuccess) return "nd_bisect_device: memset failed";

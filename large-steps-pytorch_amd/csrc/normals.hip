@@ -15,6 +15,7 @@
 // No atomics: the per-vertex sums go through the corner ranking of meshface.h (measured at 2M faces: 18M fp32 atomics took 0.44 ms
 // per scatter, the two-pass form ~0.05 ms) -- and the result is bitwise reproducible, unlike the reference's index_add_.
 #include "meshface.h"
+#include "workspace.h"
 
 namespace ls {
 
@@ -552,22 +553,21 @@ static int64_t part_slots(int64_t F) { return std::max<int64_t>(MESH_MAXG, div_u
 
 using namespace ls;
 
-extern "C" int ls_normals_workspace_bytes(int64_t F, int64_t V, size_t* h_bytes) {
-    LS_REQUIRE(h_bytes && F >= 0 && V >= 0, LS_E_INVALID, "ls_normals_workspace_bytes: bad argument");
-    // reduction partials (one slot per block of faces) | 4 floats | g_raw (V, 3) | one 3-vector per corner (3 F, 3)
-    *h_bytes = sizeof(double) * 3 * (size_t)part_slots(F) + sizeof(float) * 4 + sizeof(float) * 3 * (size_t)std::max<int64_t>(V, 1) +
-               sizeof(float) * 9 * (size_t)std::max<int64_t>(F, 1);
-    return LS_OK;
+// reduction partials (one slot per block of faces) | 4 floats | g_raw (V, 3) | one 3-vector per corner (3 F, 3): packed at natural alignment
+struct NormalsWs { double* part; float* gN; float* g_raw; float* corner; size_t total; };
+static NormalsWs carve(void* workspace, int64_t V, int64_t F) {
+    WsWalk w(workspace);
+    double* part = w.take<double>(3 * (size_t)part_slots(F), 8);
+    float* gN = w.take<float>(4, 4);
+    float* g_raw = w.take<float>(3 * (size_t)std::max<int64_t>(V, 1), 4);
+    float* corner = w.take<float>(9 * (size_t)std::max<int64_t>(F, 1), 4);
+    return {part, gN, g_raw, corner, w.bytes()};
 }
 
-struct NormalsWs { double* part; float* gN; float* g_raw; float* corner; };
-static NormalsWs carve(void* workspace, int64_t V, int64_t F) {
-    NormalsWs w;
-    w.part = (double*)workspace;
-    w.gN = (float*)(w.part + 3 * part_slots(F));
-    w.g_raw = w.gN + 4;
-    w.corner = w.g_raw + 3 * (size_t)std::max<int64_t>(V, 1);
-    return w;
+extern "C" int ls_normals_workspace_bytes(int64_t F, int64_t V, size_t* h_bytes) {
+    LS_REQUIRE(h_bytes && F >= 0 && V >= 0, LS_E_INVALID, "ls_normals_workspace_bytes: bad argument");
+    *h_bytes = carve(nullptr, V, F).total;
+    return LS_OK;
 }
 
 extern "C" int ls_face_normals(const float* verts, const void* faces, int idx_bytes, int64_t F, int64_t V, float* fn, int device,

@@ -7,6 +7,7 @@
 // rasterizer and of the texture lookup (raster.hip, texture.hip).
 #pragma once
 #include "common.h"
+#include "workspace.h"
 #include <algorithm>
 #include <utility>
 
@@ -241,6 +242,11 @@ static inline SortScratch sort_scratch_carve(void* base, int64_t n, bool carried
     int* hist = (int*)(keys + (carried ? 2 * n : 0));
     const int64_t table = sort_table_ints(n);
     return {ord_b, hist, hist + table, hist + 2 * table, carried ? keys : nullptr, carried ? keys + n : nullptr};
+}
+// the scratch as the next region of a workspace walk (workspace.h): measured by a walk without a base, carved by one with it
+static inline SortScratch sort_scratch_take(ls::WsWalk& w, int64_t n, bool carried, int64_t scan_n = 0, size_t align = 256) {
+    char* p = w.take<char>(sort_scratch_bytes(n, carried, scan_n), align);
+    return p ? sort_scratch_carve(p, n, carried) : SortScratch{};
 }
 
 // the same scratch with the CALLER's second id buffer (n ints) in place of its own, for a caller that keeps both buffers afterwards

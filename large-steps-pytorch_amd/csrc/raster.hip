@@ -706,26 +706,27 @@ using namespace ls;
 namespace {
 
 struct RsWs {          // the workspace's regions (sized from the shapes alone)
-    size_t depth, tiles, toff, bsum, keys, sort, rows, total;
+    u64* depth;
+    int *tiles, *toff, *bsum, *keys;
+    SortScratch sort;
+    float* rows;
+    size_t total;
 };
 
 // N pixels, nk keys (B F faces of an instanced frame, the items of a range-mode one)
-RsWs rs_layout_keys(int64_t N, int64_t nk, int64_t C) {
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    RsWs w;
-    size_t o = 0;
-    w.depth = o; o += al(8 * (size_t)N);
-    w.tiles = o; o += al(4 * (size_t)(nk + 1));
-    w.toff = o; o += al(4 * (size_t)(nk + 2));
-    w.bsum = o; o += al(4 * (size_t)scan_scratch_ints(nk));
-    w.keys = o; o += al(4 * (size_t)N);
-    w.sort = o; o += al(sort_scratch_bytes(N, false));         // the pixel order sorts by gathered key bytes
-    w.rows = o; o += al(4 * (size_t)nk * (size_t)std::max<int64_t>(9, 3 * C));
-    w.total = o;
-    return w;
+RsWs rs_carve_keys(void* ws, int64_t N, int64_t nk, int64_t C) {
+    WsWalk w(ws);
+    u64* depth = w.take<u64>((size_t)N);
+    int* tiles = w.take<int>((size_t)(nk + 1));
+    int* toff = w.take<int>((size_t)(nk + 2));
+    int* bsum = w.take<int>((size_t)scan_scratch_ints(nk));
+    int* keys = w.take<int>((size_t)N);
+    const SortScratch sort = sort_scratch_take(w, N, false);   // the pixel order sorts by gathered key bytes
+    float* rows = w.take<float>((size_t)nk * (size_t)std::max<int64_t>(9, 3 * C));
+    return {depth, tiles, toff, bsum, keys, sort, rows, w.bytes()};
 }
 
-RsWs rs_layout(int64_t B, int64_t F, int64_t H, int64_t W, int64_t C) { return rs_layout_keys(B * H * W, B * F, C); }
+RsWs rs_carve(void* ws, int64_t B, int64_t F, int64_t H, int64_t W, int64_t C) { return rs_carve_keys(ws, B * H * W, B * F, C); }
 
 int rs_check(int64_t B, int64_t V, int64_t F, int H, int W, const char* who) {
     LS_REQUIRE(B >= 1 && V >= 0 && F >= 0 && H >= 1 && W >= 1 && H <= 4096 && W <= 4096, LS_E_INVALID, "%s: bad sizes (B %lld V %lld F %lld H %d W %d)",
@@ -746,7 +747,7 @@ int rg_check(int64_t B, int64_t N, int64_t V, int64_t F, int H, int W, const cha
     return LS_OK;
 }
 
-// ---- a mode above the kernels: its key map, B images, nk keys (the workspace is rs_layout_keys(B H W, nk, C)), V vertices (per image when
+// ---- a mode above the kernels: its key map, B images, nk keys (the workspace is rs_carve_keys(ws, B H W, nk, C)), V vertices (per image when
 // instanced) and F faces -- and, by overload, its size check and the launches of its two gather kernels (whose summation orders differ: the
 // slice law). Each extern "C" function below hands its mode `m`, its name `who` and its pointer test `ok` to a body written once -------------
 template <class Map>
@@ -792,7 +793,7 @@ int rs_forward(const Mode<Map>& m, const char* who, bool ok, const float* pos, c
                void* ws, size_t ws_bytes, int device, void* stream) {
     int rc = rs_check(m, H, W, who);
     if (rc) return rc;
-    const RsWs L = rs_layout_keys(m.B * H * W, m.nk, 0);
+    const RsWs L = rs_carve_keys(ws, m.B * H * W, m.nk, 0);
     LS_REQUIRE(ok, LS_E_INVALID, "%s: null argument", who);
     LS_REQUIRE(!PEEL || prev != rast, LS_E_INVALID, "%s: prev_rast and rast are the same buffer (the layer before is read while this one is written)",
                who);
@@ -800,10 +801,7 @@ int rs_forward(const Mode<Map>& m, const char* who, bool ok, const float* pos, c
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)ws;
-    u64* depth = (u64*)(w + L.depth);
-    int* tiles = (int*)(w + L.tiles);
-    int* toff = (int*)(w + L.toff);
+    u64* depth = L.depth;
     const int64_t N = m.B * H * W, nk = m.nk;
     LS_HIP(hipMemsetAsync(depth, 0xff, 8 * (size_t)N, st));
     if (nk > 0) {
@@ -812,10 +810,10 @@ int rs_forward(const Mode<Map>& m, const char* who, bool ok, const float* pos, c
             else return m.map;
         }();
         using DepthMap = std::remove_const_t<decltype(dmap)>;
-        hipLaunchKernelGGL(k_rs_small<DepthMap>, dim3(div_up(nk, 256)), dim3(256), 0, st, dmap, pos, tri, nk, m.V, m.F, H, W, depth, tiles);
-        rc = exclusive_scan(tiles, nk, toff, (int*)(w + L.bsum), st);
+        hipLaunchKernelGGL(k_rs_small<DepthMap>, dim3(div_up(nk, 256)), dim3(256), 0, st, dmap, pos, tri, nk, m.V, m.F, H, W, depth, L.tiles);
+        rc = exclusive_scan(L.tiles, nk, L.toff, L.bsum, st);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_rs_large<DepthMap>, dim3(RS_LARGE_GRID), dim3(256), 0, st, dmap, pos, tri, nk, m.V, m.F, H, W, (const int*)toff, depth);
+        hipLaunchKernelGGL(k_rs_large<DepthMap>, dim3(RS_LARGE_GRID), dim3(256), 0, st, dmap, pos, tri, nk, m.V, m.F, H, W, (const int*)L.toff, depth);
     }
     hipLaunchKernelGGL(k_rs_resolve<Map>, dim3(div_up(N, 256)), dim3(256), 0, st, m.map, pos, tri, (int)m.B, m.V, m.F, H, W, (const u64*)depth,
                        rast);
@@ -828,16 +826,15 @@ int rs_pixel_order(const Mode<Map>& m, const char* who, bool ok, const float* ra
                    size_t ws_bytes, int device, void* stream) {
     int rc = rs_check(m, H, W, who);
     if (rc) return rc;
-    const RsWs L = rs_layout_keys(m.B * H * W, m.nk, 0);
+    const RsWs L = rs_carve_keys(ws, m.B * H * W, m.nk, 0);
     LS_REQUIRE(ok, LS_E_INVALID, "%s: null argument", who);
     LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, L.total);
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
     const int64_t N = m.B * H * W, nk = m.nk;
-    int* keys = (int*)((char*)ws + L.keys);
-    hipLaunchKernelGGL(k_rs_keys<Map>, dim3(div_up(N, 256)), dim3(256), 0, st, m.map, rast, N, (int64_t)H * W, m.F, nk, keys);
-    return group_by_key<false>(keys, N, nk, order, seg, sort_scratch_carve((char*)ws + L.sort, N, false), st);
+    hipLaunchKernelGGL(k_rs_keys<Map>, dim3(div_up(N, 256)), dim3(256), 0, st, m.map, rast, N, (int64_t)H * W, m.F, nk, L.keys);
+    return group_by_key<false>(L.keys, N, nk, order, seg, L.sort, st);
 }
 
 template <class Map>
@@ -846,19 +843,18 @@ int rs_backward(const Mode<Map>& m, const char* who, bool ok, const float* pos, 
                 size_t ws_bytes, int device, void* stream) {
     int rc = rs_check(m, H, W, who);
     if (rc) return rc;
-    const RsWs L = rs_layout_keys(m.B * H * W, m.nk, 0);
+    const RsWs L = rs_carve_keys(ws, m.B * H * W, m.nk, 0);
     LS_REQUIRE(ok, LS_E_INVALID, "%s: null argument", who);
     LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, L.total);
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
-    float* rows = (float*)((char*)ws + L.rows);
     const int64_t nk = m.nk;
     if (nk > 0) {
         RowRaster<Map> r{m.map, pos, tri, grad_rast, m.V, m.F, H, W};
-        hipLaunchKernelGGL(k_rs_seg_sum<RowRaster<Map>>, dim3(div_up(nk, 256)), dim3(256), 0, st, r, order, seg, nk, 9, 0, rows);
+        hipLaunchKernelGGL(k_rs_seg_sum<RowRaster<Map>>, dim3(div_up(nk, 256)), dim3(256), 0, st, r, order, seg, nk, 9, 0, L.rows);
     }
-    rs_gather_pos(m, rows, vptr, corner_order, grad_pos, st);
+    rs_gather_pos(m, L.rows, vptr, corner_order, grad_pos, st);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
@@ -876,8 +872,15 @@ void rs_interp_grad_attr(const Mode<Map>& m, const float* rast, int64_t attr_bat
     rs_gather_attr(m, rows, vptr, corner_order, attr_batch, C, grad_attr, st);
 }
 
-// the half-edge ids of nk faces or items, the sort's scratch behind them
-size_t rs_adjacency_bytes(int64_t nk) { return 4 * (size_t)(3 * nk) + sort_scratch_bytes(3 * nk, true); }
+// the ids of n half-edges, the sort's scratch behind them: packed at 4 bytes
+struct AdjWs { int* ord_a; SortScratch sort; size_t total; };
+AdjWs rs_adjacency_carve(void* ws, int64_t n) {
+    WsWalk w(ws);
+    int* ord_a = w.take<int>((size_t)n, 4);
+    const SortScratch sort = sort_scratch_take(w, n, true, 0, 4);
+    return {ord_a, sort, w.bytes()};
+}
+size_t rs_adjacency_bytes(int64_t nk) { return rs_adjacency_carve(nullptr, 3 * nk).total; }      // nk faces or items
 
 // the n half-edges sorted by the WORDS words of `key` (the last one `last_bytes` wide), each paired with the other one of its edge
 template <class Key, int WORDS>
@@ -885,9 +888,9 @@ int rs_adjacency(Key key, int64_t n, int last_bytes, int32_t* adj, void* ws, int
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
-    int* ord_a = (int*)ws;
+    const AdjWs w = rs_adjacency_carve(ws, n);
     const int* sorted = nullptr;
-    int rc = radix_argsort_words(key, n, WORDS, ord_a, sort_scratch_carve(ord_a + n, n, true), st, &sorted, last_bytes);
+    int rc = radix_argsort_words(key, n, WORDS, w.ord_a, w.sort, st, &sorted, last_bytes);
     if (rc) return rc;
     hipLaunchKernelGGL((k_rs_adjacency<Key, WORDS>), dim3(div_up(n, 256)), dim3(256), 0, st, key, sorted, n, adj);
     LS_HIP(hipGetLastError());
@@ -916,7 +919,7 @@ int rs_antialias_backward(const Mode<Map>& m, const char* who, bool ok, const fl
     int rc = rs_check(m, H, W, who);
     if (rc) return rc;
     const int64_t N = m.B * H * W, nk = m.nk;
-    const RsWs L = rs_layout_keys(N, nk, 0);
+    const RsWs L = rs_carve_keys(ws, N, nk, 0);
     LS_REQUIRE(ok, LS_E_INVALID, "%s: bad argument", who);
     LS_REQUIRE(!grad_pos || (order && seg && vptr && ws && (corner_order || m.F == 0)), LS_E_INVALID,
                "%s: grad_pos needs the pixel order, the corner ranking and a workspace", who);
@@ -927,12 +930,11 @@ int rs_antialias_backward(const Mode<Map>& m, const char* who, bool ok, const fl
     AAMesh<Map> mesh{m.map, pos, tri, adj, rast, m.V, m.F, H, W};
     if (grad_color) hipLaunchKernelGGL(k_aa_grad_color<Map>, dim3(div_up(N, 256)), dim3(256), 0, st, mesh, (int)m.B, grad_out, C, grad_color);
     if (grad_pos) {
-        float* rows = (float*)((char*)ws + L.rows);
         if (nk > 0) {
             RowAA<Map> r{mesh, color, grad_out, C, boost};
-            hipLaunchKernelGGL(k_rs_seg_sum<RowAA<Map>>, dim3(div_up(nk, 256)), dim3(256), 0, st, r, order, seg, nk, 9, 0, rows);
+            hipLaunchKernelGGL(k_rs_seg_sum<RowAA<Map>>, dim3(div_up(nk, 256)), dim3(256), 0, st, r, order, seg, nk, 9, 0, L.rows);
         }
-        rs_gather_pos(m, rows, vptr, corner_order, grad_pos, st);
+        rs_gather_pos(m, L.rows, vptr, corner_order, grad_pos, st);
     }
     LS_HIP(hipGetLastError());
     return LS_OK;
@@ -944,7 +946,7 @@ extern "C" int ls_raster_workspace_bytes(int64_t B, int64_t F, int H, int W, int
     int rc = rs_check(B, 0, F, H, W, "ls_raster_workspace_bytes");
     if (rc) return rc;
     LS_REQUIRE(bytes && C >= 0, LS_E_INVALID, "ls_raster_workspace_bytes: bad argument");
-    *bytes = rs_layout(B, F, H, W, C).total;
+    *bytes = rs_carve(nullptr, B, F, H, W, C).total;
     return LS_OK;
 }
 
@@ -991,7 +993,7 @@ extern "C" int ls_raster_interpolate_backward(const float* attr, int64_t attr_ba
     if (rc) return rc;
     LS_REQUIRE(C >= 1 && (attr_batch == 1 || attr_batch == B), LS_E_INVALID, "ls_raster_interpolate_backward: C %d, attribute batch %lld of %lld",
                C, (long long)attr_batch, (long long)B);
-    const RsWs L = rs_layout(B, F, H, W, C);
+    const RsWs L = rs_carve(ws, B, F, H, W, C);
     LS_REQUIRE(rast && grad_out && (attr || V == 0) && (tri || F == 0), LS_E_INVALID, "ls_raster_interpolate_backward: null argument");
     LS_REQUIRE(!grad_attr || (order && seg && vptr && ws && (corner_order || F == 0)), LS_E_INVALID,
                "ls_raster_interpolate_backward: grad_attr needs the pixel order, the corner ranking and a workspace");
@@ -1004,8 +1006,7 @@ extern "C" int ls_raster_interpolate_backward(const float* attr, int64_t attr_ba
         hipLaunchKernelGGL(k_rs_interp_grad_rast, dim3(div_up(B * H * W, 256)), dim3(256), 0, st, attr, (int)attr_batch, V, C, rast, (int)B,
                            (int64_t)H * W, tri, F, grad_out, grad_rast);
     if (grad_attr)
-        rs_interp_grad_attr(inst(B, V, F), rast, attr_batch, C, grad_out, order, seg, vptr, corner_order, grad_attr,
-                            (float*)((char*)ws + L.rows), st);
+        rs_interp_grad_attr(inst(B, V, F), rast, attr_batch, C, grad_out, order, seg, vptr, corner_order, grad_attr, L.rows, st);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
@@ -1046,7 +1047,7 @@ extern "C" int ls_range_workspace_bytes(int64_t B, int64_t N, int H, int W, int 
     int rc = rg_check(B, N, 0, 0, H, W, "ls_range_workspace_bytes");
     if (rc) return rc;
     LS_REQUIRE(bytes && C >= 0, LS_E_INVALID, "ls_range_workspace_bytes: bad argument");
-    *bytes = rs_layout_keys(B * H * W, N, C).total;
+    *bytes = rs_carve_keys(nullptr, B * H * W, N, C).total;
     return LS_OK;
 }
 
@@ -1076,14 +1077,13 @@ extern "C" int ls_range_interpolate_backward(const float* rast, const int32_t* r
     int rc = rg_check(B, N, V, 0, H, W, "ls_range_interpolate_backward");
     if (rc) return rc;
     LS_REQUIRE(C >= 1, LS_E_INVALID, "ls_range_interpolate_backward: C %d", C);
-    const RsWs L = rs_layout_keys(B * H * W, N, C);
+    const RsWs L = rs_carve_keys(ws, B * H * W, N, C);
     LS_REQUIRE(rast && ranges && grad_out && order && seg && vptr && grad_attr && ws && (corner_order || N == 0), LS_E_INVALID,
                "ls_range_interpolate_backward: null argument");
     LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_range_interpolate_backward: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
     DeviceGuard g(device);
     LS_HIP(g.err);
-    rs_interp_grad_attr(range(ranges, B, N, V, 0), rast, 1, C, grad_out, order, seg, vptr, corner_order, grad_attr, (float*)((char*)ws + L.rows),
-                        (hipStream_t)stream);
+    rs_interp_grad_attr(range(ranges, B, N, V, 0), rast, 1, C, grad_out, order, seg, vptr, corner_order, grad_attr, L.rows, (hipStream_t)stream);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }

@@ -270,7 +270,7 @@ extern "C" int ls_mesh_ray_any(void* handle, const float* O, const float* D, int
 extern "C" int ls_mesh_ray_backward_workspace_bytes(int64_t n, int64_t F, size_t* bytes) {
     LS_REQUIRE(bytes && n >= 0 && F > 0, LS_E_INVALID, "ls_mesh_ray_backward_workspace_bytes: bad argument");
     LS_REQUIRE(n < INT32_MAX - BLOCK && 3 * F < INT32_MAX, LS_E_OVERFLOW, "ls_mesh_ray_backward_workspace_bytes: more than 2^31 rays or corners");
-    *bytes = md_layout(n, F, false, sizeof(float) * 9).total;
+    *bytes = md_carve<float>(nullptr, n, F, false).total;
     return LS_OK;
 }
 
@@ -282,18 +282,16 @@ extern "C" int ls_mesh_ray_backward(void* handle, const float* O, const float* D
                "ls_mesh_ray_backward: the vertex gradient needs W, the corner ranking and a workspace");
     LS_REQUIRE(n < INT32_MAX - BLOCK, LS_E_OVERFLOW, "ls_mesh_ray_backward: more than 2^31 rays");
     MeshDistanceHandle* H = (MeshDistanceHandle*)handle;
-    const MdWs L = md_layout(n, H->T, false, sizeof(float) * 9);
-    LS_REQUIRE(!gV || ws_bytes >= L.total, LS_E_WORKSPACE, "ls_mesh_ray_backward: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
+    const MdCarved<float> c = md_carve<float>(ws, n, H->T, false);
+    LS_REQUIRE(!gV || ws_bytes >= c.total, LS_E_WORKSPACE, "ls_mesh_ray_backward: workspace too small (%zu < %zu bytes)", ws_bytes, c.total);
     DeviceGuard guard(H->device);
     LS_HIP(guard.err);
     const hipStream_t st = (hipStream_t)stream;
     if ((gO || gD) && n > 0)
         hipLaunchKernelGGL(k_ray_grad_rays, dim3(div_up(n, BLOCK)), dim3(BLOCK), 0, st, D, (int)n, H->view(), I, t, g, gO, gD);
     if (gV && n == 0) LS_HIP(hipMemsetAsync(gV, 0, sizeof(float) * 3 * (size_t)H->V, st));
-    if (gV && n > 0) {
-        const MdCarved<float> c = md_carve<float>(ws, L, n);
+    if (gV && n > 0)
         if (int rc = md_vertex_grad<float>(I, n, H->T, H->V, RcRows{D, H->view(), g, W, c.order, c.seg, c.rows}, vptr, corner_order, gV, c, st)) return rc;
-    }
     LS_HIP(hipGetLastError());
     return LS_OK;
 }

@@ -266,25 +266,22 @@ struct SpRows {
 using namespace ls;
 
 namespace {
-struct SpWs {          // the regions of the workspace: the forward's and the backward's overlap (a call is one or the other)
-    size_t scal, cumq, lev1, lev2, tsum, fwd;           // forward: [0] amax bits, [1] Q; F, F / 16, F / 256 and tiles + 1 words
-    MdWs bwd;                                           // backward: md_vertex_grad's, with fp64 rows
-    size_t total;
+struct SpWs {          // the workspace: the forward's and the backward's regions both start at the base (a call is one or the other)
+    u64 *scal, *cumq, *lev1, *lev2, *tsum;              // forward: [0] amax bits, [1] Q; F, F / 16, F / 256 and tiles + 1 words
+    MdCarved<double> bwd;                               // backward: md_vertex_grad's, with fp64 rows
+    size_t total;                                       // the larger of the two walks
 };
-size_t sp_al(size_t x) { return (x + 255) & ~(size_t)255; }
-SpWs sp_layout(int64_t F, int64_t n) {
-    SpWs w;
-    const int64_t tiles = (F + SP_TILE - 1) / SP_TILE;
-    size_t o = 0;
-    w.scal = o; o += sp_al(16);
-    w.cumq = o; o += sp_al(8 * (size_t)std::max<int64_t>(F, 1));
-    w.lev1 = o; o += sp_al(8 * (size_t)((F + SP_FAN1 - 1) / SP_FAN1 + 1));
-    w.lev2 = o; o += sp_al(8 * (size_t)((F + SP_FAN2 - 1) / SP_FAN2 + 1));
-    w.tsum = o; o += sp_al(8 * (size_t)(tiles + 1));
-    w.fwd = o;
-    w.bwd = md_layout(n, F, false, sizeof(double) * 9);
-    w.total = std::max(w.fwd, w.bwd.total);
-    return w;
+SpWs sp_carve(void* ws, int64_t F, int64_t n) {
+    SpWs r;
+    WsWalk w(ws);
+    r.scal = w.take<u64>(2);
+    r.cumq = w.take<u64>((size_t)std::max<int64_t>(F, 1));
+    r.lev1 = w.take<u64>((size_t)((F + SP_FAN1 - 1) / SP_FAN1 + 1));
+    r.lev2 = w.take<u64>((size_t)((F + SP_FAN2 - 1) / SP_FAN2 + 1));
+    r.tsum = w.take<u64>((size_t)((F + SP_TILE - 1) / SP_TILE + 1));
+    r.bwd = md_carve<double>(ws, n, F, false);
+    r.total = std::max(w.bytes(), r.bwd.total);
+    return r;
 }
 // n is bounded below 2^31 - BLOCK: the sort's grids round it up to a workgroup
 int sp_check_sizes(int64_t F, int64_t n, const char* who) {
@@ -297,7 +294,7 @@ int sp_check_sizes(int64_t F, int64_t n, const char* who) {
 extern "C" int ls_sample_workspace_bytes(int64_t F, int64_t n, size_t* bytes) {
     LS_REQUIRE(bytes, LS_E_INVALID, "ls_sample_workspace_bytes: bad argument");
     if (int rc = sp_check_sizes(F, n, "ls_sample_workspace_bytes")) return rc;
-    *bytes = sp_layout(F, n).total;
+    *bytes = sp_carve(nullptr, F, n).total;
     return LS_OK;
 }
 
@@ -310,18 +307,12 @@ extern "C" int ls_sample_surface(const float* verts, const void* faces, int idx_
     if (int rc = sp_check_sizes(F, n, "ls_sample_surface")) return rc;
     LS_REQUIRE(offset < ((uint64_t)1 << 31) && offset + (uint64_t)n < ((uint64_t)1 << 31), LS_E_OVERFLOW,
                "ls_sample_surface: offset + n must be below 2^31");
-    const SpWs L = sp_layout(F, n);
-    LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_sample_surface: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
+    const auto [scal, cumq, lev1, lev2, tsum, bwd, total] = sp_carve(ws, F, n);
+    LS_REQUIRE(ws_bytes >= total, LS_E_WORKSPACE, "ls_sample_surface: workspace too small (%zu < %zu bytes)", ws_bytes, total);
     if (n == 0) return LS_OK;
     DeviceGuard guard(device);
     LS_HIP(guard.err);
     const hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)ws;
-    u64* scal = (u64*)(w + L.scal);
-    u64* cumq = (u64*)(w + L.cumq);
-    u64* tsum = (u64*)(w + L.tsum);
-    u64* lev1 = (u64*)(w + L.lev1);
-    u64* lev2 = (u64*)(w + L.lev2);
     LS_HIP(hipMemsetAsync(scal, 0, 16, st));
     const int tiles = div_up(F, SP_TILE);
     if (F > 0) {
@@ -344,7 +335,7 @@ extern "C" int ls_sample_surface_backward(const void* faces, int idx_bytes, int6
                    && (n <= 0 || (I && W && gP)),
                LS_E_INVALID, "ls_sample_surface_backward: bad argument (V in [1, 2^31), no null pointer)");
     if (int rc = sp_check_sizes(F, n, "ls_sample_surface_backward")) return rc;
-    const SpWs L = sp_layout(F, n);
+    const SpWs L = sp_carve(ws, F, n);
     LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_sample_surface_backward: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
     DeviceGuard guard(device);
     LS_HIP(guard.err);
@@ -353,7 +344,7 @@ extern "C" int ls_sample_surface_backward(const void* faces, int idx_bytes, int6
         LS_HIP(hipMemsetAsync(gV, 0, sizeof(float) * 3 * (size_t)V, st));
         return LS_OK;
     }
-    const MdCarved<double> c = md_carve<double>(ws, L.bwd, n);
+    const MdCarved<double>& c = L.bwd;
     if (int rc = md_vertex_grad<double>(I, n, F, V, SpRows{W, gP, c.order, c.seg, c.rows}, vptr, corner_order, gV, c, st)) return rc;
     LS_HIP(hipGetLastError());
     return LS_OK;

@@ -194,20 +194,17 @@ __global__ __launch_bounds__(BLOCK) void k_selfx_emit(const int* __restrict__ or
 }
 
 struct SxWs {          // the regions of the fill pass's workspace
-    size_t off, pf, pg, order, sort, total;
+    int *off, *pf, *pg, *order;
+    SortScratch sort;
+    size_t total;
 };
-static inline SxWs sx_layout(int64_t F, int64_t k) {
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+static inline SxWs sx_carve(void* ws, int64_t F, int64_t k) {
     const int64_t m = std::max<int64_t>(k, 1);
-    SxWs w;
-    size_t o = 0;
-    w.off = o; o += al(4 * (size_t)(F + 1));
-    w.pf = o; o += al(4 * (size_t)m);
-    w.pg = o; o += al(4 * (size_t)m);
-    w.order = o; o += al(4 * (size_t)m);
-    w.sort = o; o += al(sort_scratch_bytes(m, true, F));       // its bsum also serves the scan of the F counts
-    w.total = o;
-    return w;
+    WsWalk w(ws);
+    int* off = w.take<int>((size_t)(F + 1));
+    int *pf = w.take<int>((size_t)m), *pg = w.take<int>((size_t)m), *order = w.take<int>((size_t)m);
+    const SortScratch sort = sort_scratch_take(w, m, true, F);       // its bsum also serves the scan of the F counts
+    return {off, pf, pg, order, sort, w.bytes()};
 }
 
 }  // namespace ls
@@ -230,7 +227,7 @@ extern "C" int ls_mesh_selfx_count(void* handle, int32_t* counts, int64_t* total
 extern "C" int ls_mesh_selfx_workspace_bytes(int64_t F, int64_t k, size_t* bytes) {
     LS_REQUIRE(bytes && F > 0 && k >= 0, LS_E_INVALID, "ls_mesh_selfx_workspace_bytes: bad argument");
     LS_REQUIRE(3 * F < INT32_MAX && 2 * k < INT32_MAX - BLOCK, LS_E_OVERFLOW, "ls_mesh_selfx_workspace_bytes: more than 2^31 corners or pair entries");
-    *bytes = sx_layout(F, k).total;
+    *bytes = sx_carve(nullptr, F, k).total;
     return LS_OK;
 }
 
@@ -240,22 +237,20 @@ extern "C" int ls_mesh_selfx_pairs(void* handle, const int32_t* counts, int64_t 
     if (k == 0) return LS_OK;
     MeshDistanceHandle* H = (MeshDistanceHandle*)handle;
     const int64_t F = H->T;
-    const SxWs L = sx_layout(F, k);
-    LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_mesh_selfx_pairs: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
+    const SxWs w = sx_carve(ws, F, k);
+    LS_REQUIRE(ws_bytes >= w.total, LS_E_WORKSPACE, "ls_mesh_selfx_pairs: workspace too small (%zu < %zu bytes)", ws_bytes, w.total);
     DeviceGuard g(H->device);
     LS_HIP(g.err);
     const hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)ws;
-    int *off = (int*)(w + L.off), *pf = (int*)(w + L.pf), *pg = (int*)(w + L.pg), *order = (int*)(w + L.order);
-    const SortScratch s = sort_scratch_carve(w + L.sort, k, true);
-    if (int rc = exclusive_scan(counts, F, off, s.bsum, st)) return rc;
-    LS_HIP(hipMemsetAsync(pf, 0, L.order - L.pf, st));          // counts that are not this mesh's leave zeros, never stale memory
-    hipLaunchKernelGGL(k_selfx_fill, dim3(div_up(F, BLOCK)), dim3(BLOCK), 0, st, H->view(), (const int*)off, (int)k, pf, pg);
+    if (int rc = exclusive_scan(counts, F, w.off, w.sort.bsum, st)) return rc;
+    // pf and pg are adjacent: one memset up to order. Counts that are not this mesh's leave zeros, never stale memory
+    LS_HIP(hipMemsetAsync(w.pf, 0, (size_t)((char*)w.order - (char*)w.pf), st));
+    hipLaunchKernelGGL(k_selfx_fill, dim3(div_up(F, BLOCK)), dim3(BLOCK), 0, st, H->view(), (const int*)w.off, (int)k, w.pf, w.pg);
     LS_HIP(hipGetLastError());
     const int* sorted = nullptr;
     // f takes radix_passes(F - 1) bytes, g all four: radix_argsort_words shortens its last word only
-    if (int rc = radix_argsort_words(KeyPair{pf, pg}, k, 2, order, s, st, &sorted, radix_passes(F - 1))) return rc;
-    hipLaunchKernelGGL(k_selfx_emit, dim3(div_up(k, BLOCK)), dim3(BLOCK), 0, st, sorted, (const int*)pf, (const int*)pg, (int)k, pairs);
+    if (int rc = radix_argsort_words(KeyPair{w.pf, w.pg}, k, 2, w.order, w.sort, st, &sorted, radix_passes(F - 1))) return rc;
+    hipLaunchKernelGGL(k_selfx_emit, dim3(div_up(k, BLOCK)), dim3(BLOCK), 0, st, sorted, (const int*)w.pf, (const int*)w.pg, (int)k, pairs);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }

@@ -269,22 +269,19 @@ static inline bool tx_aligned(const void* p, size_t a) { return ((uintptr_t)p & 
 // the workspace of an item order: the keys and the scratch of the sort with carried keys, both 256-byte aligned. The plain texture has
 // one item per pixel; the mipmapped lookup is always sized for the two of linear-mipmap-linear, the cube lookup for the four of linear.
 struct TxOrderWs {
-    size_t keys, sort, total;
+    int* keys;
+    char* sort;             // sort_scratch_bytes(items, true): carved for the n <= items keys a call sorts (tx_order_finish)
+    size_t total;
 };
 
-static inline TxOrderWs tx_order_layout(int64_t items) {
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    TxOrderWs w;
-    size_t o = 0;
-    w.keys = o; o += al(4 * (size_t)items);
-    w.sort = o; o += al(sort_scratch_bytes(items, true));
-    w.total = o;
-    return w;
+static inline TxOrderWs tx_order_carve(void* ws, int64_t items) {
+    ls::WsWalk w(ws);
+    int* keys = w.take<int>((size_t)items);
+    char* sort = w.take<char>(sort_scratch_bytes(items, true));
+    return {keys, sort, w.bytes()};
 }
 
-static inline int* tx_order_keys(void* ws, const TxOrderWs& L) { return (int*)((char*)ws + L.keys); }
-
 // the tail of the three *_order entry points: the n keys in [0, nk] that a key kernel wrote on st -> order, seg (groupby.h)
-static inline int tx_order_finish(void* ws, const TxOrderWs& L, int64_t n, int64_t nk, int* order, int* seg, hipStream_t st) {
-    return group_by_key<true>(tx_order_keys(ws, L), n, nk, order, seg, sort_scratch_carve((char*)ws + L.sort, n, true), st);
+static inline int tx_order_finish(const TxOrderWs& w, int64_t n, int64_t nk, int* order, int* seg, hipStream_t st) {
+    return group_by_key<true>(w.keys, n, nk, order, seg, sort_scratch_carve(w.sort, n, true), st);
 }

@@ -145,7 +145,7 @@ int tx_check(int64_t Bt, int Ht, int Wt, int C, int64_t B, int H, int W, int fil
 extern "C" int ls_texture_workspace_bytes(int64_t B, int H, int W, size_t* bytes) {
     LS_REQUIRE(bytes && B >= 1 && H >= 1 && W >= 1, LS_E_INVALID, "ls_texture_workspace_bytes: bad argument");
     LS_REQUIRE(B * (int64_t)H * W < ((int64_t)1 << 31) - 1, LS_E_OVERFLOW, "ls_texture_workspace_bytes: B H W does not fit int32");
-    *bytes = tx_order_layout(B * (int64_t)H * W).total;
+    *bytes = tx_order_carve(nullptr, B * (int64_t)H * W).total;
     return LS_OK;
 }
 
@@ -171,15 +171,15 @@ extern "C" int ls_texture_order(const float* uv, int64_t B, int H, int W, int64_
     TxShape s;
     int rc = tx_check(Bt, Ht, Wt, 1, B, H, W, filter, boundary, "ls_texture_order", &s);
     if (rc) return rc;
-    const TxOrderWs L = tx_order_layout(s.N);
+    const TxOrderWs L = tx_order_carve(ws, s.N);
     LS_REQUIRE(uv && order && seg && ws, LS_E_INVALID, "ls_texture_order: null argument");
     LS_REQUIRE(tx_aligned(uv, 8), LS_E_INVALID, "ls_texture_order: uv must be 8-byte aligned");
     LS_REQUIRE(ws_bytes >= L.total, LS_E_WORKSPACE, "ls_texture_order: workspace too small (%zu < %zu bytes)", ws_bytes, L.total);
     DeviceGuard g(device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_tx_keys, dim3(div_up(s.N, 256)), dim3(256), 0, st, uv, s, tx_order_keys(ws, L));
-    return tx_order_finish(ws, L, s.N, (int64_t)s.Bt * (s.Ht + 1) * (s.Wt + 1), order, seg, st);
+    hipLaunchKernelGGL(k_tx_keys, dim3(div_up(s.N, 256)), dim3(256), 0, st, uv, s, L.keys);
+    return tx_order_finish(L, s.N, (int64_t)s.Bt * (s.Ht + 1) * (s.Wt + 1), order, seg, st);
 }
 
 extern "C" int ls_texture_backward(const float* tex, int64_t Bt, int Ht, int Wt, int C, const float* uv, int64_t B, int H, int W, int filter,

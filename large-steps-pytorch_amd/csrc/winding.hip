@@ -228,14 +228,14 @@ __global__ __launch_bounds__(WN_TILE) void k_wn_exact(const float* __restrict__ 
     if (i < n) w[i] = (isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2])) ? acc : wn_nan();
 }
 
-struct WnLayout { size_t mom, flag, total; };
-static inline WnLayout wn_layout(int64_t F) {
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    WnLayout L;
-    L.mom = 0;
-    L.flag = al(sizeof(double) * WN_STRIDE * (size_t)(2 * F - 1));
-    L.total = L.flag + al(sizeof(int) * (size_t)F);
-    return L;
+// the moment buffer of F faces: the moments of the 2 F - 1 nodes, then the build's one flag per face. The queries hold it const: they
+// carve it the same way and read only mom
+struct WnBuf { double* mom; int* flag; size_t total; };
+static inline WnBuf wn_carve(const void* moments, int64_t F) {
+    WsWalk w(moments);
+    double* mom = w.take<double>(WN_STRIDE * (size_t)(2 * F - 1));
+    int* flag = w.take<int>((size_t)F);
+    return {mom, flag, w.bytes()};
 }
 
 }  // namespace ls
@@ -245,7 +245,7 @@ using namespace ls;
 extern "C" int ls_mesh_winding_bytes(int64_t F, size_t* bytes) {
     LS_REQUIRE(bytes && F > 0, LS_E_INVALID, "ls_mesh_winding_bytes: bad argument");
     LS_REQUIRE(3 * F < INT32_MAX, LS_E_OVERFLOW, "ls_mesh_winding_bytes: more than 2^31 corners");
-    *bytes = wn_layout(F).total;
+    *bytes = wn_carve(nullptr, F).total;
     return LS_OK;
 }
 
@@ -256,12 +256,10 @@ extern "C" int ls_mesh_winding_prepare(void* handle, void* moments, void* stream
     LS_HIP(g.err);
     const hipStream_t st = (hipStream_t)stream;
     const int T = H->T, N = 2 * T - 1;
-    const WnLayout L = wn_layout(T);
-    double* mom = (double*)((char*)moments + L.mom);
-    int* flag = (int*)((char*)moments + L.flag);
-    LS_HIP(hipMemsetAsync(flag, 0, sizeof(int) * (size_t)T, st));
-    hipLaunchKernelGGL(k_wn_raw, dim3(div_up(T, BLOCK)), dim3(BLOCK), 0, st, H->view(), (const unsigned*)H->bvh.bb, (const int*)H->bvh.parent, flag, mom);
-    hipLaunchKernelGGL(k_wn_centre, dim3(div_up(N, BLOCK)), dim3(BLOCK), 0, st, N, (const unsigned*)H->bvh.bb, (const float*)H->bvh.box, mom);
+    const WnBuf b = wn_carve(moments, T);
+    LS_HIP(hipMemsetAsync(b.flag, 0, sizeof(int) * (size_t)T, st));
+    hipLaunchKernelGGL(k_wn_raw, dim3(div_up(T, BLOCK)), dim3(BLOCK), 0, st, H->view(), (const unsigned*)H->bvh.bb, (const int*)H->bvh.parent, b.flag, b.mom);
+    hipLaunchKernelGGL(k_wn_centre, dim3(div_up(N, BLOCK)), dim3(BLOCK), 0, st, N, (const unsigned*)H->bvh.bb, (const float*)H->bvh.box, b.mom);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
@@ -288,7 +286,7 @@ extern "C" int ls_mesh_winding_query(void* handle, const void* moments, const fl
     DeviceGuard g(H->device);
     LS_HIP(g.err);
     hipLaunchKernelGGL(k_wn_walk, dim3(div_up(n, BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, P, (int)n, H->view(),
-                       (const double*)((const char*)moments + wn_layout(H->T).mom), beta, w);
+                       (const double*)wn_carve(moments, H->T).mom, beta, w);
     LS_HIP(hipGetLastError());
     return LS_OK;
 }
@@ -306,6 +304,6 @@ extern "C" int ls_mesh_winding_arrays(void* handle, const void* moments, int32_t
     if (esc) LS_HIP(hipMemcpyAsync(esc, H->bvh.esc, 4 * N, hipMemcpyDeviceToDevice, st));
     if (tri) LS_HIP(hipMemcpyAsync(tri, H->bvh.tri, 4 * T, hipMemcpyDeviceToDevice, st));
     if (box) LS_HIP(hipMemcpyAsync(box, H->bvh.box, 24 * N, hipMemcpyDeviceToDevice, st));
-    if (mom) LS_HIP(hipMemcpyAsync(mom, (const char*)moments + wn_layout(H->T).mom, sizeof(double) * WN_STRIDE * N, hipMemcpyDeviceToDevice, st));
+    if (mom) LS_HIP(hipMemcpyAsync(mom, wn_carve(moments, H->T).mom, sizeof(double) * WN_STRIDE * N, hipMemcpyDeviceToDevice, st));
     return LS_OK;
 }

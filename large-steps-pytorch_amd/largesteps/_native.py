@@ -492,6 +492,19 @@ def csr_of(M):
     return csr
 
 
+def workspace_bytes(size_fn_name, sizes):
+    """what the native size function of that name (an ls_*_bytes) asks for `sizes`"""
+    n = c_size_t(0)
+    check(getattr(lib(), size_fn_name)(*sizes, ctypes.byref(n)))
+    return n.value
+
+
+def workspace(size_fn_name, sizes, device, nbytes=None):
+    """the uint8 buffer on `device` that the native size function of that name asks for `sizes`: every caller's workspace comes from
+    here. nbytes: that answer, for a caller that kept it (normals.py) or bounds it (geometry.py)"""
+    return torch.empty(workspace_bytes(size_fn_name, sizes) if nbytes is None else nbytes, dtype=torch.uint8, device=device)
+
+
 def csr_from_coo(M):
     if not isinstance(M, torch.Tensor) or M.layout != torch.sparse_coo:
         raise TypeError("expected a torch sparse COO matrix (as returned by largesteps.geometry.compute_matrix)")
@@ -510,6 +523,7 @@ def csr_from_coo(M):
     dev = M.device
     rowptr = torch.empty(V + 1, dtype=torch.int32, device=dev)
     col = torch.empty(nnz, dtype=torch.int32, device=dev)
+    # no size function in the ABI: the bound of include/largesteps_hip.h ("scratch: >= 4*(V+1) + 4*((V+1)/2048+4) + 1024 bytes")
     scratch = torch.empty(4 * (V + 1) + 4 * ((V + 1) // 2048 + 4) + 1024, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         check(lib().ls_csr_from_coo(ptr(rows), ptr(cols), ptr(val), nnz, V, ptr(rowptr), ptr(col), None, ptr(scratch),
@@ -532,9 +546,7 @@ def csr_transposed(csr):
     if t is not None and csr._transposed_version == csr.val._version:     # (the values may have been updated in place since)
         return t
     dev = csr.device
-    n = c_size_t(0)
-    check(lib().ls_csr_transpose_workspace_bytes(csr.V, csr.nnz, ctypes.byref(n)))
-    ws = torch.empty(n.value, dtype=torch.uint8, device=dev)
+    ws = workspace("ls_csr_transpose_workspace_bytes", (csr.V, csr.nnz), dev)
     rowptr = torch.empty(csr.V + 1, dtype=torch.int32, device=dev)
     col = torch.empty(max(csr.nnz, 1), dtype=torch.int32, device=dev)[: csr.nnz]
     val = torch.empty(max(csr.nnz, 1), dtype=torch.float32, device=dev)[: csr.nnz]

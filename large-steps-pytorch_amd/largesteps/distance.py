@@ -118,13 +118,6 @@ def _on(x, device):
     return torch.from_numpy(x).to(device)
 
 
-def _workspace(size_fn_name, *sizes, device):
-    """a uint8 buffer on `device` of as many bytes as the native size function of that name asks for `sizes`"""
-    c = ctypes.c_size_t(0)
-    _native.check(getattr(_native.lib(), size_fn_name)(*sizes, ctypes.byref(c)))
-    return torch.empty(c.value, dtype=torch.uint8, device=device)
-
-
 @_native.retry_on_oom
 def _gradients(m, p, I, C, g, need_p, need_v):
     """(gP or None, gV or None) of one backward pass: its allocations and the native call"""
@@ -257,7 +250,7 @@ class MeshDistance:
             return None, None, None, None
         gV = torch.empty_like(self.V)
         vptr, order = self._corner_ranks()
-        return gV, vptr, order, _workspace(size_fn_name, n, self._f.shape[0], device=self.device)
+        return gV, vptr, order, _native.workspace(size_fn_name, (n, self._f.shape[0]), self.device)
 
     def _corner_ranks(self):
         """(vptr, rank -> corner) of the faces, the summation order of the gradient to V (largesteps.normals._plan)"""
@@ -320,7 +313,7 @@ class MeshDistance:
         """the moment buffer of the winding walk, prepared on the first winding query after construction or `update`"""
         if self._wn_version != self._version:
             if self._wn is None:
-                self._wn = _workspace("ls_mesh_winding_bytes", self._f.shape[0], device=self.device)
+                self._wn = _native.workspace("ls_mesh_winding_bytes", (self._f.shape[0],), self.device)
             self._call("ls_mesh_winding_prepare", _native.ptr(self._wn))
             self._wn_version = self._version
         return self._wn
@@ -407,7 +400,7 @@ class MeshDistance:
         k = int(total)
         pairs = torch.empty((k, 2), dtype=torch.int64, device=self.device)
         if k:
-            ws = _workspace("ls_mesh_selfx_workspace_bytes", self._f.shape[0], k, device=self.device)
+            ws = _native.workspace("ls_mesh_selfx_workspace_bytes", (self._f.shape[0], k), self.device)
             self._call("ls_mesh_selfx_pairs", _native.ptr(counts), k, _native.ptr(pairs), _native.ptr(ws), ws.numel())
         return pairs.cpu().numpy() if self._numpy else pairs
 

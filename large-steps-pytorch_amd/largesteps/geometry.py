@@ -38,10 +38,9 @@ def _assemble(verts, faces, kind, a, b):
             raise ValueError(f"verts must have shape (V, 3), got {tuple(verts.shape)}")
         verts_c = verts.detach().to(torch.float32).contiguous()
     lib = _native.lib()
-    nbytes = ctypes.c_size_t(0)
-    _native.check(lib.ls_assemble_workspace_bytes(V, F, ctypes.byref(nbytes)))
+    nbytes = _native.workspace_bytes("ls_assemble_workspace_bytes", (V, F))
     with torch.cuda.device(dev):
-        ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+        ws = _native.workspace("ls_assemble_workspace_bytes", (V, F), dev, nbytes=max(nbytes, 1))
         rowptr = torch.empty(V + 1, dtype=torch.int32, device=dev)
         nnz = ctypes.c_int64(0)
         st = _native.stream_of(dev)

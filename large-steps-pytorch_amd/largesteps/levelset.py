@@ -39,7 +39,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _native
-from .distance import MeshDistance, _as_beta, _as_faces, _as_points, _current_device, _workspace
+from .distance import MeshDistance, _as_beta, _as_faces, _as_points, _current_device
 
 
 def _fits(shape):
@@ -110,7 +110,7 @@ class _Isosurface(Function):
         nx, ny, nz = s.shape
         lib = _native.lib()
         with torch.cuda.device(dev):
-            ws = _workspace("ls_iso_workspace_bytes", nx, ny, nz, device=dev)
+            ws = _native.workspace("ls_iso_workspace_bytes", (nx, ny, nz), dev)
             totals = torch.empty(2, dtype=torch.int64, device=dev)
             _native.check(lib.ls_iso_count(_native.ptr(s), nx, ny, nz, iso, _native.ptr(ws), ws.numel(), _native.ptr(totals), dev.index,
                                            _native.stream_of(dev)))

@@ -51,9 +51,7 @@ def remove_duplicates(v, f):
     vc, fc = v.detach().contiguous(), f.contiguous()
     V, F, dev = vc.shape[0], fc.shape[0], vc.device
     lib = _native.lib()
-    n = ctypes.c_size_t(0)
-    _native.check(lib.ls_remove_duplicates_workspace_bytes(V, ctypes.byref(n)))
-    ws = torch.empty(n.value, dtype=torch.uint8, device=dev)
+    ws = _native.workspace("ls_remove_duplicates_workspace_bytes", (V,), dev)
     unique = torch.empty((V, 3), dtype=torch.float32, device=dev)
     inverse = torch.empty(V, dtype=torch.int64, device=dev)
     new_faces = torch.empty((F, 3), dtype=torch.int64, device=dev)

@@ -33,9 +33,7 @@ def _plan(f, V):
     if plan is not None:
         return plan
     F = f.shape[0]
-    n = ctypes.c_size_t(0)
-    _native.check(_native.lib().ls_corner_ranks_workspace_bytes(F, V, ctypes.byref(n)))
-    ws = torch.empty(n.value, dtype=torch.uint8, device=f.device)
+    ws = _native.workspace("ls_corner_ranks_workspace_bytes", (F, V), f.device)
     vcorner = torch.empty(max(3 * F, 1), dtype=torch.int32, device=f.device)[: 3 * F]     # corner -> rank ("cpos" of the C ABI)
     vptr = torch.empty(V + 1, dtype=torch.int32, device=f.device)
     with torch.cuda.device(f.device):                  # range check + counting + stable radix sort by vertex id, all native
@@ -73,12 +71,10 @@ def _workspace_of(size_fn):
     def workspace(F, V, dev):
         n = known.get((F, V))
         if n is None:
-            c = ctypes.c_size_t(0)
-            _native.check(getattr(_native.lib(), size_fn)(F, V, ctypes.byref(c)))
             if len(known) > 64:
                 known.clear()
-            n = known[(F, V)] = c.value
-        return torch.empty(n, dtype=torch.uint8, device=dev)
+            n = known[(F, V)] = _native.workspace_bytes(size_fn, (F, V))
+        return _native.workspace(size_fn, (F, V), dev, nbytes=n)
     return workspace
 
 

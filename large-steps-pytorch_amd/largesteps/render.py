@@ -97,13 +97,6 @@ def _faces(tri, V):
     return f, narrow, vptr, order
 
 
-def _scratch(dev, size_fn, *shape):
-    """the workspace whose size the native `size_fn` gives for `shape`"""
-    n = ctypes.c_size_t(0)
-    _native.check(size_fn(*shape, ctypes.byref(n)))
-    return torch.empty(n.value, dtype=torch.uint8, device=dev)
-
-
 def _plain(t, align):
     """detached, contiguous and aligned for the kernels' vector loads (float2 / float4 rows: torch's allocations are 256-byte aligned, a
     view into one need not be); None stays None"""
@@ -118,7 +111,7 @@ def _adjacent(f, narrow):
     adj = _adjacency.get(f)
     if adj is None:
         F, dev = narrow.shape[0], f.device
-        ws = _scratch(dev, _native.lib().ls_raster_adjacency_workspace_bytes, F)
+        ws = _native.workspace("ls_raster_adjacency_workspace_bytes", (F,), dev)
         adj = torch.empty(max(3 * F, 1), dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
             _native.check(_native.lib().ls_raster_adjacency(_native.ptr(narrow), F, _native.ptr(adj), _native.ptr(ws), ws.numel(), dev.index,
@@ -164,7 +157,7 @@ class _RangeTable:
         adj = self.adj.get(f)
         if adj is None:
             dev = self.dev.device
-            ws = _scratch(dev, _native.lib().ls_range_adjacency_workspace_bytes, self.N)
+            ws = _native.workspace("ls_range_adjacency_workspace_bytes", (self.N,), dev)
             adj = torch.empty(max(3 * self.N, 1), dtype=torch.int32, device=dev)
             with torch.cuda.device(dev):
                 _native.check(_native.lib().ls_range_adjacency(_native.ptr(narrow), narrow.shape[0], _native.ptr(self.dev), self.B, self.N,
@@ -251,9 +244,7 @@ class _InstancedFrame(_Frame):
         return p.shape[0]
 
     def workspace(self, B, H, W, C, dev):
-        n = ctypes.c_size_t(0)
-        _native.check(_native.lib().ls_raster_workspace_bytes(B, self.F, H, W, C, ctypes.byref(n)))
-        return torch.empty(n.value, dtype=torch.uint8, device=dev)
+        return _native.workspace("ls_raster_workspace_bytes", (B, self.F, H, W, C), dev)
 
     def sort_pixels(self, r, B, H, W, order, seg, ws, dev):
         _native.check(_native.lib().ls_raster_pixel_order(_native.ptr(r), B, self.F, H, W, _native.ptr(order), _native.ptr(seg), _native.ptr(ws),
@@ -324,9 +315,7 @@ class _RangeFrame(_Frame):
         return self.tab.adjacency(f, narrow)
 
     def workspace(self, B, H, W, C, dev):
-        n = ctypes.c_size_t(0)
-        _native.check(_native.lib().ls_range_workspace_bytes(B, self.tab.N, H, W, C, ctypes.byref(n)))
-        return torch.empty(n.value, dtype=torch.uint8, device=dev)
+        return _native.workspace("ls_range_workspace_bytes", (B, self.tab.N, H, W, C), dev)
 
     def sort_pixels(self, r, B, H, W, order, seg, ws, dev):
         tab = self.tab
@@ -840,7 +829,7 @@ class _Order:
             tensors, conf = args[:kind.tensors], args[kind.tensors:]
             B, H, W, _ = tensors[0].shape
             dev = tensors[0].device
-            ws = _scratch(dev, getattr(lib, kind.workspace), B, H, W)
+            ws = _native.workspace(kind.workspace, (B, H, W), dev)
             order = torch.empty(kind.items(*conf) * B * H * W, dtype=torch.int32, device=dev)
             seg = torch.empty(kind.nkeys(*conf) + 1, dtype=torch.int32, device=dev)
             with torch.cuda.device(dev):

@@ -41,7 +41,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _native
-from .distance import _as_faces, _as_points, _current_device, _on, _workspace
+from .distance import _as_faces, _as_points, _current_device, _on
 from .normals import _plan
 
 SCAN_TILE = 2048            # LS_SAMPLE_SCAN_TILE of the header: the faces one workgroup of the 64-bit scan owns
@@ -63,7 +63,7 @@ def _forward(v, f, n, seed, stream, offset):
     I = torch.empty(n, dtype=torch.int64, device=dev)
     W = torch.empty((n, 3), dtype=torch.float32, device=dev)
     if n:
-        ws = _workspace("ls_sample_workspace_bytes", f.shape[0], n, device=dev)
+        ws = _native.workspace("ls_sample_workspace_bytes", (f.shape[0], n), dev)
         with torch.cuda.device(dev):
             _native.check(_native.lib().ls_sample_surface(_native.ptr(v), _native.ptr(f), f.element_size(), f.shape[0], v.shape[0], n, seed, stream,
                                                           offset, _native.ptr(P), _native.ptr(I), _native.ptr(W), _native.ptr(ws), ws.numel(),
@@ -78,7 +78,7 @@ def _backward(f, nv, I, W, gP):
         return torch.zeros((nv, 3), dtype=torch.float32, device=dev)
     gV = torch.empty((nv, 3), dtype=torch.float32, device=dev)
     vptr, _, _, order = _plan(f, nv)
-    ws = _workspace("ls_sample_workspace_bytes", f.shape[0], n, device=dev)
+    ws = _native.workspace("ls_sample_workspace_bytes", (f.shape[0], n), dev)
     gP = gP.to(torch.float32).contiguous()
     with torch.cuda.device(dev):
         _native.check(_native.lib().ls_sample_surface_backward(_native.ptr(f), f.element_size(), f.shape[0], nv, n, _native.ptr(I), _native.ptr(W),

@@ -15,7 +15,7 @@ sys.path[:0] = [_R, os.path.join(_R, "large-steps-pytorch_amd")]
 import numpy as np
 import torch
 from largesteps import _native, synthetic
-from largesteps.distance import MeshDistance, _workspace
+from largesteps.distance import MeshDistance
 
 out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(_R, "profiles", "distance_grad_bench.json")
 repeats = int(sys.argv[2]) if len(sys.argv) > 2 else 10
@@ -120,7 +120,7 @@ for w in workloads:
     with MeshDistance(V, F) as m:
         sqrD, I, C = m.squared_distance(P)
         vptr, order = m._corner_ranks()
-        ws = _workspace("ls_mesh_distance_backward_workspace_bytes", n, F.shape[0], device=dev)
+        ws = _native.workspace("ls_mesh_distance_backward_workspace_bytes", (n, F.shape[0]), dev)
         gP, gV = torch.empty_like(P), torch.empty_like(V)
 
         def backward(gp, gv):

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 from largesteps import _native, synthetic
 from largesteps.normals import _plan
-from largesteps.sampling import _workspace, sample_surface
+from largesteps.sampling import sample_surface
 
 out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(_R, "profiles", "sample_bench.json")
 repeats = int(sys.argv[2]) if len(sys.argv) > 2 else 10
@@ -98,7 +98,7 @@ for spec in workloads:
     W = torch.empty((n, 3), dtype=torch.float32, device=dev)
     gP = torch.randn((n, 3), dtype=torch.float32, device=dev)
     gV = torch.empty_like(V)
-    ws = _workspace("ls_sample_workspace_bytes", nF, n, device=dev)
+    ws = _native.workspace("ls_sample_workspace_bytes", (nF, n), dev)
     vptr, _, _, order = _plan(F, nV)
 
     def forward():

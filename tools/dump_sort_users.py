@@ -17,7 +17,10 @@ point's weights, max_squared_distance, RayMesh.intersect with its three gradient
 the hierarchy and the node moments, signed_distance with its gradients, sample_surface with its vertex gradient, chamfer_distance
 with both gradients, and the distance again after one update. The query points are 2^16 surface samples pushed along the normal to
 both sides with a share uniform in the grown box, and 1024 more around one face's centroid, so that some face owns more than 64 points
-and some face between 1 and 64 (asserted): both arms of the segmented sum again."""
+and some face between 1 and 64 (asserted): both arms of the segmented sum again.
+With the pairs of self_intersections on two icospheres that cross, the isosurface of a noisy ball on a 24^3 grid with its gradient in
+the field, and massmatrix_voronoi and average_edge_length with their gradients, every entry point that carves a caller's workspace
+(csrc/workspace.h) is in the comparison; the handle's own buffer and the bisection's are under the mesh queries and the direct solve."""
 import os
 import sys
 
@@ -292,6 +295,26 @@ def dump(out):
     gA, gB = grads(ch, Vg, VB)
     save("chamfer", ch), save("chamfer_grad_VA", gA), save("chamfer_grad_VB", gB)
     del ch, Sd, sqrD, t
+
+    # ---- the remaining caller workspaces: the pairs of two icospheres that cross, the level set of a noisy ball with its gradient in
+    # the field, the two mesh-geometry functions with their gradients
+    from largesteps.distance import self_intersections
+    from largesteps.levelset import isosurface
+    from largesteps.meshops import average_edge_length, massmatrix_voronoi
+
+    vx, fx = synthetic.icosphere(8)
+    pairs = self_intersections(dev_f32(np.concatenate([vx, vx + np.array([0.7, 0.1, 0.05])])), torch.from_numpy(np.concatenate([fx, fx + vx.shape[0]])).to(dev))
+    assert pairs.shape[0] > 64, "the two spheres must cross"
+    save("selfx_pairs", pairs)
+    ax = np.linspace(-1.0, 1.0, 24)
+    ball = np.sqrt(ax[:, None, None] ** 2 + ax[None, :, None] ** 2 + ax[None, None, :] ** 2) - 0.6 + 0.02 * rng.standard_normal((24, 24, 24))
+    field = dev_f32(ball).requires_grad_(True)
+    IV, IF, IE = isosurface(field, 0.0, (-1.0, -1.0, -1.0), 2.0 / 23.0, return_edges=True)
+    assert IV.shape[0] > 0 and IF.shape[0] > 0
+    save("iso_V", IV), save("iso_F", IF), save("iso_E", IE), save("iso_grad_S", grads((IV * weights(IV)).sum(), field)[0])
+    mass, ael = massmatrix_voronoi(Vg, tf), average_edge_length(Vg, tf)
+    save("meshgeom_mass", mass), save("meshgeom_mass_grad_V", grads((mass * weights(mass)).sum(), Vg)[0])
+    save("meshgeom_edge_length", ael), save("meshgeom_edge_length_grad_V", grads(ael.sum(), Vg)[0])
 
     torch.cuda.synchronize()
     print(f"wrote {len(os.listdir(out))} files to {out} with {os.environ.get('LARGESTEPS_HIP_LIB', 'the package library')}")
