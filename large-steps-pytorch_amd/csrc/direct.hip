@@ -772,9 +772,19 @@ __global__ __launch_bounds__(64) void k_nd_down_p(const PackedTile* __restrict__
 // and measured in round 3: 166-207 us against 103-120 us for nine launches at 1M vertices. Archived: tools/archive/lab/.)
 namespace ls {
 
-// down tiles of a level: compute tiles, then forward tiles
-struct LevelPlan { int up_first = 0, up_tiles = 0, up_nw = 1, down_first = 0, down_tiles = 0, down_nw = 1, s_cap = 0, b_cap = 0, up_b = 0, down_b = 0, up_chunks = 1, down_chunks = 1, up_s = 0,
-                   up_p = 0, down_p = 0, up_p_first = 0, up_p_tiles = 0, down_p_first = 0, down_p_tiles = 0, up_p_lds = 0, down_p_s = 0, down_p_lds = 0; };
+// One launch of a solve. The handle keeps them in execution order (ls_direct::launches, built once by ls_direct_create): the solve, the
+// launch count, the index-byte accounting and the launch profile all walk that list. Kinds from UP_P to DOWN are one tree level above
+// the tier each (plan_level chooses them); the tier is one launch per sweep.
+enum LaunchKind { TIER_UP, UP_P, UP_S, UP_B, UP, DOWN_P, DOWN_B, DOWN, TIER_DOWN };   // _P packed tiles, _S staged W, _B lanes along the reduction, plain: a row per lane
+struct Launch {
+    LaunchKind kind = UP;
+    int sweep = 0, lo = 0, hi = 0;          // sweep 0 up, 1 down; the tree levels [lo, hi] it runs
+    int grid = 0, block = WAVE;             // grid: tiles (level kernels) or subtrees (tier); 0 = nothing to launch
+    size_t lds_col = 0, lds_fix = 0;        // dynamic LDS: lds_col * K + lds_fix bytes
+    int first = 0;                          // first tile: of ptiles (_P kinds) or of tiles. Down tiles of a level: compute tiles, then forward tiles
+    int s_cap = 0, b_cap = 0, chunks = 1, down_p_s = 0;
+    bool root_fill = false;                 // the root's down launch forms b' itself: the root has no up launch
+};
 
 }  // namespace ls
 
@@ -826,15 +836,17 @@ struct ls_direct {
     bool nt_levels = false, nt_tier = false, nt_rule[2] = {false, false};
     double factor_s[3] = {0, 0, 0};     // ls_direct_factor: symbolic analysis, layout / sparse tables, numeric factorisation
     double plan_q[4] = {0, 0, 0, 0};    // ls_direct_factor: the dissection's ordering rule, factor numbers per vertex, spread, the other plan's numbers (nd_plan.h)
-    std::vector<LevelPlan> plan;
+    // every launch of a solve in execution order: the up sweep [0, n_up) -- tier, then the levels above it from the deepest to the
+    // root -- and the down sweep, root first, tier last. Part 0 of a sharded solve is [0, part_cut), part 1 the rest.
+    std::vector<Launch> launches;
+    int n_up = 0, part_cut = 0;
     int64_t factor_entries = 0, words_up = 0, words_down = 0;    // 4-byte words of factor data per solve / per sweep
     int profile = 0;
     std::vector<hipEvent_t> ev;
     // "profile" = 3: one event in front of every launch of a solve (+ one behind the last)
-    struct LaunchMeta { int lo, hi, sweep; };         // tree levels [lo, hi] the launch runs; sweep 0 up, 1 down, 2 both
     std::vector<hipEvent_t> lev;
-    std::vector<LaunchMeta> lmeta;
-    std::vector<double> launch_ms;
+    std::vector<double> launch_ms;                    // of launches[prof_first ...]: the last profiled solve or part
+    int prof_first = 0;
     std::vector<int64_t> lvl_up, lvl_down;            // 4-byte words of factor data per tree level and sweep
     std::vector<int64_t> lvl_rows, lvl_bnd;           // own rows / boundary entries per tree level (the vectors' share of a launch's bytes)
     std::vector<int64_t> lvl_idx_up, lvl_idx_down;    // bytes of STATIC index data a level's launch reads per sweep besides perm: tile / item records, mask, ppos, pull, push lists
@@ -1059,7 +1071,6 @@ static size_t plan_tier(const std::vector<NodeD>& nd, const std::vector<int64_t>
     return (size_t)std::max(vec_floats + pbuf_need, leaf_need);
 }
 
-
 // Host only: the dynamic LDS in bytes a tier workgroup of `waves` waves needs for this tree (0 = the tier cannot be planned). Exported as
 // ls_direct_tier_lds_bytes: the CPU tests hold the 1M-vertex closed scan against the 160 KB of a CU with it (round 6: its leaves' 83 boundary
 // rows once made the 16-wave plan 2668 floats per wave -- 4 % over -- and the solve fell back, silently, to 11 launches).
@@ -1115,7 +1126,6 @@ bool direct_tier_full16(int64_t V, int arity, int levels, int tier_levels, int s
     if (tier_waves == TIER_WAVES || tier_waves == TIER_WAVES_WIDE) return false;
     return shard_count <= 1 && arity == 4 && levels >= 8 && V >= 800000 && tier_levels == levels - 4 && tier_levels <= TIER_MAX_H;
 }
-
 
 // ---- ls_direct_create's host stages (no device call): the caller's tree (nodes by id, 1-based, level-major), this rank's share of
 // the subtrees of level `cut`, and the tables they build for the upload
@@ -1268,8 +1278,9 @@ int choose_tier(CreatePlan& T, const int32_t* h_ppos, int tier_waves, const NdEn
     return LS_OK;
 }
 
-// One level above the tier: kernel shapes, tiles and packed tiles of this rank's nodes. Returns the LDS bytes its front needs.
-size_t plan_level(CreatePlan& T, int lv, int long_up, const NdEnv& env, int kmax, LevelPlan& p) {
+// One level above the tier: which kernel runs each sweep of this rank's nodes, its launch record (grid 0: nothing to launch) and the
+// tiles of that kernel -- and of no other. Returns the LDS bytes the level's front needs.
+size_t plan_level(CreatePlan& T, int lv, int long_up, const NdEnv& env, int kmax, Launch& up, Launch& down) {
     std::vector<Tile>& tiles = T.tiles;
     // this rank's nodes of the level: one contiguous range (all of them above the cut)
     int64_t a0 = T.level_off[lv], a1 = T.level_off[lv + 1];
@@ -1282,13 +1293,30 @@ size_t plan_level(CreatePlan& T, int lv, int long_up, const NdEnv& env, int kmax
         t.forward = forward; t.arity = T.arity; t.finv_off = n.finv_off; t.w_off = n.w_off;
         return t;
     };
-    int red_up = 0, red_down = 0;
+    int s_cap = 0, b_cap = 0, red_down = 0;
+    int64_t rows_up = 0, rows_down = 0;
     for (int64_t i = a0; i < a1; ++i) {
-        p.s_cap = std::max(p.s_cap, T.nd[i].s); p.b_cap = std::max(p.b_cap, T.nd[i].b);
-        red_up = std::max(red_up, T.nd[i].s); red_down = std::max(red_down, T.nd[i].s + T.nd[i].b);
+        s_cap = std::max(s_cap, T.nd[i].s); b_cap = std::max(b_cap, T.nd[i].b); red_down = std::max(red_down, T.nd[i].s + T.nd[i].b);
+        rows_up += T.nd[i].b; rows_down += T.nd[i].s;
     }
-    // long reductions: lanes along the reduction (k_nd_*_b), ND_ROWS * ND_BW rows per tile; short: a row per lane
-    p.up_b = red_up >= long_up; p.down_b = red_down >= env.long_red;
+    const int red_up = s_cap;
+    // The kind of each sweep, first match:
+    //  * tiny nodes: several nodes per wave (packed tiles), when at least two nodes of the level fit a wave. Largest row count of a
+    //    level that is still packed: a wave up, half a wave down (measured at 1M: packing pairs of ~31-row leaves helps the up
+    //    sweep, 42 -> 37 us, while packed down tiles only pay below half a wave);
+    //  * small nodes, up sweep: the whole W staged in 40 KB of LDS at most, one workgroup per node, a row per thread
+    //    (measured at 1M: staging pays for the up sweep -- W only, 42 + 18 + 15 us against 45 + 21 + 17 -- but not for the
+    //    down sweep, whose Finv + W footprint left 6 single-wave workgroups per CU: 151 us against 57: the down sweep has no staged kernel);
+    //  * long reductions: lanes along the reduction (k_nd_*_b), ND_ROWS * ND_BW rows per tile; short: a row per lane.
+    // The root's down tiles of the last two kinds form b' themselves (RootFill): such a root has no up launch and no up tiles.
+    down.kind = !env.no_pack && s_cap <= WAVE / 2 ? DOWN_P : red_down >= env.long_red ? DOWN_B : DOWN;
+    down.root_fill = lv == 0 && down.kind != DOWN_P;
+    const size_t up_s_bytes = ((size_t)s_cap * b_cap + (size_t)s_cap * kmax) * sizeof(float);
+    up.kind = !env.no_pack && b_cap <= WAVE && s_cap <= 256 && lv > 0 ? UP_P
+            : b_cap <= 256 && s_cap <= 256 && up_s_bytes <= 40 * 1024 && !env.no_small ? UP_S
+            : red_up >= long_up ? UP_B : UP;
+    up.sweep = 0; down.sweep = 1; up.lo = up.hi = down.lo = down.hi = lv;
+    up.s_cap = down.s_cap = s_cap; up.b_cap = down.b_cap = b_cap;
     // *_b kernels, shape per level (measured at 1M vertices, profiles/r03_level_kernel_variants.txt):
     //  * every tile assembles its node's whole reduction vector -- long vectors (the top levels: 2000 entries, four 16-byte slot
     //    records each) want FEW, FAT workgroups: 8 waves from ~1400 entries on (root 15.0 -> 13.9 us, level 1 15.2 -> 14.3 / 17.3 -> 16.3);
@@ -1297,31 +1325,20 @@ size_t plan_level(CreatePlan& T, int lv, int long_up, const NdEnv& env, int kmax
     // (round 5, docs/measurements.md: 900 or 2100 entries for 8 waves, 250 or 1000 tiles per level: up to 3 % slower at 1M and 4M)
     const int up_bw = std::min(ND_BW, red_up >= 1400 ? 8 : 4), down_bw = std::min(ND_BW, red_down >= 1400 ? 8 : 4);
     // (the row-per-lane up kernel: 32 reduction steps per wave; 16 or 64 cost 3-13 % of a 1M-vertex solve, round 5)
-    p.up_nw = p.up_b ? up_bw : pick_nw(red_up, 32); p.down_nw = p.down_b ? down_bw : pick_nw(red_down, env.steps);
-    int64_t rows_up = 0, rows_down = 0;
-    for (int64_t i = a0; i < a1; ++i) { rows_up += T.nd[i].b; rows_down += T.nd[i].s; }
+    const int up_nw = up.kind == UP_S ? std::max(1, div_up(b_cap, WAVE)) : up.kind == UP_B ? up_bw : pick_nw(red_up, 32);
+    const int down_nw = down.kind == DOWN_B ? down_bw : pick_nw(red_down, env.steps);
     auto pick_chunks = [&](int64_t rows, int bw) {
         int c = 4;
         while (c > 1 && rows / (ND_ROWS * bw * c) < 500) --c;
         return c;
     };
-    p.up_chunks = pick_chunks(rows_up, up_bw);
-    p.down_chunks = pick_chunks(rows_down, down_bw);
-    const int up_rows = p.up_b ? ND_ROWS * up_bw * p.up_chunks : WAVE, down_rows = p.down_b ? ND_ROWS * down_bw * p.down_chunks : WAVE;
-    // small nodes, up sweep: the whole W staged in 40 KB of LDS at most, one workgroup per node, a row per thread
-    // (measured at 1M: staging pays for the up sweep -- W only, 42 + 18 + 15 us against 45 + 21 + 17 -- but not for the
-    //  down sweep, whose Finv + W footprint left 6 single-wave workgroups per CU: 151 us against 57: the down sweep has no staged kernel)
-    const size_t up_s_bytes = ((size_t)p.s_cap * p.b_cap + (size_t)p.s_cap * kmax) * sizeof(float);
-    p.up_s = p.b_cap <= 256 && p.s_cap <= 256 && up_s_bytes <= 40 * 1024 && !env.no_small;
-    if (p.up_s) { p.up_b = 0; p.up_nw = std::max(1, div_up(p.b_cap, WAVE)); }
-    // tiny nodes: several nodes per wave (packed tiles), when at least two nodes of the level fit a wave. Largest row count of a
-    // level that is still packed: a wave up, half a wave down (measured at 1M: packing pairs of ~31-row leaves helps the up
-    // sweep, 42 -> 37 us, while packed down tiles only pay below half a wave)
-    p.up_p = !env.no_pack && p.b_cap <= WAVE && p.s_cap <= 256 && lv > 0;
-    p.down_p = !env.no_pack && p.s_cap <= WAVE / 2;
-    auto pack_level = [&](bool up_sweep, int& first, int& count, int& lds_rows_s, int& lds_rows_b) {
-        first = (int)T.ptiles.size();
-        lds_rows_s = lds_rows_b = 0;
+    up.chunks = pick_chunks(rows_up, up_bw);
+    down.chunks = pick_chunks(rows_down, down_bw);
+    const size_t f4 = sizeof(float);
+    // the packed tiles of one sweep; their LDS holds the most own rows one of them has, in the down sweep the most boundary rows too
+    auto pack_level = [&](bool up_sweep, Launch& L) {
+        L.first = (int)T.ptiles.size();
+        int lds_rows_s = 0, lds_rows_b = 0;
         int64_t i = a0;
         while (i < a1) {
             PackedTile t;
@@ -1344,28 +1361,9 @@ size_t plan_level(CreatePlan& T, int lv, int long_up, const NdEnv& env, int kmax
             lds_rows_s = std::max(lds_rows_s, t.sb0[t.n]); lds_rows_b = std::max(lds_rows_b, t.sx0[t.n]);
             T.ptiles.push_back(t);
         }
-        count = (int)T.ptiles.size() - first;
+        L.grid = (int)T.ptiles.size() - L.first; L.block = WAVE; L.down_p_s = lds_rows_s;
+        L.lds_col = (size_t)std::max(up_sweep ? lds_rows_s : lds_rows_s + lds_rows_b, 1) * f4;
     };
-    int dummy = 0;
-    if (p.up_p) { pack_level(true, p.up_p_first, p.up_p_tiles, p.up_p_lds, dummy); p.up_s = 0; p.up_b = 0; }
-    if (p.down_p) { pack_level(false, p.down_p_first, p.down_p_tiles, p.down_p_s, p.down_p_lds); p.down_b = 0; }
-    p.up_first = (int)tiles.size();
-    const int up_threads = WAVE * p.up_nw;
-    std::vector<int> up_nodes;                                 // node (index within the level) of every tile pushed below
-    for (int64_t i = a0; i < a1; ++i) {
-        // b' of the own rows is kept for the down sweep: by the first compute tile (small nodes, or nodes whose only
-        // tile exists for that purpose), or by store-only tiles of blockDim rows each (large nodes: the one tile
-        // would walk s / blockDim dependent load chains)
-        const bool store_tiles = !p.up_s && T.nd[i].s > 2 * up_threads;
-        const int rows = std::max(T.nd[i].b, (T.nd[i].s && !store_tiles) ? 1 : 0);
-        for (int r = 0; r < rows; r += (p.up_s ? 1 << 30 : up_rows)) {
-            tiles.push_back(tile_of(i, r, 0));
-            tiles.back().store = (r == 0 && !store_tiles) ? 1 : 0;
-            up_nodes.push_back((int)(i - a0));
-        }
-        if (store_tiles)
-            for (int r = 0; r < T.nd[i].s; r += up_threads) { tiles.push_back(tile_of(i, r, 0)); tiles.back().store = 2; up_nodes.push_back((int)(i - a0)); }
-    }
     // XCD-aware order: workgroup b runs on XCD b % 8 (observed placement, speed only) and every tile of a node re-assembles the node's
     // reduction vector (slots, masks, b) -- with a node's tiles on ONE XCD those reads hit that XCD's L2 instead of being fetched once per
     // XCD (PMC, round 3: 55 MB per launch of the row-per-lane up kernel for 29 MB of factor). Levels with fewer than 8 nodes keep the
@@ -1384,18 +1382,48 @@ size_t plan_level(CreatePlan& T, int lv, int long_up, const NdEnv& env, int kmax
         for (size_t r = 0; r < longest; ++r)
             for (int x = 0; x < 8; ++x) tiles.push_back(r < bucket[(size_t)x].size() ? bucket[(size_t)x][r] : idle);
     };
-    xcd_order(p.up_first, up_nodes);
-    p.up_tiles = (int)tiles.size() - p.up_first;
-    p.down_first = (int)tiles.size();
-    std::vector<int> down_nodes;
-    for (int64_t i = a0; i < a1; ++i)
-        for (int r = 0; r < T.nd[i].s; r += down_rows) { tiles.push_back(tile_of(i, r, 0)); down_nodes.push_back((int)(i - a0)); }
-    if (lv + 1 < T.levels)      // forward tiles: boundary rows of every node
+    if (up.kind == UP_P) pack_level(true, up);
+    else if (!down.root_fill) {
+        const bool staged = up.kind == UP_S;
+        const int up_threads = WAVE * up_nw, up_rows = staged ? 1 << 30 : up.kind == UP_B ? ND_ROWS * up_bw * up.chunks : WAVE;
+        up.first = (int)tiles.size();
+        std::vector<int> up_nodes;                             // node (index within the level) of every tile pushed below
+        for (int64_t i = a0; i < a1; ++i) {
+            // b' of the own rows is kept for the down sweep: by the first compute tile (small nodes, or nodes whose only
+            // tile exists for that purpose), or by store-only tiles of blockDim rows each (large nodes: the one tile
+            // would walk s / blockDim dependent load chains)
+            const bool store_tiles = !staged && T.nd[i].s > 2 * up_threads;
+            const int rows = std::max(T.nd[i].b, (T.nd[i].s && !store_tiles) ? 1 : 0);
+            for (int r = 0; r < rows; r += up_rows) {
+                tiles.push_back(tile_of(i, r, 0));
+                tiles.back().store = (r == 0 && !store_tiles) ? 1 : 0;
+                up_nodes.push_back((int)(i - a0));
+            }
+            if (store_tiles)
+                for (int r = 0; r < T.nd[i].s; r += up_threads) { tiles.push_back(tile_of(i, r, 0)); tiles.back().store = 2; up_nodes.push_back((int)(i - a0)); }
+        }
+        xcd_order(up.first, up_nodes);
+        up.grid = (int)tiles.size() - up.first; up.block = WAVE * up_nw;
+        if (staged) { up.lds_col = (size_t)s_cap * f4; up.lds_fix = (size_t)s_cap * b_cap * f4; }
+        else if (up.kind == UP_B) { up.lds_col = (size_t)s_cap * f4; up.lds_fix = 16 * f4; }
+        else up.lds_col = ((size_t)s_cap + (size_t)(up_nw - 1) * WAVE) * f4;
+    }
+    if (down.kind == DOWN_P) pack_level(false, down);
+    else {
+        const int down_rows = down.kind == DOWN_B ? ND_ROWS * down_bw * down.chunks : WAVE;
+        down.first = (int)tiles.size();
+        std::vector<int> down_nodes;
         for (int64_t i = a0; i < a1; ++i)
-            for (int r = 0; r < T.nd[i].b; r += WAVE * p.down_nw) { tiles.push_back(tile_of(i, r, 1)); down_nodes.push_back((int)(i - a0)); }
-    xcd_order(p.down_first, down_nodes);
-    p.down_tiles = (int)tiles.size() - p.down_first;
-    return ((size_t)p.s_cap + p.b_cap + 16 * WAVE) * kmax * sizeof(float);
+            for (int r = 0; r < T.nd[i].s; r += down_rows) { tiles.push_back(tile_of(i, r, 0)); down_nodes.push_back((int)(i - a0)); }
+        if (lv + 1 < T.levels)      // forward tiles: boundary rows of every node
+            for (int64_t i = a0; i < a1; ++i)
+                for (int r = 0; r < T.nd[i].b; r += WAVE * down_nw) { tiles.push_back(tile_of(i, r, 1)); down_nodes.push_back((int)(i - a0)); }
+        xcd_order(down.first, down_nodes);
+        down.grid = (int)tiles.size() - down.first; down.block = WAVE * down_nw;
+        if (down.kind == DOWN_B) { down.lds_col = ((size_t)s_cap + b_cap) * f4; down.lds_fix = 32 * f4; }
+        else down.lds_col = ((size_t)s_cap + b_cap + (size_t)(down_nw - 1) * WAVE) * f4;
+    }
+    return ((size_t)s_cap + b_cap + 16 * WAVE) * kmax * sizeof(float);
 }
 
 // the static index bytes of every level's launches, and how evenly the tier's subtrees are loaded
@@ -1406,14 +1434,15 @@ void account_index_bytes(const CreatePlan& T, ls_direct* d) {
     for (int lv = 0; lv < levels; ++lv)
         for (int64_t i = T.level_off[lv]; i < T.level_off[lv + 1]; ++i)
             if (T.active(i, lv)) { fpos[(size_t)lv] += T.nd[i].s + T.nd[i].b; bsum[(size_t)lv] += T.nd[i].b; }
+    // up: tile records, the children mask of every front position, the parent positions of the boundary rows (+ perm when no
+    // tier launch gathered b into the tree's numbering); down: tile records, row pointers of the push lists, the children's targets
     for (int lv = 0; lv < d->tier_root; ++lv) {
-        const LevelPlan& p = d->plan[lv];
-        // up: tile records, the children mask of every front position, the parent positions of the boundary rows (+ perm when no
-        // tier launch gathered b into the tree's numbering); down: tile records, row pointers of the push lists, the children's targets
-        d->lvl_idx_up[(size_t)lv] = (p.up_p ? (int64_t)p.up_p_tiles * (int64_t)sizeof(PackedTile) : (int64_t)p.up_tiles * (int64_t)sizeof(Tile)) + fpos[(size_t)lv] + 4 * bsum[(size_t)lv];
-        d->lvl_idx_down[(size_t)lv] = (p.down_p ? (int64_t)p.down_p_tiles * (int64_t)sizeof(PackedTile) : (int64_t)p.down_tiles * (int64_t)sizeof(Tile)) + 4 * fpos[(size_t)lv] +
-                                      4 * bsum[(size_t)lv + 1];
+        d->lvl_idx_up[(size_t)lv] = fpos[(size_t)lv] + 4 * bsum[(size_t)lv];
+        d->lvl_idx_down[(size_t)lv] = 4 * fpos[(size_t)lv] + 4 * bsum[(size_t)lv + 1];
     }
+    for (const Launch& L : d->launches)
+        if (L.kind != TIER_UP && L.kind != TIER_DOWN)
+            (L.sweep ? d->lvl_idx_down : d->lvl_idx_up)[(size_t)L.lo] += (int64_t)L.grid * (int64_t)(L.kind == UP_P || L.kind == DOWN_P ? sizeof(PackedTile) : sizeof(Tile));
     if (d->tier_root >= levels) return;
     const int H = levels - d->tier_root;
     // item records by the level they belong to: phase ph of the up sweep is level levels - 1 - ph, of the down sweep tier_root + ph
@@ -1501,12 +1530,24 @@ extern "C" int ls_direct_create(const ls_direct_arrays* A, int device, void* str
     int rc = LS_OK;
     if ((rc = read_nodes(A, T, d.get())) || (rc = choose_tier(T, A->h_ppos, A->tier_waves, env, d.get()))) return rc;
     d->upper_lo = (d->tier_root < levels && d->tier_root > 0) ? T.nd[T.level_off[d->tier_root - 1]].own_start : (int)V;
-    d->plan.resize(levels);
     size_t lds_max = 0;
     // (measured over 576 .. 1M vertices, tools/tier_sweep.py: the down sweep of levels with s + b of 90 .. 250 runs 5-10 % of a
     //  whole solve faster with the lanes along the reduction; the up sweep of the s = 125 nodes of an 8-level tree loses 2-3 %)
     const int long_up = env.long_up > 0 ? env.long_up : levels >= 8 ? 256 : 64;      // up sweep (reduction s): small trees gain 1-3 % from 64
-    for (int lv = 0; lv < d->tier_root; ++lv) lds_max = std::max(lds_max, plan_level(T, lv, long_up, env, d->kmax, d->plan[lv]));
+    std::vector<Launch> ups((size_t)d->tier_root), downs((size_t)d->tier_root);
+    for (int lv = 0; lv < d->tier_root; ++lv) lds_max = std::max(lds_max, plan_level(T, lv, long_up, env, d->kmax, ups[(size_t)lv], downs[(size_t)lv]));
+    // the launch list: levels [tier_root, levels) are the bottom tier, one launch per sweep; the levels above, those with tiles, one each
+    auto add = [&](const Launch& L) { if (L.grid) d->launches.push_back(L); };
+    Launch tier;
+    tier.kind = TIER_UP; tier.lo = d->tier_root; tier.hi = levels - 1; tier.grid = d->tier_wgs; tier.block = WAVE * d->tier_waves;
+    tier.lds_fix = (size_t)d->tier_region * d->tier_waves * sizeof(float);
+    add(tier);
+    for (int lv = d->tier_root - 1; lv >= 0; --lv) add(ups[(size_t)lv]);
+    d->n_up = (int)d->launches.size();
+    for (const Launch& L : d->launches) d->part_cut += L.lo >= cut;          // the up launches of this rank's subtrees: a prefix
+    for (int lv = 0; lv < d->tier_root; ++lv) add(downs[(size_t)lv]);
+    tier.kind = TIER_DOWN; tier.sweep = 1;
+    add(tier);
     account_index_bytes(T, d.get());
     if (lds_max > LEVEL_LDS) {
         set_error("ls_direct_create: a front needs %zu bytes of LDS (separator too large for this kernel)", lds_max);
@@ -1599,11 +1640,47 @@ extern "C" int ls_direct_destroy(ls_direct* d) {
     return LS_OK;
 }
 
+// the tier's kernel for the handle's workgroup shape and cache policy (the 8-wave kernel has no non-temporal variant)
+template <int K, bool UP>
+static void launch_tier(const ls_direct* d, const Launch& L, const TierArgs& ta, const float* b, float* x, hipStream_t st) {
+#define LS_TIER(W, NT) hipLaunchKernelGGL((k_nd_tier<K, UP, W, NT>), dim3(L.grid), dim3(L.block), L.lds_fix, st, ta, b, x, d->tier_tri)
+    switch (d->tier_waves) {
+        case TIER_WAVES_FULL: if (d->nt_tier) LS_TIER(TIER_WAVES_FULL, true); else LS_TIER(TIER_WAVES_FULL, false); break;
+        case TIER_WAVES_WIDE: LS_TIER(TIER_WAVES_WIDE, false); break;
+        default: if (d->nt_tier) LS_TIER(TIER_WAVES, true); else LS_TIER(TIER_WAVES, false); break;
+    }
+#undef LS_TIER
+}
+
+// one record of the launch list, for K right-hand sides
+template <int K>
+static void launch(const ls_direct* d, const Launch& L, const TierArgs& ta, const float* b, float* x, hipStream_t st) {
+    const bool nt = d->nt_levels;
+#define LS_LEVEL(kernel, ...) hipLaunchKernelGGL(kernel, dim3(L.grid), dim3(L.block), L.lds_col * K + L.lds_fix, st, __VA_ARGS__)
+    // the tier's up-sweep launch gathers b of the upper levels' rows into the tree's numbering (braw): their kernels skip perm -> b
+    const int* up_perm = d->tier_wgs ? nullptr : d->perm;
+    const float* up_b = d->tier_wgs ? d->braw : b;
+    const RootFill rf = L.root_fill ? RootFill{up_perm, d->mask, d->slots, up_b} : RootFill{nullptr, nullptr, nullptr, nullptr};
+    switch (L.kind) {
+        case TIER_UP: launch_tier<K, true>(d, L, ta, b, x, st); break;
+        case TIER_DOWN: launch_tier<K, false>(d, L, ta, b, x, st); break;
+        case UP_P: LS_LEVEL(k_nd_up_p<K>, d->ptiles + L.first, up_perm, d->mask, d->ppos, d->wf, up_b, d->bp, d->slots); break;
+        case UP_S: LS_LEVEL(k_nd_up_s<K>, d->tiles + L.first, up_perm, d->mask, d->ppos, d->wf, up_b, d->bp, d->slots, L.s_cap, L.b_cap); break;
+        case UP_B: LS_LEVEL((nt ? k_nd_up_b<K, true> : k_nd_up_b<K, false>), d->tiles + L.first, up_perm, d->mask, d->ppos, d->wb, up_b, d->bp, d->slots, L.s_cap, L.chunks); break;
+        case UP: LS_LEVEL((nt ? k_nd_up<K, true> : k_nd_up<K, false>), d->tiles + L.first, up_perm, d->mask, d->ppos, d->wf, up_b, d->bp, d->slots, L.s_cap); break;
+        case DOWN_P: LS_LEVEL(k_nd_down_p<K>, d->ptiles + L.first, d->perm, d->push_ptr, d->push_tgt, d->finv, d->wb, (const float*)d->bp, d->xb, x, L.down_p_s); break;
+        case DOWN_B: LS_LEVEL((nt ? k_nd_down_b<K, true> : k_nd_down_b<K, false>), d->tiles + L.first, d->perm, d->push_ptr, d->push_tgt, d->finv, d->wf, (const float*)d->bp,
+                              d->xb, x, L.s_cap, L.b_cap, L.chunks, rf); break;
+        case DOWN: LS_LEVEL((nt ? k_nd_down<K, true> : k_nd_down<K, false>), d->tiles + L.first, d->perm, d->push_ptr, d->push_tgt, d->finv, d->wb, (const float*)d->bp,
+                            d->xb, x, L.s_cap, L.b_cap, rf); break;
+    }
+#undef LS_LEVEL
+}
+
 // part: -1 the whole solve; sharded handles: 0 = this rank's subtrees upwards, level cut - 1's slots -> exchange buffer;
 //       1 = exchange buffer (summed over the ranks by the caller) -> slots, the replicated levels, everything downwards
 template <int K>
 static int direct_solve_k(ls_direct* d, const float* b, float* x, hipStream_t st, int part, float* exchange) {
-    const int top = d->tier_root - 1;            // levels [0, tier_root) are one launch each, the rest is the bottom tier
     TierArgs ta;
     ta.items = d->d_items; ta.wgs = d->d_wgs; ta.perm = d->perm; ta.mask = d->mask; ta.ppos = d->ppos;
     ta.pull = d->pull ? d->pull - (size_t)d->pull_base * d->arity : nullptr; ta.push_ptr = d->push_ptr; ta.push_tgt = d->push_tgt; ta.u4 = d->u4; ta.d4 = d->d4; ta.tri = d->tri;
@@ -1616,65 +1693,26 @@ static int direct_solve_k(ls_direct* d, const float* b, float* x, hipStream_t st
     if (d->profile == 2 && d->stamps) LS_HIP(hipMemsetAsync(d->stamps, 0, 2 * stamp_n * sizeof(long long), st));
     ta.stamps = d->profile == 2 ? d->stamps : nullptr;
 #endif
-    const size_t tier_lds = (size_t)d->tier_region * d->tier_waves * sizeof(float);
-    const bool nt_tier = d->nt_tier && d->tier_waves != TIER_WAVES_WIDE, nt = d->nt_levels;
+    // this part's range of the launch list
+    const int n = (int)d->launches.size(), first = part == 1 ? d->part_cut : 0, last = part == 0 ? d->part_cut : n;
     int n_mark = 0;
-    auto mark = [&](int lo, int hi, int sweep) -> hipError_t {        // "profile" = 3: an event in front of every launch
-        if (d->profile != 3) return hipSuccess;
-        while ((int)d->lev.size() <= n_mark + 1) { hipEvent_t e; const hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; d->lev.push_back(e); }
-        if ((int)d->lmeta.size() <= n_mark) d->lmeta.resize((size_t)n_mark + 1);
-        d->lmeta[(size_t)n_mark] = {lo, hi, sweep};
-        return hipEventRecord(d->lev[(size_t)n_mark++], st);
-    };
-    auto mark_end = [&]() -> hipError_t {
-        if (d->profile != 3) return hipSuccess;
-        hipError_t r = hipEventRecord(d->lev[(size_t)n_mark], st);
-        if (r == hipSuccess) r = hipStreamSynchronize(st);
-        d->launch_ms.assign((size_t)n_mark, 0.0);
-        d->lmeta.resize((size_t)n_mark);
-        for (int i = 0; i < n_mark && r == hipSuccess; ++i) { float ms = 0; r = hipEventElapsedTime(&ms, d->lev[(size_t)i], d->lev[(size_t)i + 1]); d->launch_ms[(size_t)i] = ms; }
-        return r;
+    auto run = [&](int i0, int i1) -> hipError_t {
+        for (int i = i0; i < i1; ++i) {
+            if (d->profile == 3) {                                        // an event in front of every launch
+                while ((int)d->lev.size() <= n_mark + 1) { hipEvent_t e; const hipError_t r = hipEventCreate(&e); if (r != hipSuccess) return r; d->lev.push_back(e); }
+                const hipError_t r = hipEventRecord(d->lev[(size_t)n_mark++], st);
+                if (r != hipSuccess) return r;
+            }
+            launch<K>(d, d->launches[(size_t)i], ta, b, x, st);
+        }
+        return hipSuccess;
     };
     const size_t exch_off = (size_t)d->exch_f0 * d->arity * K, exch_n = (size_t)(d->exch_f1 - d->exch_f0) * d->arity * K;
-    if (part != 1) {
-    if (d->profile) LS_HIP(hipEventRecord(d->ev[0], st));
+    if (part != 1 && d->profile) LS_HIP(hipEventRecord(d->ev[0], st));
     if (part == 0 && exch_n) LS_HIP(hipMemsetAsync(d->slots + exch_off, 0, exch_n * sizeof(float), st));
-    if (d->tier_wgs) {
-        LS_HIP(mark(d->tier_root, d->levels - 1, 0));
-        if (d->tier_waves == TIER_WAVES_FULL && nt_tier) hipLaunchKernelGGL((k_nd_tier<K, true, TIER_WAVES_FULL, true>), dim3(d->tier_wgs), dim3(WAVE * TIER_WAVES_FULL), tier_lds, st, ta, b, x, d->tier_tri);
-        else if (d->tier_waves == TIER_WAVES_FULL) hipLaunchKernelGGL((k_nd_tier<K, true, TIER_WAVES_FULL, false>), dim3(d->tier_wgs), dim3(WAVE * TIER_WAVES_FULL), tier_lds, st, ta, b, x, d->tier_tri);
-        else if (d->tier_waves == TIER_WAVES_WIDE) hipLaunchKernelGGL((k_nd_tier<K, true, TIER_WAVES_WIDE, false>), dim3(d->tier_wgs), dim3(WAVE * TIER_WAVES_WIDE), tier_lds, st, ta, b, x, d->tier_tri);
-        else if (nt_tier) hipLaunchKernelGGL((k_nd_tier<K, true, TIER_WAVES, true>), dim3(d->tier_wgs), dim3(WAVE * TIER_WAVES), tier_lds, st, ta, b, x, d->tier_tri);
-        else hipLaunchKernelGGL((k_nd_tier<K, true, TIER_WAVES, false>), dim3(d->tier_wgs), dim3(WAVE * TIER_WAVES), tier_lds, st, ta, b, x, d->tier_tri);
-    }
-    }
     if (part == 1 && exch_n && exchange != d->slots + exch_off)
         LS_HIP(hipMemcpyAsync(d->slots + exch_off, exchange, exch_n * sizeof(float), hipMemcpyDeviceToDevice, st));
-    // the tier's up-sweep launch gathers b of the upper levels' rows into the tree's numbering (braw): their kernels skip perm -> b
-    const int* up_perm = d->tier_wgs ? nullptr : d->perm;
-    const float* up_b = d->tier_wgs ? d->braw : b;
-    // the root (level 0, when it is a level of its own launches): b' is formed by its down-sweep tiles, no up-sweep launch
-    const bool fuse_root = top >= 0 && !d->plan[0].down_p;
-    const RootFill rf = fuse_root ? RootFill{up_perm, d->mask, d->slots, up_b} : RootFill{nullptr, nullptr, nullptr, nullptr};
-    for (int lv = (part == 1 ? std::min(top, d->cut - 1) : top); lv >= (part == 0 ? d->cut : 0); --lv) {
-        const LevelPlan& p = d->plan[lv];
-        if (!(p.up_p ? p.up_p_tiles : p.up_tiles)) continue;
-        if (lv == 0 && fuse_root) continue;
-        LS_HIP(mark(lv, lv, 0));
-        if (p.up_p)
-            hipLaunchKernelGGL(k_nd_up_p<K>, dim3(p.up_p_tiles), dim3(WAVE), (size_t)std::max(p.up_p_lds, 1) * K * sizeof(float), st,
-                               d->ptiles + p.up_p_first, up_perm, d->mask, d->ppos, d->wf, up_b, d->bp, d->slots);
-        else if (p.up_s)
-            hipLaunchKernelGGL(k_nd_up_s<K>, dim3(p.up_tiles), dim3(WAVE * p.up_nw), ((size_t)p.s_cap * p.b_cap + (size_t)p.s_cap * K) * sizeof(float), st,
-                               d->tiles + p.up_first, up_perm, d->mask, d->ppos, d->wf, up_b, d->bp, d->slots, p.s_cap, p.b_cap);
-        else if (p.up_b)
-            hipLaunchKernelGGL((nt ? k_nd_up_b<K, true> : k_nd_up_b<K, false>), dim3(p.up_tiles), dim3(WAVE * p.up_nw), ((size_t)p.s_cap * K + 16) * sizeof(float), st,
-                               d->tiles + p.up_first, up_perm, d->mask, d->ppos, d->wb, up_b, d->bp, d->slots, p.s_cap, p.up_chunks);
-        else
-            hipLaunchKernelGGL((nt ? k_nd_up<K, true> : k_nd_up<K, false>), dim3(p.up_tiles), dim3(WAVE * p.up_nw),
-                               ((size_t)p.s_cap + (size_t)(p.up_nw - 1) * WAVE) * K * sizeof(float),
-                               st, d->tiles + p.up_first, up_perm, d->mask, d->ppos, d->wf, up_b, d->bp, d->slots, p.s_cap);
-    }
+    LS_HIP(run(first, std::min(last, d->n_up)));
     if (part == 0) {
         if (exch_n && exchange != d->slots + exch_off)
             LS_HIP(hipMemcpyAsync(exchange, d->slots + exch_off, exch_n * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -1682,38 +1720,18 @@ static int direct_solve_k(ls_direct* d, const float* b, float* x, hipStream_t st
         return LS_OK;
     }
     if (d->profile) LS_HIP(hipEventRecord(d->ev[1], st));
-    for (int lv = 0; lv <= top; ++lv) {
-        const LevelPlan& p = d->plan[lv];
-        if (!(p.down_p ? p.down_p_tiles : p.down_tiles)) continue;
-        LS_HIP(mark(lv, lv, 1));
-        if (p.down_p)
-            hipLaunchKernelGGL(k_nd_down_p<K>, dim3(p.down_p_tiles), dim3(WAVE), (size_t)std::max(p.down_p_s + p.down_p_lds, 1) * K * sizeof(float), st,
-                               d->ptiles + p.down_p_first, d->perm, d->push_ptr, d->push_tgt, d->finv, d->wb, (const float*)d->bp, d->xb, x,
-                               p.down_p_s);
-        else if (p.down_b)
-            hipLaunchKernelGGL((nt ? k_nd_down_b<K, true> : k_nd_down_b<K, false>), dim3(p.down_tiles), dim3(WAVE * p.down_nw), (((size_t)p.s_cap + p.b_cap) * K + 32) * sizeof(float), st,
-                               d->tiles + p.down_first, d->perm, d->push_ptr, d->push_tgt, d->finv, d->wf, (const float*)d->bp, d->xb, x,
-                               p.s_cap, p.b_cap, p.down_chunks, lv == 0 ? rf : RootFill{nullptr, nullptr, nullptr, nullptr});
-        else
-            hipLaunchKernelGGL((nt ? k_nd_down<K, true> : k_nd_down<K, false>), dim3(p.down_tiles), dim3(WAVE * p.down_nw),
-                               ((size_t)p.s_cap + p.b_cap + (size_t)(p.down_nw - 1) * WAVE) * K * sizeof(float), st, d->tiles + p.down_first,
-                               d->perm, d->push_ptr, d->push_tgt, d->finv, d->wb, (const float*)d->bp, d->xb, x, p.s_cap, p.b_cap,
-                               lv == 0 ? rf : RootFill{nullptr, nullptr, nullptr, nullptr});
-    }
 #ifdef LS_TIER_STAMPS
-    if (ta.stamps) ta.stamps += stamp_n;
+    if (ta.stamps) ta.stamps += stamp_n;          // the down sweep's half (only the tier's launch, the sweep's last, writes stamps)
 #endif
-    if (d->tier_wgs) {
-        LS_HIP(mark(d->tier_root, d->levels - 1, 1));
-        if (d->tier_waves == TIER_WAVES_FULL && nt_tier) hipLaunchKernelGGL((k_nd_tier<K, false, TIER_WAVES_FULL, true>), dim3(d->tier_wgs), dim3(WAVE * TIER_WAVES_FULL), tier_lds, st, ta, b, x, d->tier_tri);
-        else if (d->tier_waves == TIER_WAVES_FULL) hipLaunchKernelGGL((k_nd_tier<K, false, TIER_WAVES_FULL, false>), dim3(d->tier_wgs), dim3(WAVE * TIER_WAVES_FULL), tier_lds, st, ta, b, x, d->tier_tri);
-        else if (d->tier_waves == TIER_WAVES_WIDE) hipLaunchKernelGGL((k_nd_tier<K, false, TIER_WAVES_WIDE, false>), dim3(d->tier_wgs), dim3(WAVE * TIER_WAVES_WIDE), tier_lds, st, ta, b, x, d->tier_tri);
-        else if (nt_tier) hipLaunchKernelGGL((k_nd_tier<K, false, TIER_WAVES, true>), dim3(d->tier_wgs), dim3(WAVE * TIER_WAVES), tier_lds, st, ta, b, x, d->tier_tri);
-        else hipLaunchKernelGGL((k_nd_tier<K, false, TIER_WAVES, false>), dim3(d->tier_wgs), dim3(WAVE * TIER_WAVES), tier_lds, st, ta, b, x, d->tier_tri);
-    }
+    LS_HIP(run(d->n_up, n));
     if (d->profile) LS_HIP(hipEventRecord(d->ev[2], st));
     LS_HIP(hipGetLastError());
-    LS_HIP(mark_end());
+    if (d->profile == 3) {                        // what each launch of launches[first ...] took
+        d->launch_ms.assign((size_t)n_mark, 0.0); d->prof_first = first;
+        LS_HIP(hipEventRecord(d->lev[(size_t)n_mark], st));
+        LS_HIP(hipStreamSynchronize(st));
+        for (int i = 0; i < n_mark; ++i) { float ms = 0; LS_HIP(hipEventElapsedTime(&ms, d->lev[(size_t)i], d->lev[(size_t)i + 1])); d->launch_ms[(size_t)i] = ms; }
+    }
     if (d->profile) {
         LS_HIP(hipStreamSynchronize(st));
         float a = 0, c = 0;
@@ -1724,10 +1742,8 @@ static int direct_solve_k(ls_direct* d, const float* b, float* x, hipStream_t st
     return LS_OK;
 }
 
-extern "C" int ls_direct_solve(ls_direct* d, const float* b, float* x, int k, void* stream) {
-    LS_REQUIRE(d && b && x && k >= 1 && k <= d->kmax, LS_E_INVALID, "ls_direct_solve: bad argument (1 <= k <= %d)", d ? d->kmax : 4);
-    LS_REQUIRE(b != x, LS_E_INVALID, "ls_direct_solve: b and x must not alias");
-    LS_REQUIRE(d->factored, LS_E_STATE, "ls_direct_solve: the handle is unfactored (its last ls_direct_refactor failed)");
+// what ls_direct_solve and ls_direct_solve_part do once their arguments are checked
+static int direct_solve(ls_direct* d, const float* b, float* x, int k, int part, float* exchange, void* stream) {
     DeviceGuard g(d->device);
     LS_HIP(g.err);
     hipStream_t st = (hipStream_t)stream;
@@ -1742,30 +1758,6 @@ extern "C" int ls_direct_solve(ls_direct* d, const float* b, float* x, int k, vo
     if (!capturing && d->used && st != d->last_stream) LS_HIP(hipStreamWaitEvent(st, d->busy, 0));
     int rc;
     switch (k) {
-        case 1: rc = direct_solve_k<1>(d, b, x, st, -1, nullptr); break;
-        case 2: rc = direct_solve_k<2>(d, b, x, st, -1, nullptr); break;
-        case 3: rc = direct_solve_k<3>(d, b, x, st, -1, nullptr); break;
-        default: rc = direct_solve_k<4>(d, b, x, st, -1, nullptr); break;
-    }
-    if (rc == LS_OK && !capturing) { LS_HIP(hipEventRecord(d->busy, st)); d->last_stream = st; d->used = true; }
-    return rc;
-}
-
-extern "C" int ls_direct_solve_part(ls_direct* d, const float* b, float* x, int k, int part, float* exchange, void* stream) {
-    LS_REQUIRE(d && b && x && k >= 1 && k <= d->kmax && (part == 0 || part == 1), LS_E_INVALID, "ls_direct_solve_part: bad argument");
-    LS_REQUIRE(b != x, LS_E_INVALID, "ls_direct_solve_part: b and x must not alias");
-    LS_REQUIRE(d->factored, LS_E_STATE, "ls_direct_solve_part: the handle is unfactored (its last ls_direct_refactor failed)");
-    LS_REQUIRE(exchange || d->exch_f1 == d->exch_f0, LS_E_INVALID, "ls_direct_solve_part: the exchange buffer is missing");
-    DeviceGuard g(d->device);
-    LS_HIP(g.err);
-    hipStream_t st = (hipStream_t)stream;
-    // one workspace per handle, as in ls_direct_solve: a part issued on another stream than the previous call waits for it
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (st) (void)hipStreamIsCapturing(st, &cap);
-    const bool capturing = cap == hipStreamCaptureStatusActive;
-    if (!capturing && d->used && st != d->last_stream) LS_HIP(hipStreamWaitEvent(st, d->busy, 0));
-    int rc;
-    switch (k) {
         case 1: rc = direct_solve_k<1>(d, b, x, st, part, exchange); break;
         case 2: rc = direct_solve_k<2>(d, b, x, st, part, exchange); break;
         case 3: rc = direct_solve_k<3>(d, b, x, st, part, exchange); break;
@@ -1773,6 +1765,21 @@ extern "C" int ls_direct_solve_part(ls_direct* d, const float* b, float* x, int 
     }
     if (rc == LS_OK && !capturing) { LS_HIP(hipEventRecord(d->busy, st)); d->last_stream = st; d->used = true; }
     return rc;
+}
+
+extern "C" int ls_direct_solve(ls_direct* d, const float* b, float* x, int k, void* stream) {
+    LS_REQUIRE(d && b && x && k >= 1 && k <= d->kmax, LS_E_INVALID, "ls_direct_solve: bad argument (1 <= k <= %d)", d ? d->kmax : 4);
+    LS_REQUIRE(b != x, LS_E_INVALID, "ls_direct_solve: b and x must not alias");
+    LS_REQUIRE(d->factored, LS_E_STATE, "ls_direct_solve: the handle is unfactored (its last ls_direct_refactor failed)");
+    return direct_solve(d, b, x, k, -1, nullptr, stream);
+}
+
+extern "C" int ls_direct_solve_part(ls_direct* d, const float* b, float* x, int k, int part, float* exchange, void* stream) {
+    LS_REQUIRE(d && b && x && k >= 1 && k <= d->kmax && (part == 0 || part == 1), LS_E_INVALID, "ls_direct_solve_part: bad argument");
+    LS_REQUIRE(b != x, LS_E_INVALID, "ls_direct_solve_part: b and x must not alias");
+    LS_REQUIRE(d->factored, LS_E_STATE, "ls_direct_solve_part: the handle is unfactored (its last ls_direct_refactor failed)");
+    LS_REQUIRE(exchange || d->exch_f1 == d->exch_f0, LS_E_INVALID, "ls_direct_solve_part: the exchange buffer is missing");
+    return direct_solve(d, b, x, k, part, exchange, stream);
 }
 
 // the part of the handle's slot array that the ranks of a sharded solve sum (k columns): ls_dist_direct_solve reduces it in place
@@ -1932,7 +1939,7 @@ extern "C" int ls_direct_launch_profile(const ls_direct* d, int cap, int* h_n, d
     const int n = (int)d->launch_ms.size();
     if (h_n) *h_n = n;
     for (int i = 0; i < n && i < cap; ++i) {
-        const ls_direct::LaunchMeta m = d->lmeta[(size_t)i];
+        const Launch& m = d->launches[(size_t)(d->prof_first + i)];
         int64_t w = 0;
         for (int lv = std::max(m.lo, 0); lv <= m.hi && lv < d->levels; ++lv) {
             if (m.sweep != 1) w += d->lvl_up[(size_t)lv];
@@ -1950,15 +1957,7 @@ extern "C" int ls_direct_launch_profile(const ls_direct* d, int cap, int* h_n, d
 extern "C" int ls_direct_info(const ls_direct* d, int64_t* h_factor_entries, int* h_launches, double* h_ms3) {
     LS_REQUIRE(d, LS_E_INVALID, "ls_direct_info: bad argument");
     if (h_factor_entries) *h_factor_entries = d->factor_entries;
-    if (h_launches) {
-        int n = 0;
-        for (int lv = 0; lv < d->levels; ++lv) {
-            const LevelPlan& p = d->plan[lv];
-            const bool fused = lv == 0 && d->tier_root > 0 && !p.down_p;     // the root's up step rides in its down tiles
-            n += (((p.up_p ? p.up_p_tiles : p.up_tiles) && !fused) ? 1 : 0) + ((p.down_p ? p.down_p_tiles : p.down_tiles) ? 1 : 0);
-        }
-        *h_launches = n + (d->tier_wgs ? 2 : 0);
-    }
+    if (h_launches) *h_launches = (int)d->launches.size();
     if (h_ms3) for (int i = 0; i < 3; ++i) h_ms3[i] = d->prof_ms[i];
     return LS_OK;
 }
