@@ -27,6 +27,10 @@ class AdamUniform(torch.optim.Optimizer):
     capturable=True (as in torch.optim.Adam) keeps the step count on the device -- state["step"] is then an int32 tensor whose
     first element counts the steps -- so that `step()` can be recorded in a `torch.cuda.graph` together with the forward and
     backward pass and replayed; the update is the same.
+
+    Every optimizer of a device hands its parameters the same 4 KiB scratch buffer (`_scratch_for`) for the partial maxima, one
+    parameter after the other on the current stream. Two optimizers stepping at the same time on DIFFERENT streams of one device
+    would race on it: step them on one stream, or order the streams.
     """
     def __init__(self, params, lr=0.1, betas=(0.9, 0.999), capturable=False):
         defaults = dict(lr=lr, betas=betas, capturable=bool(capturable))
