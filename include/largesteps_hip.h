@@ -41,6 +41,7 @@
  *   ls_mesh_winding_*    igl.winding_number / igl.fast_winding_number, the sign of igl.signed_distance: over the same handle
  *   ls_mesh_selfx_*      igl.fast_find_self_intersections: which faces of the handle's mesh cut through each other
  *   ls_iso_*             igl.marching_tets on the Kuhn split of a regular grid: a level set as a mesh, with the gradient to the field
+ *   ls_subdiv_*          igl.upsample / igl.loop: midpoint and Loop subdivision as a topology built once and a linear map with its transpose
  */
 #ifndef LARGESTEPS_HIP_H
 #define LARGESTEPS_HIP_H
@@ -1060,6 +1061,50 @@ int ls_cube_order(const float* uv, int64_t B, int H, int W, int64_t Bt, int n, i
 int ls_cube_backward(const float* tex, int64_t Bt, int n, int C, const float* uv, int64_t B, int H, int W, int filter,
                      const float* grad_out, const int32_t* order, const int32_t* seg, float* grad_tex, float* grad_uv, int device,
                      void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * One level of midpoint or Loop subdivision (libigl's upsample / loop) as a topology built once and a linear map S applied every step
+ * (largesteps/subdivide.py). The rule is stated in csrc/subdiv.hip and DESIGN.md section 2.14 and restated in numpy by
+ * tests/subdiv_statement.py, and the device answers with the same bits. Half-edge h = 3 f + e runs from F[f, e] to F[f, (e + 1) % 3];
+ * the half-edges of one unordered vertex pair form an edge, owned by the one of lowest id; edges are numbered by ascending owner.
+ * faces (F, 3) int32 / int64 (idx_bytes 4 / 8). The arrays of a topology, all device buffers of the caller:
+ *   tri (3 F) int32       the faces narrowed
+ *   he (3 F) int32        per half-edge: edge id << 2 | boundary << 1 | owner
+ *   edges (E, 2) int32    the ends of edge e, the smaller id first: new vertex V + e sits on it   } both with room for 3 F rows:
+ *   opp (E, 2) int32      the corners opposite the owner and opposite the other half-edge (or -1) } E is not known before the call
+ *   valence (V) int32, bflag (V) uint8, bnbr (V, 2) int32   the number of edges at a vertex, whether it is a boundary vertex, and then
+ *                         the far ends of its two boundary edges (else -1, -1)
+ *   vptr (V + 1), order (3 F) int32   the corner ranking of ls_corner_ranks: the corners of v are order[vptr[v] .. vptr[v + 1])
+ *   ls_subdiv_workspace_bytes  the workspace of ls_subdiv_topology (256-byte aligned regions).
+ *   ls_subdiv_topology         fills the arrays above and fine_faces (4 F, 3) of the index type of `faces`; *h_E = E; *h_status = 0 or
+ *                              the LS_SUBDIV_* flags of what is wrong with the mesh (the arrays then hold nothing of use, but nothing
+ *                              was written or read out of bounds: a bad index is never followed). Radix sorts of the corners by vertex
+ *                              and of the half-edges by (smaller end, larger end), an exclusive scan of the owner flags. SYNC (once).
+ *   ls_subdiv_apply            out (V + E, C) fp32 = S X for X (V, C) fp32, 1 <= C <= 32, scheme LS_SUBDIV_MIDPOINT / _LOOP. Every row
+ *                              is formed in fp64 from the fp32 inputs in the order the rule states and rounded once. ASYNC, capturable:
+ *                              no allocation, no synchronisation.
+ *   ls_subdiv_apply_backward   gX (V, C) fp32 = S^T g for g (V + E, C) fp32, overwritten: a gather per coarse vertex over the same walk,
+ *                              fp64, rounded once, no float atomics, bitwise reproducible. ASYNC, capturable.
+ * LS_E_INVALID for a null required pointer, a negative size, E > 3 F, C outside [1, 32], another idx_bytes or scheme; LS_E_OVERFLOW when
+ * 12 F, V or V + E reaches 2^31; LS_E_WORKSPACE for a workspace below ls_subdiv_workspace_bytes. The apply calls follow the arrays
+ * without a range check: they must come from an ls_subdiv_topology that returned status 0 for the same F and V.
+ * --------------------------------------------------------------------------------------------- */
+#define LS_SUBDIV_MIDPOINT 0
+#define LS_SUBDIV_LOOP 1
+#define LS_SUBDIV_BAD_INDEX 1          /* a face index outside [0, V) */
+#define LS_SUBDIV_REPEATED_VERTEX 2    /* a face names a vertex twice */
+#define LS_SUBDIV_NONMANIFOLD_EDGE 4   /* an edge with more than two half-edges */
+#define LS_SUBDIV_NONMANIFOLD_VERTEX 8 /* a vertex with a number of boundary edges other than 0 or 2 */
+int ls_subdiv_workspace_bytes(int64_t F, int64_t V, size_t* bytes);
+int ls_subdiv_topology(const void* faces, int idx_bytes, int64_t F, int64_t V, int32_t* tri, int32_t* he, int32_t* edges, int32_t* opp,
+                       int32_t* valence, unsigned char* bflag, int32_t* bnbr, int32_t* vptr, int32_t* order, void* fine_faces,
+                       int64_t* h_E, int* h_status, void* ws, size_t ws_bytes, int device, void* stream);
+int ls_subdiv_apply(const float* X, int64_t F, int64_t V, int64_t E, int C, int scheme, const int32_t* tri, const int32_t* he,
+                    const int32_t* edges, const int32_t* opp, const int32_t* valence, const unsigned char* bflag, const int32_t* bnbr,
+                    const int32_t* vptr, const int32_t* order, float* out, int device, void* stream);
+int ls_subdiv_apply_backward(const float* g, int64_t F, int64_t V, int64_t E, int C, int scheme, const int32_t* tri, const int32_t* he,
+                             const int32_t* edges, const int32_t* opp, const int32_t* valence, const unsigned char* bflag,
+                             const int32_t* bnbr, const int32_t* vptr, const int32_t* order, float* gX, int device, void* stream);
 
 #ifdef __cplusplus
 }

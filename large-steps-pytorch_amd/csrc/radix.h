@@ -3,8 +3,8 @@
 // stable by construction, no atomics in the scatter), and the one description of the scratch it needs (SortScratch below).
 // Users: remove_duplicates, the CSR transpose and the corner ranking (assemble.hip); the coordinate orders of the device bisection
 // (nd_bisect.hip); the Morton order of the LBVH (lbvh.h: the remesher's projection in remesh.hip, the point-to-mesh distance in
-// distance.hip); the edge adjacency of the rasterizer (raster.hip); and, through the group-by of groupby.h, the pixel orders of the
-// rasterizer and of the texture lookup (raster.hip, texture.hip).
+// distance.hip); the edge adjacency of the rasterizer (raster.hip); the edges of the subdivision topology (subdiv.hip); and, through
+// the group-by of groupby.h, the pixel orders of the rasterizer and of the texture lookup (raster.hip, texture.hip).
 #pragma once
 #include "common.h"
 #include "workspace.h"
@@ -35,6 +35,17 @@ struct KeyInt {
     const int* keys;
     __device__ __forceinline__ unsigned digit(int row, int pass) const { return ((unsigned)keys[row] >> (8 * pass)) & 255u; }
     __device__ __forceinline__ unsigned word(int row, int) const { return (unsigned)keys[row]; }
+};
+
+// the 8 bytes of a mesh edge (the edge adjacency of raster.hip, the subdivision topology of subdiv.hip)
+struct KeyEdge {       // half-edge h = 3 f + e, edge (tri[h], tri[3 f + (e + 1) % 3]): word 0 = the smaller vertex id, word 1 = the larger
+    const int* tri;
+    __device__ __forceinline__ unsigned word(int h, int w) const {
+        const int f = h / 3, e = h - 3 * f;
+        const unsigned a = (unsigned)tri[h], b = (unsigned)tri[3 * f + (e + 1) % 3];
+        return w == 0 ? min(a, b) : max(a, b);
+    }
+    __device__ __forceinline__ unsigned digit(int h, int pass) const { return (word(h, pass / 4) >> (8 * (pass & 3))) & 255u; }
 };
 
 // lanes of the wave that hold the same digit as this lane (eight ballots); `ok` = the lane takes part

@@ -652,15 +652,7 @@ __global__ __launch_bounds__(256) void k_rs_interp_grad_rast(const float* __rest
 }
 
 // ---- edge adjacency ---------------------------------------------------------------------------------------------------------------------
-struct KeyEdge {       // half-edge h = 3 f + e, edge (tri[h], tri[3 f + (e + 1) % 3]): word 0 = the smaller vertex id, word 1 = the larger
-    const int* tri;
-    __device__ __forceinline__ unsigned word(int h, int w) const {
-        const int f = h / 3, e = h - 3 * f;
-        const unsigned a = (unsigned)tri[h], b = (unsigned)tri[3 * f + (e + 1) % 3];
-        return w == 0 ? min(a, b) : max(a, b);
-    }
-    __device__ __forceinline__ unsigned digit(int h, int pass) const { return (word(h, pass / 4) >> (8 * (pass & 3))) & 255u; }
-};
+// (KeyEdge, the two-word key of a half-edge, is in radix.h: subdiv.hip sorts by it too)
 
 // range mode: half-edge h = 3 n + e of item n = (b, f): KeyEdge's two words over face f, and the image as word 2 -- an edge pairs its
 // half-edges within one image only

@@ -12,6 +12,7 @@ largesteps/ 0.2.2). Same modules, symbols and call forms as the reference:
     from largesteps.distance import hausdorff, point_mesh_squared_distance   (igl's: the figures' error column)
     from largesteps.sampling import sample_surface; from largesteps.distance import chamfer_distance   (mesh-to-mesh measures)
     from largesteps.raycast import RayMesh, ray_mesh_intersect, ambient_occlusion   (igl's ray queries, on the distance handle's LBVH)
+    from largesteps.subdivide import Subdivision, loop, upsample   (igl's loop / upsample as a linear map applied every step)
 
 Device work is done by hand-written HIP kernels for gfx950 in lib/liblargesteps_hip.so (C ABI in
 include/largesteps_hip.h); there is no CPU or stock-PyTorch fallback.

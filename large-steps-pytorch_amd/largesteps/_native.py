@@ -128,6 +128,12 @@ _SIGNATURES = {
                             c_void_p, c_void_p, c_int, c_void_p]),
     "ls_iso_backward": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_i64, c_void_p,
                                 c_void_p, c_int, c_void_p]),
+    "ls_subdiv_workspace_bytes": (c_int, [c_i64, c_i64, ctypes.POINTER(c_size_t)]),
+    "ls_subdiv_topology": (c_int, [c_void_p, c_int, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_i64), ctypes.POINTER(c_int), c_void_p, c_size_t, c_int,
+                                   c_void_p]),
+    "ls_subdiv_apply": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_int, c_int] + [c_void_p] * 10 + [c_int, c_void_p]),
+    "ls_subdiv_apply_backward": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_int, c_int] + [c_void_p] * 10 + [c_int, c_void_p]),
     "ls_mesh_ray_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ls_sample_workspace_bytes": (c_int, [c_i64, c_i64, ctypes.POINTER(c_size_t)]),
