@@ -42,6 +42,7 @@
  *   ls_mesh_selfx_*      igl.fast_find_self_intersections: which faces of the handle's mesh cut through each other
  *   ls_iso_*             igl.marching_tets on the Kuhn split of a regular grid: a level set as a mesh, with the gradient to the field
  *   ls_subdiv_*          igl.upsample / igl.loop: midpoint and Loop subdivision as a topology built once and a linear map with its transpose
+ *   ls_topo_*            igl.vertex_components / facet_components / boundary_loop / remove_unreferenced: components, loops, component filters
  */
 #ifndef LARGESTEPS_HIP_H
 #define LARGESTEPS_HIP_H
@@ -1105,6 +1106,67 @@ int ls_subdiv_apply(const float* X, int64_t F, int64_t V, int64_t E, int C, int 
 int ls_subdiv_apply_backward(const float* g, int64_t F, int64_t V, int64_t E, int C, int scheme, const int32_t* tri, const int32_t* he,
                              const int32_t* edges, const int32_t* opp, const int32_t* valence, const unsigned char* bflag,
                              const int32_t* bnbr, const int32_t* vptr, const int32_t* order, float* gX, int device, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Mesh topology (libigl's vertex_components / facet_components / boundary_loop / remove_unreferenced, largesteps/topology.py): the
+ * components of a triangle mesh, its edges with their faces and flags, its boundary loops, the area and signed volume of every facet
+ * component, and the compaction that keeps some of them. The rule is stated in csrc/topology.hip and DESIGN.md section 2.15 and
+ * restated in numpy by tests/topology_statement.py; the device returns the statement's arrays, the fp64 measures bit for bit. Half-edges
+ * and edges are those of ls_subdiv_*: edge e of ls_topo_build is edge e of ls_subdiv_topology. Components come from hooking the larger
+ * root under the smaller with integer atomicMin and one compression: the root of a component is its lowest id whatever the
+ * interleaving, so the labels are deterministic. faces (F, 3) int32 / int64 (idx_bytes 4 / 8). The arrays, all device buffers of the caller:
+ *   tri (3 F) int32             the faces narrowed
+ *   vcomp (V), fcomp (F) int32  the vertex component of a vertex (numbered by ascending lowest vertex id; a vertex in no face is its own)
+ *                               and the facet component of a face (faces that share an EDGE, numbered by ascending lowest face id)
+ *   edges (E, 2) int32          the ends of edge e, the smaller id first                                      } with room for 3 F rows:
+ *   edge_faces (E, 2) int32     the faces of the edge's two lowest half-edges, the second -1 on a boundary    } E is not known before
+ *   eflag (E) uint8             LS_TOPO_EDGE_BOUNDARY / _NONMANIFOLD / _MISORIENTED                           } the call
+ *   corder (3 F) int32          the corners sorted stably by vertex
+ *   forder (F), fseg (F + 2) int32   the faces grouped by facet component: those of k are forder[fseg[k] .. fseg[k + 1]), ascending
+ *   loops (V), loop_ptr (V + 1) int32   the B boundary vertices loop after loop: loop l is loops[loop_ptr[l] .. loop_ptr[l + 1]), from
+ *                               its lowest vertex along the boundary half-edges, the loops by ascending lowest vertex
+ *   ls_topo_workspace_bytes       the workspace of ls_topo_build (256-byte aligned regions).
+ *   ls_topo_build                 fills the arrays above. h_sizes[LS_TOPO_SIZES] = E, vertex components, facet components, B, loops,
+ *                                 boundary edges, non-manifold edges, misoriented edges; *h_status = 0 or LS_TOPO_* flags. With
+ *                                 LS_TOPO_BAD_INDEX or _REPEATED_VERTEX the arrays hold nothing of use; with LS_TOPO_BAD_BOUNDARY (a
+ *                                 boundary vertex without exactly one boundary half-edge leaving and one entering) only loops and
+ *                                 loop_ptr do not. Nothing is read or written out of bounds in either case: a bad index is never
+ *                                 followed. No host loop over device results: SYNC (once, at the end).
+ *   ls_topo_counts                counts (K, 6) int64, zeroed first: per facet component its faces, distinct vertices, edges, boundary,
+ *                                 non-manifold and misoriented edges. Integer atomic adds, one per wave where its lanes share a
+ *                                 component. ASYNC, capturable.
+ *   ls_topo_measures              out (K, 2) fp64 = area and signed volume of every facet component from verts (V, 3) fp32; terms
+ *                                 (F, 2) fp64 is the caller's scratch for the per-face terms. The sums run in the one order of the
+ *                                 segmented sum of csrc/groupby.h over a component's faces in ascending id: no float atomics, bitwise
+ *                                 reproducible. ASYNC, capturable: no allocation, no synchronisation.
+ *   ls_topo_keep_workspace_bytes  the workspace of ls_topo_keep.
+ *   ls_topo_keep                  mask (K) uint8 over the facet components. faces_out (cap_faces, 3), I (V) and J (cap_vertices) of
+ *                                 idx_bytes: the kept faces in their order renumbered through I, I[v] = the new id of v or -1,
+ *                                 J = the kept vertices in ascending old id; sizes[2] (device, int64) = the kept faces and vertices.
+ *                                 Rows past cap_faces / cap_vertices are dropped, never written. ASYNC, capturable.
+ * LS_E_INVALID for a null required pointer, a negative size, E > 3 F, K > F or another idx_bytes; LS_E_OVERFLOW when 3 F or V reaches
+ * 2^31; LS_E_WORKSPACE for a workspace below the size function's answer. counts, measures and keep follow the arrays without a range
+ * check: they must come from an ls_topo_build that returned no LS_TOPO_BAD_INDEX / _REPEATED_VERTEX for the same F and V.
+ * --------------------------------------------------------------------------------------------- */
+#define LS_TOPO_BAD_INDEX 1            /* a face index outside [0, V) */
+#define LS_TOPO_REPEATED_VERTEX 2      /* a face names a vertex twice */
+#define LS_TOPO_BAD_BOUNDARY 4         /* the boundary is not a set of oriented cycles */
+#define LS_TOPO_EDGE_BOUNDARY 1        /* an edge of one half-edge */
+#define LS_TOPO_EDGE_NONMANIFOLD 2     /* an edge of more than two half-edges */
+#define LS_TOPO_EDGE_MISORIENTED 4     /* an edge of exactly two half-edges that run the same way */
+#define LS_TOPO_SIZES 8
+int ls_topo_workspace_bytes(int64_t F, int64_t V, size_t* bytes);
+int ls_topo_build(const void* faces, int idx_bytes, int64_t F, int64_t V, int32_t* tri, int32_t* vcomp, int32_t* fcomp, int32_t* edges,
+                  int32_t* edge_faces, unsigned char* eflag, int32_t* corder, int32_t* forder, int32_t* fseg, int32_t* loops,
+                  int32_t* loop_ptr, int64_t* h_sizes, int* h_status, void* ws, size_t ws_bytes, int device, void* stream);
+int ls_topo_counts(const int32_t* tri, const int32_t* fcomp, const int32_t* edge_faces, const unsigned char* eflag, const int32_t* corder,
+                   int64_t F, int64_t E, int64_t K, int64_t* counts, int device, void* stream);
+int ls_topo_measures(const float* verts, const int32_t* tri, const int32_t* forder, const int32_t* fseg, int64_t F, int64_t V, int64_t K,
+                     double* terms, double* out, int device, void* stream);
+int ls_topo_keep_workspace_bytes(int64_t F, int64_t V, size_t* bytes);
+int ls_topo_keep(const int32_t* tri, const int32_t* fcomp, const unsigned char* mask, int64_t F, int64_t V, int64_t K, int idx_bytes,
+                 int64_t cap_faces, int64_t cap_vertices, void* faces_out, void* I, void* J, int64_t* sizes, void* ws, size_t ws_bytes,
+                 int device, void* stream);
 
 #ifdef __cplusplus
 }

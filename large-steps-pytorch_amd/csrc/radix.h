@@ -3,7 +3,7 @@
 // stable by construction, no atomics in the scatter), and the one description of the scratch it needs (SortScratch below).
 // Users: remove_duplicates, the CSR transpose and the corner ranking (assemble.hip); the coordinate orders of the device bisection
 // (nd_bisect.hip); the Morton order of the LBVH (lbvh.h: the remesher's projection in remesh.hip, the point-to-mesh distance in
-// distance.hip); the edge adjacency of the rasterizer (raster.hip); the edges of the subdivision topology (subdiv.hip); and, through
+// distance.hip); the edge adjacency of the rasterizer (raster.hip); the edges of the subdivision topology (subdiv.hip) and of the mesh topology (topology.hip); and, through
 // the group-by of groupby.h, the pixel orders of the rasterizer and of the texture lookup (raster.hip, texture.hip).
 #pragma once
 #include "common.h"

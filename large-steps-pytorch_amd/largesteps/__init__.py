@@ -13,6 +13,7 @@ largesteps/ 0.2.2). Same modules, symbols and call forms as the reference:
     from largesteps.sampling import sample_surface; from largesteps.distance import chamfer_distance   (mesh-to-mesh measures)
     from largesteps.raycast import RayMesh, ray_mesh_intersect, ambient_occlusion   (igl's ray queries, on the distance handle's LBVH)
     from largesteps.subdivide import Subdivision, loop, upsample   (igl's loop / upsample as a linear map applied every step)
+    from largesteps.topology import MeshTopology, facet_components, boundary_loops, keep_largest_component   (igl's components and loops)
 
 Device work is done by hand-written HIP kernels for gfx950 in lib/liblargesteps_hip.so (C ABI in
 include/largesteps_hip.h); there is no CPU or stock-PyTorch fallback.

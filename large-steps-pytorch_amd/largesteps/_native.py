@@ -134,6 +134,14 @@ _SIGNATURES = {
                                    c_void_p]),
     "ls_subdiv_apply": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_int, c_int] + [c_void_p] * 10 + [c_int, c_void_p]),
     "ls_subdiv_apply_backward": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_int, c_int] + [c_void_p] * 10 + [c_int, c_void_p]),
+    "ls_topo_workspace_bytes": (c_int, [c_i64, c_i64, ctypes.POINTER(c_size_t)]),
+    "ls_topo_build": (c_int, [c_void_p, c_int, c_i64, c_i64] + [c_void_p] * 11 + [ctypes.POINTER(c_i64 * 8), ctypes.POINTER(c_int), c_void_p,
+                              c_size_t, c_int, c_void_p]),
+    "ls_topo_counts": (c_int, [c_void_p] * 5 + [c_i64, c_i64, c_i64, c_void_p, c_int, c_void_p]),
+    "ls_topo_measures": (c_int, [c_void_p] * 4 + [c_i64, c_i64, c_i64, c_void_p, c_void_p, c_int, c_void_p]),
+    "ls_topo_keep_workspace_bytes": (c_int, [c_i64, c_i64, ctypes.POINTER(c_size_t)]),
+    "ls_topo_keep": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_int, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_size_t, c_int, c_void_p]),
     "ls_mesh_ray_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ls_sample_workspace_bytes": (c_int, [c_i64, c_i64, ctypes.POINTER(c_size_t)]),

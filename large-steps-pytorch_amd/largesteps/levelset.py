@@ -188,6 +188,10 @@ def remesh_level_set(V, F, h, field="winding", offset=0.0, pad=2, beta=2.0):
     lost. Its triangles include poorly shaped ones (slivers where the surface passes near a node): follow with `remesh_botsch`
     before compute_matrix. Not differentiable in V. numpy input gives numpy, tensors give tensors on their device.
 
+    The level set has every closed sheet of the field: the outer skin, the inward-facing shells around enclosed voids, specks of a noisy
+    winding field. largesteps.topology filters them on the device: keep_outer_components(V2, F2) drops every facet component whose
+    signed volume is <= 0 (the shells around voids), keep_largest_component(V2, F2, by='volume') keeps the one of largest |volume|.
+
     ValueError when the grid would pass the int32 limits of the kernels; the message names the smallest h that fits."""
     h = _real(h, "h")
     offset = _real(offset, "offset")
